@@ -8,8 +8,9 @@ Default workload (BASELINE.json configs[2], the configuration the metric is quot
   One "step" = --inner (default 12) passes of that pipeline over a batch of B = 1024 independent ciphertext pairs per GPU,
                inputs and evaluation keys already resident in HBM (12 x 1024 ops per step: 20 driver steps time about a second).
   value = whole-job ops/s = n_gpus * B * inner * steps / time (max over ranks);  "scaling": "weak".
-  The same line carries the three-call figure (Evaluator::multiply + relinearize + rescale_to_next as three library calls, the
-  reference's own operator boundary) next to the fused entry's, the roofline of the dominant kernel, the CPU baseline, and
+  A plain run sets up, warms up, times --steps steps and prints that line (and writes the last step's results with --dump-outputs DIR).
+  With --full the same line also carries the three-call figure (Evaluator::multiply + relinearize + rescale_to_next as three library calls, the
+  reference's own operator boundary) next to the fused entry's, the roofline of the dominant kernel, parity with the CPU oracle, the CPU baseline, and
   `other_configs`: BASELINE configs[3] (cfg4) and configs[4] (cfg5) each with value + roofline + cpu_baseline + parity, north_star's
   other ring sizes, and the C++ mirror (troy::Evaluator) timed by tests/cpp/he_bench_driver.
 
@@ -23,6 +24,7 @@ BEFORE this process touches the GPU, relays rank 0's JSON line, and ends every r
 Evaluation keys are broadcast once from rank 0 before the timed region; the data path has no collective.
 """
 import argparse
+import contextlib
 import glob
 import hashlib
 import json
@@ -46,8 +48,12 @@ TIMER_KS, TIMER_TENSOR, TIMER_PLAIN_MAC, TIMER_FLOOR = 0, 1, 2, 3   # include/tr
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: cfg3 20, cfg4 5)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: roofline and kernel timers, the three-call figure, "
+                                                        "parity with the CPU oracle and the CPU baseline, other_configs (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                                                                          "(float64, a fixed sample of items, at most 64 MB in all; rank 0)")
     ap.add_argument("--inner", type=int, default=0, help="passes over the batch per step (cfg3: 12; cfg4: 1 = the whole job once)")
     ap.add_argument("--workload", choices=["cfg3", "cfg4"], default="cfg3")
     ap.add_argument("--batch", type=int, default=0, help="ciphertext pairs per GPU per launch (cfg3: 1024; cfg4: chunk of 64)")
@@ -60,7 +66,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true", help="run the launcher / rendezvous / key broadcast / timing reduction with the gloo backend on "
                                                               "CPU tensors and no evaluation (exercises the N > 1 plumbing where there is no GPU)")
     ap.add_argument("--dry-fail-rank", type=int, default=-1, help="--dry-run only: this rank exits non-zero before the rendezvous (launcher watchdog test)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps is None:
+        args.steps = 5 if args.workload == "cfg4" else 20     # cfg4: one step = the whole 1024-op job
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -196,7 +205,8 @@ def split_output(result):
     if roof:
         extras.extend(_pack("roofline_detail", roof))
     head = {k: result.pop(k) for k in HEADLINE_KEYS if k in result}
-    head["roofline"] = head_roof
+    if "roofline" in head:          # (a plain run measures no roofline: --full)
+        head["roofline"] = head_roof
     if result:                      # anything a run_* function added that is not a headline key
         extras.extend(_pack("more", result))
     small = {k: v for k, v in other.items() if k not in ("cfg4", "cfg5", "cpp_api", "single_object_latency_us")}
@@ -253,6 +263,20 @@ def timed_broadcast(torch, shard, keys):
     shard.broadcast_tensors(keys, src=0)
     torch.cuda.synchronize()
     return time.perf_counter() - t0
+
+
+DUMP_BYTES = 32 * 2**20        # --dump-outputs: the sample written, well below the 64 MB the option allows
+
+
+def dump_outputs(dirname, torch, name, out, valid_items):
+    """--dump-outputs: the first `valid_items` items of a result buffer [items][...] of int64 residues as dirname/<name>.npy in float64 (every residue
+    is below 2^53: exact); a fixed, seeded sample of them (sorted item order) when they would take more than DUMP_BYTES"""
+    import numpy as np
+    k = max(1, min(valid_items, DUMP_BYTES // (out[0].numel() * 8)))
+    items = np.sort(np.random.default_rng(0).choice(valid_items, size=k, replace=False)) if k < valid_items else np.arange(valid_items)
+    sample = out[torch.as_tensor(items, device=out.device)].to(torch.float64).cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), sample)
 
 
 def timed(torch, fn, reps):
@@ -391,7 +415,7 @@ def run_cfg3(args, torch, pkg, shard, entry, rank, world, device):
     for _ in range(args.warmup):
         step()
     lib = plan.lib
-    with KernelTimer(pkg, lib, TIMER_KS) as kt:
+    with (KernelTimer(pkg, lib, TIMER_KS) if args.full else contextlib.nullcontext()) as kt:
         shard.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -401,10 +425,26 @@ def run_cfg3(args, torch, pkg, shard, entry, rank, world, device):
         local_elapsed = time.perf_counter() - t0          # this rank's own work (the contract's clock runs to the closing barrier)
         shard.barrier()
         elapsed = time.perf_counter() - t0
-        ks_ms, ks_n = kt.read()
+        ks_ms, ks_n = kt.read() if kt else (0.0, 0)
     ranks = shard.rank_report(local_elapsed, args.steps, torch.cuda.get_device_name(device), key_broadcast_s, device=device)
     elapsed = shard.max_over_ranks(elapsed, device=device)
     value = world * B * inner * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, "ckks_mul_relin_rescale", out, B)      # every pass of a step writes `out` from the same operands
+    result = {
+        "metric": "homomorphic mul+relinearize ops/sec (CKKS mul+relin+rescale), N=16384",
+        "value": round(value, 1), "unit": "ops/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "config": {"workload": "CKKS N=16384, 6x50-bit coeff modulus (K=6, L=5): multiply + relinearize + rescale_to_next (BASELINE configs[2])",
+                   "batch_per_gpu": B, "passes_per_step": inner, "ops_per_step": world * B * inner,
+                   "entry": "troyn_ckks_multiply_relinearize_rescale" if fused else "troyn_dyadic_convolute + troyn_relinearize + troyn_divide_and_round_q_last_ntt",
+                   "parallelism": "batch-sharded x%d, keys broadcast once (RCCL)" % world,
+                   # what the backend saw, per rank (a first multi-GPU run that goes wrong must be readable from this line alone)
+                   **ranks},
+    }
+    if not args.full:
+        return result
 
     # ---- roofline of the kernel with the largest share of the timed step: the fused key-switch inner product ----
     # The fused entry runs the whole batch as one launch sequence on the caller's stream (the default), so the launches timed inside the
@@ -497,20 +537,8 @@ def run_cfg3(args, torch, pkg, shard, entry, rank, world, device):
         del probe, sink
         torch.cuda.empty_cache()
 
-    result = {
-        "metric": "homomorphic mul+relinearize ops/sec (CKKS mul+relin+rescale), N=16384",
-        "value": round(value, 1), "unit": "ops/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-        "config": {"workload": "CKKS N=16384, 6x50-bit coeff modulus (K=6, L=5): multiply + relinearize + rescale_to_next (BASELINE configs[2])",
-                   "batch_per_gpu": B, "passes_per_step": inner, "ops_per_step": world * B * inner,
-                   "entry": "troyn_ckks_multiply_relinearize_rescale" if fused else "troyn_dyadic_convolute + troyn_relinearize + troyn_divide_and_round_q_last_ntt",
-                   "three_call_ops_per_s": three_call,
-                   "parallelism": "batch-sharded x%d, keys broadcast once (RCCL)" % world,
-                   # what the backend saw, per rank (a first multi-GPU run that goes wrong must be readable from this line alone)
-                   **ranks},
-        "roofline": roofline,
-    }
+    result["config"]["three_call_ops_per_s"] = three_call
+    result["roofline"] = roofline
 
     # ---- in-run parity + CPU baseline (rank 0, N = 1 only): the oracle is the checker / reported baseline ----
     if rank == 0 and world > 1 and not args.no_cpu_baseline:
@@ -588,7 +616,7 @@ def run_cfg3(args, torch, pkg, shard, entry, rank, world, device):
         del a, b, prod, relin, out, plan
         torch.cuda.empty_cache()
         other = extra_configs(torch, pkg, device)
-        sub = parse_args(["--workload", "cfg4", "--total", "256", "--steps", "3", "--warmup", "2", "--cpu-seconds", "4"] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []))
+        sub = parse_args(["--workload", "cfg4", "--total", "256", "--steps", "3", "--warmup", "2", "--cpu-seconds", "4", "--full"] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []))
         other["cfg4"] = run_cfg4(sub, torch, pkg, shard, entry, 0, 1, device)
         other["cfg4"]["note"] = "BASELINE configs[3] on one GPU with a 256-op job per step (`bench.py --workload cfg4` runs the 1024-op job and shards it over --gpus ranks)"
         torch.cuda.empty_cache()
@@ -799,7 +827,8 @@ def run_cfg4(args, torch, pkg, shard, entry, rank, world, device):
         step()
     lib = plan.lib
     launches[0] = 0
-    with KernelTimer(pkg, lib, TIMER_KS) as kt_ks, KernelTimer(pkg, lib, TIMER_TENSOR) as kt_t, KernelTimer(pkg, lib, TIMER_FLOOR) as kt_f:
+    timers = (KernelTimer(pkg, lib, TIMER_KS), KernelTimer(pkg, lib, TIMER_TENSOR), KernelTimer(pkg, lib, TIMER_FLOOR)) if args.full else (contextlib.nullcontext(),) * 3
+    with timers[0] as kt_ks, timers[1] as kt_t, timers[2] as kt_f:
         shard.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -809,13 +838,29 @@ def run_cfg4(args, torch, pkg, shard, entry, rank, world, device):
         local_elapsed = time.perf_counter() - t0          # this rank's own work (the contract's clock runs to the closing barrier)
         shard.barrier()
         elapsed = time.perf_counter() - t0
-        ks_ms, ks_n = kt_ks.read()
-        tn_ms, tn_n = kt_t.read()
-        fl_ms, fl_n = kt_f.read()
+        ks_ms, ks_n = kt_ks.read() if kt_ks else (0.0, 0)
+        tn_ms, tn_n = kt_t.read() if kt_t else (0.0, 0)
+        fl_ms, fl_n = kt_f.read() if kt_f else (0.0, 0)
     ranks = shard.rank_report(local_elapsed, args.steps, torch.cuda.get_device_name(device), key_broadcast_s, device=device)
     ranks["items_per_rank"] = [int(v) for v in shard.gather_over_ranks(mine, device=device)]
     elapsed = shard.max_over_ranks(elapsed, device=device)
     value = args.total * args.steps / elapsed
+    if rank == 0 and args.dump_outputs and mine:
+        # `out` holds the rank's LAST chunk of the step: items ((mine - 1) // nb) * nb .. mine - 1 of its slice (the last chunk may be ragged)
+        dump_outputs(args.dump_outputs, torch, "bfv_mul_relin", out, mine - ((mine - 1) // nb) * nb)
+    result = {
+        "metric": "homomorphic mul+relinearize ops/sec (BFV BEHZ multiply + relinearize), N=32768", "value": round(value, 1), "unit": "ops/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "u64", "data": "synthetic",
+        "config": {"workload": "BFV N=32768, 11x50-bit coeff modulus (K=11, L=10), t=1032193: %d independent multiply + relinearize ops per step, "
+                               "block-partitioned over %d rank(s) (rank 0: items [%d, %d)), %d per launch" % (args.total, world, lo, hi, nb),
+                   "total_ops_per_step": args.total, "operands": "%d distinct ciphertext pairs per rank resident in HBM" % mine,
+                   "parallelism": "batch-sharded x%d (shard.shard_range), keys broadcast once (RCCL)" % world, **ranks},
+    }
+    if not args.full:
+        del x, y, prod, out, keys, behz, plan
+        return result
 
     # ---- roofline: the launch with the largest share of the step.  Full chunks only (the job is a multiple of the chunk in every quoted run).
     share = lambda ms: 100.0 * ms / (elapsed * 1e3)
@@ -865,17 +910,7 @@ def run_cfg4(args, torch, pkg, shard, entry, rank, world, device):
                 "pipeline": {"bytes_per_op_keys_per_op": 89.2e6, "frac_keys_per_op": round(per_gpu * 89.2e6 / (HBM_PEAK_GBS * 1e9), 4),
                              "bytes_per_op_keys_once_per_launch": 18.4e6 + 13.1e6 + 57.7e6 / nb,
                              "frac_keys_once_per_launch": round(per_gpu * (18.4e6 + 13.1e6 + 57.7e6 / nb) / (HBM_PEAK_GBS * 1e9), 4)}}
-    result = {
-        "metric": "homomorphic mul+relinearize ops/sec (BFV BEHZ multiply + relinearize), N=32768", "value": round(value, 1), "unit": "ops/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "u64", "data": "synthetic",
-        "config": {"workload": "BFV N=32768, 11x50-bit coeff modulus (K=11, L=10), t=1032193: %d independent multiply + relinearize ops per step, "
-                               "block-partitioned over %d rank(s) (rank 0: items [%d, %d)), %d per launch" % (args.total, world, lo, hi, nb),
-                   "total_ops_per_step": args.total, "operands": "%d distinct ciphertext pairs per rank resident in HBM" % mine,
-                   "parallelism": "batch-sharded x%d (shard.shard_range), keys broadcast once (RCCL)" % world, **ranks},
-        "roofline": roofline,
-    }
+    result["roofline"] = roofline
     if rank == 0 and not args.no_cpu_baseline:
         import numpy as np
         O = entry.load_oracle()
@@ -1121,8 +1156,6 @@ def main():
     if world != args.gpus:
         sys.stderr.write("bench.py: --gpus %d but WORLD_SIZE=%d\n" % (args.gpus, world))
         return 2
-    if args.workload == "cfg4" and args.steps == 20:
-        args.steps = 5                          # one step = the whole 1024-op job
     if args.dry_run:
         return dry_run(args, rank, world)
 

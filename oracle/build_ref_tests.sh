@@ -1,9 +1,9 @@
 #!/bin/bash
 # Builds the reference's OWN test suite (/root/reference/test/*.cu and test/app/*.cu: 362 googletest cases; compiled where they lie -- nothing of the reference is
-# copied into the repository) against this repository's host-side mirror (troy-nova_amd/troy/*.h, libtroy_amd.so) into tests/_ref_tests/ref_tests.
+# copied into the repository) against this repository's host-side mirror (troy-nova_amd/troy/*.h, libtroy_amd.so) into oracle/_ref/ref_tests.
 # Purpose: the drop-in check of SURVEY 8b taken to its end -- the tests the reference's maintainers wrote pass on the HIP path through the mirror
 # (tests/test_gpu_ref_tests.py runs the Device* cases; the mirror has no host path, so Host* cases do not apply).  Test infrastructure only; needs /root/reference,
-# so it runs in the build container (the GPU box uses the prebuilt binary, which is git-ignored like tests/_ref_examples).  This is NOT a build of the reference
+# so it runs in the build container (the GPU box uses the prebuilt binary, which is git-ignored under oracle/_ref/ and travels with the tree).  This is NOT a build of the reference
 # library: only the reference's test CALLERS, linked against this implementation.
 #   * the sources include "../src/<name>.h": they are compiled in a scratch directory where those resolve to one-line forwarders to the mirror's headers;
 #   * <gtest/gtest.h> (an un-vendored submodule of the reference) resolves to tests/ref_tests_support/gtest/gtest.h, a 50-line runner written for this repository;
@@ -42,25 +42,25 @@ for f in test_adv test_multithread evaluator evaluator_batched encryptor encrypt
 done
 wait
 g++ $CXXFLAGS -c -o "$W/main.o" "$ROOT/tests/ref_tests_support/ref_tests_main.cpp"
-mkdir -p "$ROOT/tests/_ref_tests"
-g++ -o "$ROOT/tests/_ref_tests/ref_tests" $OBJS "$W/main.o" -L"$PKG" -ltroy_amd -ltroyn -L/opt/rocm/lib -lamdhip64 -lpthread \
+mkdir -p "$ROOT/oracle/_ref"
+g++ -o "$ROOT/oracle/_ref/ref_tests" $OBJS "$W/main.o" -L"$PKG" -ltroy_amd -ltroyn -L/opt/rocm/lib -lamdhip64 -lpthread \
     -Wl,-rpath,'$ORIGIN/../../troy-nova_amd' -Wl,-rpath,/opt/rocm/lib
-echo "built tests/_ref_tests/ref_tests ($("$ROOT/tests/_ref_tests/ref_tests" --list | wc -l) cases)"
-# the reference's bench tool (test/bench/he_operations.cu = `troybench`, its own main) against the mirror: tests/_ref_tests/ref_troybench -D ... is the tool a
+echo "built oracle/_ref/ref_tests ($("$ROOT/oracle/_ref/ref_tests" --list | wc -l) cases)"
+# the reference's bench tool (test/bench/he_operations.cu = `troybench`, its own main) against the mirror: oracle/_ref/ref_troybench -D ... is the tool a
 # maintainer of the reference would run (tests/cpp/he_bench_driver.cpp is this repository's counterpart, which also times the batched and fused entries)
 mkdir -p "$W/test/bench"
 cp "$REF"/test/bench/he_operations.cu "$REF"/test/bench/argument_helper.h "$W/test/bench/"
 cp "$REF"/test/argparse.cpp "$W/test/"
 ( cd "$W/test/bench" && g++ $CXXFLAGS -I.. -x c++ -c -o "$W/troybench.o" he_operations.cu )
 g++ $CXXFLAGS -c -o "$W/argparse.o" "$W/test/argparse.cpp"
-g++ -o "$ROOT/tests/_ref_tests/ref_troybench" "$W/troybench.o" "$W/argparse.o" "$W/test_adv.o" "$W/test_multithread.o" -L"$PKG" -ltroy_amd -ltroyn -L/opt/rocm/lib -lamdhip64 -lpthread \
+g++ -o "$ROOT/oracle/_ref/ref_troybench" "$W/troybench.o" "$W/argparse.o" "$W/test_adv.o" "$W/test_multithread.o" -L"$PKG" -ltroy_amd -ltroyn -L/opt/rocm/lib -lamdhip64 -lpthread \
     -Wl,-rpath,'$ORIGIN/../../troy-nova_amd' -Wl,-rpath,/opt/rocm/lib
-echo "built tests/_ref_tests/ref_troybench"
+echo "built oracle/_ref/ref_troybench"
 # ... and its matmul / conv2d bench tools (test/bench/matmul.cu, conv2d.cu: BASELINE config 5 is `bench_matmul -D --bfv -m 512 -r 512 -n 512 ...`)
 cp "$REF"/test/bench/matmul.cu "$REF"/test/bench/conv2d.cu "$W/test/bench/"
 for t in matmul conv2d; do
   ( cd "$W/test/bench" && g++ $CXXFLAGS -I.. -x c++ -c -o "$W/bench_$t.o" $t.cu )
-  g++ -o "$ROOT/tests/_ref_tests/ref_bench_$t" "$W/bench_$t.o" "$W/argparse.o" "$W/test_adv.o" "$W/test_multithread.o" -L"$PKG" -ltroy_amd -ltroyn -L/opt/rocm/lib -lamdhip64 -lpthread \
+  g++ -o "$ROOT/oracle/_ref/ref_bench_$t" "$W/bench_$t.o" "$W/argparse.o" "$W/test_adv.o" "$W/test_multithread.o" -L"$PKG" -ltroy_amd -ltroyn -L/opt/rocm/lib -lamdhip64 -lpthread \
       -Wl,-rpath,'$ORIGIN/../../troy-nova_amd' -Wl,-rpath,/opt/rocm/lib
-  echo "built tests/_ref_tests/ref_bench_$t"
+  echo "built oracle/_ref/ref_bench_$t"
 done

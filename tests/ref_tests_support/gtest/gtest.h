@@ -1,5 +1,5 @@
 // A few dozen lines standing where <gtest/gtest.h> would be (googletest is an un-vendored submodule of the reference and absent from this image): just enough
-// of its macro surface to RUN the reference's own test sources against this repository's mirror (tests/build_ref_tests.sh).  Written for this repository; the
+// of its macro surface to RUN the reference's own test sources against this repository's mirror (oracle/build_ref_tests.sh).  Written for this repository; the
 // semantics follow googletest's documented behaviour: TEST registers a void function; ASSERT_* records a failure and returns from the CURRENT function; EXPECT_*
 // records and continues; GTEST_SKIP() marks the test skipped and returns.  The runner (ref_tests_main.cpp) runs the tests whose full name contains a filter string.
 #pragma once

@@ -1,4 +1,4 @@
-// Runner of tests/_ref_tests/ref_tests: the reference's own test sources linked against this repository's mirror (tests/build_ref_tests.sh).
+// Runner of oracle/_ref/ref_tests: the reference's own test sources linked against this repository's mirror (oracle/build_ref_tests.sh).
 //   ref_tests [filter]      runs the tests whose "Suite.Name" contains `filter` (default "Device": the mirror has no host path), prints one line per test
 //   ref_tests --list        the names
 #include <cstring>

@@ -69,7 +69,7 @@ import pytest
 @pytest.mark.gpu
 def test_self_launcher_one_gpu():
     """the launcher path on real hardware: a fresh rank process is started before anything touches the GPU"""
-    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--inner", "1", "--batch", "64", "--no-cpu-baseline", "--no-extra"], env_extra={"TROYN_BENCH_SPAWN": "1"})
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--inner", "1", "--batch", "64", "--full", "--no-cpu-baseline", "--no-extra"], env_extra={"TROYN_BENCH_SPAWN": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert j["n_gpus"] == 1 and j["value"] > 0 and j["roofline"]["launches_timed"] == 3
@@ -81,7 +81,7 @@ def test_two_ranks_on_hardware_oversubscribed(workload, extra):
     """SURVEY 8e on a one-GPU box: TWO rank processes through the self-launcher, both on the visible device, collectives over gloo (RCCL refuses a duplicate
     device).  Everything but the transport is the real N > 1 path: fresh rank processes, rendezvous, key broadcast from rank 0, the block partition, evaluation on
     the GPU in both ranks at once, max-over-ranks, the per-rank block of the line -- and rank 0's results equal the oracle's.  (Timings mean nothing here.)"""
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", workload, "--no-extra", "--cpu-seconds", "0"] + extra,
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", workload, "--full", "--no-extra", "--cpu-seconds", "0"] + extra,
              env_extra={"TROYN_BENCH_OVERSUBSCRIBE": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -93,3 +93,36 @@ def test_two_ranks_on_hardware_oversubscribed(workload, extra):
         assert c["items_per_rank"] == [3, 3] and c["total_ops_per_step"] == 6
     else:
         assert c["ops_per_step"] == 2 * 16
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_what_the_full_run_checks(tmp_path):
+    """a plain run prints the headline line alone, times exactly --steps steps, and --dump-outputs writes the last step's results; a --full run of the same
+    arguments checks its results against the oracle (parity) and dumps the same arrays"""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--inner", "1", "--batch", "64"]
+    r = _run(args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "ops/s" and j["dtype"] == "u64"
+    assert "roofline" not in j and "parity" not in j and "cpu_baseline" not in j
+    plain = np.load(tmp_path / "plain" / "ckks_mul_relin_rescale.npy")
+    assert plain.dtype == np.float64 and plain.shape[1:] == (2, 4, 16384) and 0 < plain.shape[0] <= 64 and plain.nbytes <= 64 * 10**6
+    r = _run(args + ["--full", "--no-extra", "--cpu-seconds", "0", "--dump-outputs", str(tmp_path / "full")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert "bit-exact" in j.get("parity", "") and j["roofline"]["launches_timed"] == 3
+    assert np.array_equal(np.load(tmp_path / "full" / "ckks_mul_relin_rescale.npy"), plain)
+
+
+@pytest.mark.gpu
+def test_plain_cfg4_run_dumps_its_last_chunk(tmp_path):
+    import numpy as np
+    r = _run(["--gpus", "1", "--workload", "cfg4", "--total", "6", "--batch", "4", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and "roofline" not in j
+    d = np.load(tmp_path / "bfv_mul_relin.npy")
+    assert d.dtype == np.float64 and d.shape == (2, 2, 10, 32768) and np.all(d == np.floor(d)) and d.max() < 2**50

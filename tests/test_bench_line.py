@@ -88,3 +88,44 @@ def test_dry_run_last_stdout_line_parses():
     last = r.stdout.strip().splitlines()[-1]
     assert len(last) < bench.HEADLINE_LIMIT
     assert json.loads(last)["dry_run"] is True
+
+
+def test_steps_mean_the_timed_steps_and_full_is_off_by_default():
+    assert bench.parse_args([]).steps == 20 and bench.parse_args(["--workload", "cfg4"]).steps == 5
+    assert bench.parse_args(["--workload", "cfg4", "--steps", "20"]).steps == 20
+    a = bench.parse_args(["--steps", "7"])
+    assert a.steps == 7 and not a.full and a.dump_outputs is None
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_plain_run_prints_the_headline_alone():
+    """a plain run measures no roofline, parity, CPU baseline or other configuration: its output is the headline line and nothing else"""
+    src = sample()
+    plain = {k: src[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                                 "data", "config")}
+    buf = io.StringIO()
+    line = bench.emit(plain, out=buf)
+    assert buf.getvalue().splitlines() == [line]
+    head = json.loads(line)
+    assert "roofline" not in head and head["extras"] == []
+    assert {k: head[k] for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")} == \
+           {k: src[k] for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")}
+
+
+def test_dump_outputs_writes_a_fixed_exact_sample(tmp_path):
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(1)
+    out = torch.randint(0, 2**50, (64, 2, 4, 16384), dtype=torch.int64, generator=g)       # 64 MiB of residues, the headline's result shape
+    out[:, 0, 0, 0] = torch.arange(64)                                                         # item index, to find the sampled items again
+    bench.dump_outputs(str(tmp_path / "a"), torch, "r", out, 64)
+    bench.dump_outputs(str(tmp_path / "b"), torch, "r", out, 64)
+    a, b = np.load(tmp_path / "a" / "r.npy"), np.load(tmp_path / "b" / "r.npy")
+    assert a.dtype == np.float64 and a.nbytes <= 64 * 10**6 and 1 < a.shape[0] < 64 and a.shape[1:] == (2, 4, 16384)
+    assert np.array_equal(a, b)
+    items = a[:, 0, 0, 0].astype(np.int64)
+    assert np.all(np.diff(items) > 0)
+    assert np.array_equal(a.astype(np.int64), out[torch.as_tensor(items)].numpy())           # float64 holds every residue below 2^53 exactly
+    # a few valid items (a ragged last chunk): all of them, nothing past them
+    bench.dump_outputs(str(tmp_path / "c"), torch, "r", out, 3)
+    assert np.array_equal(np.load(tmp_path / "c" / "r.npy").astype(np.int64), out[:3].numpy())

@@ -1,6 +1,6 @@
 """The reference's OWN test suite (its test/*.cu and test/app/*.cu, 392 googletest cases, the zstd serialization group included) run against this repository's mirror on the GPU: the strongest form of
-the drop-in check of SURVEY 8b.  tests/build_ref_tests.sh compiles those sources WHERE THEY LIE in the build container against the mirror's headers (nothing of
-the reference enters the repository; the binary tests/_ref_tests/ref_tests is git-ignored and travels to the GPU box like the built libraries) with a 50-line
+the drop-in check of SURVEY 8b.  oracle/build_ref_tests.sh compiles those sources WHERE THEY LIE in the build container against the mirror's headers (nothing of
+the reference enters the repository; the binary oracle/_ref/ref_tests is git-ignored and travels to the GPU box like the built libraries) with a 50-line
 stand-in for the googletest macros (tests/ref_tests_support/gtest/gtest.h).  Run here: every case whose name contains "Device" (the mirror has no host path).
 
 Not expected to pass, each for a stated reason that the test itself shows:
@@ -27,9 +27,9 @@ MARGINAL_TOLERANCE = {"SerializeTest.DeviceCKKSCiphertext"}
 
 
 def test_reference_test_suite_on_the_mirror(dev):
-    exe = os.path.join(ROOT, "tests", "_ref_tests", "ref_tests")
+    exe = os.path.join(ROOT, "oracle", "_ref", "ref_tests")
     if not os.path.exists(exe):
-        pytest.skip("tests/_ref_tests/ref_tests is not built (bash tests/build_ref_tests.sh, needs the reference tree: build container only)")
+        pytest.skip("oracle/_ref/ref_tests is not built (bash oracle/build_ref_tests.sh, needs the reference tree: build container only)")
     r = subprocess.run([exe, "Device"], capture_output=True, text=True, timeout=1800)
     lines = r.stdout.splitlines()
     verdicts = {}
@@ -61,9 +61,9 @@ def test_reference_bench_tool_on_the_mirror(dev, args):
     """the reference's own bench tool (test/bench/he_operations.cu = `troybench`, its own main and argument parser) linked against the mirror: device mode with its
     default parameters (N = 8192, {60,40,40,60}, every scheme), the headline shape, the -c N -mp thread mode and -B (its batched operations).  The tool checks the
     first result of everything it times and exits with 1 on a wrong one (he_operations.cu:254-259).  Timings of full runs: profiles/r06_ref_troybench_*.txt."""
-    exe = os.path.join(ROOT, "tests", "_ref_tests", "ref_troybench")
+    exe = os.path.join(ROOT, "oracle", "_ref", "ref_troybench")
     if not os.path.exists(exe):
-        pytest.skip("tests/_ref_tests/ref_troybench is not built (bash tests/build_ref_tests.sh, build container only)")
+        pytest.skip("oracle/_ref/ref_troybench is not built (bash oracle/build_ref_tests.sh, build container only)")
     r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "failed" not in r.stderr.lower() and "exception" not in (r.stdout + r.stderr).lower(), r.stdout[-3000:] + r.stderr[-3000:]
@@ -78,9 +78,9 @@ def test_reference_matmul_and_conv2d_tools_on_the_mirror(dev, tool, args):
     """the reference's matmul / conv2d bench tools (test/bench/matmul.cu, conv2d.cu: encode, encrypt, serialise, multiply, pack, serialise, decrypt -- the flow of BASELINE
     config 5) linked against the mirror; they verify the decrypted product themselves and return 1 when it is wrong.  A full run at 512 x 512 x 512:
     profiles/r06_ref_bench_matmul.txt."""
-    exe = os.path.join(ROOT, "tests", "_ref_tests", tool)
+    exe = os.path.join(ROOT, "oracle", "_ref", tool)
     if not os.path.exists(exe):
-        pytest.skip("tests/_ref_tests/%s is not built (bash tests/build_ref_tests.sh, build container only)" % tool)
+        pytest.skip("oracle/_ref/%s is not built (bash oracle/build_ref_tests.sh, build container only)" % tool)
     r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "Time cost" in r.stdout and "exception" not in (r.stdout + r.stderr).lower(), r.stdout[-3000:] + r.stderr[-3000:]

@@ -8,7 +8,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/gpurun_out"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --steps 10 --warmup 1 --inner 4 --no-cpu-baseline --no-extra"
+ARGS="$ROOT/bench.py --full --steps 10 --warmup 1 --inner 4 --no-cpu-baseline --no-extra"
 # the fused chain on ONE stream (the library's default) for the kernel trace and the counter passes
 export TROYN_MRR_CHUNK=0
 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$TAG/trace" -o bench -- python3 $ARGS > "$OUT/${TAG}_bench.log" 2>&1

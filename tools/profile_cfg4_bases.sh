@@ -6,7 +6,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/gpurun_out"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --workload cfg4 --total 256 --steps 5 --warmup 2 --no-cpu-baseline --no-extra"
+ARGS="$ROOT/bench.py --full --workload cfg4 --total 256 --steps 5 --warmup 2 --no-cpu-baseline --no-extra"
 for BASE in ref small; do
   if [ "$BASE" = small ]; then unset TROYN_BEHZ_BASE; else export TROYN_BEHZ_BASE=ref; fi
   rocprofv3 --kernel-trace --stats -d "$OUT/prof_${TAG}_$BASE/trace" -o bench -- python3 $ARGS > "$OUT/${TAG}_${BASE}_bench.log" 2>&1
