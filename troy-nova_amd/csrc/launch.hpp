@@ -47,6 +47,8 @@ inline void launch_ntt_u64_small_pass(unsigned log_n, int which, const NttArgs& 
 }
 void launch_mrr_quartet(unsigned log_n, size_t batch, const NttArgs& sp, const NttArgs& la, const NttArgs& ta, hipStream_t s, bool limb_parallel);
 void launch_mrr_quartet_load(unsigned log_n, size_t groups, const NttArgs& iv, const NttArgs& fw, hipStream_t s, bool f64);
+// the same tail on whole-limb tiles for the batches that fill the chip (troyn_mrr_tail.hip; log_n = 14, all-FP64 chains): one launch for steps (3)-(5)
+void launch_mrr_tail(unsigned log_n, size_t batch, const NttArgs& sp, const NttArgs& la, const NttArgs& ta, hipStream_t s);
 inline bool launch_ntt_f64(unsigned log_n, const NttArgs& a, size_t lp, bool inverse, const LaunchCtx& lc, u64* scratch) {
     return log_n <= 13 ? launch_ntt_f64_small(log_n, a, lp, inverse, lc, scratch) : launch_ntt_f64_large(log_n, a, lp, inverse, lc, scratch);
 }

@@ -262,6 +262,10 @@ __device__ __forceinline__ unsigned ntt_table_index(const NttArgs& a, unsigned k
     return a.table_start + idx;
 }
 
+// merged chain tail (mrr_tail_kernel): 16-byte pairs of the epilogue operand Q_j kept in flight per thread (0: loaded where they are used)
+#ifndef TROYN_MRR_TAIL_WINDOW
+#define TROYN_MRR_TAIL_WINDOW 4
+#endif
 constexpr int NTT_PAD_SHIFT = 5;
 __host__ __device__ constexpr unsigned ntt_lds_words(int tb) { return (1u << tb) + ((1u << tb) >> NTT_PAD_SHIFT); }
 __device__ __forceinline__ unsigned lds_phys(unsigned loc) { return loc + (loc >> NTT_PAD_SHIFT); }
@@ -414,6 +418,7 @@ struct ArithU64 {
         return shoup_lazy(final_fwd(v, m), m.ninv_op, m.ninv_quo, m.q);   // the reference's lazy N^-1 multiply
     }
     static __device__ __forceinline__ void inv_fold(elem&, elem&, const Mod&) {}   // FOLD_NINV is false: never used
+    static __device__ __forceinline__ elem held_t(elem x, bool, const Mod&) { return x; }   // held T rows are an FP64 form (REGIO 3): never used
     // register hand-over between a forward and an inverse transform (tensor_core_kernel): canonical residues
     static __device__ __forceinline__ elem keep(elem x, const Mod& m) { return final_fwd(x, m); }
     static __device__ __forceinline__ elem prod(elem x, elem y, const Mod& m) {
@@ -540,6 +545,12 @@ struct ArithF64 {
         const double t = x_canon + 0.5 * (m.m.p - 1.0);
         return t >= m.m.p ? t - m.m.p : t;
     }
+    // T of the last inverse round's word for a row that stays in registers (ntt_pass_body REGIO 3): final_inv (scaled: the folded layer applied
+    // N^-1 already) and round_half without the u64 round trip -- the canonical value in [0, p) is an exact double either way
+    static __device__ __forceinline__ double held_t(elem x, bool scaled, const Mod& m) {
+        const double c = f64_corr(scaled ? x : f64_mulc(x, m.ninv, m.ninv_p, m.m.p), m.m);
+        return round_half(c < 0.0 ? c + m.m.p : c, m);
+    }
     static __device__ __forceinline__ elem round_fix_t(u64 t_bits, double hm, const Mod& m) { return f64_corr(f64_bits_to_double(t_bits) - hm, m.m); }
     // the same for a T row that may hold u64 words of a prime of 2^50 or more (NTT_FUSED_*_W): T < 2^61 = hi 2^30 + lo, hi 2^30 is exact in a
     // double, so (hi 2^30 mod p) comes out of one quotient estimate and one exact fma; |.| <= p/2 + 2^30 before the constant is subtracted
@@ -628,6 +639,10 @@ __host__ __device__ constexpr bool ROUNDS_OK(int G, int EB) { return (G + EB - 1
 
 // REGIO (tensor_core_kernel): 1 = a forward last pass leaves its E consecutive outputs per thread in xio (A::keep form) instead of
 // storing them, 2 = an inverse first pass takes its E consecutive inputs per thread from xio (A::inv_in form) instead of loading them.
+// REGIO 3 / 4 (mrr_tail_kernel, troyn_mrr_tail.hip; FP64 policy, whole-limb tiles): the rows T_s = (s + qk/2) mod qk and T_l = (l + ql/2) mod ql
+// of the fused chain stay in xio[0, E) / xio[E, 2E) instead of passing through memory -- the last inverse round and the first forward round
+// keep the same E words {t + R 2^(TB-EB)} per thread.  3 = an inverse transform ends in xio (IOM 0: T_s; NTT_FUSED_LAST_LIMB: reads T_s, leaves
+// T_l), 4 = NTT_FUSED_TAIL_RESCALE takes its input from both.  The values are the doubles the separate launches store and load.
 // HALF: the LDS tile holds 32-bit words (half the bytes): every exchange moves the low halves, then the high halves of its E words
 // (three barriers instead of one).  A whole-limb N = 16384 tile then takes 66 KB instead of 132 KB and TWO 1024-thread workgroups
 // share a CU, so one can load / store while the other computes -- what N = 8192 gets for free.
@@ -635,7 +650,10 @@ template <class A, int LOGN, int LO, int G, int TB, int EB, bool INV, bool FIRST
 __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* keys, u64* lds, unsigned bid, unsigned t, typename A::elem* xio = nullptr) {
     constexpr int C = TB - G;
     static_assert(!HALF || (!KSMAC && REGIO == 0), "half-word LDS tiles: plain and fused transform kernels only");
-    static_assert(REGIO == 0 || (!KSMAC && IOM == 0 && C == 0 && (G + EB - 1) / EB > 1 && (REGIO == 1 ? (!INV && LAST) : (INV && FIRST))), "register hand-over: last forward / first inverse pass on whole tiles");
+    static_assert(REGIO == 0 || REGIO >= 3 || (!KSMAC && IOM == 0 && C == 0 && (G + EB - 1) / EB > 1 && (REGIO == 1 ? (!INV && LAST) : (INV && FIRST))), "register hand-over: last forward / first inverse pass on whole tiles");
+    static_assert(REGIO < 3 || (std::is_same<A, ArithF64>::value && !KSMAC && !HALF && C == 0 && LO == 0 && G == TB && TB == LOGN && (G + EB - 1) / EB > 1 &&
+                                (REGIO == 3 ? (INV && (IOM == 0 || IOM == NTT_FUSED_LAST_LIMB)) : (REGIO == 4 && !INV && IOM == NTT_FUSED_TAIL_RESCALE))),
+                  "held T rows: whole-limb FP64 transforms of the merged chain tail");
     constexpr int E = 1 << EB;
     constexpr unsigned N = 1u << LOGN;
     constexpr int TILE_BITS = LOGN - TB;               // tiles per limb-polynomial = 2^TILE_BITS
@@ -822,6 +840,13 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
         if constexpr (REGIO == 2 && r == 0) {
             static_assert(r != 0 || REGIO != 2 || S == 0, "register hand-over: E consecutive coefficients per thread");
             static_for<0, E>([&](auto Rc) { x[decltype(Rc)::value] = xio[decltype(Rc)::value]; });
+        } else if constexpr (REGIO == 4 && r == 0) {
+            // r_j(s) qk^-1 + f_j(l) from the held T_s, T_l (exact doubles: the bit pattern NTT_FUSED_TAIL_RESCALE's loader reads from the rows)
+            static_assert(r != 0 || REGIO != 4 || S == TB - EB, "held T rows: the first forward round keeps the words the last inverse round left");
+            static_for<0, E>([&](auto Rc) {
+                constexpr int R = decltype(Rc)::value;
+                x[R] = A::template tail_in<false>(io, f64_double_to_bits(xio[R]), f64_double_to_bits(xio[E + R]), md);
+            });
         } else if constexpr (r == 0 && INV && S == 0 && C == 0 && ROUNDS > 1) {
             // Mirror image of the forward store transpose: a thread starts with E consecutive coefficients.  Loading
             // them directly makes every load instruction touch 64 different 128-byte lines; instead the wave loads
@@ -921,6 +946,17 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
             }
         }
 
+        // merged chain tail (REGIO 4): one workgroup per CU, so nobody else keeps memory busy while this one computes -- the epilogue's operand
+        // Q_j is requested in a rolling window of QW 16-byte pairs: the first QW ahead of the last round's butterflies, one more per pair consumed
+        constexpr int QW = (REGIO == 4 && r == ROUNDS - 1) ? TROYN_MRR_TAIL_WINDOW : 0;
+        ulonglong2 pq[QW > 0 ? E / 2 : 1];
+        auto request_q = [&](auto mc) {
+            constexpr int m = decltype(mc)::value;
+            pq[m] = ld2_at(io.ext0, (gindex((t >> 6) * (64u * E)) + m * 128u + (t & 63u) * 2u) * 8u, true);
+        };
+        (void)request_q;
+        if constexpr (QW > 0) static_for<0, QW>(request_q);
+
         constexpr int NLAYERS = BHI - BLO + 1;
         unsigned tw_dep = 0;      // see below
         static_for<0, NLAYERS>([&](auto lc) {
@@ -967,6 +1003,16 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
         if constexpr (REGIO == 1 && r == ROUNDS - 1) {
             static_assert(r != ROUNDS - 1 || REGIO != 1 || S == 0, "register hand-over: E consecutive coefficients per thread");
             static_for<0, E>([&](auto Rc) { xio[decltype(Rc)::value] = A::keep(x[decltype(Rc)::value], md); });
+        } else if constexpr (REGIO == 3 && r == ROUNDS - 1) {
+            static_assert(r != ROUNDS - 1 || REGIO != 3 || S == TB - EB, "held T rows: the last inverse round leaves the words the first forward round keeps");
+            static_for<0, E>([&](auto Rc) {
+                constexpr int R = decltype(Rc)::value;
+                constexpr bool scaled = A::FOLD_NINV && ((R >> (EB - 1)) & 1);      // the folded final layer applied N^-1 already
+                // T_l from the held T_s (the epilogue of NTT_FUSED_LAST_LIMB), or T_s itself (NTT_FLAG_STORE_ROUND_HALF's epilogue; the canonical
+                // value stays a double: 0 <= . < p < 2^50, exact)
+                if constexpr (F_LAST_ST) xio[E + R] = f64_bits_to_double(A::template last_out<false>(io, x[R], scaled, f64_double_to_bits(xio[R]), md));
+                else xio[R] = A::held_t(x[R], scaled, md);
+            });
         } else if constexpr (KSMAC && r == ROUNDS - 1) {
             // transpose inside the wave's own LDS slice (see the store path below), then multiply-accumulate with
             // 16-byte coalesced key loads
@@ -1060,7 +1106,11 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
                     // (Q_kj - y) ql^-1 with Q_kj = P_j qk^-1 + c_kj as ksmac2 left it: relinearize's divide-and-add happened there, the
                     // rescale's divide happens here
                     const unsigned boff = (gbase + idx) * 8u;
-                    const ulonglong2 pr = ld2_at(io.ext0, boff, true);
+                    ulonglong2 pr;
+                    if constexpr (QW > 0) {
+                        pr = pq[m];
+                        if constexpr (m + QW < E / 2) request_q(std::integral_constant<int, m + QW>{});
+                    } else pr = ld2_at(io.ext0, boff, true);
                     v0 = A::tail_out(io, pr.x, A::from_lds(v0), md);
                     v1 = A::tail_out(io, pr.y, A::from_lds(v1), md);
                 }

@@ -1608,6 +1608,25 @@ static int mrr_chain(const troyn_plan* p, uint32_t L, const u64* a, const u64* b
         LAUNCH_CHECK();
         return TROYN_OK;
     }
+    // N = 16384, batches that fill the chip (whole-limb tiles): steps (3)-(5) below as ONE launch, one workgroup per (item, polynomial) with T_s
+    // and T_l in registers (troyn_mrr_tail.hip) -- the spec_intt / last_intt rows are not touched.  TROYN_MRR_SMALL=0 keeps the three launches.
+    if (all_f64 && p->log_n == 14 && !p->opt.mrr_small_off) {
+        auto prep = [&](NttArgs& x, bool inverse) {
+            x.mods = p->d_mods; x.stream_loads = 1u; x.xcd_groups = 0u;
+            x.tw = inverse ? (const void*)p->d_inv_f64 : (const void*)p->d_fwd_f64;
+        };
+        NttArgs sp = contiguous_args(p, ws + w.poly_prod + (size_t)L * n, nullptr, 2, 1, K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
+        sp.in_pstride = pp_p; sp.in_bstride = pp_b;
+        sp.flags = NTT_FLAG_STORE_ROUND_HALF;
+        prep(sp, true);
+        NttArgs la = last_args();
+        prep(la, true);
+        NttArgs ta = tail_args(0, L - 1);
+        prep(ta, false);
+        launch_mrr_tail(p->log_n, batch, sp, la, ta, s);
+        LAUNCH_CHECK();
+        return TROYN_OK;
+    }
     // (3) s = INTT of the special-prime rows (:991-996, only the two rows the NTT-form tail needs)
     {
         NttArgs x = contiguous_args(p, ws + w.poly_prod + (size_t)L * n, ws + w.spec_intt, 2, 1, K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
