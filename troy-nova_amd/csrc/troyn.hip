@@ -611,6 +611,43 @@ static bool use_f64(const troyn_plan* p, unsigned table_start, unsigned table_co
     return f64;
 }
 
+static inline const void* twiddles(const troyn_plan* p, bool f64, bool inverse) {
+    if (f64) return inverse ? (const void*)p->d_inv_f64 : (const void*)p->d_fwd_f64;
+    return inverse ? (const void*)p->d_inv : (const void*)p->d_fwd;
+}
+// what launch_ntt sets, for the launches of one arithmetic class that bypass it (inputs read once, no XCD grouping)
+static inline void prep_direct(const troyn_plan* p, NttArgs& x, bool f64, bool inverse) {
+    x.mods = p->d_mods; x.stream_loads = 1u; x.xcd_groups = 0u;
+    x.tw = twiddles(p, f64, inverse);
+}
+// `next` reads what `prev` wrote (next may be prev itself: a second pass in place in its own output)
+static inline void as_input_of(NttArgs& next, const NttArgs& prev) {
+    next.in = prev.out; next.in_bstride = prev.out_bstride; next.in_pstride = prev.out_pstride; next.in_cstride = prev.out_cstride;
+}
+
+// The two notions of a limb's arithmetic class.  by_table: the modulus is below 2^50 (its FP64 twiddles exist); by_policy: it takes the FP64
+// kernels now (also TROYN_NTT_ARITH=u64 and log_n >= 10).  They differ under TROYN_NTT_ARITH=u64: a by_table split of {60,40,40,60} still
+// issues one launch per run, each on the integer kernels.
+static inline bool class_by_table(const troyn_plan* p, unsigned mi) { return p->small_modulus[mi] != 0; }
+static inline bool class_by_policy(const troyn_plan* p, unsigned mi) { return use_f64(p, mi, 1); }
+template <typename Cls>
+static inline bool one_class(const troyn_plan* p, unsigned table_start, unsigned count, Cls cls) {
+    for (unsigned j = 1; j < count; j++) if (cls(p, table_start + j) != cls(p, table_start)) return false;
+    return true;
+}
+// f(j0, j1, stream) once per run [j0, j1) of consecutive limbs of one class inside [table_start, table_start + count), j relative to table_start.
+// overlap: runs of different classes in flight together (RunOverlap above; forked and joined here, also when f fails); a launch that is one
+// run stays on the caller's stream.
+template <typename Cls, typename F>
+static int for_class_runs(const troyn_plan* p, unsigned table_start, unsigned count, Cls cls, bool overlap, hipStream_t s, F&& f) {
+    RunOverlap ov(p, s, overlap);
+    for (unsigned j0 = 0, j1; j0 < count; j0 = j1) {
+        for (j1 = j0 + 1; j1 < count && cls(p, table_start + j1) == cls(p, table_start + j0); j1++) {}
+        if (int rc = f(j0, j1, (j0 == 0 && j1 == count) ? s : ov.next())) return rc;
+    }
+    return ov.join();
+}
+
 static int launch_ntt(const troyn_plan* p, NttArgs a, size_t batch, bool inverse, hipStream_t s, u64* two_pass_scratch = nullptr) {
     a.mods = p->d_mods;
     // inputs shared by several limb-polynomials of the launch (stride 0) should stay cached
@@ -638,14 +675,8 @@ static int launch_ntt(const troyn_plan* p, NttArgs a, size_t batch, bool inverse
         // default at N <= 8192.  N >= 16384 (round 5): the integer kernels are one 1024-thread workgroup per CU (whole-limb tiles) or two strided
         // passes, the FP64 ones run on half-word tiles: {60,50,50,50,50,60} key-switch tail 835 us unsplit for 512 items, i.e. 163 ns per row
         // against 83 ns -- split by default (TROYN_NTT_SPLIT=0: one integer launch).
-        bool mixed = false;
-        for (unsigned j = 1; j < a.ncomp && !mixed; j++) mixed = p->small_modulus[a.table_start + j] != p->small_modulus[a.table_start];
-        if (mixed) {
-            RunOverlap ov(p, s, lp >= OVERLAP_MIN_LIMB_POLYS);
-            unsigned j0 = 0;
-            while (j0 < a.ncomp) {
-                unsigned j1 = j0 + 1;
-                while (j1 < a.ncomp && p->small_modulus[a.table_start + j1] == p->small_modulus[a.table_start + j0]) j1++;
+        if (!one_class(p, a.table_start, a.ncomp, class_by_table))
+            return for_class_runs(p, a.table_start, a.ncomp, class_by_table, lp >= OVERLAP_MIN_LIMB_POLYS, s, [&](unsigned j0, unsigned j1, hipStream_t rs) {
                 NttArgs r = a;
                 r.in = a.in + (long long)j0 * a.in_cstride; r.out = a.out + (long long)j0 * a.out_cstride;
                 r.ncomp = j1 - j0; r.table_start = a.table_start + j0; r.table_count = j1 - j0;
@@ -654,22 +685,14 @@ static int launch_ntt(const troyn_plan* p, NttArgs a, size_t batch, bool inverse
                 if (a.inv_table) r.inv_table = a.inv_table + j0;
                 // (two-pass sizes: every run keeps its own part of the scratch -- the runs may be in flight together)
                 u64* run_scratch = two_pass_scratch ? two_pass_scratch + batch * (size_t)a.pcount * j0 * p->n : nullptr;
-                if (int rc = launch_ntt(p, r, batch, inverse, ov.next(), run_scratch)) return rc;
-                j0 = j1;
-            }
-            return ov.join();
-        }
+                return launch_ntt(p, r, batch, inverse, rs, run_scratch);
+            });
     }
-    bool done;
-    if (f64) {
-        a.tw = inverse ? (const void*)p->d_inv_f64 : (const void*)p->d_fwd_f64;
-        done = launch_ntt_f64(p->log_n, a, lp, inverse, launch_ctx(p, s), two_pass_scratch);
-    } else {
-        a.tw = inverse ? (const void*)p->d_inv : (const void*)p->d_fwd;
-        done = launch_ntt_u64(p->log_n, a, lp, inverse, launch_ctx(p, s), two_pass_scratch);
-    }
+    a.tw = twiddles(p, f64, inverse);
+    const bool done = f64 ? launch_ntt_f64(p->log_n, a, lp, inverse, launch_ctx(p, s), two_pass_scratch)
+                          : launch_ntt_u64(p->log_n, a, lp, inverse, launch_ctx(p, s), two_pass_scratch);
     if (!done) {
-        a.tw = inverse ? (const void*)p->d_inv : (const void*)p->d_fwd;
+        a.tw = twiddles(p, false, inverse);
         launch_ntt_generic(a, p->log_n, inverse, lp, launch_ctx(p, s));
     }
     LAUNCH_CHECK();
@@ -686,34 +709,28 @@ static int tensor_path_kind(const troyn_plan* p, unsigned ncomp) {
     // 16 coefficients per thread under the 128-register cap of a 1024-thread workgroup only with 78-93 spilled registers, and is
     // still 8 % faster than the separate launches (83.8 k vs 77.2 k products/s at 6 x 50-bit)
     if (p->log_n >= 10 && p->log_n <= 14) return 1;
-    for (unsigned j = 1; j < ncomp; j++) if (p->small_modulus[j] != p->small_modulus[0]) return 0;
+    if (!one_class(p, 0, ncomp, class_by_table)) return 0;
     if (p->log_n == 15 || p->log_n == 16) return 2;
     return 0;
 }
-static int tensor_stage(const troyn_plan* p, int stage, NttArgs a, NttArgs b, NttArgs d, size_t batch, hipStream_t s) {
-    // limbs of both arithmetic classes ({60,40,40,60}): one launch per run of limbs of one class (limbs are independent)
-    for (unsigned j0 = 0, j1; j0 < a.ncomp; j0 = j1) {
-        for (j1 = j0 + 1; j1 < a.ncomp && p->small_modulus[a.table_start + j1] == p->small_modulus[a.table_start + j0]; j1++) {}
-        if (j0 == 0 && j1 == a.ncomp) break;   // one class: fall through to the single launch
-        auto sub = [&](NttArgs x) {
-            x.in += (long long)j0 * x.in_cstride; if (x.out) x.out += (long long)j0 * x.out_cstride;
-            x.ncomp = j1 - j0; x.table_start += j0; x.table_count = j1 - j0;
-            return x;
-        };
-        if (int rc = tensor_stage(p, stage, sub(a), sub(b), sub(d), batch, s)) return rc;
-        if (j1 == a.ncomp) return TROYN_OK;
+// one launch: limbs [j0, j1) of a, b, d, all of one class
+static int tensor_stage_run(const troyn_plan* p, int stage, NttArgs a, NttArgs b, NttArgs d, unsigned j0, unsigned j1, size_t batch, hipStream_t s) {
+    for (NttArgs* x : {&a, &b, &d}) {
+        x->in += (long long)j0 * x->in_cstride; if (x->out) x->out += (long long)j0 * x->out_cstride;
+        x->ncomp = j1 - j0; x->table_start += j0; x->table_count = j1 - j0;
     }
     const bool f64 = use_f64(p, a.table_start, a.ncomp);
-    auto prep = [&](NttArgs& x, bool inverse) {
-        x.mods = p->d_mods; x.stream_loads = 1u; x.xcd_groups = 0u;
-        x.tw = f64 ? (inverse ? (const void*)p->d_inv_f64 : (const void*)p->d_fwd_f64) : (inverse ? (const void*)p->d_inv : (const void*)p->d_fwd);
-    };
-    prep(a, stage == 2); prep(b, false); prep(d, true);
+    prep_direct(p, a, f64, stage == 2); prep_direct(p, b, f64, false); prep_direct(p, d, f64, true);
     if ((batch * a.pcount * a.ncomp) << (p->log_n > 12 ? p->log_n - 12 : 0) > 0x7fffffffull) return fail(TROYN_E_INVALID, "[troyn_ntt] batch too large for one launch");
     if (!(f64 ? launch_tensor_f64(p->log_n, stage, a, b, d, batch, launch_ctx(p, s)) : launch_tensor_u64(p->log_n, stage, a, b, d, batch, launch_ctx(p, s))))
         return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] no fused tensor kernel for this size");
     LAUNCH_CHECK();
     return TROYN_OK;
+}
+static int tensor_stage(const troyn_plan* p, int stage, const NttArgs& a, const NttArgs& b, const NttArgs& d, size_t batch, hipStream_t s) {
+    // limbs of both arithmetic classes ({60,40,40,60}): one launch per run of limbs of one class (limbs are independent), one after the other
+    return for_class_runs(p, a.table_start, a.ncomp, class_by_table, false, s,
+                          [&](unsigned j0, unsigned j1, hipStream_t rs) { return tensor_stage_run(p, stage, a, b, d, j0, j1, batch, rs); });
 }
 
 static NttArgs contiguous_args(const troyn_plan* p, const u64* in, u64* out, size_t pcount, size_t ncomp,
@@ -920,26 +937,22 @@ static bool small_tail_wanted(const troyn_plan* p, size_t limb_polys) {
 }
 static int small_tail(const troyn_plan* p, bool f64, NttArgs pa, size_t pa_limb_polys, NttArgs fw, u64* between, size_t groups, hipStream_t s) {
     const LaunchCtx lc = launch_ctx(p, s);
-    auto prep = [&](NttArgs& x, bool inverse) {
-        x.mods = p->d_mods; x.stream_loads = 1u; x.xcd_groups = 0u;
-        x.tw = f64 ? (inverse ? (const void*)p->d_inv_f64 : (const void*)p->d_fwd_f64) : (inverse ? (const void*)p->d_inv : (const void*)p->d_fwd);
-    };
     auto pass = [&](int which, const NttArgs& x, size_t lp) {
         if (f64) launch_ntt_f64_small_pass(p->log_n, which, x, lp, lc); else launch_ntt_u64_small_pass(p->log_n, which, x, lp, lc);
     };
-    prep(pa, true);
+    prep_direct(p, pa, f64, true);
     pass(0, pa, pa_limb_polys);
     LAUNCH_CHECK();
     NttArgs iv = pa;
-    iv.in = pa.out; iv.in_bstride = pa.out_bstride; iv.in_pstride = pa.out_pstride; iv.in_cstride = pa.out_cstride;
-    prep(fw, false);
+    as_input_of(iv, pa);
+    prep_direct(p, fw, f64, false);
     NttArgs first = fw;                 // the pass in between: [group][limb][N], contiguous (the layout launch_two_pass gives a scratch buffer)
     const long long N = (long long)p->n;
     first.out = between; first.out_cstride = N; first.out_pstride = (long long)fw.ncomp * N; first.out_bstride = (long long)fw.pcount * fw.ncomp * N;
     launch_mrr_quartet_load(p->log_n, groups, iv, first, s, f64);
     LAUNCH_CHECK();
     NttArgs second = fw;
-    second.in = first.out; second.in_bstride = first.out_bstride; second.in_pstride = first.out_pstride; second.in_cstride = first.out_cstride;
+    as_input_of(second, first);
     second.reduce_input = 0;
     pass(1, second, groups * fw.ncomp);
     LAUNCH_CHECK();
@@ -961,12 +974,90 @@ static bool ks_small_mixed(const troyn_plan* p, unsigned L, size_t batch) {
     return (batch * (size_t)(L + 1) << (p->log_n - 13)) <= (p->log_n == 13 ? 384u : 256u);      // (N = 8192: equal at ~400, 96 items of {60,40,40,60})
 }
 
+// Output rows k = 0 .. L of the inner product (row L: the special prime) by arithmetic class, as bit masks; wide_digits: some digit limb is 2^50
+// or wider.  Computed ONCE per call and passed down: key preparation and launch must agree on the rows.
+struct KsRows { unsigned long long small, wide; bool wide_digits; };
+static KsRows ks_rows(const troyn_plan* p, unsigned L) {
+    KsRows r{0, 0, false};
+    for (unsigned k = 0; k <= L; k++) {
+        const bool f64 = class_by_policy(p, k == L ? p->K - 1 : k);
+        (f64 ? r.small : r.wide) |= 1ull << k;
+        if (k < L && !f64) r.wide_digits = true;
+    }
+    return r;
+}
+
+// Argument blocks of the second-generation inner products, what every caller shares; call sites add diag*, ten_*, row_mask / no_load_corr and the
+// digit-parallel part / raw fields.
+static KsMacArgs ksmac2_args(const troyn_plan* p, unsigned L, size_t batch, const u64* digits, long long dig_bstride, u64* poly_prod, const double* keys) {
+    const unsigned K = p->K, n = p->n;
+    KsMacArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.digits = digits; a.dig_bstride = dig_bstride; a.dig_cstride = n;
+    a.out = poly_prod; a.out_bstride = 2ll * (L + 1) * n; a.out_pstride = (long long)(L + 1) * n; a.out_cstride = n;
+    a.mods = p->d_mods; a.tw = p->d_fwd_f64; a.tw_r1 = p->d_fwd_r1; a.tw_r2 = p->d_fwd_r2;
+    a.keys = keys; a.key_jstride = 2ll * K * n; a.key_pstride = (long long)K * n;
+    a.L = L; a.table_start = 0; a.table_count = K; a.batch = (unsigned)batch;
+    a.grouped = ksmac_order(p, batch, p->log_n);
+    return a;
+}
+// rows: the rows of moduli >= 2^50 (KsRows::wide, never 0); keys: their (key, quotient) pairs [L][2][slots][N], then the diagonal blocks [slots][2][N]
+static KsMacIArgs ksmaci_args(const troyn_plan* p, unsigned L, size_t batch, const u64* digits, long long dig_bstride, u64* poly_prod, const ulonglong2* keys,
+                              unsigned long long rows) {
+    const unsigned K = p->K, n = p->n, slots = (unsigned)__builtin_popcountll(rows);
+    KsMacIArgs m;
+    std::memset(&m, 0, sizeof(m));
+    m.digits = digits; m.dig_bstride = dig_bstride; m.dig_cstride = n;
+    m.out = poly_prod; m.out_bstride = 2ll * (L + 1) * n; m.out_pstride = (long long)(L + 1) * n; m.out_cstride = n;
+    m.mods = p->d_mods; m.tw = p->d_fwd; m.tw_r1 = p->d_fwd_r1i; m.tw_r2 = p->d_fwd_r2i;
+    m.keys = keys; m.key_jstride = 2ll * slots * n; m.key_pstride = (long long)slots * n;
+    m.diag_keys = keys + (size_t)L * 2 * slots * n;
+    m.L = L; m.table_start = 0; m.table_count = K; m.batch = (unsigned)batch;
+    m.grouped = (batch % 8 == 0 && p->opt.ks_order != 0) ? 1u : 0u;
+    m.row_mask = rows;
+    return m;
+}
+// Keys of ksmac2_kernel, once per call: exact doubles in the accumulators' layout [L][2][K][N]; want_diag: the block (key j, modulus j) a second
+// time in natural order behind them (DG / TEN epilogues).  scale_rows != 0 (fused chain): the rows r < scale_rows carry the factor qk^-1 mod q_r.
+static int prepare_keys_f64(const troyn_plan* p, const KeyPtrs& kp, unsigned L, double* kf, unsigned scale_rows, bool want_diag, hipStream_t s) {
+    const unsigned K = p->K, n = p->n;
+    const size_t pairs = (size_t)L * 2 * K * (n / 2);
+    launch_ksmac_prepare_keys(kp, L, 2 * K, n, kf, (unsigned)std::min<size_t>((pairs + 255) / 256, 4096), s,
+                              scale_rows ? p->d_inv_last + (size_t)K * K : nullptr, scale_rows ? p->d_mods : nullptr, scale_rows,
+                              want_diag ? kf + (size_t)L * 2 * K * n : nullptr);
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+// Keys of ksmaci_kernel, once per call: (key, Shoup quotient) pairs of exactly the rows in `rows`, in the accumulators' layout; want_diag: their
+// diagonal blocks in natural order behind them.  scale_rows as above.
+static int prepare_keys_int(const troyn_plan* p, const KeyPtrs& kp, unsigned L, unsigned long long rows, ulonglong2* ki, unsigned scale_rows, bool want_diag,
+                            hipStream_t s) {
+    const unsigned K = p->K, n = p->n;
+    const size_t words = (size_t)L * 2 * (unsigned)__builtin_popcountll(rows) * n;
+    launch_ksmaci_prepare_keys(kp, L, K, n, rows, ki, (unsigned)std::min<size_t>((words + 255) / 256, 4096), s,
+                               scale_rows ? p->d_inv_last + (size_t)K * K : nullptr, p->d_mods, scale_rows, want_diag ? ki + words : nullptr);
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+// INTT of the two special-prime rows of poly_prod [item][2][L+1][N] into dst [item][2][N]
+static NttArgs special_rows_args(const troyn_plan* p, const u64* poly_prod, u64* dst, unsigned L) {
+    const unsigned n = p->n;
+    NttArgs a = contiguous_args(p, poly_prod + (size_t)L * n, dst, 2, 1, p->K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
+    a.in_pstride = (long long)(L + 1) * n; a.in_bstride = 2ll * (L + 1) * n;
+    return a;
+}
+
+// (N >= 8192: the half-tile kernels, whose grid is up to 4 (L + 2) workgroups per item; the first-generation whole-limb kernel stays the path
+// of N = 1024 .. 4096 -- its N = 8192 / 16384 instantiations left the library in round 5)
+static int ks_mac_generation(const troyn_plan* p) { return p->log_n >= 13 ? 2 : 1; }
+
 struct KsLayout {
     size_t target_intt, temp_ntt, poly_prod, prod_intt, temp_last, keys_f64, split, keys_quo, total;  // element offsets
 };
 
 static KsLayout ks_layout(const troyn_plan* p, unsigned L, size_t batch) {
     const size_t n = p->n;
+    const bool gen2 = ks_mac_generation(p) == 2;
     KsLayout w;
     size_t off = 0;
     w.target_intt = off; off += batch * L * n;
@@ -978,7 +1069,7 @@ static KsLayout ks_layout(const troyn_plan* p, unsigned L, size_t batch) {
     w.split = off;       off += ks_split_words(p, batch, L, p->log_n);                        // slots of the digit-parallel inner product (small batches)
     // Shoup quotients of the keys for the integer inner product: chains with a modulus of 2^50 or more on the whole-limb sizes
     // (N >= 8192: (key, quotient) pairs of the wide rows in the accumulators' layout + the diagonal blocks in natural order, ksmaci_kernel)
-    w.keys_quo = off;    off += (p->log_n >= 10 && p->log_n <= 15 && !use_f64(p, 0, p->K)) ? (size_t)L * 2 * p->K * n * (p->log_n >= 13 ? 2 : 1) + (p->log_n >= 13 ? (size_t)p->K * 2 * n * 2 : 0) : 0;
+    w.keys_quo = off;    off += (p->log_n >= 10 && p->log_n <= 15 && !use_f64(p, 0, p->K)) ? (size_t)L * 2 * p->K * n * (gen2 ? 2 : 1) + (gen2 ? (size_t)p->K * 2 * n * 2 : 0) : 0;
     w.total = off;
     return w;
 }
@@ -994,14 +1085,276 @@ extern "C" size_t troyn_relinearize_workspace_bytes(const troyn_plan* plan, uint
 // BGV divides by the special prime with a correction computed mod t (ski_util5); everything before the tail is shared.
 struct BgvTail { DevModulus t; u64 inv_special_mod_t; };
 
-// target: [batch] items of L limbs, `target_bstride` elements apart.
 static bool coeff_tail_fused(const troyn_plan* p) { return !p->opt.ks_tail_split; }   // TROYN_KS_TAIL=split: inverse transforms and ski_util7 in separate launches
+
+// The launches a key switch of one shape takes, decided ONCE per call; the steps below only read it, and ks_layout provisions from the same
+// predicates (ks_split_words, ks_mac_generation).  Inner product: ksmac2 for every row | ksmac2<WIDE> + ksmaci | ks_mac_kernel | two launches.
+enum KsMacForm { KS_MAC_F64, KS_MAC_MIXED, KS_MAC_GEN1, KS_MAC_TWO_LAUNCH };
+enum KsTailForm { KS_TAIL_SMALL, KS_TAIL_NTT_FUSED, KS_TAIL_COEFF_FUSED, KS_TAIL_UNFUSED };
+struct KsPath {
+    bool fused;         // the optimised NTT kernels carry fused prologues / epilogues; tiny rings (generic kernel) and BGV use the unfused chain
+    KsMacForm mac;
+    bool dg;            // NTT-form target: the diagonal digit is applied in ksmac2's epilogue (DG), from the block (key j, modulus j) in natural order
+    bool split;         // the digit-parallel form of ksmac2 (small launches)
+    KsTailForm tail;
+};
+static KsPath ks_path(const troyn_plan* p, unsigned L, size_t batch, bool is_ntt_form, bool bgv) {
+    KsPath k;
+    k.fused = is_ntt_form && p->log_n >= 10 && !bgv;
+    const bool two_launch = p->opt.ks_mac_split || ks_small_mixed(p, L, batch);
+    // (2)+(3) in ONE launch for whole-limb rings (N <= 16384): every workgroup owns one output row of one item,
+    //     transforms that row's L digits one after the other and multiplies them into register accumulators with
+    //     the key (kernel_set_accumulate + ntt + kernel_accumulate_products, fgk/switch_key.cu:6-154); the
+    //     (L+1)*L transformed digits never reach HBM.
+    // (the band order pads an odd row count with one row of workgroups that exit: the grid guard counts L + 2 rows)
+    const bool one_launch = !two_launch && p->log_n >= 10 && p->log_n <= 15 && batch * (size_t)(L + 1) <= 0x7fffffffull &&
+                            (p->log_n <= 12 || (p->d_fwd_r2 && p->d_fwd_r2i && L + 1 <= 64 && batch * (size_t)(L + 2) * 4 <= 0x7fffffffull));
+    k.mac = !one_launch ? KS_MAC_TWO_LAUNCH : ks_mac_generation(p) == 1 ? KS_MAC_GEN1 : use_f64(p, 0, p->K) ? KS_MAC_F64 : KS_MAC_MIXED;
+    // The switch is read ONCE per call: the preparation and the instantiation choice must agree.
+    k.dg = is_ntt_form && !p->opt.ks_diag_loop;
+    // the digit-parallel form reads the caller's keys as they are, so its diagonal digit can only live in the epilogue
+    k.split = k.mac == KS_MAC_F64 && ksmac_split_wanted(p, batch, L, p->log_n) && (k.dg || !is_ntt_form);
+    if (k.fused) k.tail = small_tail_wanted(p, batch * 2 * L) ? KS_TAIL_SMALL : KS_TAIL_NTT_FUSED;
+    else k.tail = (!is_ntt_form && !bgv && p->log_n >= 10 && p->log_n <= 17 && coeff_tail_fused(p)) ? KS_TAIL_COEFF_FUSED : KS_TAIL_UNFUSED;
+    return k;
+}
+
+// one validated call; target: [batch] items of L limbs, `target_bstride` elements apart
+struct KsCall {
+    const troyn_plan* p; unsigned L; int is_ckks; bool is_ntt_form;
+    const u64* target; size_t target_bstride; int assign_method;
+    u64* dest; const u64* addend; size_t addend_bstride;
+    u64* ws; KsLayout w; size_t batch; hipStream_t s; const BgvTail* bgv;
+    const u64* digits; size_t digits_bstride;      // the target in coefficient form: the caller's rows, or target_intt after ks_digits
+};
+
+// (1) NTT form: bring the target back to coefficient form (evaluator_keyswitching_core.cu:817-821)
+static int ks_digits(KsCall& c) {
+    if (!c.is_ntt_form) return TROYN_OK;
+    NttArgs a = contiguous_args(c.p, c.target, c.ws + c.w.target_intt, 1, c.L, 0, c.L, TROYN_IDX_COMPONENTWISE, 0);
+    a.in_bstride = (long long)c.target_bstride;
+    c.digits = c.ws + c.w.target_intt; c.digits_bstride = (size_t)c.L * c.p->n;
+    return launch_ntt(c.p, a, c.batch, true, c.s);
+}
+
+// ksmac2_kernel: tiles of 2^13 outputs, two workgroups per CU, keys prepared once per call (ksmac_kernels.hpp)
+static int ks_mac_f64(const KsCall& c, const KeyPtrs& kp, const KsPath& path) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    double* kf = reinterpret_cast<double*>(c.ws + c.w.keys_f64);
+    // the digit-parallel form (small launches) reads the caller's keys as they are: no preparation pass
+    if (!path.split) if (int rc = prepare_keys_f64(p, kp, L, kf, 0, path.dg, c.s)) return rc;
+    KsMacArgs a = ksmac2_args(p, L, c.batch, c.digits, (long long)c.digits_bstride, c.ws + c.w.poly_prod, kf);
+    a.diag = c.is_ntt_form ? c.target : nullptr; a.diag_bstride = (long long)c.target_bstride; a.diag_cstride = n;
+    if (path.dg) a.diag_keys = kf + (size_t)L * 2 * K * n;
+    {
+        TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, c.s);
+        if (path.split) {
+            a.grouped = 0;
+            a.part = reinterpret_cast<double*>(c.ws + c.w.split); a.part_jstride = (long long)c.batch * a.out_bstride;
+            a.split_skip_diag = path.dg ? 1u : 0u;
+            a.raw = kp; a.raw_pstride = (long long)K * n;
+            launch_ksmac2_split(p->log_n, c.batch, a, c.s, false, path.dg ? 2 : 0);
+        } else launch_ksmac2(p->log_n, c.batch, L + 1, a, c.s);
+    }
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+// A chain with moduli of 2^50 and more (the reference's default {60,40,40,60}; {60,50,...,60} CKKS chains): the output rows of the
+// moduli below 2^50 take ksmac2_kernel (exact FP64 butterflies; digits of wider limbs are reduced while loading), the rows of the wide
+// moduli the integer kernel of the same shape (ksmaci_kernel, N = 8192 / 16384 / 32768; round 5).  Rows are independent; results are
+// unchanged.  TROYN_NTT_ARITH=u64 sends every row to the integer kernel; N < 8192 keeps the first-generation kernel.
+static int ks_mac_mixed(const KsCall& c, const KeyPtrs& kp, const KsPath& path) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    const KsRows rows = ks_rows(p, L);
+    TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, c.s);
+    if (rows.small) {
+        double* kf = reinterpret_cast<double*>(c.ws + c.w.keys_f64);
+        // NTT-form target: the diagonal digit in the epilogue (DG) as in the all-FP64 path -- needs the diagonal key blocks in natural order
+        if (int rc = prepare_keys_f64(p, kp, L, kf, 0, path.dg, c.s)) return rc;
+        KsMacArgs m = ksmac2_args(p, L, c.batch, c.digits, (long long)c.digits_bstride, c.ws + c.w.poly_prod, kf);
+        m.diag = c.is_ntt_form ? c.target : nullptr; m.diag_bstride = (long long)c.target_bstride; m.diag_cstride = n;
+        if (path.dg) m.diag_keys = kf + (size_t)L * 2 * K * n;
+        m.row_mask = rows.small;
+        launch_ksmac2(p->log_n, c.batch, (unsigned)__builtin_popcountll(rows.small), m, c.s, false, rows.wide_digits);
+        LAUNCH_CHECK();
+    }
+    // (no wide row: every row this level touches is narrow although the chain holds a wide modulus elsewhere -- ksmac2 above took all of them)
+    if (rows.wide) {
+        // integer rows: (key, Shoup quotient) pairs of exactly these rows, in the accumulators' layout, once per call
+        ulonglong2* ki = reinterpret_cast<ulonglong2*>(c.ws + c.w.keys_quo);
+        if (int rc = prepare_keys_int(p, kp, L, rows.wide, ki, 0, c.is_ntt_form, c.s)) return rc;
+        KsMacIArgs m = ksmaci_args(p, L, c.batch, c.digits, (long long)c.digits_bstride, c.ws + c.w.poly_prod, ki, rows.wide);
+        m.diag = c.is_ntt_form ? c.target : nullptr; m.diag_bstride = (long long)c.target_bstride; m.diag_cstride = n;
+        launch_ksmaci(p->log_n, c.batch, m, c.s, c.is_ntt_form ? 1 : 0);
+        LAUNCH_CHECK();
+    }
+    return TROYN_OK;
+}
+// the first-generation kernel: one workgroup per output row of an item, either arithmetic class
+static int ks_mac_gen1(const KsCall& c, const KeyPtrs& kp) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, c.s);
+    NttArgs a = contiguous_args(p, c.digits, c.ws + c.w.poly_prod, 1, L + 1, 0, K, TROYN_IDX_KS_SET_PRODUCTS, L);
+    a.in_bstride = (long long)c.digits_bstride; a.in_pstride = 0; a.in_cstride = n;
+    a.out_bstride = 2ll * (L + 1) * n; a.out_pstride = (long long)(L + 1) * n; a.out_cstride = n;
+    a.reduce_input = 1;
+    a.stream_loads = 0;                      // the L+1 rows of an item re-read the same digits
+    a.skip_diag = c.is_ntt_form ? 1 : 0;     // digit k of row k is the NTT-form input limb itself
+    a.ext0 = c.target; a.ext0_bstride = (long long)c.target_bstride; a.ext0_cstride = n;
+    a.batch = (unsigned)c.batch; a.key_pstride = (long long)K * n;
+    // rows of an item co-scheduled per XCD: all L+1 by default (the item's digits are then fetched once per XCD instead of
+    // once per row; measured 1265 vs 1310 us per 512-item launch at cfg3), TROYN_KS_ROWS=1 restores plain row-major order
+    const unsigned R = p->opt.ks_rows > 0 ? (unsigned)p->opt.ks_rows : L + 1;
+    a.xcd_groups = (R > 1 && c.batch % 8 == 0 && (L + 1) % R == 0) ? R : 0u;
+    a.mods = p->d_mods;
+    const bool f64 = use_f64(p, 0, K);
+    a.tw = twiddles(p, f64, false);
+    if (!f64 && !p->opt.ks_mac_shoup_off) {
+        // integer policy: the keys' Shoup quotients, once per call (TROYN_KS_MAC_SHOUP=0: Barrett-128 terms as in rounds 1-3; A/B, tests)
+        u64* kq = c.ws + c.w.keys_quo;
+        const size_t words = (size_t)L * 2 * K * n;
+        hipLaunchKernelGGL(ks_key_quotients_kernel, dim3((unsigned)std::min<size_t>((words + 255) / 256, 4096)), dim3(256), 0, c.s, kp, L, K, n, p->d_mods, kq);
+        LAUNCH_CHECK();
+        a.key_quo = kq; a.key_quo_jstride = 2ll * K * n;
+    }
+    if (f64) launch_ks_mac_f64(p->log_n, a, kp, c.batch * (size_t)(L + 1), launch_ctx(p, c.s));
+    else launch_ks_mac_u64(p->log_n, a, kp, c.batch * (size_t)(L + 1), launch_ctx(p, c.s));
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+static int ks_mac_two_launch(const KsCall& c, const KeyPtrs& kp, const KsPath& path) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    // (2) digit decomposition fused into the forward NTT (replaces kernel_set_accumulate, fgk/switch_key.cu:6-54,
+    //     + ntt_inplace_ps with key_switching_set_products, :907-908): row i = digits reduced mod q_key(i)
+    NttArgs a = contiguous_args(p, c.digits, c.ws + c.w.temp_ntt, L + 1, L, 0, K, TROYN_IDX_KS_SET_PRODUCTS, L);
+    a.in_bstride = (long long)c.digits_bstride;
+    a.in_pstride = 0;                 // every row re-reads the same L digits
+    a.reduce_input = 1;
+    a.skip_diag = path.fused ? 1 : 0; // row i, digit i is the NTT-form input itself: not recomputed
+    if (int rc = launch_ntt(p, a, c.batch, false, c.s)) return rc;
+    // (3) <digits, key> inner product (fgk/switch_key.cu:83-154)
+    const unsigned ch = chunks_pairs(n);
+    const size_t rows = c.batch * (L + 1);
+    if (int rc = check_rows(rows, ch)) return rc;
+    hipLaunchKernelGGL(ks_accumulate_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, c.s,
+                       ch, p->d_mods, K, L, n, c.ws + c.w.temp_ntt, kp, c.ws + c.w.poly_prod,
+                       path.fused ? c.target : (const u64*)nullptr, c.target_bstride);
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+// (2)+(3): poly_prod [item][2][L+1][N] = <digits, keys> in NTT form
+static int ks_inner_product(const KsCall& c, const KeyPtrs& kp, const KsPath& path) {
+    if (path.mac == KS_MAC_F64) return ks_mac_f64(c, kp, path);
+    if (path.mac == KS_MAC_MIXED) return ks_mac_mixed(c, kp, path);
+    return path.mac == KS_MAC_GEN1 ? ks_mac_gen1(c, kp) : ks_mac_two_launch(c, kp, path);
+}
+// (5)-(7) in ONE launch: the forward NTT reads the INTT'd special rows `src` [item][2][N] through the rounding-fix prologue (ski_util6_merged) and
+// finishes with the divide-by-special-prime / assign epilogue (ski_util7_merged)
+static NttArgs ks_ntt_tail_args(const KsCall& c, const u64* src) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    NttArgs a = contiguous_args(p, src, c.dest, 2, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
+    a.in_bstride = 2ll * n; a.in_pstride = n; a.in_cstride = 0;
+    a.load_mode = NTT_LOAD_KS_ROUND; a.aux_mod = K - 1;
+    a.store_mode = NTT_STORE_KS_FINISH;
+    a.flags = (c.is_ckks ? 1u : 0u) | ((unsigned)c.assign_method << 1);
+    a.ext0 = c.ws + c.w.poly_prod; a.ext0_bstride = 2ll * (L + 1) * n; a.ext0_pstride = (long long)(L + 1) * n; a.ext0_cstride = n;
+    a.ext1 = c.addend; a.ext1_bstride = (long long)c.addend_bstride; a.ext1_pstride = (long long)L * n; a.ext1_cstride = n;
+    a.inv_table = p->d_inv_last + (size_t)K * K;
+    return a;
+}
+// a few ciphertexts at N = 16384: first inverse pass of the special rows in place (nothing else reads them), then the strided passes of both
+// transforms as one launch (small_tail)
+static int ks_tail_small(const KsCall& c) {
+    const troyn_plan* p = c.p;
+    const bool tail_f64 = use_f64(p, 0, c.L) && use_f64(p, p->K - 1, 1);      // else both transforms on the integer kernels (small launches are not split by class)
+    u64* special = c.ws + c.w.poly_prod + (size_t)c.L * p->n;
+    NttArgs pa = special_rows_args(p, c.ws + c.w.poly_prod, special, c.L);
+    pa.out_pstride = pa.in_pstride; pa.out_bstride = pa.in_bstride;
+    return small_tail(p, tail_f64, pa, c.batch * 2, ks_ntt_tail_args(c, c.ws + c.w.prod_intt), c.ws + c.w.temp_last, c.batch * 2, c.s);
+}
+// (4) INTT of only the special-prime rows, the result stays in NTT form (:991-996); then (5)-(7) as one launch
+static int ks_tail_ntt_fused(const KsCall& c) {
+    u64* spec = c.ws + c.w.prod_intt;
+    if (int rc = launch_ntt(c.p, special_rows_args(c.p, c.ws + c.w.poly_prod, spec, c.L), c.batch, true, c.s)) return rc;
+    // N >= 32768 transforms in two passes: the pass in between goes to temp_last (unused on this path), never to dest
+    return launch_ntt(c.p, ks_ntt_tail_args(c, spec), c.batch, false, c.s, c.ws + c.w.temp_last);
+}
+// coefficient form: INTT of the two special-prime rows, then the INTT of the 2L data rows finishes the key switch in its epilogue
+// ((5) + (7), ski_util6_merged / ski_util7_merged) and writes the destination -- the INTT'd rows never reach HBM
+static int ks_tail_coeff_fused(const KsCall& c) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    u64* spec = c.ws + c.w.prod_intt;
+    if (int rc = launch_ntt(p, special_rows_args(p, c.ws + c.w.poly_prod, spec, L), c.batch, true, c.s)) return rc;
+    NttArgs f = contiguous_args(p, c.ws + c.w.poly_prod, c.dest, 2, L, 0, K, TROYN_IDX_COMPONENTWISE, 0);
+    f.in_pstride = (long long)(L + 1) * n; f.in_bstride = 2ll * (L + 1) * n;
+    f.load_mode = NTT_LOAD_KS_ROUND; f.aux_mod = K - 1;      // constants of the rounding fix (no forward prologue runs)
+    f.store_mode = NTT_STORE_KS_FINISH;
+    f.flags = (c.is_ckks ? 1u : 0u) | ((unsigned)c.assign_method << 1);
+    f.in2 = spec; f.in2_bstride = 2ll * n; f.in2_pstride = n;
+    f.ext0 = c.dest; f.ext0_bstride = 2ll * L * n; f.ext0_pstride = (long long)L * n; f.ext0_cstride = n;   // unused by this epilogue
+    f.ext1 = c.addend; f.ext1_bstride = (long long)c.addend_bstride; f.ext1_pstride = (long long)L * n; f.ext1_cstride = n;
+    f.inv_table = p->d_inv_last + (size_t)K * K;
+    // two-pass sizes: the pass in between goes to the free part of prod_intt, never to dest (AddInplace reads the old destination)
+    return launch_ntt(p, f, c.batch, true, c.s, spec + c.batch * 2 * (size_t)n);
+}
+// steps (4)-(7) as separate launches: tiny rings, BGV, TROYN_KS_TAIL=split
+static int ks_tail_unfused(const KsCall& c) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    const bool ntt = c.is_ntt_form;
+    const size_t batch = c.batch, rows = batch * 2 * L;
+    const unsigned ch = c.bgv ? chunks_single(n) : chunks_pairs(n);
+    hipStream_t s = c.s;
+    u64* prod_intt = c.ws + c.w.prod_intt;
+    u64* temp_last = c.ws + c.w.temp_last;
+    int rc;
+    // (4) INTT: only the special-prime rows when the result stays in NTT form; all rows otherwise (:991-996)
+    if (ntt) rc = launch_ntt(p, special_rows_args(p, c.ws + c.w.poly_prod, prod_intt, L), batch, true, s);
+    else rc = launch_ntt(p, contiguous_args(p, c.ws + c.w.poly_prod, prod_intt, 2, L + 1, 0, K, TROYN_IDX_KS_SKIP_FINALS, L), batch, true, s);
+    if (rc || (rc = check_rows(rows, ch))) return rc;
+    const u64* last_src = ntt ? prod_intt : prod_intt + (size_t)L * n;      // the special-prime rows in coefficient form
+    const size_t last_stride = ntt ? n : (size_t)(L + 1) * n;
+    const u64* prod_for_util7 = ntt ? c.ws + c.w.poly_prod : prod_intt;
+    // (5) rounding fix of the special-prime component, per data limb (:570-598).  In NTT form the result goes to
+    //     the unused tail of the prod_intt region so that step (6) can transform out of place.
+    u64* util6_out = ntt ? prod_intt + batch * 2 * (size_t)n : temp_last;
+    if (c.bgv) {
+        // kernel_ski_util5_merged_step1 (:436-476): delta_j = (k mod q_j) * q_special + c mod q_j, k = -c * q_special^-1 mod t
+        hipLaunchKernelGGL(bgv_delta_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
+                           ch, p->d_mods, L, n, c.bgv->t, c.bgv->inv_special_mod_t, p->moduli[K - 1], last_src, last_stride, util6_out);
+        LAUNCH_CHECK();
+    } else if (ntt) {
+        hipLaunchKernelGGL(ks_util6_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
+                           ch, p->d_mods, K, L, n, last_src, last_stride, util6_out);
+        LAUNCH_CHECK();
+    }   // coefficient form: ks_util7_kernel forms the fix itself from the special-prime row
+    // (6) back to NTT form when needed (:1033-1036)
+    if (ntt && (rc = launch_ntt(p, contiguous_args(p, util6_out, temp_last, 2, L, 0, L, TROYN_IDX_COMPONENTWISE, 0), batch, false, s))) return rc;
+    // (7) divide by the special prime and assign (:625-658; BGV: kernel_ski_util5_merged_step2 :506-538)
+    if (c.bgv) {
+        hipLaunchKernelGGL(bgv_finish_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
+                           ch, p->d_mods, L, L + 1, n, prod_for_util7, temp_last, p->d_inv_last + (size_t)K * K, c.assign_method, c.dest, c.addend, c.addend_bstride);
+        LAUNCH_CHECK();
+    } else {
+        hipLaunchKernelGGL(ks_util7_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
+                           ch, p->d_mods, L, L + 1, n, prod_for_util7, temp_last,
+                           p->d_inv_last + (size_t)K * K, c.is_ckks, c.assign_method, c.dest, c.addend, c.addend_bstride,
+                           ntt ? (const u64*)nullptr : last_src, last_stride, K);
+        LAUNCH_CHECK();
+    }
+    return TROYN_OK;
+}
+// (4)-(7): divide poly_prod by the special prime and assign to dest
+static int ks_tail(const KsCall& c, const KsPath& path) {
+    if (path.tail == KS_TAIL_SMALL) return ks_tail_small(c);
+    if (path.tail == KS_TAIL_NTT_FUSED) return ks_tail_ntt_fused(c);
+    return path.tail == KS_TAIL_COEFF_FUSED ? ks_tail_coeff_fused(c) : ks_tail_unfused(c);
+}
 
 static int switch_key_impl(const troyn_plan* p, unsigned L, int is_ckks, int is_ntt_form,
                            const u64* target, size_t target_bstride, const uint64_t* const* keys, int assign_method,
                            u64* dest, const u64* addend, size_t addend_bstride,
                            void* workspace, size_t workspace_bytes, size_t batch, hipStream_t s, const BgvTail* bgv = nullptr) {
-    const unsigned K = p->K, n = p->n;
+    const unsigned K = p->K;
     if (K < 2) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] Keyswitching is not supported.");
     if (L < 1 || L > K - 1) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] Invalid target size.");
     if (!target || !keys || !dest || !workspace) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] null argument");
@@ -1009,292 +1362,18 @@ static int switch_key_impl(const troyn_plan* p, unsigned L, int is_ckks, int is_
     const KsLayout w = ks_layout(p, L, batch);
     if (workspace_bytes < w.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, "[troyn_switch_key] workspace too small");
     if (batch == 0) return TROYN_OK;
-    u64* ws = (u64*)workspace;
     KeyPtrs kp;
     std::memset(&kp, 0, sizeof(kp));
     for (unsigned j = 0; j < L; j++) {
         if (!keys[j]) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] null key pointer");
         kp.p[j] = (const u64*)keys[j];
     }
-    int rc;
-    const u64* digits_src = target;
-    size_t digits_bstride = target_bstride;
-    // the optimised NTT kernels carry fused prologues / epilogues; tiny rings (generic kernel) use the unfused chain
-    const bool fused = is_ntt_form && p->log_n >= 10 && !bgv;
-
-    // (1) NTT form: bring the target back to coefficient form (evaluator_keyswitching_core.cu:817-821)
-    if (is_ntt_form) {
-        NttArgs a = contiguous_args(p, target, ws + w.target_intt, 1, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
-        a.in_bstride = (long long)target_bstride;
-        if ((rc = launch_ntt(p, a, batch, true, s))) return rc;
-        digits_src = ws + w.target_intt;
-        digits_bstride = (size_t)L * n;
-    }
-    const bool ks_unfused_mac = p->opt.ks_mac_split || ks_small_mixed(p, L, batch);
-    // (2)+(3) in ONE launch for whole-limb rings (N <= 16384): every workgroup owns one output row of one item,
-    //     transforms that row's L digits one after the other and multiplies them into register accumulators with
-    //     the key (kernel_set_accumulate + ntt + kernel_accumulate_products, fgk/switch_key.cu:6-154); the
-    //     (L+1)*L transformed digits never reach HBM.
-    // (N >= 8192: the half-tile kernels, whose grid is up to 4 (L + 2) workgroups per item; the first-generation whole-limb kernel stays the path
-    // of N = 1024 .. 4096 -- its N = 8192 / 16384 instantiations left the library in round 5)
-    const bool mac_fused = !ks_unfused_mac && p->log_n >= 10 && p->log_n <= 15 && batch * (size_t)(L + 1) <= 0x7fffffffull &&
-                           (p->log_n <= 12 || (p->d_fwd_r2 && p->d_fwd_r2i && L + 1 <= 64 && batch * (size_t)(L + 2) * 4 <= 0x7fffffffull));
-    const int ks_mac_gen = p->log_n >= 13 ? 2 : 1;
-    // (the band order pads an odd row count with one row of workgroups that exit: the grid guard counts L + 2 rows)
-    if (mac_fused && ks_mac_gen == 2 && use_f64(p, 0, K)) {
-        // ksmac2_kernel: tiles of 2^13 outputs, two workgroups per CU, keys prepared once per call (ksmac_kernels.hpp)
-        double* kf = reinterpret_cast<double*>(ws + w.keys_f64);
-        // NTT-form target: the block (key j, modulus j) a second time in natural order -- the diagonal digit is applied in the kernel's
-        // epilogue (DG).  The switch is read ONCE per call: the preparation and the instantiation choice must agree.
-        const bool dg = is_ntt_form && !p->opt.ks_diag_loop;
-        // the digit-parallel form (small launches) reads the caller's keys as they are: no preparation pass
-        const bool split = ksmac_split_wanted(p, batch, L, p->log_n) && (dg || !is_ntt_form);
-        if (!split) {
-            const size_t pairs = (size_t)L * 2 * K * (n / 2);
-            const unsigned blocks = (unsigned)std::min<size_t>((pairs + 255) / 256, 4096);
-            launch_ksmac_prepare_keys(kp, L, 2 * K, n, kf, blocks, s, nullptr, nullptr, 0, dg ? kf + (size_t)L * 2 * K * n : nullptr);
-            LAUNCH_CHECK();
-        }
-        KsMacArgs a;
-        std::memset(&a, 0, sizeof(a));
-        if (dg) a.diag_keys = kf + (size_t)L * 2 * K * n;
-        a.digits = digits_src; a.dig_bstride = (long long)digits_bstride; a.dig_cstride = n;
-        a.diag = is_ntt_form ? target : nullptr; a.diag_bstride = (long long)target_bstride; a.diag_cstride = n;
-        a.out = ws + w.poly_prod; a.out_bstride = 2ll * (L + 1) * n; a.out_pstride = (long long)(L + 1) * n; a.out_cstride = n;
-        a.mods = p->d_mods; a.tw = p->d_fwd_f64; a.tw_r1 = p->d_fwd_r1; a.tw_r2 = p->d_fwd_r2;
-        a.keys = kf; a.key_jstride = 2ll * K * n; a.key_pstride = (long long)K * n;
-        a.L = L; a.table_start = 0; a.table_count = K; a.batch = (unsigned)batch;
-        a.grouped = ksmac_order(p, batch, p->log_n);
-        {
-            TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, s);
-            if (split) {
-                a.grouped = 0;
-                a.part = reinterpret_cast<double*>(ws + w.split); a.part_jstride = (long long)batch * a.out_bstride;
-                a.split_skip_diag = dg ? 1u : 0u;
-                a.raw = kp; a.raw_pstride = (long long)K * n;
-                launch_ksmac2_split(p->log_n, batch, a, s, false, dg ? 2 : 0);
-            } else launch_ksmac2(p->log_n, batch, L + 1, a, s);
-        }
-        LAUNCH_CHECK();
-    } else if (mac_fused) {
-        // A chain with moduli of 2^50 and more (the reference's default {60,40,40,60}; {60,50,...,60} CKKS chains): the output rows of the
-        // moduli below 2^50 take ksmac2_kernel (exact FP64 butterflies; digits of wider limbs are reduced while loading), the rows of the wide
-        // moduli the integer kernel of the same shape (ksmaci_kernel, N = 8192 / 16384 / 32768; round 5).  Rows are independent; results are
-        // unchanged.  TROYN_NTT_ARITH=u64 sends every row to the integer kernel; N < 8192 keeps the first-generation kernel.
-        unsigned long long small_rows = 0, wide_rows = 0;
-        bool wide_digits = false;
-        const bool all_integer = force_integer_ntt(p);
-        for (unsigned k = 0; k <= L; k++) {
-            const unsigned mrow = (k == L) ? K - 1 : k;
-            if (p->small_modulus[mrow] && !all_integer) small_rows |= 1ull << k; else wide_rows |= 1ull << k;
-            if (k < L && !p->small_modulus[k]) wide_digits = true;
-        }
-        const bool gen2 = ks_mac_gen == 2;
-        const bool mixed = gen2 && small_rows != 0;
-        TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, s);
-        if (mixed) {
-            double* kf = reinterpret_cast<double*>(ws + w.keys_f64);
-            const size_t pairs = (size_t)L * 2 * K * (n / 2);
-            // NTT-form target: the diagonal digit in the epilogue (DG) as in the all-FP64 path -- needs the diagonal key blocks in natural order
-            const bool dg = is_ntt_form && !p->opt.ks_diag_loop;
-            launch_ksmac_prepare_keys(kp, L, 2 * K, n, kf, (unsigned)std::min<size_t>((pairs + 255) / 256, 4096), s, nullptr, nullptr, 0,
-                                      dg ? kf + (size_t)L * 2 * K * n : nullptr);
-            LAUNCH_CHECK();
-            KsMacArgs m;
-            std::memset(&m, 0, sizeof(m));
-            if (dg) m.diag_keys = kf + (size_t)L * 2 * K * n;
-            m.digits = digits_src; m.dig_bstride = (long long)digits_bstride; m.dig_cstride = n;
-            m.diag = is_ntt_form ? target : nullptr; m.diag_bstride = (long long)target_bstride; m.diag_cstride = n;
-            m.out = ws + w.poly_prod; m.out_bstride = 2ll * (L + 1) * n; m.out_pstride = (long long)(L + 1) * n; m.out_cstride = n;
-            m.mods = p->d_mods; m.tw = p->d_fwd_f64; m.tw_r1 = p->d_fwd_r1; m.tw_r2 = p->d_fwd_r2;
-            m.keys = kf; m.key_jstride = 2ll * K * n; m.key_pstride = (long long)K * n;
-            m.L = L; m.table_start = 0; m.table_count = K; m.batch = (unsigned)batch;
-            m.grouped = ksmac_order(p, batch, p->log_n);
-            m.row_mask = small_rows;
-            launch_ksmac2(p->log_n, batch, (unsigned)__builtin_popcountll(small_rows), m, s, false, wide_digits);
-            LAUNCH_CHECK();
-        }
-        if (gen2 && wide_rows == 0) {
-            // (every row this level touches is narrow although the chain holds a wide modulus elsewhere: ksmac2 above took all of them)
-        } else if (gen2) {
-            // integer rows: (key, Shoup quotient) pairs of exactly these rows, in the accumulators' layout, once per call
-            const unsigned slots = (unsigned)__builtin_popcountll(wide_rows);
-            ulonglong2* ki = reinterpret_cast<ulonglong2*>(ws + w.keys_quo);
-            ulonglong2* kdiag = ki + (size_t)L * 2 * slots * n;
-            const size_t words = (size_t)L * 2 * slots * n;
-            launch_ksmaci_prepare_keys(kp, L, K, n, wide_rows, ki, (unsigned)std::min<size_t>((words + 255) / 256, 4096), s, nullptr, p->d_mods, 0,
-                                       is_ntt_form ? kdiag : nullptr);
-            LAUNCH_CHECK();
-            KsMacIArgs m;
-            std::memset(&m, 0, sizeof(m));
-            m.digits = digits_src; m.dig_bstride = (long long)digits_bstride; m.dig_cstride = n;
-            m.diag = is_ntt_form ? target : nullptr; m.diag_bstride = (long long)target_bstride; m.diag_cstride = n;
-            m.out = ws + w.poly_prod; m.out_bstride = 2ll * (L + 1) * n; m.out_pstride = (long long)(L + 1) * n; m.out_cstride = n;
-            m.mods = p->d_mods; m.tw = p->d_fwd; m.tw_r1 = p->d_fwd_r1i; m.tw_r2 = p->d_fwd_r2i;
-            m.keys = ki; m.key_jstride = 2ll * slots * n; m.key_pstride = (long long)slots * n;
-            m.diag_keys = kdiag;
-            m.L = L; m.table_start = 0; m.table_count = K; m.batch = (unsigned)batch;
-            m.grouped = (batch % 8 == 0 && p->opt.ks_order != 0) ? 1u : 0u;
-            m.row_mask = wide_rows;
-            launch_ksmaci(p->log_n, batch, m, s, is_ntt_form ? 1 : 0);
-            LAUNCH_CHECK();
-        } else {
-        NttArgs a = contiguous_args(p, digits_src, ws + w.poly_prod, 1, L + 1, 0, K, TROYN_IDX_KS_SET_PRODUCTS, L);
-        a.in_bstride = (long long)digits_bstride; a.in_pstride = 0; a.in_cstride = n;
-        a.out_bstride = 2ll * (L + 1) * n; a.out_pstride = (long long)(L + 1) * n; a.out_cstride = n;
-        a.reduce_input = 1;
-        a.stream_loads = 0;                      // the L+1 rows of an item re-read the same digits
-        a.skip_diag = is_ntt_form ? 1 : 0;       // digit k of row k is the NTT-form input limb itself
-        a.ext0 = target; a.ext0_bstride = (long long)target_bstride; a.ext0_cstride = n;
-        a.batch = (unsigned)batch; a.key_pstride = (long long)K * n;
-        {
-            // rows of an item co-scheduled per XCD: all L+1 by default (the item's digits are then fetched once per XCD instead of
-            // once per row; measured 1265 vs 1310 us per 512-item launch at cfg3), TROYN_KS_ROWS=1 restores plain row-major order
-            const int ks_rows = p->opt.ks_rows;
-            const unsigned R = ks_rows > 0 ? (unsigned)ks_rows : L + 1;
-            a.xcd_groups = (R > 1 && batch % 8 == 0 && (L + 1) % R == 0) ? R : 0u;
-        }
-        a.mods = p->d_mods;
-        const bool f64 = use_f64(p, 0, K);
-        a.tw = f64 ? (const void*)p->d_fwd_f64 : (const void*)p->d_fwd;
-        if (!f64 && !p->opt.ks_mac_shoup_off) {
-            // integer policy: the keys' Shoup quotients, once per call (TROYN_KS_MAC_SHOUP=0: Barrett-128 terms as in rounds 1-3; A/B, tests)
-            u64* kq = ws + w.keys_quo;
-            const size_t words = (size_t)L * 2 * K * n;
-            hipLaunchKernelGGL(ks_key_quotients_kernel, dim3((unsigned)std::min<size_t>((words + 255) / 256, 4096)), dim3(256), 0, s, kp, L, K, n, p->d_mods, kq);
-            LAUNCH_CHECK();
-            a.key_quo = kq; a.key_quo_jstride = 2ll * K * n;
-        }
-        if (f64) launch_ks_mac_f64(p->log_n, a, kp, batch * (size_t)(L + 1), launch_ctx(p, s));
-        else launch_ks_mac_u64(p->log_n, a, kp, batch * (size_t)(L + 1), launch_ctx(p, s));
-        LAUNCH_CHECK();
-        }
-    } else {
-    // (2) digit decomposition fused into the forward NTT (replaces kernel_set_accumulate, fgk/switch_key.cu:6-54,
-    //     + ntt_inplace_ps with key_switching_set_products, :907-908): row i = digits reduced mod q_key(i)
-    {
-        NttArgs a = contiguous_args(p, digits_src, ws + w.temp_ntt, L + 1, L, 0, K, TROYN_IDX_KS_SET_PRODUCTS, L);
-        a.in_bstride = (long long)digits_bstride;
-        a.in_pstride = 0;            // every row re-reads the same L digits
-        a.reduce_input = 1;
-        a.skip_diag = fused ? 1 : 0; // row i, digit i is the NTT-form input itself: not recomputed
-        if ((rc = launch_ntt(p, a, batch, false, s))) return rc;
-    }
-    // (3) <digits, key> inner product (fgk/switch_key.cu:83-154)
-    {
-        const unsigned ch = chunks_pairs(n);
-        const size_t rows = batch * (L + 1);
-        if ((rc = check_rows(rows, ch))) return rc;
-        hipLaunchKernelGGL(ks_accumulate_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
-                           ch, p->d_mods, K, L, n, ws + w.temp_ntt, kp, ws + w.poly_prod,
-                           fused ? target : (const u64*)nullptr, target_bstride);
-        LAUNCH_CHECK();
-    }
-    }
-    // (4) INTT: only the special-prime rows when the result stays in NTT form; all rows otherwise (:991-996)
-    const u64* last_src;
-    size_t last_stride;
-    const u64* prod_for_util7;
-    // (5)-(7) in ONE launch: the forward NTT reads the INTT'd special rows through the rounding-fix prologue (ski_util6_merged) and finishes
-    // with the divide-by-special-prime / assign epilogue (ski_util7_merged)
-    auto fused_tail_args = [&](const u64* src) {
-        NttArgs a = contiguous_args(p, src, dest, 2, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
-        a.in_bstride = 2ll * n; a.in_pstride = n; a.in_cstride = 0;
-        a.load_mode = NTT_LOAD_KS_ROUND; a.aux_mod = K - 1;
-        a.store_mode = NTT_STORE_KS_FINISH;
-        a.flags = (is_ckks ? 1u : 0u) | ((unsigned)assign_method << 1);
-        a.ext0 = ws + w.poly_prod; a.ext0_bstride = 2ll * (L + 1) * n; a.ext0_pstride = (long long)(L + 1) * n; a.ext0_cstride = n;
-        a.ext1 = addend; a.ext1_bstride = (long long)addend_bstride; a.ext1_pstride = (long long)L * n; a.ext1_cstride = n;
-        a.inv_table = p->d_inv_last + (size_t)K * K;
-        return a;
-    };
-    if (fused && small_tail_wanted(p, batch * 2 * L)) {
-        const bool tail_f64 = use_f64(p, 0, L) && use_f64(p, K - 1, 1);      // else both transforms on the integer kernels (small launches are not split by class)
-        // a few ciphertexts at N = 16384: first inverse pass of the special rows in place (nothing else reads them), then the strided passes of both
-        // transforms as one launch (small_tail)
-        NttArgs pa = contiguous_args(p, ws + w.poly_prod + (size_t)L * n, ws + w.poly_prod + (size_t)L * n, 2, 1, K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
-        pa.in_pstride = pa.out_pstride = (long long)(L + 1) * n;
-        pa.in_bstride = pa.out_bstride = 2ll * (L + 1) * n;
-        return small_tail(p, tail_f64, pa, batch * 2, fused_tail_args(ws + w.prod_intt), ws + w.temp_last, batch * 2, s);
-    }
-    if (is_ntt_form) {
-        NttArgs a = contiguous_args(p, ws + w.poly_prod + (size_t)L * n, ws + w.prod_intt, 2, 1, K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
-        a.in_pstride = (long long)(L + 1) * n;
-        a.in_bstride = 2ll * (L + 1) * n;
-        if ((rc = launch_ntt(p, a, batch, true, s))) return rc;
-        last_src = ws + w.prod_intt; last_stride = n;
-        prod_for_util7 = ws + w.poly_prod;
-    } else if (!bgv && p->log_n >= 10 && p->log_n <= 17 && coeff_tail_fused(p)) {
-        // coefficient form: INTT of the two special-prime rows, then the INTT of the 2L data rows finishes the key switch in its epilogue
-        // ((5) + (7), ski_util6_merged / ski_util7_merged) and writes the destination -- the INTT'd rows never reach HBM
-        NttArgs a = contiguous_args(p, ws + w.poly_prod + (size_t)L * n, ws + w.prod_intt, 2, 1, K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
-        a.in_pstride = (long long)(L + 1) * n;
-        a.in_bstride = 2ll * (L + 1) * n;
-        if ((rc = launch_ntt(p, a, batch, true, s))) return rc;
-        NttArgs f = contiguous_args(p, ws + w.poly_prod, dest, 2, L, 0, K, TROYN_IDX_COMPONENTWISE, 0);
-        f.in_pstride = (long long)(L + 1) * n;
-        f.in_bstride = 2ll * (L + 1) * n;
-        f.load_mode = NTT_LOAD_KS_ROUND; f.aux_mod = K - 1;      // constants of the rounding fix (no forward prologue runs)
-        f.store_mode = NTT_STORE_KS_FINISH;
-        f.flags = (is_ckks ? 1u : 0u) | ((unsigned)assign_method << 1);
-        f.in2 = ws + w.prod_intt; f.in2_bstride = 2ll * n; f.in2_pstride = n;
-        f.ext0 = dest; f.ext0_bstride = 2ll * L * n; f.ext0_pstride = (long long)L * n; f.ext0_cstride = n;   // unused by this epilogue
-        f.ext1 = addend; f.ext1_bstride = (long long)addend_bstride; f.ext1_pstride = (long long)L * n; f.ext1_cstride = n;
-        f.inv_table = p->d_inv_last + (size_t)K * K;
-        // two-pass sizes: the pass in between goes to the free part of prod_intt, never to dest (AddInplace reads the old destination)
-        return launch_ntt(p, f, batch, true, s, ws + w.prod_intt + batch * 2 * (size_t)n);
-    } else {
-        NttArgs a = contiguous_args(p, ws + w.poly_prod, ws + w.prod_intt, 2, L + 1, 0, K, TROYN_IDX_KS_SKIP_FINALS, L);
-        if ((rc = launch_ntt(p, a, batch, true, s))) return rc;
-        last_src = ws + w.prod_intt + (size_t)L * n; last_stride = (size_t)(L + 1) * n;
-        prod_for_util7 = ws + w.prod_intt;
-    }
-    if (fused) {
-        // N >= 32768 transforms in two passes: the pass in between goes to temp_last (unused on this path), never to dest
-        return launch_ntt(p, fused_tail_args(last_src), batch, false, s, ws + w.temp_last);
-    }
-    // (5) rounding fix of the special-prime component, per data limb (:570-598).  In NTT form the result goes to
-    //     the unused tail of the prod_intt region so that step (6) can transform out of place.
-    u64* util6_out = is_ntt_form ? ws + w.prod_intt + batch * 2 * (size_t)n : ws + w.temp_last;
-    if (bgv) {
-        // kernel_ski_util5_merged_step1 (:436-476): delta_j = (k mod q_j) * q_special + c mod q_j, k = -c * q_special^-1 mod t
-        const unsigned ch = chunks_single(n);
-        const size_t rows = batch * 2 * L;
-        if ((rc = check_rows(rows, ch))) return rc;
-        hipLaunchKernelGGL(bgv_delta_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
-                           ch, p->d_mods, L, n, bgv->t, bgv->inv_special_mod_t, p->moduli[K - 1], last_src, last_stride, util6_out);
-        LAUNCH_CHECK();
-    } else if (is_ntt_form) {
-        const unsigned ch = chunks_pairs(n);
-        const size_t rows = batch * 2 * L;
-        if ((rc = check_rows(rows, ch))) return rc;
-        hipLaunchKernelGGL(ks_util6_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
-                           ch, p->d_mods, K, L, n, last_src, last_stride, util6_out);
-        LAUNCH_CHECK();
-    }   // coefficient form: ks_util7_kernel forms the fix itself from the special-prime row
-    // (6) back to NTT form when needed (:1033-1036)
-    if (is_ntt_form) {
-        NttArgs a = contiguous_args(p, util6_out, ws + w.temp_last, 2, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
-        if ((rc = launch_ntt(p, a, batch, false, s))) return rc;
-    }
-    // (7) divide by the special prime and assign (:625-658; BGV: kernel_ski_util5_merged_step2 :506-538)
-    if (bgv) {
-        const unsigned ch = chunks_single(n);
-        const size_t rows = batch * 2 * L;
-        hipLaunchKernelGGL(bgv_finish_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
-                           ch, p->d_mods, L, L + 1, n, prod_for_util7, ws + w.temp_last, p->d_inv_last + (size_t)K * K, assign_method, dest, addend, addend_bstride);
-        LAUNCH_CHECK();
-    } else {
-        const unsigned ch = chunks_pairs(n);
-        const size_t rows = batch * 2 * L;
-        if ((rc = check_rows(rows, ch))) return rc;
-        hipLaunchKernelGGL(ks_util7_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
-                           ch, p->d_mods, L, L + 1, n, prod_for_util7, ws + w.temp_last,
-                           p->d_inv_last + (size_t)K * K, is_ckks, assign_method, dest, addend, addend_bstride,
-                           is_ntt_form ? (const u64*)nullptr : last_src, last_stride, K);
-        LAUNCH_CHECK();
-    }
-    return TROYN_OK;
+    KsCall c{p, L, is_ckks, is_ntt_form != 0, target, target_bstride, assign_method, dest, addend, addend_bstride,
+             (u64*)workspace, w, batch, s, bgv, target, target_bstride};
+    const KsPath path = ks_path(p, L, batch, c.is_ntt_form, bgv != nullptr);
+    if (int rc = ks_digits(c)) return rc;
+    if (int rc = ks_inner_product(c, kp, path)) return rc;
+    return ks_tail(c, path);
 }
 
 extern "C" int troyn_switch_key(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form,
@@ -1452,10 +1531,6 @@ static MrrStreams* mrr_streams(int device) {
     return &pool.back();
 }
 
-// launches (1)-(5) of the fused chain for `batch` items whose intermediates live in `ws` (layout w); kf: the prepared keys
-// raw != nullptr: digit-parallel inner product on the caller's own keys (small launches; the workspace has its slots and kf was not prepared)
-// Chains with moduli of 2^50 and more: every launch is issued once per run of limbs of one arithmetic class (limbs are independent), the rows
-// that cross classes are canonical u64 words (digits; T rows written by an integer kernel) and each consumer reduces what it reads.
 // ksmac2's NLC instantiation (half tiles, N = 16384, all-FP64 fused chain): the words of a digit enter layer 0 as they are (u, v < max q_j), leave it
 // as |x| <= max q_j + 0.875 p and run the three layers of round 0 without a re-centring in between.  Growth per layer: |x'| <= |x| + (0.5 + 1.5 |x| 2^-52) p
 // (dev_math_f64.hpp); the chain qualifies when every value stays below 2^53 with a 2 % margin for EVERY row modulus p of the launch.
@@ -1472,173 +1547,153 @@ static bool ksmac_no_load_corr_ok(const troyn_plan* p, unsigned L) {
     return true;
 }
 
-// ki: the integer rows' prepared keys (chains with wide moduli; nullptr otherwise)
-static int mrr_chain(const troyn_plan* p, uint32_t L, const u64* a, const u64* b, const double* kf, const ulonglong2* ki, u64* out, u64* ws, const MrrLayout& w,
-                     size_t batch, hipStream_t s, const KeyPtrs* raw = nullptr) {
-    const unsigned K = p->K, n = p->n;
-    int rc;
-    const long long ct_b = 2ll * L * n, ct_p = (long long)L * n;           // strides of a, b
-    const long long pp_b = 2ll * (L + 1) * n, pp_p = (long long)(L + 1) * n;   // strides of poly_prod
-    auto mul_operands = [&](NttArgs& x, unsigned limb0) { x.mul_a = a; x.mul_b = b; x.mul_bstride = ct_b; x.mul_pstride = ct_p; x.mul_limb0 = limb0; };
-    const bool all_f64 = mrr_all_f64(p, L);
-    auto small = [&](unsigned mi) { return use_f64(p, mi, 1); };          // this modulus takes the FP64 kernels
-    // runs of data limbs [j0, j1) of one class within [0, count)
-    // (runs of different classes in flight together: RunOverlap above)
-    auto for_runs = [&](unsigned count, unsigned polys, auto&& f) -> int {
-        RunOverlap ov(p, s, !all_f64 && batch * (size_t)polys * count >= OVERLAP_MIN_LIMB_POLYS);
-        for (unsigned j0 = 0, j1; j0 < count; j0 = j1) {
-            for (j1 = j0 + 1; j1 < count && small(j1) == small(j0); j1++) {}
-            if (int r = f(j0, j1, (j0 == 0 && j1 == count) ? s : ov.next())) return r;
-        }
-        return ov.join();
-    };
-    const bool special_wide = !small(K - 1), last_wide = !small(L - 1);
-    bool wide_digits = false;
-    unsigned long long small_rows = 0, wide_rows = 0;
-    for (unsigned k = 0; k <= L; k++) {
-        const unsigned mrow = (k == L) ? K - 1 : k;
-        if (small(mrow)) small_rows |= 1ull << k; else wide_rows |= 1ull << k;
-        if (k < L && !small(k)) wide_digits = true;
+// ki: the integer rows' prepared keys (chains with wide moduli; nullptr otherwise); rows: ks_rows(p, L), the masks the keys were prepared for
+struct MrrCall {
+    const troyn_plan* p; uint32_t L; const u64* a; const u64* b; u64* out; u64* ws; const MrrLayout& w; size_t batch; hipStream_t s;
+    bool all_f64, special_wide, last_wide;                               // classes of the chain, of the special prime, of the dropped limb
+    unsigned t_flags() const { return (special_wide ? NTT_FLAG_TS_U64 : 0u) | (last_wide ? NTT_FLAG_TL_U64 : 0u); }
+    long long ct_b() const { return 2ll * L * p->n; }                     // strides of a, b
+    long long ct_p() const { return (long long)L * p->n; }
+    u64* poly_prod() const { return ws + w.poly_prod; }
+    // runs of data limbs [j0, j1) of one class within [0, count); runs of different classes in flight together (RunOverlap above)
+    template <typename F> int for_runs(unsigned count, unsigned polys, F&& f) const {
+        return for_class_runs(p, 0, count, class_by_policy, !all_f64 && batch * (size_t)polys * count >= OVERLAP_MIN_LIMB_POLYS, s, f);
     }
-    // (1) digits = INTT(c2), c2 = a1 (.) b1 formed in the loader (kernel_dyadic_convolute's third output + transform_from_ntt, :817-821)
-    if ((rc = for_runs(L, 1, [&](unsigned j0, unsigned j1, hipStream_t rs) {
-        NttArgs x = contiguous_args(p, a + (size_t)j0 * n, ws + w.digits + (size_t)j0 * n, 1, j1 - j0, j0, j1 - j0, TROYN_IDX_COMPONENTWISE, 0);
-        x.in_bstride = ct_b; x.in_pstride = ct_p;                          // (the loader reads mul_a / mul_b; `in` only anchors the shapes)
+};
+
+// (1) digits = INTT(c2), c2 = a1 (.) b1 formed in the loader (kernel_dyadic_convolute's third output + transform_from_ntt, :817-821)
+static int mrr_digits(const MrrCall& c) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, n = p->n;
+    return c.for_runs(L, 1, [&](unsigned j0, unsigned j1, hipStream_t rs) {
+        NttArgs x = contiguous_args(p, c.a + (size_t)j0 * n, c.ws + c.w.digits + (size_t)j0 * n, 1, j1 - j0, j0, j1 - j0, TROYN_IDX_COMPONENTWISE, 0);
+        x.in_bstride = c.ct_b(); x.in_pstride = c.ct_p();                  // (the loader reads mul_a / mul_b; `in` only anchors the shapes)
         x.out_bstride = (long long)L * n; x.out_pstride = (long long)L * n;
-        mul_operands(x, j0);
+        x.mul_a = c.a; x.mul_b = c.b; x.mul_bstride = c.ct_b(); x.mul_pstride = c.ct_p(); x.mul_limb0 = j0;
         x.fused_mode = NTT_FUSED_MULPAIR;
-        if (all_f64) x.flags = NTT_FLAG_STORE_F64;            // the digits go to ksmac2 as doubles (one conversion here instead of L + 1 there)
-        return launch_ntt(p, x, batch, true, rs);
-    }))) return rc;
-    // (2) key-switch inner product; the digit of row k under its own modulus is a1 (.) b1 again
-    {
-        TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, s);
-        if (small_rows) {
-            KsMacArgs m;
-            std::memset(&m, 0, sizeof(m));
-            m.digits = ws + w.digits; m.dig_bstride = (long long)L * n; m.dig_cstride = n;
-            m.diag = a + ct_p; m.diag_b = b + ct_p; m.diag_bstride = ct_b; m.diag_cstride = n;
-            m.ten_a = a; m.ten_b = b; m.ten_bstride = ct_b; m.ten_pstride = ct_p;      // data rows leave as Q = P qk^-1 + c (keys prepared times qk^-1)
-            m.diag_keys = kf + (size_t)L * 2 * K * n;
-            m.out = ws + w.poly_prod; m.out_bstride = pp_b; m.out_pstride = pp_p; m.out_cstride = n;
-            m.mods = p->d_mods; m.tw = p->d_fwd_f64; m.tw_r1 = p->d_fwd_r1; m.tw_r2 = p->d_fwd_r2;
-            m.keys = kf; m.key_jstride = 2ll * K * n; m.key_pstride = (long long)K * n;
-            m.L = L; m.table_start = 0; m.table_count = K; m.batch = (unsigned)batch; m.grouped = ksmac_order(p, batch, p->log_n);
-            if (wide_rows) m.row_mask = small_rows;
-            m.no_load_corr = (all_f64 && ksmac_no_load_corr_ok(p, L)) ? 1u : 0u;
-            if (raw) {
-                m.grouped = 0;
-                m.part = reinterpret_cast<double*>(ws + w.split); m.part_jstride = (long long)batch * pp_b;
-                m.split_skip_diag = 1;
-                m.raw = *raw; m.raw_pstride = (long long)K * n; m.split_scale = p->d_inv_last + (size_t)K * K;
-                launch_ksmac2_split(p->log_n, batch, m, s, true, 1);
-            } else launch_ksmac2(p->log_n, batch, (unsigned)__builtin_popcountll(small_rows), m, s, all_f64, wide_digits);
-            LAUNCH_CHECK();
-        }
-        if (wide_rows) {
-            const unsigned slots = (unsigned)__builtin_popcountll(wide_rows);
-            KsMacIArgs m;
-            std::memset(&m, 0, sizeof(m));
-            m.digits = ws + w.digits; m.dig_bstride = (long long)L * n; m.dig_cstride = n;
-            m.ten_a = a; m.ten_b = b; m.ten_bstride = ct_b; m.ten_pstride = ct_p;
-            m.out = ws + w.poly_prod; m.out_bstride = pp_b; m.out_pstride = pp_p; m.out_cstride = n;
-            m.mods = p->d_mods; m.tw = p->d_fwd; m.tw_r1 = p->d_fwd_r1i; m.tw_r2 = p->d_fwd_r2i;
-            m.keys = ki; m.key_jstride = 2ll * slots * n; m.key_pstride = (long long)slots * n;
-            m.diag_keys = ki + (size_t)L * 2 * slots * n;
-            m.L = L; m.table_start = 0; m.table_count = K; m.batch = (unsigned)batch;
-            m.grouped = (batch % 8 == 0 && p->opt.ks_order != 0) ? 1u : 0u;
-            m.row_mask = wide_rows;
-            launch_ksmaci(p->log_n, batch, m, s, 2);
-            LAUNCH_CHECK();
-        }
+        if (c.all_f64) x.flags = NTT_FLAG_STORE_F64;          // the digits go to ksmac2 as doubles (one conversion here instead of L + 1 there)
+        return launch_ntt(p, x, c.batch, true, rs);
+    });
+}
+
+// (2) key-switch inner product; the digit of row k under its own modulus is a1 (.) b1 again
+static int mrr_inner_product(const MrrCall& c, const KsRows& rows, const double* kf, const ulonglong2* ki, const KeyPtrs* raw) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, c.s);
+    if (rows.small) {
+        KsMacArgs m = ksmac2_args(p, L, c.batch, c.ws + c.w.digits, (long long)L * n, c.poly_prod(), kf);
+        m.diag = c.a + c.ct_p(); m.diag_b = c.b + c.ct_p(); m.diag_bstride = c.ct_b(); m.diag_cstride = n;
+        m.ten_a = c.a; m.ten_b = c.b; m.ten_bstride = c.ct_b(); m.ten_pstride = c.ct_p();      // data rows leave as Q = P qk^-1 + c (keys prepared times qk^-1)
+        m.diag_keys = kf + (size_t)L * 2 * K * n;
+        if (rows.wide) m.row_mask = rows.small;
+        m.no_load_corr = (c.all_f64 && ksmac_no_load_corr_ok(p, L)) ? 1u : 0u;
+        if (raw) {
+            m.grouped = 0;
+            m.part = reinterpret_cast<double*>(c.ws + c.w.split); m.part_jstride = (long long)c.batch * m.out_bstride;
+            m.split_skip_diag = 1;
+            m.raw = *raw; m.raw_pstride = (long long)K * n; m.split_scale = p->d_inv_last + (size_t)K * K;
+            launch_ksmac2_split(p->log_n, c.batch, m, c.s, true, 1);
+        } else launch_ksmac2(p->log_n, c.batch, (unsigned)__builtin_popcountll(rows.small), m, c.s, c.all_f64, rows.wide_digits);
+        LAUNCH_CHECK();
     }
-    const unsigned t_flags = (special_wide ? NTT_FLAG_TS_U64 : 0u) | (last_wide ? NTT_FLAG_TL_U64 : 0u);
-    // arguments of steps (4) and (5) below (also read by the single-object form of the tail)
-    auto last_args = [&]() {
-        NttArgs x = contiguous_args(p, ws + w.poly_prod + (size_t)(L - 1) * n, ws + w.last_intt, 2, 1, L - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
-        x.in_pstride = pp_p; x.in_bstride = pp_b;
-        x.in2 = ws + w.spec_intt; x.in2_bstride = 2ll * n; x.in2_pstride = n;
-        x.aux_mod = K - 1; x.inv_table = p->d_inv_last + (size_t)K * K + (L - 1);
-        x.fused_mode = (!last_wide && special_wide) ? NTT_FUSED_LAST_LIMB_W : NTT_FUSED_LAST_LIMB;
-        x.flags = t_flags;
-        return x;
-    };
-    auto tail_args = [&](unsigned j0, unsigned j1) {
-        NttArgs x = contiguous_args(p, ws + w.spec_intt, out + (size_t)j0 * n, 2, j1 - j0, j0, j1 - j0, TROYN_IDX_COMPONENTWISE, 0);
-        x.in_bstride = 2ll * n; x.in_pstride = n; x.in_cstride = 0;
-        x.out_bstride = 2ll * (L - 1) * n; x.out_pstride = (long long)(L - 1) * n;
-        x.in2 = ws + w.last_intt; x.in2_bstride = 2ll * n; x.in2_pstride = n;
-        x.aux_mod = K - 1; x.inv_table = p->d_inv_last + (size_t)K * K + j0;
-        x.aux2_mod = L - 1; x.inv_table2 = p->d_inv_last + (size_t)L * K + j0;
-        x.ext0 = ws + w.poly_prod + (size_t)j0 * n; x.ext0_bstride = pp_b; x.ext0_pstride = pp_p; x.ext0_cstride = n;
-        x.fused_mode = (small(j0) && t_flags) ? NTT_FUSED_TAIL_RESCALE_W : NTT_FUSED_TAIL_RESCALE;     // (launch_ntt co-locates the limbs that share the two input rows on one XCD)
-        x.flags = t_flags;
-        return x;
-    };
-    // Single objects at N = 16384 (every launch of the tail in its two-pass form, FP64 policy): the three strided passes between the first
-    // inverse pass of {limb L-1, special rows} and the last forward pass of the output limbs run as ONE launch with T_s and T_l in registers
-    // (troyn_mrr_small.hip): 3 launches instead of 6.  TROYN_MRR_SMALL=0 keeps the six.
-    // N = 32768 (two-pass transforms at every size): the merged form at EVERY batch -- T_s and T_l never reach memory, three strided passes
-    // become one (one thread per octet loops over the output limbs when the launch is not small): fused chain 6 x 50-bit, 256 items 117.5 k -> 126 k ops/s
-    if (all_f64 && (small_tail_wanted(p, batch * 2 * (size_t)(L - 1)) || (p->log_n == 15 && !p->opt.mrr_small_off))) {
-        const LaunchCtx lc = launch_ctx(p, s);
-        auto prep = [&](NttArgs& x, bool inverse) {
-            x.mods = p->d_mods; x.stream_loads = 1u; x.xcd_groups = 0u;
-            x.tw = inverse ? (const void*)p->d_inv_f64 : (const void*)p->d_fwd_f64;
-        };
+    if (rows.wide) {
+        KsMacIArgs m = ksmaci_args(p, L, c.batch, c.ws + c.w.digits, (long long)L * n, c.poly_prod(), ki, rows.wide);
+        m.ten_a = c.a; m.ten_b = c.b; m.ten_bstride = c.ct_b(); m.ten_pstride = c.ct_p();
+        launch_ksmaci(p->log_n, c.batch, m, c.s, 2);
+        LAUNCH_CHECK();
+    }
+    return TROYN_OK;
+}
+
+// arguments of steps (4) and (5) (also read by the merged forms of the tail)
+static NttArgs mrr_last_args(const MrrCall& c) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    NttArgs x = contiguous_args(p, c.poly_prod() + (size_t)(L - 1) * n, c.ws + c.w.last_intt, 2, 1, L - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
+    x.in_pstride = (long long)(L + 1) * n; x.in_bstride = 2ll * (L + 1) * n;
+    x.in2 = c.ws + c.w.spec_intt; x.in2_bstride = 2ll * n; x.in2_pstride = n;
+    x.aux_mod = K - 1; x.inv_table = p->d_inv_last + (size_t)K * K + (L - 1);
+    x.fused_mode = (!c.last_wide && c.special_wide) ? NTT_FUSED_LAST_LIMB_W : NTT_FUSED_LAST_LIMB;
+    x.flags = c.t_flags();
+    return x;
+}
+static NttArgs mrr_tail_args(const MrrCall& c, unsigned j0, unsigned j1) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    NttArgs x = contiguous_args(p, c.ws + c.w.spec_intt, c.out + (size_t)j0 * n, 2, j1 - j0, j0, j1 - j0, TROYN_IDX_COMPONENTWISE, 0);
+    x.in_bstride = 2ll * n; x.in_pstride = n; x.in_cstride = 0;
+    x.out_bstride = 2ll * (L - 1) * n; x.out_pstride = (long long)(L - 1) * n;
+    x.in2 = c.ws + c.w.last_intt; x.in2_bstride = 2ll * n; x.in2_pstride = n;
+    x.aux_mod = K - 1; x.inv_table = p->d_inv_last + (size_t)K * K + j0;
+    x.aux2_mod = L - 1; x.inv_table2 = p->d_inv_last + (size_t)L * K + j0;
+    x.ext0 = c.poly_prod() + (size_t)j0 * n; x.ext0_bstride = 2ll * (L + 1) * n; x.ext0_pstride = (long long)(L + 1) * n; x.ext0_cstride = n;
+    x.fused_mode = (class_by_policy(p, j0) && c.t_flags()) ? NTT_FUSED_TAIL_RESCALE_W : NTT_FUSED_TAIL_RESCALE;     // (launch_ntt co-locates the limbs that share the two input rows on one XCD)
+    x.flags = c.t_flags();
+    return x;
+}
+
+// The merged forms of the tail (all-FP64 chains), T_s and T_l in registers: steps (3)-(5) on the special rows, the dropped limb and all L - 1 output limbs.
+//   quartet (troyn_mrr_small.hip): single objects at N = 16384 (every launch of the tail in its two-pass form): the three strided passes between
+//     the first inverse pass of {limb L-1, special rows} and the last forward pass of the output limbs run as ONE launch: 3 launches instead of 6.
+//     N = 32768 (two-pass transforms at every size): this form at EVERY batch -- T_s and T_l never reach memory, three strided passes become one
+//     (one thread per octet loops over the output limbs when the launch is not small): fused chain 6 x 50-bit, 256 items 117.5 k -> 126 k ops/s
+//   whole-limb (troyn_mrr_tail.hip): N = 16384, batches that fill the chip: ONE launch, one workgroup per (item, polynomial) -- the spec_intt /
+//     last_intt rows are not touched.
+// TROYN_MRR_SMALL=0 keeps the six / three launches.
+static int mrr_tail_merged(const MrrCall& c, bool quartet) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    const LaunchCtx lc = launch_ctx(p, c.s);
+    if (quartet) {
         // first inverse pass of rows L-1 and L (special) of both polynomials, in place in poly_prod (nothing else reads those rows)
-        NttArgs pa = contiguous_args(p, ws + w.poly_prod + (size_t)(L - 1) * n, ws + w.poly_prod + (size_t)(L - 1) * n, 2, 2, L - 1, K - (L - 1), TROYN_IDX_KS_SKIP_FINALS, 1);
-        pa.in_pstride = pa.out_pstride = pp_p; pa.in_bstride = pa.out_bstride = pp_b;
-        prep(pa, true);
-        launch_ntt_f64_small_pass(p->log_n, 0, pa, batch * 4, lc);
+        u64* rows = c.poly_prod() + (size_t)(L - 1) * n;
+        NttArgs pa = contiguous_args(p, rows, rows, 2, 2, L - 1, K - (L - 1), TROYN_IDX_KS_SKIP_FINALS, 1);
+        pa.in_pstride = pa.out_pstride = (long long)(L + 1) * n; pa.in_bstride = pa.out_bstride = 2ll * (L + 1) * n;
+        prep_direct(p, pa, true, true);
+        launch_ntt_f64_small_pass(p->log_n, 0, pa, c.batch * 4, lc);
         LAUNCH_CHECK();
-        NttArgs sp = contiguous_args(p, ws + w.poly_prod + (size_t)L * n, nullptr, 2, 1, K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
-        sp.in_pstride = pp_p; sp.in_bstride = pp_b;
-        prep(sp, true);
-        NttArgs la = last_args();
-        prep(la, true);
-        NttArgs ta = tail_args(0, L - 1);
-        prep(ta, false);
-        launch_mrr_quartet(p->log_n, batch, sp, la, ta, s, !p->opt.mrr_small_serial && batch * 2 * (size_t)(L - 1) * TROYN_SMALL_LP_FACTOR <= device_cu_count());
-        LAUNCH_CHECK();
-        // last forward pass of the output limbs, in place in `out`, with step (5)'s epilogue
-        ta.in = ta.out; ta.in_bstride = ta.out_bstride; ta.in_pstride = ta.out_pstride; ta.in_cstride = ta.out_cstride;
-        ta.reduce_input = 0;
-        launch_ntt_f64_small_pass(p->log_n, 1, ta, batch * 2 * (L - 1), lc);
+    }
+    NttArgs sp = special_rows_args(p, c.poly_prod(), nullptr, L);
+    if (!quartet) sp.flags = NTT_FLAG_STORE_ROUND_HALF;
+    prep_direct(p, sp, true, true);
+    NttArgs la = mrr_last_args(c);
+    prep_direct(p, la, true, true);
+    NttArgs ta = mrr_tail_args(c, 0, L - 1);
+    prep_direct(p, ta, true, false);
+    if (!quartet) {
+        launch_mrr_tail(p->log_n, c.batch, sp, la, ta, c.s);
         LAUNCH_CHECK();
         return TROYN_OK;
     }
-    // N = 16384, batches that fill the chip (whole-limb tiles): steps (3)-(5) below as ONE launch, one workgroup per (item, polynomial) with T_s
-    // and T_l in registers (troyn_mrr_tail.hip) -- the spec_intt / last_intt rows are not touched.  TROYN_MRR_SMALL=0 keeps the three launches.
-    if (all_f64 && p->log_n == 14 && !p->opt.mrr_small_off) {
-        auto prep = [&](NttArgs& x, bool inverse) {
-            x.mods = p->d_mods; x.stream_loads = 1u; x.xcd_groups = 0u;
-            x.tw = inverse ? (const void*)p->d_inv_f64 : (const void*)p->d_fwd_f64;
-        };
-        NttArgs sp = contiguous_args(p, ws + w.poly_prod + (size_t)L * n, nullptr, 2, 1, K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
-        sp.in_pstride = pp_p; sp.in_bstride = pp_b;
-        sp.flags = NTT_FLAG_STORE_ROUND_HALF;
-        prep(sp, true);
-        NttArgs la = last_args();
-        prep(la, true);
-        NttArgs ta = tail_args(0, L - 1);
-        prep(ta, false);
-        launch_mrr_tail(p->log_n, batch, sp, la, ta, s);
-        LAUNCH_CHECK();
-        return TROYN_OK;
-    }
+    launch_mrr_quartet(p->log_n, c.batch, sp, la, ta, c.s, !p->opt.mrr_small_serial && c.batch * 2 * (size_t)(L - 1) * TROYN_SMALL_LP_FACTOR <= device_cu_count());
+    LAUNCH_CHECK();
+    // last forward pass of the output limbs, in place in `out`, with step (5)'s epilogue
+    as_input_of(ta, ta);
+    ta.reduce_input = 0;
+    launch_ntt_f64_small_pass(p->log_n, 1, ta, c.batch * 2 * (L - 1), lc);
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+
+// launches (1)-(5) of the fused chain for `batch` items whose intermediates live in `ws` (layout w); kf: the prepared keys
+// raw != nullptr: digit-parallel inner product on the caller's own keys (small launches; the workspace has its slots and kf was not prepared)
+// Chains with moduli of 2^50 and more: every launch is issued once per run of limbs of one arithmetic class (limbs are independent), the rows
+// that cross classes are canonical u64 words (digits; T rows written by an integer kernel) and each consumer reduces what it reads.
+static int mrr_chain(const troyn_plan* p, uint32_t L, const KsRows& rows, const u64* a, const u64* b, const double* kf, const ulonglong2* ki, u64* out, u64* ws,
+                     const MrrLayout& w, size_t batch, hipStream_t s, const KeyPtrs* raw = nullptr) {
+    const MrrCall c{p, L, a, b, out, ws, w, batch, s, mrr_all_f64(p, L), !class_by_policy(p, p->K - 1), !class_by_policy(p, L - 1)};
+    int rc;
+    if ((rc = mrr_digits(c))) return rc;
+    if ((rc = mrr_inner_product(c, rows, kf, ki, raw))) return rc;
+    if (c.all_f64 && (small_tail_wanted(p, batch * 2 * (size_t)(L - 1)) || (p->log_n == 15 && !p->opt.mrr_small_off))) return mrr_tail_merged(c, true);
+    if (c.all_f64 && p->log_n == 14 && !p->opt.mrr_small_off) return mrr_tail_merged(c, false);
     // (3) s = INTT of the special-prime rows (:991-996, only the two rows the NTT-form tail needs)
     {
-        NttArgs x = contiguous_args(p, ws + w.poly_prod + (size_t)L * n, ws + w.spec_intt, 2, 1, K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
-        x.in_pstride = pp_p; x.in_bstride = pp_b;
+        NttArgs x = special_rows_args(p, c.poly_prod(), ws + w.spec_intt, L);
         x.flags = NTT_FLAG_STORE_ROUND_HALF;     // stored as (s + qk/2) mod qk, the limb-independent part of the key switch's rounding fix
         if ((rc = launch_ntt(p, x, batch, true, s))) return rc;
     }
     // (4) l = INTT(relin_{L-1}) = INTT(Q_{L-1}) - r(s) qk^-1 with Q = P qk^-1 + c as ksmac2 left it   (divide_and_round_q_last_ntt's INTT of the last limb, :675)
-    if ((rc = launch_ntt(p, last_args(), batch, true, s))) return rc;
+    if ((rc = launch_ntt(p, mrr_last_args(c), batch, true, s))) return rc;
     // (5) out_j = (Q_j - NTT_j(r_j(s) qk^-1 + f_j(l))) ql^-1, Q_j = P_j qk^-1 + c_j, for the L-1 remaining limbs: ski_util6/7 (:570-658), the
     //     trailing add of relinearize (:143) and both steps of divide_and_round_q_last_ntt (utils/rns_tool.cu:523-627) around ONE transform
-    return for_runs(L - 1, 2, [&](unsigned j0, unsigned j1, hipStream_t rs) { return launch_ntt(p, tail_args(j0, j1), batch, false, rs); });
+    return c.for_runs(L - 1, 2, [&](unsigned j0, unsigned j1, hipStream_t rs) { return launch_ntt(p, mrr_tail_args(c, j0, j1), batch, false, rs); });
 }
 
 extern "C" size_t troyn_ckks_multiply_relinearize_rescale_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t batch) {
@@ -1687,23 +1742,11 @@ extern "C" int troyn_ckks_multiply_relinearize_rescale(const troyn_plan* p, uint
     // otherwise: keys prepared once per call (converted to exact doubles in the accumulators' layout), shared by every chunk
     double* kf = reinterpret_cast<double*>(ws + w.keys_f64);
     ulonglong2* ki = reinterpret_cast<ulonglong2*>(ws + w.keys_int);
-    unsigned long long wide_rows = 0, small_rows = 0;
-    for (unsigned k = 0; k <= L; k++) { if (use_f64(p, k == L ? K - 1 : k, 1)) small_rows |= 1ull << k; else wide_rows |= 1ull << k; }
-    if (!split && small_rows) {
-        const size_t pairs = (size_t)L * 2 * K * (n / 2);
-        // the rows of the data moduli carry the factor qk^-1: the inner product leaves ksmac2 as P qk^-1 (+ the tensor term, KsMacArgs::ten_a)
-        launch_ksmac_prepare_keys(kp, L, 2 * K, n, kf, (unsigned)std::min<size_t>((pairs + 255) / 256, 4096), s,
-                                  p->d_inv_last + (size_t)K * K, p->d_mods, L, kf + (size_t)L * 2 * K * n);
-        LAUNCH_CHECK();
-    }
-    if (wide_rows) {
-        // the integer rows' (key qk^-1, Shoup quotient) pairs in the accumulators' layout + their diagonal blocks in natural order
-        const unsigned slots = (unsigned)__builtin_popcountll(wide_rows);
-        const size_t words = (size_t)L * 2 * slots * n;
-        launch_ksmaci_prepare_keys(kp, L, K, n, wide_rows, ki, (unsigned)std::min<size_t>((words + 255) / 256, 4096), s,
-                                   p->d_inv_last + (size_t)K * K, p->d_mods, L, ki + words);
-        LAUNCH_CHECK();
-    }
+    const KsRows rows = ks_rows(p, L);                   // once per call: preparation and every chunk's launches read the same masks
+    // the rows of the data moduli carry the factor qk^-1: the inner product leaves ksmac2 as P qk^-1 (+ the tensor term, KsMacArgs::ten_a)
+    if (!split && rows.small && (rc = prepare_keys_f64(p, kp, L, kf, L, true, s))) return rc;
+    // the integer rows' (key qk^-1, Shoup quotient) pairs in the accumulators' layout + their diagonal blocks in natural order
+    if (rows.wide && (rc = prepare_keys_int(p, kp, L, rows.wide, ki, L, true, s))) return rc;
     // Chunked execution of the 5-launch chain on internal streams (round 3, an option: TROYN_MRR_CHUNK=<items, multiple of 8>,
     // TROYN_MRR_STREAMS=<1..4>, default 2): the batch is cut into chunks that alternate on internal streams, forked from and joined to
     // the caller's stream by events; chunks are independent (the batch is), results are unchanged.  The kernels of one chunk bound
@@ -1713,14 +1756,14 @@ extern "C" int troyn_ckks_multiply_relinearize_rescale(const troyn_plan* p, uint
     // caller's stream is faster at every batch size measured (1024 items: 263.6 - 265.2 k vs 260.4 - 260.8 k ops/s with two halves,
     // 263.2 - 264.1 k with three thirds; 2048: 264.1 - 264.6 k vs 260.1 - 262.7 k; 512: 262.3 - 262.9 k vs 257.4 - 258.1 k) and is the default.
     const int ns = std::min(std::max(p->opt.mrr_streams, 1), MRR_MAX_STREAMS);
-    if (chunk == batch) return mrr_chain(p, L, a, b, kf, ki, out, ws, w, batch, s, split ? &kp : nullptr);
+    if (chunk == batch) return mrr_chain(p, L, rows, a, b, kf, ki, out, ws, w, batch, s, split ? &kp : nullptr);
     MrrStreams* ms = mrr_streams(p->device);
     if (!ms) return fail(TROYN_E_INVALID, std::string(P) + " cannot create the internal streams");
     const MrrLayout wc = mrr_layout(p, L, chunk);        // two chunk-sized workspaces side by side in the caller's workspace
     const size_t slot_words = wc.keys_f64;               // a chunk's intermediates end where its (unused) key area would start
     if ((size_t)ns * slot_words > w.keys_f64) {
         if (split) return fail(TROYN_E_INVALID, std::string(P) + " internal: chunk layout");      // unreachable: split implies one chunk
-        return mrr_chain(p, L, a, b, kf, ki, out, ws, w, batch, s);
+        return mrr_chain(p, L, rows, a, b, kf, ki, out, ws, w, batch, s);
     }
     HIP_TRY(hipEventRecord(ms->fork, s));
     for (int q = 0; q < ns; q++) HIP_TRY(hipStreamWaitEvent(ms->s[q], ms->fork, 0));
@@ -1729,7 +1772,7 @@ extern "C" int troyn_ckks_multiply_relinearize_rescale(const troyn_plan* p, uint
     while (done < batch) {
         const size_t c = std::min(chunk, batch - done);
         const int q = (int)(idx % (size_t)ns);
-        if ((rc = mrr_chain(p, L, a + done * 2 * (size_t)L * n, b + done * 2 * (size_t)L * n, kf, ki, out + done * 2 * (size_t)(L - 1) * n,
+        if ((rc = mrr_chain(p, L, rows, a + done * 2 * (size_t)L * n, b + done * 2 * (size_t)L * n, kf, ki, out + done * 2 * (size_t)(L - 1) * n,
                             ws + (size_t)q * slot_words, wc, c, ms->s[q]))) break;
         done += c; idx++;
     }
