@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -353,14 +354,97 @@ static DevModulus make_dev_modulus(u64 q, unsigned log_n, bool with_inv_n) {
     return m;
 }
 
+static inline ulonglong2 shoup_pair(u64 w, u64 m) {
+    const host::Shoup s = host::shoup(w % m, m);
+    return make_ulonglong2(s.operand, s.quotient);
+}
+
+static auto element_of(const std::vector<u64>& v) { return [&v](size_t i) { return v[i]; }; }
+
+// (q/q_i)^-1 mod q_i for every prime of a base (RNSBase::initialize); 1 for a base of one prime
+static int inv_punctured(const std::vector<u64>& q, std::vector<u64>& out) {
+    out.assign(q.size(), 1);
+    for (size_t i = 0; q.size() > 1 && i < q.size(); i++)
+        if (!host::invmod(host::product_mod(q, i, q[i]) % q[i], q[i], out[i])) return fail(TROYN_E_MODULUS, "[RNSBase::initialize] RNSBase product is not invertible.");
+    return TROYN_OK;
+}
+
+template <typename T>
+static int upload_vector(T** dev, const std::vector<T>& v) {
+    HIP_TRY(hipMalloc(dev, v.size() * sizeof(T)));
+    HIP_TRY(hipMemcpy(*dev, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return TROYN_OK;
+}
+
+// The constant tables of one handle (troyn_behz, troyn_bgv, troyn_ring2k): rows are appended on the host and uploaded as one allocation.
+// An append returns the offset (in words) of its row; bind() names the pointer that upload() sets to that row.  A row of 16-byte elements starts on 16 bytes.
+struct ConstBlob {
+    std::vector<u64> host;
+    std::vector<std::function<void(const u64*)>> bound;
+    std::vector<u64>& aligned() { if (host.size() & 1) host.push_back(0); return host; }
+    template <typename F>
+    size_t words(size_t count, F f) {
+        const size_t off = host.size();
+        for (size_t i = 0; i < count; i++) host.push_back(f(i));
+        return off;
+    }
+    // (operand, quotient) of f(i) mod modulus_of(i)
+    template <typename F, typename M>
+    size_t shoup(size_t count, F f, M modulus_of) {
+        const size_t off = aligned().size();
+        for (size_t i = 0; i < count; i++) { const ulonglong2 s = shoup_pair(f(i), modulus_of(i)); host.push_back(s.x); host.push_back(s.y); }
+        return off;
+    }
+    template <typename T> static const T* at(const u64* dev, size_t off) { return reinterpret_cast<const T*>(dev + off); }
+    template <typename T> void bind(const T** field, size_t off) { bound.push_back([=](const u64* dev) { *field = at<T>(dev, off); }); }
+    int upload(int device, u64** dev) const {
+        HIP_TRY(hipSetDevice(device));
+        if (int rc = upload_vector(dev, host)) return rc;
+        for (const auto& set : bound) set(*dev);
+        return TROYN_OK;
+    }
+};
+
+// One value per twiddle of every modulus, [K][N]: conv(i, w) of table entry w of modulus i
+template <typename T, typename Conv>
+static std::vector<T> twiddle_rows(const troyn_plan* p, bool inverse, Conv conv) {
+    std::vector<T> rows;
+    rows.reserve((size_t)p->K * p->n);
+    for (size_t i = 0; i < p->K; i++)
+        for (const host::Shoup& w : inverse ? p->tables[i].inv : p->tables[i].fwd) rows.push_back(conv(i, w));
+    return rows;
+}
+
+// Round vectors of ksmac2_kernel / ksmaci_kernel, the forward twiddles in the order their register rounds read them: slot s = (1 << lvl) + g of the
+// thread (round 2) / of the index bits above bit 9 (round 1) holds the twiddle of butterfly group g of the round's layer lvl (ksmac_kernels.hpp).
+// r1: [K][N/1024][32], r2: [K][N] lane-interleaved (ksm_perm); conv(i, w) as in twiddle_rows.
+template <typename T, typename Conv>
+static void round_vectors(const troyn_plan* p, Conv conv, std::vector<T>& r1, std::vector<T>& r2) {
+    const size_t K = p->K, n = p->n, r1n = (n >> 10) * 32;
+    r1.assign(K * r1n, conv(0, host::Shoup{0, 0}));
+    r2.assign(K * n, conv(0, host::Shoup{0, 0}));
+    for (size_t i = 0; i < K; i++) {
+        const auto& fw = p->tables[i].fwd;
+        for (unsigned s = 1; s < 32; s++) {
+            unsigned lvl = 0;
+            while ((2u << lvl) <= s) lvl++;
+            const unsigned g = s - (1u << lvl);
+            for (size_t th = 0; th < (n >> 10); th++) r1[i * r1n + th * 32 + s] = conv(i, fw[(((n >> 10) + th) << lvl) + g]);
+            for (size_t T_ = 0; T_ < (n >> 5); T_++) r2[i * n + ksm_perm((unsigned)(T_ * 32 + s))] = conv(i, fw[(((n >> 5) + T_) << lvl) + g]);
+        }
+    }
+}
+
 static int plan_upload(troyn_plan* p) {
     const size_t K = p->K, n = p->n;
     std::vector<DevModulus> mods(K);
+    p->small_modulus.assign(K, 0);
     for (size_t i = 0; i < K; i++) {
         mods[i] = make_dev_modulus(p->moduli[i], p->log_n, true);
         mods[i].inv_n_op = p->tables[i].inv_degree.operand;
         mods[i].inv_n_quo = p->tables[i].inv_degree.quotient;
-        if (p->moduli[i] < F64_MODULUS_LIMIT && n >= 2) {
+        p->small_modulus[i] = p->moduli[i] < F64_MODULUS_LIMIT;
+        if (p->small_modulus[i] && n >= 2) {
             // the final Gentleman-Sande layer has one twiddle (table index N-1); N^-1 is folded into it
             const u64 nw = host::mulmod(p->tables[i].inv[n - 1].operand, p->tables[i].inv_degree.operand, p->moduli[i]);
             mods[i].inv_n_w_d = (double)nw;
@@ -368,78 +452,32 @@ static int plan_upload(troyn_plan* p) {
         }
     }
     std::vector<ulonglong2> inv_last((K + 1) * K, make_ulonglong2(0, 0));
-    for (size_t L = 2; L <= K; L++) {
+    for (size_t L = 2; L <= K; L++)
         for (size_t i = 0; i + 1 < L; i++) {
             u64 inv = 0;
             if (!host::invmod(p->moduli[L - 1] % p->moduli[i], p->moduli[i], inv))
                 return fail(TROYN_E_MODULUS, "[troyn_plan_create] Unable to invert q[last] mod q[i].");
-            host::Shoup s = host::shoup(inv, p->moduli[i]);
-            inv_last[L * K + i] = make_ulonglong2(s.operand, s.quotient);
+            inv_last[L * K + i] = shoup_pair(inv, p->moduli[i]);
         }
-    }
-    HIP_TRY(hipMalloc(&p->d_mods, K * sizeof(DevModulus)));
-    HIP_TRY(hipMalloc(&p->d_fwd, K * n * sizeof(ulonglong2)));
-    HIP_TRY(hipMalloc(&p->d_inv, K * n * sizeof(ulonglong2)));
-    HIP_TRY(hipMalloc(&p->d_inv_last, inv_last.size() * sizeof(ulonglong2)));
-    HIP_TRY(hipMemcpy(p->d_mods, mods.data(), K * sizeof(DevModulus), hipMemcpyHostToDevice));
-    for (size_t i = 0; i < K; i++) {
-        static_assert(sizeof(host::Shoup) == sizeof(ulonglong2), "Shoup layout");
-        HIP_TRY(hipMemcpy(p->d_fwd + i * n, p->tables[i].fwd.data(), n * sizeof(ulonglong2), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(p->d_inv + i * n, p->tables[i].inv.data(), n * sizeof(ulonglong2), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(p->d_inv_last, inv_last.data(), inv_last.size() * sizeof(ulonglong2), hipMemcpyHostToDevice));
-    // FP64 twiddles (w as an exact double) for the moduli below 2^50
-    p->small_modulus.assign(K, 0);
-    HIP_TRY(hipMalloc(&p->d_fwd_f64, K * n * sizeof(double)));
-    HIP_TRY(hipMalloc(&p->d_inv_f64, K * n * sizeof(double)));
-    HIP_TRY(hipMemset(p->d_fwd_f64, 0, K * n * sizeof(double)));
-    HIP_TRY(hipMemset(p->d_inv_f64, 0, K * n * sizeof(double)));
-    std::vector<double> tmp(n);
-    for (size_t i = 0; i < K; i++) {
-        const u64 q = p->moduli[i];
-        if (q >= F64_MODULUS_LIMIT) continue;
-        p->small_modulus[i] = 1;
-        for (size_t x = 0; x < n; x++) tmp[x] = (double)p->tables[i].fwd[x].operand;
-        HIP_TRY(hipMemcpy(p->d_fwd_f64 + i * n, tmp.data(), n * sizeof(double), hipMemcpyHostToDevice));
-        for (size_t x = 0; x < n; x++) tmp[x] = (double)p->tables[i].inv[x].operand;
-        HIP_TRY(hipMemcpy(p->d_inv_f64 + i * n, tmp.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    }
+    static_assert(sizeof(host::Shoup) == sizeof(ulonglong2), "Shoup layout");
+    // the integer kernels read (operand, quotient); the FP64 ones w as an exact double, for the moduli below 2^50 (zeros otherwise)
+    auto pair = [](size_t, const host::Shoup& w) { return make_ulonglong2(w.operand, w.quotient); };
+    auto f64 = [&](size_t i, const host::Shoup& w) { return p->small_modulus[i] ? (double)w.operand : 0.0; };
+    int rc;
+    if ((rc = upload_vector(&p->d_mods, mods))) return rc;
+    if ((rc = upload_vector(&p->d_fwd, twiddle_rows<ulonglong2>(p, false, pair)))) return rc;
+    if ((rc = upload_vector(&p->d_inv, twiddle_rows<ulonglong2>(p, true, pair)))) return rc;
+    if ((rc = upload_vector(&p->d_inv_last, inv_last))) return rc;
+    if ((rc = upload_vector(&p->d_fwd_f64, twiddle_rows<double>(p, false, f64)))) return rc;
+    if ((rc = upload_vector(&p->d_inv_f64, twiddle_rows<double>(p, true, f64)))) return rc;
     if (p->log_n >= 13 && p->log_n <= 15) {
-        // round vectors of ksmac2_kernel: slot s = (1 << lvl) + g of the thread (round 2) / of the index bits above
-        // bit 9 (round 1) holds the twiddle of butterfly group g of the round's layer lvl (ksmac_kernels.hpp)
-        const size_t r1n = (n >> 10) * 32;
-        std::vector<double> r1(K * r1n, 0.0), r2(K * n, 0.0);
-        for (size_t i = 0; i < K; i++) {
-            if (!p->small_modulus[i]) continue;
-            const auto& fw = p->tables[i].fwd;
-            for (unsigned s = 1; s < 32; s++) {
-                unsigned lvl = 0;
-                while ((2u << lvl) <= s) lvl++;
-                const unsigned g = s - (1u << lvl);
-                for (size_t th = 0; th < (n >> 10); th++) r1[i * r1n + th * 32 + s] = (double)fw[(((n >> 10) + th) << lvl) + g].operand;
-                for (size_t T = 0; T < (n >> 5); T++) r2[i * n + ksm_perm((unsigned)(T * 32 + s))] = (double)fw[(((n >> 5) + T) << lvl) + g].operand;
-            }
-        }
-        HIP_TRY(hipMalloc(&p->d_fwd_r1, r1.size() * sizeof(double)));
-        HIP_TRY(hipMalloc(&p->d_fwd_r2, r2.size() * sizeof(double)));
-        HIP_TRY(hipMemcpy(p->d_fwd_r1, r1.data(), r1.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(p->d_fwd_r2, r2.data(), r2.size() * sizeof(double), hipMemcpyHostToDevice));
+        std::vector<double> r1, r2;
+        round_vectors(p, f64, r1, r2);
+        if ((rc = upload_vector(&p->d_fwd_r1, r1)) || (rc = upload_vector(&p->d_fwd_r2, r2))) return rc;
         // the integer copies (ksmaci_kernel), every modulus: a chain of narrow moduli can be forced onto the integer kernels (TROYN_NTT_ARITH=u64)
-        std::vector<ulonglong2> r1i(K * r1n, make_ulonglong2(0, 0)), r2i(K * n, make_ulonglong2(0, 0));
-        for (size_t i = 0; i < K; i++) {
-            const auto& fw = p->tables[i].fwd;
-            for (unsigned s = 1; s < 32; s++) {
-                unsigned lvl = 0;
-                while ((2u << lvl) <= s) lvl++;
-                const unsigned g = s - (1u << lvl);
-                for (size_t th = 0; th < (n >> 10); th++) { const auto& w = fw[(((n >> 10) + th) << lvl) + g]; r1i[i * r1n + th * 32 + s] = make_ulonglong2(w.operand, w.quotient); }
-                for (size_t T = 0; T < (n >> 5); T++) { const auto& w = fw[(((n >> 5) + T) << lvl) + g]; r2i[i * n + ksm_perm((unsigned)(T * 32 + s))] = make_ulonglong2(w.operand, w.quotient); }
-            }
-        }
-        HIP_TRY(hipMalloc(&p->d_fwd_r1i, r1i.size() * sizeof(ulonglong2)));
-        HIP_TRY(hipMalloc(&p->d_fwd_r2i, r2i.size() * sizeof(ulonglong2)));
-        HIP_TRY(hipMemcpy(p->d_fwd_r1i, r1i.data(), r1i.size() * sizeof(ulonglong2), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(p->d_fwd_r2i, r2i.data(), r2i.size() * sizeof(ulonglong2), hipMemcpyHostToDevice));
+        std::vector<ulonglong2> r1i, r2i;
+        round_vectors(p, pair, r1i, r2i);
+        if ((rc = upload_vector(&p->d_fwd_r1i, r1i)) || (rc = upload_vector(&p->d_fwd_r2i, r2i))) return rc;
     }
     return TROYN_OK;
 }
@@ -1826,23 +1864,18 @@ extern "C" int troyn_bgv_create(troyn_bgv** out, const troyn_plan* plan, uint32_
     if (t < 2 || (t >> 61) != 0) return fail(TROYN_E_MODULUS, "[troyn_bgv_create] BGV needs a plain modulus in [2, 2^61).");
     std::unique_ptr<troyn_bgv, int (*)(troyn_bgv*)> b(new troyn_bgv, troyn_bgv_destroy);
     b->plan = plan; b->L = L; b->t = t;
-    std::vector<u64> q(plan->moduli.begin(), plan->moduli.begin() + L);
-    std::vector<u64> blob;
-    for (size_t i = 0; i < L; i++) {
-        u64 inv = 1;
-        if (L > 1 && !host::invmod(host::product_mod(q, i, q[i]) % q[i], q[i], inv)) return fail(TROYN_E_MODULUS, "[RNSBase::initialize] RNSBase product is not invertible.");
-        host::Shoup sh = host::shoup(inv % q[i], q[i]);
-        blob.push_back(sh.operand); blob.push_back(sh.quotient);
-    }
-    for (size_t i = 0; i < L; i++) blob.push_back(host::product_mod(q, i, t));
+    const std::vector<u64> q(plan->moduli.begin(), plan->moduli.begin() + L);
+    std::vector<u64> inv_punc;
+    if (int rc = inv_punctured(q, inv_punc)) return rc;
+    ConstBlob blob;
+    blob.shoup(L, element_of(inv_punc), element_of(q));
+    blob.words(L, [&](size_t i) { return host::product_mod(q, i, t); });
     b->q_mod_t = host::product_mod(q, SIZE_MAX, t);
     u64 inv = 1;
     b->can_divide = host::invmod(q[L - 1] % t, t, inv);       // "[RNSTool::RNSTool] Unable to invert q[last] mod t."
     b->inv_q_last_mod_t = b->can_divide ? inv : 1;
     b->t_mod = make_dev_modulus(t, plan->log_n, false);
-    HIP_TRY(hipSetDevice(plan->device));
-    HIP_TRY(hipMalloc(&b->d_consts, blob.size() * sizeof(u64)));
-    HIP_TRY(hipMemcpy(b->d_consts, blob.data(), blob.size() * sizeof(u64), hipMemcpyHostToDevice));
+    if (int rc = blob.upload(plan->device, &b->d_consts)) return rc;
     *out = b.release();
     return TROYN_OK;
 }
@@ -1995,6 +2028,179 @@ extern "C" int troyn_behz_destroy(troyn_behz* b) {
     return TROYN_OK;
 }
 
+static const u64 BEHZ_M_TILDE = (u64)1 << 32;
+
+// troyn_behz_create, step by step
+struct BehzBase {
+    std::vector<u64> B, bsk;      // the base the multiply works in, and B + {m_sk}
+    u64 m_sk = 0;
+    bool aux50 = false;           // B and m_sk are primes below 2^50
+};
+
+// The working base.  BEHZ's result does not depend on the auxiliary primes: the conversion q -> Bsk yields the integer x + alpha q
+// (alpha < L, a function of the residues mod q only), the small Montgomery reduction works modulo m_tilde = 2^32, the floor is an exact
+// integer division in base Bsk and the Shenoy-Kumaresan conversion back to q is exact as long as the value fits B -- all statements about
+// integers, true for ANY base whose product is at least the reference's (utils/rns_tool.cu:52-80 sizes B as |q| or |q| + 1 primes of 61 bits).
+// When every q_i is below 2^50 the 61-bit base is the only reason half of the multiply's transforms, its tensor product and its two
+// conversions run on the integer butterflies (27.5 issue slots against 8 FP64 instructions): take instead NB primes BELOW 2^50 with
+//     prod(B') >= 2^(61 Bn)   and   prod(B') m_sk' >= 2^(61 (Bn + 1)),
+// i.e. at least the capacity of any base the reference could have picked, so that every transform of the multiply takes the exact-FP64
+// policy.  The oracle keeps the reference's base; equality of the final residues on every BEHZ test is the proof.
+// MEASURED (round 4, BASELINE config 4, profiles/r04_cfg4_ab.txt): bit-identical results, and no gain -- the tensor kernels drop from 1.33 to
+// 1.01 ms per 64 products, but 13 + 1 primes instead of 10 + 1 make both conversions 29 % longer (0.66 -> 0.83 ms for the floor alone) and
+// add three limbs to every strided pass: 14.0 k against 14.2 k mul+relin ops/s.  ROUND 5: 13 + 1 came from asking for the capacity of the
+// reference's base itself; the reference's own size criterion (below) is met by 11 + 1 primes -- one row more than the 61-bit base instead of
+// three: tensor launches 1.33 -> 0.95 ms per 64 products, 14.15 k -> 14.7 k ops/s same box.  It is the DEFAULT whenever it applies (every q_i
+// below 2^50, second-generation conversions); TROYN_BEHZ_BASE=ref keeps the reference's base (read here).
+static int behz_choose_base(troyn_behz* b, const std::vector<u64>& q, BehzBase& base) {
+    const troyn_plan* plan = b->plan;
+    // auxiliary base sizes and primes: utils/rns_tool.cu:52-80
+    const size_t L = q.size();
+    size_t Bn = L;
+    if (32 + host::bit_count(b->t) + host::product_bit_count(q) >= 61 * L + 61) Bn++;
+    std::vector<u64> primes, fresh;
+    try {
+        primes = host::get_primes(2 * (u64)plan->n, 61, Bn + 2);
+    } catch (const std::exception& e) {
+        return fail(TROYN_E_MODULUS, e.what());
+    }
+    base.m_sk = primes[0];
+    b->gamma = primes[1];         // decrypt side only
+    base.B.assign(primes.begin() + 2, primes.begin() + 2 + Bn);
+    b->bsk_values = base.B; b->bsk_values.push_back(base.m_sk);      // the reference's base (troyn_behz_get_base_Bsk: known-answer hook), whatever base the multiply works in
+    base.aux50 = !plan->opt.behz_base_ref && !plan->opt.behz_v1 && L <= BEHZ2_MAX_L && plan->log_n >= 10;
+    for (u64 v : q) if (v >= F64_MODULUS_LIMIT) base.aux50 = false;
+    if (base.aux50) try {
+        for (u64 c : host::get_primes(2 * (u64)plan->n, 50, plan->K + 2 * (Bn + 1) + 8))
+            if (std::find(plan->moduli.begin(), plan->moduli.end(), c) == plan->moduli.end()) fresh.push_back(c);
+    } catch (const std::exception&) { fresh.clear(); }
+    // Size of the base: the reference's own criterion (utils/rns_tool.cu:50-62: K n t q^2 < q prod(B) m_sk with 32 bits reserved for K n, i.e.
+    // bits(prod(B) m_sk) > 32 + bits(t) + bits(q); it states it for 61-bit primes as 61 (#B + 1)) evaluated on the ACTUAL product of the primes
+    // taken, with two more bits of margin.  (Round 4 asked for the capacity of the reference's base itself, 2^(61 (Bn + 1)): 13 + 1 primes at
+    // BASELINE config 4 where 11 + 1 satisfy the criterion -- every conversion and strided pass scales with the number of rows.)
+    const size_t need_bits = 32 + (size_t)host::product_bit_count(std::vector<u64>{b->t}) + (size_t)host::product_bit_count(q) + 2;
+    auto enough = [&](const std::vector<u64>& B) {
+        std::vector<u64> with_sk = B; with_sk.push_back(fresh[0]);      // fresh[0] becomes m_sk'
+        return (size_t)host::product_bit_count(with_sk) > need_bits;
+    };
+    std::vector<u64> B2;
+    for (size_t next = 1; next < fresh.size(); next++) {
+        B2.push_back(fresh[next]);
+        if (enough(B2)) break;
+    }
+    base.aux50 = !B2.empty() && enough(B2) && B2.size() <= 32;
+    if (base.aux50) { base.B = B2; base.m_sk = fresh[0]; }
+    base.bsk = base.B; base.bsk.push_back(base.m_sk);
+    // Shenoy-Kumaresan (rns_tool.cu:1000-1036): the correction term alpha_sk of the conversion B -> q is recovered modulo m_sk and satisfies
+    // |alpha_sk| <= |B| (+ the lambda of the fast floor); it is read off a centred residue, so m_sk must exceed twice that -- any prime of 50 or
+    // 61 bits does by ~45 bits, but the working base is chosen above, so state what it relies on
+    if (base.m_sk < 2 * ((u64)base.B.size() + 2) + 1) return fail(TROYN_E_MODULUS, "[troyn_behz_create] m_sk is too small for the Shenoy-Kumaresan correction of this base");
+    b->Bn = (unsigned)base.B.size(); b->Bsk = (unsigned)base.bsk.size(); b->aux50 = base.aux50;
+    return TROYN_OK;
+}
+
+// the auxiliary plan: NTT tables of the working base; it takes the options its plan has now and follows later changes (behz_follow_options)
+static int behz_create_aux_plan(troyn_behz* b, const troyn_plan* plan, const BehzBase& base) {
+    const int rc = troyn_plan_create(&b->aux, plan->device, plan->log_n, (uint32_t)base.bsk.size(), reinterpret_cast<const uint64_t*>(base.bsk.data()), nullptr);
+    if (rc != TROYN_OK) return rc;
+    b->aux->opt = plan->opt;
+    b->aux_gen.store(plan->opt_gen.load(std::memory_order_acquire), std::memory_order_release);
+    return TROYN_OK;
+}
+
+// multiply side (first-generation kernels; the second generation shares q_mt_inv_punc and q_t_inv_punc)
+static int behz_multiply_tables(troyn_behz* b, const std::vector<u64>& q, const BehzBase& base, ConstBlob& blob) {
+    const std::vector<u64>& B = base.B;
+    const std::vector<u64>& bsk = base.bsk;
+    const size_t L = q.size(), Bn = B.size(), Bsk = bsk.size();
+    const u64 mt = BEHZ_M_TILDE, m_sk = base.m_sk, t = b->t;
+    BehzDev& d = b->dev;
+    auto q_of = element_of(q), bsk_of = element_of(bsk);
+    // every inverse once
+    std::vector<u64> q_inv, B_inv, prod_q(Bsk), inv_mt(Bsk), inv_prod_q(Bsk);
+    if (int rc = inv_punctured(q, q_inv)) return rc;
+    for (size_t bi = 0; bi < Bsk; bi++) prod_q[bi] = host::product_mod(q, SIZE_MAX, bsk[bi]);
+    for (size_t bi = 0; bi < Bsk; bi++)
+        if (!host::invmod(mt % bsk[bi], bsk[bi], inv_mt[bi])) return fail(TROYN_E_MODULUS, "[RNSTool::RNSTool] Unable to invert m_tilde.");
+    for (size_t bi = 0; bi < Bsk; bi++)
+        if (!host::invmod(prod_q[bi] % bsk[bi], bsk[bi], inv_prod_q[bi])) return fail(TROYN_E_MODULUS, "[RNSTool::RNSTool] Unable to invert base_q product.");
+    if (int rc = inv_punctured(B, B_inv)) return rc;
+    blob.bind(&d.q_inv_punc, blob.shoup(L, element_of(q_inv), q_of));
+    // the scalar factor that precedes a base conversion folded into its first step: (x * c mod q_i) * inv_punc_i mod q_i
+    // = x * (c * inv_punc_i mod q_i) mod q_i -- one Shoup multiply instead of a Barrett-128 product followed by one (c = m_tilde for
+    // the lift, evaluator.cu:52-56 + rns_tool.cu:1083-1094; c = t for the floor, evaluator.cu:95-100)
+    blob.bind(&d.q_mt_inv_punc, blob.shoup(L, [&](size_t i) { return host::mulmod(mt % q[i], q_inv[i], q[i]); }, q_of));
+    blob.bind(&d.q_t_inv_punc, blob.shoup(L, [&](size_t i) { return host::mulmod(t % q[i], q_inv[i], q[i]); }, q_of));
+    blob.bind(&d.q_to_bsk, blob.words(Bsk * L, [&](size_t k) { return host::product_mod(q, k % L, bsk[k / L]); }));
+    blob.bind(&d.q_to_mt, blob.words(L, [&](size_t i) { return host::product_mod(q, i, mt); }));
+    blob.bind(&d.prod_q_mod_bsk, blob.shoup(Bsk, element_of(prod_q), bsk_of));
+    blob.bind(&d.inv_mt_mod_bsk, blob.shoup(Bsk, element_of(inv_mt), bsk_of));
+    blob.bind(&d.inv_prod_q_mod_bsk, blob.shoup(Bsk, element_of(inv_prod_q), bsk_of));
+    // (x * t - f) * q^-1 = x * (t q^-1) - f * q^-1 mod p_b: the floor's multiplication by t folded into the division by q
+    blob.bind(&d.t_inv_prod_q_mod_bsk, blob.shoup(Bsk, [&](size_t bi) { return host::mulmod(t % bsk[bi], inv_prod_q[bi], bsk[bi]); }, bsk_of));
+    blob.bind(&d.B_inv_punc, blob.shoup(Bn, element_of(B_inv), element_of(B)));
+    blob.bind(&d.B_to_q, blob.words(L * Bn, [&](size_t k) { return host::product_mod(B, k % Bn, q[k / Bn]); }));
+    blob.bind(&d.B_to_msk, blob.words(Bn, [&](size_t bi) { return host::product_mod(B, bi, m_sk); }));
+    blob.bind(&d.prod_B_mod_q, blob.shoup(L, [&](size_t i) { return host::product_mod(B, SIZE_MAX, q[i]); }, q_of));
+    blob.bind(&d.neg_prod_B_mod_q, blob.shoup(L, [&](size_t i) { return q[i] - host::product_mod(B, SIZE_MAX, q[i]); }, q_of));
+    u64 inv;
+    if (!host::invmod(host::product_mod(q, SIZE_MAX, mt) % mt, mt, inv)) return fail(TROYN_E_MODULUS, "[RNSTool::RNSTool] Unable to invert base_q product.");
+    d.neg_inv_prod_q_mod_mt = shoup_pair(mt - inv, mt);
+    if (!host::invmod(host::product_mod(B, SIZE_MAX, m_sk) % m_sk, m_sk, inv)) return fail(TROYN_E_MODULUS, "[RNSTool::RNSTool] Unable to invert base_B product.");
+    d.inv_prod_B_mod_msk = shoup_pair(inv, m_sk);
+    return TROYN_OK;
+}
+
+// second-generation conversion tables (split matrices with the scalar factors folded in); sets have2 / smallq
+static void behz_second_generation_tables(troyn_behz* b, const std::vector<u64>& q, const BehzBase& base, ConstBlob& blob) {
+    Behz2Offsets o;
+    Behz2Dev& e = b->dev2;
+    b->have2 = (base.B.size() == q.size() || base.aux50) && q.size() <= BEHZ2_MAX_L;
+    b->smallq = true;
+    for (u64 v : q) { if (v >> 60) b->have2 = false; if (v >= F64_MODULUS_LIMIT) b->smallq = false; }
+    if (b->have2) b->have2 = behz2_build_tables(q, base.B, base.m_sk, b->t, b->smallq, blob.aligned(), o);
+    if (!b->have2) return;
+    e.rs = o.rs;
+    blob.bind(&e.lift_mt, o.lift_mt); blob.bind(&e.lift_rows, o.lift_rows); blob.bind(&e.lift_rc, o.lift_rc);
+    blob.bind(&e.fa_rows, o.fa_rows); blob.bind(&e.fa_rc, o.fa_rc);
+    blob.bind(&e.fb_cols, o.fb_cols); blob.bind(&e.fb_rc, o.fb_rc);
+}
+
+// encrypt / decrypt side: constants of the same RNSTool / ContextData (context_data.cu:226-247, rns_tool.cu:168-211)
+static void behz_decrypt_tables(troyn_behz* b, const std::vector<u64>& q, ConstBlob& blob) {
+    const u64 t = b->t, gamma = b->gamma;
+    const size_t L = q.size();
+    auto q_of = element_of(q);
+    std::vector<u64> q_over_t = host::big_product(q);       // floor(q / t) as a multi-word integer
+    b->q_mod_t = host::big_divmod_small(q_over_t, t);
+    blob.bind(&b->d_delta, blob.shoup(L, [&](size_t i) { return host::big_mod_small(q_over_t, q[i]); }, q_of));
+    blob.bind(&b->d_prod_t_gamma_mod_q, blob.shoup(L, [&](size_t i) { return host::mulmod(t % q[i], gamma % q[i], q[i]); }, q_of));
+    blob.bind(&b->d_q_to_t, blob.words(L, [&](size_t i) { return host::product_mod(q, i, t); }));
+    blob.bind(&b->d_q_to_gamma, blob.words(L, [&](size_t i) { return host::product_mod(q, i, gamma); }));
+    u64 inv_gamma = 0, inv_q_t = 0, inv_q_gamma = 0;
+    b->decrypt_ready = host::invmod(gamma % t, t, inv_gamma);                // "[RNSTool::RNSTool] Unable to invert gamma mod t."
+    b->decrypt_ready &= host::invmod(host::product_mod(q, SIZE_MAX, t) % t, t, inv_q_t);
+    b->decrypt_ready &= host::invmod(host::product_mod(q, SIZE_MAX, gamma) % gamma, gamma, inv_q_gamma);
+    b->inv_gamma_mod_t = shoup_pair(inv_gamma, t);
+    b->neg_inv_q_mod_t = shoup_pair(t - inv_q_t, t);
+    b->neg_inv_q_mod_gamma = shoup_pair(gamma - inv_q_gamma, gamma);
+    b->t_mod = make_dev_modulus(t, b->plan->log_n, false);
+    b->gamma_mod = make_dev_modulus(gamma, b->plan->log_n, false);
+}
+
+// what the kernels' argument blocks hold besides the table rows (those were bound where they were built)
+static void behz_wire(troyn_behz* b) {
+    const troyn_plan* plan = b->plan;
+    BehzDev& d = b->dev;
+    d.L = b->L; d.Bn = b->Bn; d.Bsk = b->Bsk; d.n = plan->n; d.t = b->t;
+    d.q_mods = plan->d_mods; d.bsk_mods = b->aux->d_mods;
+    d.m_tilde = make_dev_modulus(BEHZ_M_TILDE, plan->log_n, false);
+    if (!b->have2) return;
+    Behz2Dev& e = b->dev2;
+    e.L = b->L; e.n = plan->n; e.NB = b->Bn;
+    e.q_mods = plan->d_mods; e.q_mt_inv_punc = d.q_mt_inv_punc; e.q_t_inv_punc = d.q_t_inv_punc;
+}
+
 extern "C" int troyn_behz_create(troyn_behz** out, const troyn_plan* plan, uint32_t L, uint64_t t) {
     if (!out || !plan) return fail(TROYN_E_INVALID, "[troyn_behz_create] null argument");
     *out = nullptr;
@@ -2002,239 +2208,18 @@ extern "C" int troyn_behz_create(troyn_behz** out, const troyn_plan* plan, uint3
     if (t == 0 || (t >> 61) != 0 || t == 1) return fail(TROYN_E_MODULUS, "[troyn_behz_create] BFV needs a plain modulus in [2, 2^61).");
     std::unique_ptr<troyn_behz, int (*)(troyn_behz*)> b(new troyn_behz, troyn_behz_destroy);
     b->plan = plan; b->L = L; b->t = t;
-    const unsigned n = plan->n;
-    std::vector<u64> q(plan->moduli.begin(), plan->moduli.begin() + L);
-    // auxiliary base sizes and primes: utils/rns_tool.cu:52-80
-    size_t total_bits = host::product_bit_count(q);
-    size_t Bn = L;
-    if (32 + host::bit_count(t) + total_bits >= 61 * (size_t)L + 61) Bn++;
-    const size_t Bsk_ref = Bn + 1;
-    std::vector<u64> primes;
-    try {
-        primes = host::get_primes(2 * (u64)n, 61, Bsk_ref + 1);
-    } catch (const std::exception& e) {
-        return fail(TROYN_E_MODULUS, e.what());
-    }
-    u64 m_sk = primes[0];   // primes[1] = gamma (decrypt side only)
-    std::vector<u64> B(primes.begin() + 2, primes.begin() + 2 + Bn);
-    std::vector<u64> bsk = B; bsk.push_back(m_sk);
-    const u64 mt = (u64)1 << 32;
-    b->bsk_values = bsk;          // the reference's base (troyn_behz_get_base_Bsk: known-answer hook), whatever base the multiply works in
-    // ---- working base.  BEHZ's result does not depend on the auxiliary primes: the conversion q -> Bsk yields the integer x + alpha q
-    // (alpha < L, a function of the residues mod q only), the small Montgomery reduction works modulo m_tilde = 2^32, the floor is an exact
-    // integer division in base Bsk and the Shenoy-Kumaresan conversion back to q is exact as long as the value fits B -- all statements about
-    // integers, true for ANY base whose product is at least the reference's (utils/rns_tool.cu:52-80 sizes B as |q| or |q| + 1 primes of 61 bits).
-    // When every q_i is below 2^50 the 61-bit base is the only reason half of the multiply's transforms, its tensor product and its two
-    // conversions run on the integer butterflies (27.5 issue slots against 8 FP64 instructions): take instead NB primes BELOW 2^50 with
-    //     prod(B') >= 2^(61 Bn)   and   prod(B') m_sk' >= 2^(61 (Bn + 1)),
-    // i.e. at least the capacity of any base the reference could have picked, so that every transform of the multiply takes the exact-FP64
-    // policy.  The oracle keeps the reference's base; equality of the final residues on every BEHZ test is the proof.
-    // MEASURED (round 4, BASELINE config 4, profiles/r04_cfg4_ab.txt): bit-identical results, and no gain -- the tensor kernels drop from 1.33 to
-    // 1.01 ms per 64 products, but 13 + 1 primes instead of 10 + 1 make both conversions 29 % longer (0.66 -> 0.83 ms for the floor alone) and
-    // add three limbs to every strided pass: 14.0 k against 14.2 k mul+relin ops/s.  ROUND 5: 13 + 1 came from asking for the capacity of the
-    // reference's base itself; the reference's own size criterion (below) is met by 11 + 1 primes -- one row more than the 61-bit base instead of
-    // three: tensor launches 1.33 -> 0.95 ms per 64 products, 14.15 k -> 14.7 k ops/s same box.  It is the DEFAULT whenever it applies (every q_i
-    // below 2^50, second-generation conversions); TROYN_BEHZ_BASE=ref keeps the reference's base (read here).
-    bool aux50 = !plan->opt.behz_base_ref;
-    for (u64 v : q) if (v >= F64_MODULUS_LIMIT) aux50 = false;
-    if (plan->opt.behz_v1 || L > BEHZ2_MAX_L || plan->log_n < 10) aux50 = false;
-    if (aux50) {
-        try {
-            std::vector<u64> cand = host::get_primes(2 * (u64)n, 50, plan->K + 2 * Bsk_ref + 8);
-            std::vector<u64> fresh;
-            for (u64 c : cand) if (std::find(plan->moduli.begin(), plan->moduli.end(), c) == plan->moduli.end()) fresh.push_back(c);
-            std::vector<u64> B2;
-            size_t next = 1;                                  // fresh[0] becomes m_sk'
-            // Size of the base: the reference's own criterion (utils/rns_tool.cu:50-62: K n t q^2 < q prod(B) m_sk with 32 bits reserved for K n, i.e.
-            // bits(prod(B) m_sk) > 32 + bits(t) + bits(q); it states it for 61-bit primes as 61 (#B + 1)) evaluated on the ACTUAL product of the primes
-            // taken, with two more bits of margin.  (Round 4 asked for the capacity of the reference's base itself, 2^(61 (Bn + 1)): 13 + 1 primes at
-            // BASELINE config 4 where 11 + 1 satisfy the criterion -- every conversion and strided pass scales with the number of rows.)
-            const size_t need_bits = 32 + (size_t)host::product_bit_count(std::vector<u64>{t}) + (size_t)host::product_bit_count(q) + 2;
-            auto enough = [&](const std::vector<u64>& base) {
-                std::vector<u64> with_sk = base; with_sk.push_back(fresh[0]);
-                return (size_t)host::product_bit_count(with_sk) > need_bits;
-            };
-            while (next < fresh.size()) {
-                B2.push_back(fresh[next++]);
-                if (enough(B2)) break;
-            }
-            if (!fresh.empty() && !B2.empty() && enough(B2) && B2.size() <= 32) {
-                B = B2; m_sk = fresh[0]; Bn = B.size();
-                bsk = B; bsk.push_back(m_sk);
-            } else aux50 = false;
-        } catch (const std::exception&) { aux50 = false; }
-    }
-    // Shenoy-Kumaresan (rns_tool.cu:1000-1036): the correction term alpha_sk of the conversion B -> q is recovered modulo m_sk and satisfies
-    // |alpha_sk| <= |B| (+ the lambda of the fast floor); it is read off a centred residue, so m_sk must exceed twice that -- any prime of 50 or
-    // 61 bits does by ~45 bits, but the working base is chosen above, so state what it relies on
-    if (m_sk < 2 * ((u64)Bn + 2) + 1) return fail(TROYN_E_MODULUS, "[troyn_behz_create] m_sk is too small for the Shenoy-Kumaresan correction of this base");
-    const size_t Bsk = Bn + 1;          // working base from here on
-    b->Bn = (unsigned)Bn; b->Bsk = (unsigned)Bsk; b->aux50 = aux50;
-
-    int rc = troyn_plan_create(&b->aux, plan->device, plan->log_n, (uint32_t)Bsk, reinterpret_cast<const uint64_t*>(bsk.data()), nullptr);
-    if (rc != TROYN_OK) return rc;
-    b->aux->opt = plan->opt;            // the auxiliary base takes the options its plan has now and follows later changes (behz_follow_options)
-    b->aux_gen.store(plan->opt_gen.load(std::memory_order_acquire), std::memory_order_release);
-
-    // constant block: all tables in one allocation
-    std::vector<u64> blob;
-    auto push_shoup = [&](u64 w, u64 m) { host::Shoup s = host::shoup(w % m, m); blob.push_back(s.operand); blob.push_back(s.quotient); };
-    auto need_inv = [&](u64 a, u64 m, u64& o) { return host::invmod(a % m, m, o); };
-    size_t off_q_inv_punc = blob.size();
-    for (size_t i = 0; i < L; i++) {
-        u64 inv = 1;
-        if (L > 1 && !need_inv(host::product_mod(q, i, q[i]), q[i], inv)) return fail(TROYN_E_MODULUS, "[RNSBase::initialize] RNSBase product is not invertible.");
-        push_shoup(inv, q[i]);
-    }
-    // the scalar factor that precedes a base conversion folded into its first step: (x * c mod q_i) * inv_punc_i mod q_i
-    // = x * (c * inv_punc_i mod q_i) mod q_i -- one Shoup multiply instead of a Barrett-128 product followed by one (c = m_tilde for
-    // the lift, evaluator.cu:52-56 + rns_tool.cu:1083-1094; c = t for the floor, evaluator.cu:95-100)
-    size_t off_q_mt_inv_punc = blob.size();
-    for (size_t i = 0; i < L; i++) {
-        u64 inv = 1;
-        if (L > 1) need_inv(host::product_mod(q, i, q[i]), q[i], inv);
-        push_shoup(host::mulmod(mt % q[i], inv, q[i]), q[i]);
-    }
-    size_t off_q_t_inv_punc = blob.size();
-    for (size_t i = 0; i < L; i++) {
-        u64 inv = 1;
-        if (L > 1) need_inv(host::product_mod(q, i, q[i]), q[i], inv);
-        push_shoup(host::mulmod(t % q[i], inv, q[i]), q[i]);
-    }
-    size_t off_q_to_bsk = blob.size();
-    for (size_t bi = 0; bi < Bsk; bi++) for (size_t i = 0; i < L; i++) blob.push_back(host::product_mod(q, i, bsk[bi]));
-    size_t off_q_to_mt = blob.size();
-    for (size_t i = 0; i < L; i++) blob.push_back(host::product_mod(q, i, mt));
-    if (blob.size() & 1) blob.push_back(0);
-    size_t off_prod_q_mod_bsk = blob.size();
-    for (size_t bi = 0; bi < Bsk; bi++) push_shoup(host::product_mod(q, SIZE_MAX, bsk[bi]), bsk[bi]);
-    size_t off_inv_mt_mod_bsk = blob.size();
-    for (size_t bi = 0; bi < Bsk; bi++) {
-        u64 inv;
-        if (!need_inv(mt, bsk[bi], inv)) return fail(TROYN_E_MODULUS, "[RNSTool::RNSTool] Unable to invert m_tilde.");
-        push_shoup(inv, bsk[bi]);
-    }
-    size_t off_inv_prod_q_mod_bsk = blob.size();
-    for (size_t bi = 0; bi < Bsk; bi++) {
-        u64 inv;
-        if (!need_inv(host::product_mod(q, SIZE_MAX, bsk[bi]), bsk[bi], inv)) return fail(TROYN_E_MODULUS, "[RNSTool::RNSTool] Unable to invert base_q product.");
-        push_shoup(inv, bsk[bi]);
-    }
-    // (x * t - f) * q^-1 = x * (t q^-1) - f * q^-1 mod p_b: the floor's multiplication by t folded into the division by q
-    size_t off_t_inv_prod_q_mod_bsk = blob.size();
-    for (size_t bi = 0; bi < Bsk; bi++) {
-        u64 inv = 0;
-        need_inv(host::product_mod(q, SIZE_MAX, bsk[bi]), bsk[bi], inv);
-        push_shoup(host::mulmod(t % bsk[bi], inv, bsk[bi]), bsk[bi]);
-    }
-    size_t off_B_inv_punc = blob.size();
-    for (size_t bi = 0; bi < Bn; bi++) {
-        u64 inv = 1;
-        if (Bn > 1 && !need_inv(host::product_mod(B, bi, B[bi]), B[bi], inv)) return fail(TROYN_E_MODULUS, "[RNSBase::initialize] RNSBase product is not invertible.");
-        push_shoup(inv, B[bi]);
-    }
-    size_t off_B_to_q = blob.size();
-    for (size_t i = 0; i < L; i++) for (size_t bi = 0; bi < Bn; bi++) blob.push_back(host::product_mod(B, bi, q[i]));
-    size_t off_B_to_msk = blob.size();
-    for (size_t bi = 0; bi < Bn; bi++) blob.push_back(host::product_mod(B, bi, m_sk));
-    if (blob.size() & 1) blob.push_back(0);
-    size_t off_prod_B_mod_q = blob.size();
-    for (size_t i = 0; i < L; i++) push_shoup(host::product_mod(B, SIZE_MAX, q[i]), q[i]);
-    size_t off_neg_prod_B_mod_q = blob.size();
-    for (size_t i = 0; i < L; i++) { u64 v = host::product_mod(B, SIZE_MAX, q[i]); push_shoup(q[i] - v, q[i]); }
-
-    // second-generation conversion tables (split matrices with the scalar factors folded in)
-    Behz2Offsets o2;
-    bool have2 = (Bn == L || aux50) && L <= BEHZ2_MAX_L, smallq = true;
-    for (u64 v : q) { if (v >> 60) have2 = false; if (v >= F64_MODULUS_LIMIT) smallq = false; }
-    if (have2) {
-        if (blob.size() & 1) blob.push_back(0);
-        have2 = behz2_build_tables(q, B, m_sk, t, smallq, blob, o2);
-    }
-
-    // ---- encrypt / decrypt side ----
-    const u64 gamma = primes[1];
-    b->gamma = gamma;
-    std::vector<u64> q_over_t;                       // floor(q / t) as a multi-word integer
-    {
-        std::vector<u64> big = host::big_product(q);
-        b->q_mod_t = host::big_divmod_small(big, t);  // big <- floor(q/t)
-        q_over_t = big;
-    }
-    if (blob.size() & 1) blob.push_back(0);
-    size_t off_delta = blob.size();
-    for (size_t i = 0; i < L; i++) push_shoup(host::big_mod_small(q_over_t, q[i]), q[i]);
-    size_t off_ptg = blob.size();
-    for (size_t i = 0; i < L; i++) push_shoup(host::mulmod(t % q[i], gamma % q[i], q[i]), q[i]);
-    size_t off_q_to_t = blob.size();
-    for (size_t i = 0; i < L; i++) blob.push_back(host::product_mod(q, i, t));
-    size_t off_q_to_gamma = blob.size();
-    for (size_t i = 0; i < L; i++) blob.push_back(host::product_mod(q, i, gamma));
-    {
-        u64 inv;
-        b->decrypt_ready = true;
-        if (need_inv(gamma % t, t, inv)) { host::Shoup s = host::shoup(inv, t); b->inv_gamma_mod_t = make_ulonglong2(s.operand, s.quotient); }
-        else b->decrypt_ready = false;                // "[RNSTool::RNSTool] Unable to invert gamma mod t."
-        if (need_inv(host::product_mod(q, SIZE_MAX, t), t, inv)) { host::Shoup s = host::shoup((t - inv) % t, t); b->neg_inv_q_mod_t = make_ulonglong2(s.operand, s.quotient); }
-        else b->decrypt_ready = false;
-        if (need_inv(host::product_mod(q, SIZE_MAX, gamma), gamma, inv)) { host::Shoup s = host::shoup((gamma - inv) % gamma, gamma); b->neg_inv_q_mod_gamma = make_ulonglong2(s.operand, s.quotient); }
-        else b->decrypt_ready = false;
-    }
-    b->t_mod = make_dev_modulus(t, plan->log_n, false);
-    b->gamma_mod = make_dev_modulus(gamma, plan->log_n, false);
-
-    HIP_TRY(hipSetDevice(plan->device));
-    HIP_TRY(hipMalloc(&b->d_consts, blob.size() * sizeof(u64)));
-    HIP_TRY(hipMemcpy(b->d_consts, blob.data(), blob.size() * sizeof(u64), hipMemcpyHostToDevice));
-
-    BehzDev& d = b->dev;
-    std::memset(&d, 0, sizeof(d));
-    d.L = L; d.Bn = (unsigned)Bn; d.Bsk = (unsigned)Bsk; d.n = n; d.t = t;
-    d.q_mods = plan->d_mods;
-    d.bsk_mods = b->aux->d_mods;
-    d.m_tilde = make_dev_modulus(mt, plan->log_n, false);
-    auto P2 = [&](size_t off) { return reinterpret_cast<const ulonglong2*>(b->d_consts + off); };
-    d.q_inv_punc = P2(off_q_inv_punc);
-    d.q_mt_inv_punc = P2(off_q_mt_inv_punc);
-    d.q_t_inv_punc = P2(off_q_t_inv_punc);
-    d.t_inv_prod_q_mod_bsk = P2(off_t_inv_prod_q_mod_bsk);
-    d.q_to_bsk = b->d_consts + off_q_to_bsk;
-    d.q_to_mt = b->d_consts + off_q_to_mt;
-    {
-        u64 inv;
-        if (!need_inv(host::product_mod(q, SIZE_MAX, mt), mt, inv)) return fail(TROYN_E_MODULUS, "[RNSTool::RNSTool] Unable to invert base_q product.");
-        host::Shoup s = host::shoup((mt - inv) % mt, mt);
-        d.neg_inv_prod_q_mod_mt = make_ulonglong2(s.operand, s.quotient);
-        if (!need_inv(host::product_mod(B, SIZE_MAX, m_sk), m_sk, inv)) return fail(TROYN_E_MODULUS, "[RNSTool::RNSTool] Unable to invert base_B product.");
-        s = host::shoup(inv, m_sk);
-        d.inv_prod_B_mod_msk = make_ulonglong2(s.operand, s.quotient);
-    }
-    d.prod_q_mod_bsk = P2(off_prod_q_mod_bsk);
-    d.inv_mt_mod_bsk = P2(off_inv_mt_mod_bsk);
-    d.inv_prod_q_mod_bsk = P2(off_inv_prod_q_mod_bsk);
-    d.B_inv_punc = P2(off_B_inv_punc);
-    d.B_to_q = b->d_consts + off_B_to_q;
-    d.B_to_msk = b->d_consts + off_B_to_msk;
-    d.prod_B_mod_q = P2(off_prod_B_mod_q);
-    d.neg_prod_B_mod_q = P2(off_neg_prod_B_mod_q);
-    b->have2 = have2; b->smallq = smallq;
+    std::memset(&b->dev, 0, sizeof(b->dev));
     std::memset(&b->dev2, 0, sizeof(b->dev2));
-    if (have2) {
-        Behz2Dev& e = b->dev2;
-        e.L = L; e.n = n; e.rs = o2.rs; e.NB = (unsigned)Bn;
-        e.q_mods = plan->d_mods; e.q_mt_inv_punc = d.q_mt_inv_punc; e.q_t_inv_punc = d.q_t_inv_punc;
-        e.lift_mt = reinterpret_cast<const u32*>(b->d_consts + o2.lift_mt);
-        e.lift_rows = reinterpret_cast<const u32*>(b->d_consts + o2.lift_rows);
-        e.lift_rc = b->d_consts + o2.lift_rc;
-        e.fa_rows = reinterpret_cast<const u32*>(b->d_consts + o2.fa_rows);
-        e.fa_rc = b->d_consts + o2.fa_rc;
-        e.fb_cols = reinterpret_cast<const u32*>(b->d_consts + o2.fb_cols);
-        e.fb_rc = b->d_consts + o2.fb_rc;
-    }
-    b->d_delta = P2(off_delta);
-    b->d_prod_t_gamma_mod_q = P2(off_ptg);
-    b->d_q_to_t = b->d_consts + off_q_to_t;
-    b->d_q_to_gamma = b->d_consts + off_q_to_gamma;
+    const std::vector<u64> q(plan->moduli.begin(), plan->moduli.begin() + L);
+    BehzBase base;
+    ConstBlob blob;              // all tables in one allocation
+    if (int rc = behz_choose_base(b.get(), q, base)) return rc;
+    if (int rc = behz_create_aux_plan(b.get(), plan, base)) return rc;
+    if (int rc = behz_multiply_tables(b.get(), q, base, blob)) return rc;
+    behz_second_generation_tables(b.get(), q, base, blob);
+    behz_decrypt_tables(b.get(), q, blob);
+    if (int rc = blob.upload(plan->device, &b->d_consts)) return rc;
+    behz_wire(b.get());
     *out = b.release();
     return TROYN_OK;
 }
@@ -2267,13 +2252,139 @@ extern "C" size_t troyn_bfv_multiply_workspace_bytes(const troyn_behz* b, size_t
     return behz_layout(b, pa, pb, batch).total * sizeof(u64);
 }
 
-template <typename F4, typename F8, typename F16, typename F64>
-static void dispatch_bound(unsigned v, F4 f4, F8 f8, F16 f16, F64 f64) {
-    if (v <= 4) f4(); else if (v <= 8) f8(); else if (v <= 16) f16(); else f64();
+// first-generation kernels: instantiated per bound on the row count
+static void launch_behz1_lift(const troyn_behz* b, dim3 grid, hipStream_t s, unsigned ch1, const u64* src, u64* dst_bsk) {
+    auto* kernel = b->L <= 4 ? behz_lift_kernel<4> : b->L <= 8 ? behz_lift_kernel<8> : b->L <= 16 ? behz_lift_kernel<16> : behz_lift_kernel<64>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ch1, b->dev, src, dst_bsk);
+}
+static void launch_behz1_floor(const troyn_behz* b, dim3 grid, hipStream_t s, unsigned ch1, const u64* d_q, const u64* d_bsk, u64* out) {
+    auto* kernel = b->Bsk <= 4 ? behz_floor_kernel<4> : b->Bsk <= 8 ? behz_floor_kernel<8> : b->Bsk <= 16 ? behz_floor_kernel<16> : behz_floor_kernel<66>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ch1, b->dev, d_q, d_bsk, out);
 }
 
-static bool behz2_enabled(const troyn_behz* b) {
-    return b->have2 && !b->plan->opt.behz_v1;   // TROYN_BEHZ=v1: first-generation kernels (A/B runs and the tests of that path)
+// one validated call: base q on plan pq (L limbs), the working base on plan px (S limbs)
+struct BfvCall {
+    const troyn_behz* b; const troyn_plan* pq; const troyn_plan* px; unsigned L, S;
+    const u64* a; size_t pa;
+    const u64* bb; size_t pb;
+    u64* out; u64* ws; BehzLayout w; size_t batch; hipStream_t s;
+};
+
+// which launches one multiply takes: decided once per call
+struct BfvPath {
+    int tkind;          // tensor_path_kind of both bases when they agree and the operands have two components: 1 whole-limb tiles, 2 two-pass sizes; 0: no tensor kernel
+    bool lift_fused;    // N = 32768: the lift inside the first forward pass, the last inverse pass inside the floor
+    bool gen2;          // second-generation conversion kernels
+    bool square;        // a ciphertext multiplied with itself: one lift, and the staged copies of b are those of a
+    bool tensor() const { return tkind != 0; }
+    bool whole() const { return tkind == 1; }
+};
+static BfvPath bfv_path(const BfvCall& c) {
+    const troyn_plan* pq = c.pq;
+    const troyn_plan* px = c.px;
+    const unsigned L = c.L, S = c.S;
+    BfvPath k;
+    k.gen2 = c.b->have2 && !pq->opt.behz_v1;   // TROYN_BEHZ=v1: first-generation kernels (A/B runs and the tests of that path)
+    // 2 x 2 components at a two-pass size: the forward transforms stop after their first pass, tensor_core_kernel finishes them, forms the
+    // product and starts the inverse transforms
+    k.tkind = (c.pa == 2 && c.pb == 2 && tensor_path_kind(pq, L) == tensor_path_kind(px, S)) ? tensor_path_kind(pq, L) : 0;
+    // Whole-limb sizes, a few ciphertexts: tensor_core_kernel puts seven transforms of a limb on ONE workgroup (L + S workgroups per item) -- a launch
+    // that cannot fill the chip is one long chain (one product at N = 16384 6 x 50-bit: 240 us).  The separate launches (two-pass transforms of many
+    // small workgroups, dyadic product) finish in 92 us (N = 8192 {60,40,40,60}: 245 -> 78 us for one product).  TROYN_BFV_TENSOR=fused / split force either.
+    // (the hand-over point, measured: ~200 workgroups where tensor_core_kernel is at its best -- N <= 8192, FP64 policy -- and ~350 where it spills
+    // (N = 16384) or runs the integer butterflies)
+    const size_t tensor_small = (pq->log_n <= 13 && use_f64(pq, 0, L) && use_f64(px, 0, S)) ? 192 : 352;
+    if (k.tkind == 1 && !pq->opt.tensor_fused && c.batch * (size_t)(L + S) <= tensor_small) k.tkind = 0;
+    // N = 32768 under the FP64 policy: first pass of base q, lift and first pass of the lifted rows as one launch, and the last inverse pass of
+    // both bases inside the floor launch (behz2_lift_pass1.hpp)
+    k.lift_fused = k.tkind == 2 && k.gen2 && c.b->aux50 && c.b->smallq && pq->log_n == 15 && !pq->opt.behz_lift_split
+                   && use_f64(pq, 0, L) && use_f64(px, 0, S) && L + S <= BEHZ2_FUSED_MAX_ROWS;
+    k.square = c.a == c.bb && c.pa == c.pb;
+    return k;
+}
+
+// steps (1)-(3) of evaluator.cu:50-60 for one operand
+static int bfv_lift(const BfvCall& c, const BfvPath& path, const u64* src, size_t pcount, u64* dst_q, u64* dst_bsk) {
+    const troyn_behz* b = c.b;
+    const size_t items = c.batch * pcount;
+    if (path.lift_fused) {
+        if (items * 512u > 0x7fffffffull) return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] batch too large for one launch");
+        // (lift_fused holds only for shapes both fused launches cover: the floor skips the last inverse pass on the same condition)
+        if (!launch_behz2_lift_pass1(c.L, items, c.s, b->dev2, src, dst_q, dst_bsk, (const double*)c.pq->d_fwd_f64, (const double*)c.px->d_fwd_f64, c.pq->d_mods, c.px->d_mods))
+            return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] no fused lift kernel for this shape");
+        LAUNCH_CHECK();
+        return TROYN_OK;
+    }
+    // the forward transform of one base; whole-limb tiles: none, the tensor kernel reads coefficient form
+    auto forward = [&](const troyn_plan* p, const u64* in, u64* dst, unsigned nc) {
+        NttArgs a = contiguous_args(p, in, dst, pcount, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
+        return path.whole() ? TROYN_OK : path.tensor() ? tensor_stage(p, 0, a, a, a, c.batch, c.s) : launch_ntt(p, a, c.batch, false, c.s);
+    };
+    const unsigned ch1 = chunks_single(c.pq->n);
+    if (int rc = forward(c.pq, src, dst_q, c.L)) return rc;
+    if (int rc = check_rows(items, ch1)) return rc;
+    dim3 grid((unsigned)(items * ch1));
+    if (path.gen2) launch_behz2_lift(c.L, b->smallq, grid.x, c.s, ch1, b->dev2, src, dst_bsk, b->aux50);
+    else launch_behz1_lift(b, grid, c.s, ch1, src, dst_bsk);
+    LAUNCH_CHECK();
+    return forward(c.px, dst_bsk, dst_bsk, c.S);
+}
+
+// steps (4)-(5), 2 x 2 components: tensor_core_kernel per base
+static int bfv_tensor(const BfvCall& c, const BfvPath& path) {
+    const BehzLayout& w = c.w;
+    for (int base = 0; base < 2; base++) {
+        const troyn_plan* p = base ? c.px : c.pq;
+        const unsigned nc = base ? c.S : c.L;
+        // whole-limb tiles: base q is read straight from the operands (coefficient form), nothing of it is staged
+        const u64* xa = (path.whole() && !base) ? c.a : c.ws + (base ? w.a_bsk : w.a_q);
+        const u64* xb = (path.whole() && !base) ? c.bb : c.ws + (base ? w.b_bsk : w.b_q);
+        u64* xd = c.ws + (base ? w.d_bsk : w.d_q);
+        NttArgs fa = contiguous_args(p, xa, nullptr, 2, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
+        NttArgs fb = contiguous_args(p, xb, nullptr, 2, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
+        NttArgs id = contiguous_args(p, xd, xd, 3, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
+        {
+            TimerScope ts(TROYN_TIMER_BFV_TENSOR, c.s);
+            if (int rc = tensor_stage(p, 1, fa, fb, id, c.batch, c.s)) return rc;
+        }
+        if (!path.whole() && !path.lift_fused)      // lift_fused: the floor launch runs the last pass
+            if (int rc = tensor_stage(p, 2, id, id, id, c.batch, c.s)) return rc;
+    }
+    return TROYN_OK;
+}
+
+// steps (4)-(5), any component counts: dyadic convolution and inverse transforms per base
+static int bfv_convolute_intt(const BfvCall& c) {
+    const BehzLayout& w = c.w;
+    const size_t po = c.pa + c.pb - 1;
+    u64* ws = c.ws;
+    if (int rc = launch_convolute(c.pq->d_mods, c.pq->n, 0, c.L, ws + w.a_q, c.pa, ws + w.b_q, c.pb, ws + w.d_q, c.batch, c.s)) return rc;
+    if (int rc = launch_convolute(c.px->d_mods, c.pq->n, 0, c.S, ws + w.a_bsk, c.pa, ws + w.b_bsk, c.pb, ws + w.d_bsk, c.batch, c.s)) return rc;
+    NttArgs a = contiguous_args(c.pq, ws + w.d_q, ws + w.d_q, po, c.L, 0, c.L, TROYN_IDX_COMPONENTWISE, 0);
+    if (int rc = launch_ntt(c.pq, a, c.batch, true, c.s)) return rc;
+    NttArgs ab = contiguous_args(c.px, ws + w.d_bsk, ws + w.d_bsk, po, c.S, 0, c.S, TROYN_IDX_COMPONENTWISE, 0);
+    return launch_ntt(c.px, ab, c.batch, true, c.s);
+}
+
+// steps (6)-(8)
+static int bfv_floor(const BfvCall& c, const BfvPath& path) {
+    const troyn_behz* b = c.b;
+    const unsigned ch1 = chunks_single(c.pq->n);
+    const u64* d_q = c.ws + c.w.d_q;
+    const u64* d_bsk = c.ws + c.w.d_bsk;
+    const size_t items = c.batch * (c.pa + c.pb - 1);
+    if (int rc = check_rows(items, ch1)) return rc;
+    dim3 grid((unsigned)(items * ch1));
+    TimerScope ts(TROYN_TIMER_BEHZ_FLOOR, c.s);
+    if (path.lift_fused) {
+        if (items * 512u > 0x7fffffffull) return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] batch too large for one launch");
+        if (!launch_behz2_floor_pass2(c.L, items, c.s, b->dev2, d_q, d_bsk, c.out, (const double*)c.pq->d_inv_f64, (const double*)c.px->d_inv_f64, c.pq->d_mods, c.px->d_mods))
+            return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] no fused floor kernel for this shape");
+    } else if (path.gen2) {
+        launch_behz2_floor(c.L, b->smallq, grid.x, c.s, ch1, b->dev2, d_q, d_bsk, c.out, b->aux50);
+    } else launch_behz1_floor(b, grid, c.s, ch1, d_q, d_bsk, c.out);
+    LAUNCH_CHECK();
+    return TROYN_OK;
 }
 
 extern "C" int troyn_bfv_multiply(const troyn_behz* b, const uint64_t* a_, size_t pa, const uint64_t* b_, size_t pb,
@@ -2281,116 +2392,17 @@ extern "C" int troyn_bfv_multiply(const troyn_behz* b, const uint64_t* a_, size_
     select_device(b);
     if (!b || !a_ || !b_ || !out || !workspace) return fail(TROYN_E_INVALID, "[Evaluator::bfv_multiply_inplace] null argument");
     if (pa < 1 || pb < 1 || pa > 16 || pb > 16) return fail(TROYN_E_INVALID, "[Evaluator::bfv_multiply_inplace] invalid ciphertext size");
-    BehzLayout w = behz_layout(b, pa, pb, batch);
+    const BehzLayout w = behz_layout(b, pa, pb, batch);
     if (workspace_bytes < w.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, "[troyn_bfv_multiply] workspace too small");
     if (batch == 0) return TROYN_OK;
     behz_follow_options(b);
-    hipStream_t s = (hipStream_t)stream;
-    const troyn_plan* pq = b->plan;
-    const troyn_plan* px = b->aux;
-    const unsigned n = pq->n, L = b->L, S = b->Bsk;
-    const size_t po = pa + pb - 1;
-    u64* ws = (u64*)workspace;
-    int rc;
-    const unsigned ch1 = chunks_single(n);
-    const bool gen2 = behz2_enabled(b);
-    // 2 x 2 components at a two-pass size: the forward transforms stop after their first pass, tensor_core_kernel finishes them, forms the
-    // product and starts the inverse transforms
-    int tkind = (pa == 2 && pb == 2 && tensor_path_kind(pq, L) == tensor_path_kind(px, S)) ? tensor_path_kind(pq, L) : 0;
-    // Whole-limb sizes, a few ciphertexts: tensor_core_kernel puts seven transforms of a limb on ONE workgroup (L + S workgroups per item) -- a launch
-    // that cannot fill the chip is one long chain (one product at N = 16384 6 x 50-bit: 240 us).  The separate launches (two-pass transforms of many
-    // small workgroups, dyadic product) finish in 92 us (N = 8192 {60,40,40,60}: 245 -> 78 us for one product).  TROYN_BFV_TENSOR=fused / split force either.
-    // (the hand-over point, measured: ~200 workgroups where tensor_core_kernel is at its best -- N <= 8192, FP64 policy -- and ~350 where it spills
-    // (N = 16384) or runs the integer butterflies)
-    const size_t tensor_small = (pq->log_n <= 13 && use_f64(pq, 0, L) && use_f64(px, 0, S)) ? 192 : 352;
-    if (tkind == 1 && !pq->opt.tensor_fused && batch * (size_t)(L + S) <= tensor_small) tkind = 0;
-    const bool tensor = tkind != 0, whole = tkind == 1;
-    // N = 32768 under the FP64 policy: first pass of base q, lift and first pass of the lifted rows as one launch, and the last inverse pass of
-    // both bases inside the floor launch (behz2_lift_pass1.hpp)
-    const bool lift_fused = tkind == 2 && gen2 && b->aux50 && b->smallq && pq->log_n == 15 && !pq->opt.behz_lift_split
-                            && use_f64(pq, 0, L) && use_f64(px, 0, S) && L + S <= BEHZ2_FUSED_MAX_ROWS;
-    auto lift = [&](const u64* src, size_t pcount, u64* dst_q, u64* dst_bsk) -> int {
-        // steps (1)-(3) of evaluator.cu:50-60 for one operand
-        if (lift_fused) {
-            if (batch * pcount * 512u > 0x7fffffffull) return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] batch too large for one launch");
-            // (lift_fused holds only for shapes both fused launches cover: the floor below skips the last inverse pass on the same condition)
-            if (!launch_behz2_lift_pass1(L, batch * pcount, s, b->dev2, src, dst_q, dst_bsk, (const double*)pq->d_fwd_f64, (const double*)px->d_fwd_f64, pq->d_mods, px->d_mods))
-                return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] no fused lift kernel for this shape");
-            LAUNCH_CHECK();
-            return TROYN_OK;
-        }
-        NttArgs a = contiguous_args(pq, src, dst_q, pcount, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
-        int r = whole ? TROYN_OK : tensor ? tensor_stage(pq, 0, a, a, a, batch, s) : launch_ntt(pq, a, batch, false, s);   // whole: the tensor kernel reads src
-        if (r) return r;
-        const size_t items = batch * pcount;
-        if ((r = check_rows(items, ch1))) return r;
-        dim3 grid((unsigned)(items * ch1)), block(256);
-        if (gen2) {
-            launch_behz2_lift(L, b->smallq, grid.x, s, ch1, b->dev2, src, dst_bsk, b->aux50);
-        } else dispatch_bound(L,
-            [&] { hipLaunchKernelGGL((behz_lift_kernel<4>), grid, block, 0, s, ch1, b->dev, src, dst_bsk); },
-            [&] { hipLaunchKernelGGL((behz_lift_kernel<8>), grid, block, 0, s, ch1, b->dev, src, dst_bsk); },
-            [&] { hipLaunchKernelGGL((behz_lift_kernel<16>), grid, block, 0, s, ch1, b->dev, src, dst_bsk); },
-            [&] { hipLaunchKernelGGL((behz_lift_kernel<64>), grid, block, 0, s, ch1, b->dev, src, dst_bsk); });
-        LAUNCH_CHECK();
-        NttArgs ab = contiguous_args(px, dst_bsk, dst_bsk, pcount, S, 0, S, TROYN_IDX_COMPONENTWISE, 0);
-        return whole ? TROYN_OK : tensor ? tensor_stage(px, 0, ab, ab, ab, batch, s) : launch_ntt(px, ab, batch, false, s);
-    };
-    // squaring (a ciphertext multiplied with itself): one lift, and the staged copies of b are those of a
-    const bool square = a_ == b_ && pa == pb;
-    if (square) { w.b_q = w.a_q; w.b_bsk = w.a_bsk; }
-    if ((rc = lift((const u64*)a_, pa, ws + w.a_q, ws + w.a_bsk))) return rc;
-    if (!square && (rc = lift((const u64*)b_, pb, ws + w.b_q, ws + w.b_bsk))) return rc;
-    if (tensor) {
-        // steps (4)-(5)
-        for (int base = 0; base < 2; base++) {
-            const troyn_plan* p = base ? px : pq;
-            const unsigned nc = base ? S : L;
-            // whole-limb tiles: base q is read straight from the operands (coefficient form), nothing of it is staged
-            const u64* xa = (whole && !base) ? (const u64*)a_ : ws + (base ? w.a_bsk : w.a_q);
-            const u64* xb = (whole && !base) ? (const u64*)b_ : ws + (base ? w.b_bsk : w.b_q);
-            u64* xd = ws + (base ? w.d_bsk : w.d_q);
-            NttArgs fa = contiguous_args(p, xa, nullptr, 2, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
-            NttArgs fb = contiguous_args(p, xb, nullptr, 2, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
-            NttArgs id = contiguous_args(p, xd, xd, 3, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
-            {
-                TimerScope ts(TROYN_TIMER_BFV_TENSOR, s);
-                if ((rc = tensor_stage(p, 1, fa, fb, id, batch, s))) return rc;
-            }
-            if (!whole && !lift_fused && (rc = tensor_stage(p, 2, id, id, id, batch, s))) return rc;      // lift_fused: the floor launch runs the last pass
-        }
-    } else {
-    // step (4)
-    if ((rc = launch_convolute(pq->d_mods, n, 0, L, ws + w.a_q, pa, ws + w.b_q, pb, ws + w.d_q, batch, s))) return rc;
-    if ((rc = launch_convolute(px->d_mods, n, 0, S, ws + w.a_bsk, pa, ws + w.b_bsk, pb, ws + w.d_bsk, batch, s))) return rc;
-    // step (5)
-    {
-        NttArgs a = contiguous_args(pq, ws + w.d_q, ws + w.d_q, po, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
-        if ((rc = launch_ntt(pq, a, batch, true, s))) return rc;
-        NttArgs ab = contiguous_args(px, ws + w.d_bsk, ws + w.d_bsk, po, S, 0, S, TROYN_IDX_COMPONENTWISE, 0);
-        if ((rc = launch_ntt(px, ab, batch, true, s))) return rc;
-    }
-    }
-    // steps (6)-(8)
-    {
-        const size_t items = batch * po;
-        if ((rc = check_rows(items, ch1))) return rc;
-        dim3 grid((unsigned)(items * ch1)), block(256);
-        TimerScope ts(TROYN_TIMER_BEHZ_FLOOR, s);
-        if (lift_fused) {
-            if (items * 512u > 0x7fffffffull) return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] batch too large for one launch");
-            if (!launch_behz2_floor_pass2(L, items, s, b->dev2, ws + w.d_q, ws + w.d_bsk, (u64*)out, (const double*)pq->d_inv_f64, (const double*)px->d_inv_f64, pq->d_mods, px->d_mods))
-                return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] no fused floor kernel for this shape");
-        } else if (gen2) {
-            launch_behz2_floor(L, b->smallq, grid.x, s, ch1, b->dev2, ws + w.d_q, ws + w.d_bsk, (u64*)out, b->aux50);
-        } else dispatch_bound(S,
-            [&] { hipLaunchKernelGGL((behz_floor_kernel<4>), grid, block, 0, s, ch1, b->dev, ws + w.d_q, ws + w.d_bsk, (u64*)out); },
-            [&] { hipLaunchKernelGGL((behz_floor_kernel<8>), grid, block, 0, s, ch1, b->dev, ws + w.d_q, ws + w.d_bsk, (u64*)out); },
-            [&] { hipLaunchKernelGGL((behz_floor_kernel<16>), grid, block, 0, s, ch1, b->dev, ws + w.d_q, ws + w.d_bsk, (u64*)out); },
-            [&] { hipLaunchKernelGGL((behz_floor_kernel<66>), grid, block, 0, s, ch1, b->dev, ws + w.d_q, ws + w.d_bsk, (u64*)out); });
-        LAUNCH_CHECK();
-    }
-    return TROYN_OK;
+    BfvCall c{b, b->plan, b->aux, b->L, b->Bsk, (const u64*)a_, pa, (const u64*)b_, pb, (u64*)out, (u64*)workspace, w, batch, (hipStream_t)stream};
+    const BfvPath path = bfv_path(c);
+    if (path.square) { c.w.b_q = w.a_q; c.w.b_bsk = w.a_bsk; }
+    if (int rc = bfv_lift(c, path, c.a, pa, c.ws + w.a_q, c.ws + w.a_bsk)) return rc;
+    if (!path.square) if (int rc = bfv_lift(c, path, c.bb, pb, c.ws + w.b_q, c.ws + w.b_bsk)) return rc;
+    if (int rc = path.tensor() ? bfv_tensor(c, path) : bfv_convolute_intt(c)) return rc;
+    return bfv_floor(c, path);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2764,42 +2776,27 @@ extern "C" int troyn_ring2k_create(troyn_ring2k** out, const troyn_plan* plan, u
         if ((t_bits % 64) && src + 1 < big.size()) v |= big[src + 1] << (64 - t_bits % 64);
         shifted[w] = v;
     }
-    std::vector<u64> blob;
-    auto push_shoup = [&](u64 w, u64 m) { host::Shoup s = host::shoup(w % m, m); blob.push_back(s.operand); blob.push_back(s.quotient); };
-    const size_t off_qdt = blob.size();
-    for (size_t l = 0; l < L; l++) push_shoup(host::big_mod_small(shifted, q[l]), q[l]);
-    const size_t off_gt = blob.size();
-    for (size_t l = 0; l < L; l++) {
-        // gamma * 2^k mod q_l, with 2^k split as 2^(k/2) * 2^(k - k/2) (bfv_ring2k.cu:183-191)
-        const u64 t0 = (u64)(((u128h)1 << (t_bits / 2)) % q[l]), t1 = (u64)(((u128h)1 << (t_bits - t_bits / 2)) % q[l]);
-        push_shoup(host::mulmod(gamma % q[l], host::mulmod(t0, t1, q[l]), q[l]), q[l]);
-    }
-    const size_t off_ip = blob.size();
-    for (size_t l = 0; l < L; l++) {
-        u64 inv = 1;
-        if (L > 1 && !host::invmod(host::product_mod(q, l, q[l]), q[l], inv)) return fail(TROYN_E_MODULUS, "[RNSBase::initialize] RNSBase product is not invertible.");
-        push_shoup(inv, q[l]);
-    }
-    const size_t off_pg = blob.size();
-    for (size_t l = 0; l < L; l++) blob.push_back(host::product_mod(q, l, gamma));
-    if (blob.size() & 1) blob.push_back(0);
-    const size_t off_pt = blob.size();
-    for (size_t l = 0; l < L; l++) { const u128h v = wrap_product(l) & mask; blob.push_back((u64)v); blob.push_back((u64)(v >> 64)); }
-    u64 inv_q_gamma = 0;
-    if (!host::invmod(host::product_mod(q, SIZE_MAX, gamma), gamma, inv_q_gamma)) return fail(TROYN_E_MODULUS, std::string(P) + " failed to invert Q_mod_gamma");
-    HIP_TRY(hipSetDevice(plan->device));
-    HIP_TRY(hipMalloc(&h->d_consts, blob.size() * sizeof(u64)));
-    HIP_TRY(hipMemcpy(h->d_consts, blob.data(), blob.size() * sizeof(u64), hipMemcpyHostToDevice));
     Ring2kDev& d = h->dev;
     std::memset(&d, 0, sizeof(d));
+    ConstBlob blob;
+    blob.bind(&d.q_div_t_mod_q, blob.shoup(L, [&](size_t l) { return host::big_mod_small(shifted, q[l]); }, element_of(q)));
+    blob.bind(&d.gamma_t_mod_q, blob.shoup(L, [&](size_t l) {
+        // gamma * 2^k mod q_l, with 2^k split as 2^(k/2) * 2^(k - k/2) (bfv_ring2k.cu:183-191)
+        const u64 t0 = (u64)(((u128h)1 << (t_bits / 2)) % q[l]), t1 = (u64)(((u128h)1 << (t_bits - t_bits / 2)) % q[l]);
+        return host::mulmod(gamma % q[l], host::mulmod(t0, t1, q[l]), q[l]);
+    }, element_of(q)));
+    std::vector<u64> inv_punc;
+    if (int rc = inv_punctured(q, inv_punc)) return rc;
+    blob.bind(&d.inv_punctured, blob.shoup(L, element_of(inv_punc), element_of(q)));
+    blob.bind(&d.punctured_mod_gamma, blob.words(L, [&](size_t l) { return host::product_mod(q, l, gamma); }));
+    blob.aligned();                                                            // [L] 128-bit values, low word first
+    blob.bind(&d.punctured_mod_t, blob.words(2 * (size_t)L, [&](size_t k) { return (u64)((wrap_product(k / 2) & mask) >> (64 * (k % 2))); }));
+    u64 inv_q_gamma = 0;
+    if (!host::invmod(host::product_mod(q, SIZE_MAX, gamma), gamma, inv_q_gamma)) return fail(TROYN_E_MODULUS, std::string(P) + " failed to invert Q_mod_gamma");
+    if (int rc = blob.upload(plan->device, &h->d_consts)) return rc;
     d.mods = plan->d_mods;
-    d.q_div_t_mod_q = reinterpret_cast<const ulonglong2*>(h->d_consts + off_qdt);
-    d.gamma_t_mod_q = reinterpret_cast<const ulonglong2*>(h->d_consts + off_gt);
-    d.inv_punctured = reinterpret_cast<const ulonglong2*>(h->d_consts + off_ip);
-    d.punctured_mod_gamma = h->d_consts + off_pg;
-    d.punctured_mod_t = h->d_consts + off_pt;
     d.gamma = make_dev_modulus(gamma, plan->log_n, false);
-    { host::Shoup s = host::shoup((gamma - inv_q_gamma) % gamma, gamma); d.neg_inv_q_mod_gamma = make_ulonglong2(s.operand, s.quotient); }
+    d.neg_inv_q_mod_gamma = shoup_pair(gamma - inv_q_gamma, gamma);
     auto set2 = [](u64* dst, u128h v) { dst[0] = (u64)v; dst[1] = (u64)(v >> 64); };
     set2(d.q_mod_t, q_mod_t); set2(d.t_half, t_half); set2(d.mask, mask); set2(d.neg_inv_q_mod_t, neg_inv_q); set2(d.inv_gamma_mod_t, inv_gamma);
     d.L = L; d.n = plan->n; d.t_bits = t_bits; d.elem_bytes = elem_bytes;
