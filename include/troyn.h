@@ -188,6 +188,38 @@ int troyn_ckks_multiply_relinearize_rescale(const troyn_plan* plan, uint32_t L, 
                                             size_t batch, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Dot product of ciphertexts with lazy relinearization.  Both entries are ADDITIONS to the reference's surface (as the fused chain above):
+ * a sum of `terms` products pays one key switch and one rescale instead of one per term.
+ *
+ * troyn_dyadic_convolute_accumulate: out (+)= SUM_t a[t] (x) b[t], the two-by-two tensor product of Evaluator::multiply
+ * (evaluator.cu:118-145) summed over the terms in ONE pass: every input word is read once, every output word written once, one
+ * Barrett reduction per output word.
+ *   a, b   host arrays of `terms` DEVICE pointers, each -> u64[batch][2][nmod][N] in NTT form, 16-byte aligned; limb l under modulus
+ *          mod_start + l
+ *   out    [batch][3][nmod][N]; accumulate = 0 overwrites it, accumulate = 1 adds to it (it must hold canonical residues)
+ * Contract: the words are bit-identical to `terms` x troyn_dyadic_convolute folded with troyn_add (the sum modulo each q_l in canonical
+ * form does not depend on where the reductions happen).  TROYN_E_INVALID: terms == 0, a null table or entry, a misaligned pointer, a
+ * modulus slice outside the plan, `out` overlapping an input.  batch == 0 returns TROYN_OK and launches nothing.  The tables are read
+ * before the call returns (they travel in the kernel arguments, 32 terms per launch; longer sums run as successive launches).
+ *
+ * troyn_ckks_multiply_accumulate_relinearize_rescale: rescale_to_next(relinearize(SUM_t multiply(a[t], b[t]))) -- the accumulated product
+ * into the workspace, then the drivers of troyn_relinearize (evaluator_keyswitching.cu:119-144) and troyn_divide_and_round_q_last_ntt
+ * (utils/rns_tool.cu:499-694) on it.
+ *   a, b as above with nmod = L;  keys as troyn_switch_key;  out [batch][2][L-1][N] NTT form
+ * Contract: bit-identical to troyn_dyadic_convolute_accumulate + troyn_relinearize + troyn_divide_and_round_q_last_ntt, hence with
+ * terms = 1 to troyn_ckks_multiply_relinearize_rescale.  Errors as above, TROYN_E_WORKSPACE for a workspace below the queried size;
+ * batch == 0 returns TROYN_OK, launches nothing and looks at neither `out` nor the workspace (both may be null).
+ * ------------------------------------------------------------------------------------- */
+int troyn_dyadic_convolute_accumulate(const troyn_plan* plan, uint32_t mod_start, uint32_t nmod,
+                                      const uint64_t* const* a, const uint64_t* const* b, size_t terms,
+                                      uint64_t* out, int accumulate, size_t batch, troyn_stream_t stream);
+size_t troyn_ckks_multiply_accumulate_relinearize_rescale_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t terms, size_t batch);
+int troyn_ckks_multiply_accumulate_relinearize_rescale(const troyn_plan* plan, uint32_t L,
+                                                       const uint64_t* const* a, const uint64_t* const* b, size_t terms,
+                                                       const uint64_t* const* keys, uint64_t* out, void* workspace, size_t workspace_bytes,
+                                                       size_t batch, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Modulus switching.
  * troyn_divide_and_round_q_last      RNSTool::divide_and_round_q_last (utils/rns_tool.cu:374-466),
  *                                    BFV mod_switch_to_next, coefficient form.

@@ -88,6 +88,69 @@ __global__ __launch_bounds__(POLY_BLOCK) void dyadic_convolute_kernel(unsigned c
     }
 }
 
+// Sum of `terms` two-by-two tensor products (an addition to the reference's kernels: lazy relinearization of a dot product,
+// troyn_dyadic_convolute_accumulate): out[i] (+)= SUM_t a[t][i] (x) b[t][i], a[t], b[t] -> [batch][2][nmod][N], out [batch][3][nmod][N].
+// Geometry of dyadic_convolute_kernel<2, 2>: a thread owns two adjacent coefficients of one (item, limb) row, every input word is read once and
+// every output word written once per launch.  The three outputs are accumulated in 128 bits (mac128, as ks_accumulate_kernel) and reduced ONCE per
+// launch; the sum modulo q in canonical form is the value the per-term reductions of dyadic_convolute + add give.
+// Bound: plan moduli are < 2^61, so 64 products plus one canonical carry-in stay below 2^128: 64 (2^61 - 1)^2 + 2^61 < 2^128.  The middle output
+// takes TWO products per term, hence at most CONV_ACC_MAX_TERMS = 32 terms per launch; the driver cuts longer sums into launches that carry `out`.
+// The pointer tables travel in the kernel arguments (GatherPtrs' pattern); the term loop is wave-uniform and unrolled by UNROLL terms with all
+// 4 * UNROLL 16-byte loads issued before the multiplies (the table entries sit in SGPRs, the loads take scalar bases).
+constexpr unsigned CONV_ACC_MAX_TERMS = 32;
+struct ConvAccPtrs { const u64* a[CONV_ACC_MAX_TERMS]; const u64* b[CONV_ACC_MAX_TERMS]; };
+
+struct ConvAcc128 {
+    u64 lo0a = 0, hi0a = 0, lo0b = 0, hi0b = 0;   // output 0, coefficients a / b of the pair
+    u64 lo1a = 0, hi1a = 0, lo1b = 0, hi1b = 0;
+    u64 lo2a = 0, hi2a = 0, lo2b = 0, hi2b = 0;
+    __device__ __forceinline__ void term(const u64x2& a0, const u64x2& a1, const u64x2& b0, const u64x2& b1) {
+        mac128(lo0a, hi0a, a0.a, b0.a); mac128(lo0b, hi0b, a0.b, b0.b);
+        mac128(lo1a, hi1a, a0.a, b1.a); mac128(lo1b, hi1b, a0.b, b1.b);
+        mac128(lo1a, hi1a, a1.a, b0.a); mac128(lo1b, hi1b, a1.b, b0.b);
+        mac128(lo2a, hi2a, a1.a, b1.a); mac128(lo2b, hi2b, a1.b, b1.b);
+    }
+};
+
+template <int UNROLL>
+__global__ __launch_bounds__(POLY_BLOCK) void dyadic_convolute_accumulate_kernel(unsigned chunks, const DevModulus* mods, unsigned mod_start, unsigned nmod,
+                                                                                 unsigned n, ConvAccPtrs ptrs, unsigned terms, u64* out, int accumulate) {
+    const unsigned limb = blk_row(chunks) % nmod;
+    const size_t item = blk_row(chunks) / nmod;
+    const DevModulus md = mods[mod_start + limb];
+    const size_t pc = (size_t)nmod * n;
+    const size_t in_off = item * 2 * pc + (size_t)limb * n;
+    u64* op = out + item * 3 * pc + (size_t)limb * n;
+    for (unsigned i = blk_col(chunks) * 2; i < n; i += chunks * blockDim.x * 2) {
+        ConvAcc128 acc;
+        if (accumulate) {    // canonical carry-in (the earlier launches of a long sum, or the caller's own `out`)
+            const u64x2 c0 = ld2(op + i), c1 = ld2(op + pc + i), c2 = ld2(op + 2 * pc + i);
+            acc.lo0a = c0.a; acc.lo0b = c0.b; acc.lo1a = c1.a; acc.lo1b = c1.b; acc.lo2a = c2.a; acc.lo2b = c2.b;
+        }
+        unsigned t = 0;
+        for (; t + UNROLL <= terms; t += UNROLL) {
+            u64x2 a0[UNROLL], a1[UNROLL], b0[UNROLL], b1[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                const u64* ap = ptrs.a[t + u] + in_off + i;
+                const u64* bp = ptrs.b[t + u] + in_off + i;
+                a0[u] = ld2(ap); a1[u] = ld2(ap + pc); b0[u] = ld2(bp); b1[u] = ld2(bp + pc);
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) acc.term(a0[u], a1[u], b0[u], b1[u]);
+        }
+        for (; t < terms; ++t) {
+            const u64* ap = ptrs.a[t] + in_off + i;
+            const u64* bp = ptrs.b[t] + in_off + i;
+            const u64x2 a0 = ld2(ap), a1 = ld2(ap + pc), b0 = ld2(bp), b1 = ld2(bp + pc);
+            acc.term(a0, a1, b0, b1);
+        }
+        st2(op + i, barrett128(acc.lo0a, acc.hi0a, md.q, md.ratio_lo, md.ratio_hi), barrett128(acc.lo0b, acc.hi0b, md.q, md.ratio_lo, md.ratio_hi));
+        st2(op + pc + i, barrett128(acc.lo1a, acc.hi1a, md.q, md.ratio_lo, md.ratio_hi), barrett128(acc.lo1b, acc.hi1b, md.q, md.ratio_lo, md.ratio_hi));
+        st2(op + 2 * pc + i, barrett128(acc.lo2a, acc.hi2a, md.q, md.ratio_lo, md.ratio_hi), barrett128(acc.lo2b, acc.hi2b, md.q, md.ratio_lo, md.ratio_hi));
+    }
+}
+
 // generic (any pa, pb) version with the reference's loop structure
 __global__ __launch_bounds__(POLY_BLOCK) void dyadic_convolute_generic_kernel(unsigned chunks, const DevModulus* mods, unsigned mod_start, unsigned nmod,
                                                                               unsigned n, const u64* a, unsigned pa, const u64* b, unsigned pb, u64* out) {

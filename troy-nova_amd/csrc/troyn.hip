@@ -895,6 +895,60 @@ extern "C" int troyn_dyadic_convolute(const troyn_plan* p, uint32_t mod_start, u
     return launch_convolute(p->d_mods, p->n, mod_start, nmod, (const u64*)a, pa, (const u64*)b, pb, (u64*)out, batch, (hipStream_t)stream);
 }
 
+// SUM_t a[t] (x) b[t] into out (poly_kernels.hpp dyadic_convolute_accumulate_kernel): launches of at most CONV_ACC_MAX_TERMS terms, the tables
+// by value in the kernel arguments (no upload, no host wait); every launch after the first carries `out`.  The caller has checked the tables.
+static int launch_convolute_accumulate(const DevModulus* mods, unsigned n, uint32_t mod_start, uint32_t nmod, const uint64_t* const* a,
+                                       const uint64_t* const* b, size_t terms, u64* out, int accumulate, size_t batch, hipStream_t s) {
+    const size_t rows = batch * nmod;
+    if (rows == 0) return TROYN_OK;
+    const unsigned ch = chunks_pairs(n);
+    if (int rc = check_rows(rows, ch)) return rc;
+    for (size_t t0 = 0; t0 < terms; t0 += CONV_ACC_MAX_TERMS) {
+        const unsigned cnt = (unsigned)std::min<size_t>(terms - t0, CONV_ACC_MAX_TERMS);
+        ConvAccPtrs g;
+        for (unsigned t = 0; t < CONV_ACC_MAX_TERMS; t++) {
+            g.a[t] = reinterpret_cast<const u64*>(a[t0 + (t < cnt ? t : 0)]);
+            g.b[t] = reinterpret_cast<const u64*>(b[t0 + (t < cnt ? t : 0)]);
+        }
+        const int carry = (accumulate || t0 > 0) ? 1 : 0;
+        if (cnt >= 4)
+            hipLaunchKernelGGL((dyadic_convolute_accumulate_kernel<4>), dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s, ch, mods, mod_start, nmod, n, g, cnt, out, carry);
+        else
+            hipLaunchKernelGGL((dyadic_convolute_accumulate_kernel<2>), dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s, ch, mods, mod_start, nmod, n, g, cnt, out, carry);
+        LAUNCH_CHECK();
+    }
+    return TROYN_OK;
+}
+
+// argument checks shared by troyn_dyadic_convolute_accumulate and the chain entry built on it (P: the caller's name for the messages)
+static int check_convolute_accumulate(const char* P, const troyn_plan* p, uint32_t mod_start, uint32_t nmod, const uint64_t* const* a,
+                                      const uint64_t* const* b, size_t terms, const uint64_t* out, size_t out_words, size_t batch) {
+    if (!p || !a || !b) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if (terms == 0) return fail(TROYN_E_INVALID, std::string(P) + " no terms");
+    if (nmod == 0 || (size_t)mod_start + nmod > p->K) return fail(TROYN_E_INVALID, std::string(P) + " modulus slice out of range");
+    if (batch == 0) return TROYN_OK;
+    if (!out) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if ((uintptr_t)out & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned destination");
+    const size_t in_bytes = batch * 2 * (size_t)nmod * p->n * sizeof(u64);
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + out_words * sizeof(u64);
+    for (size_t t = 0; t < terms; t++) {
+        for (const uint64_t* q : {a[t], b[t]}) {
+            if (!q || ((uintptr_t)q & 15)) return fail(TROYN_E_INVALID, std::string(P) + " null or misaligned pointer in the tables");
+            if ((uintptr_t)q < o1 && o0 < (uintptr_t)q + in_bytes) return fail(TROYN_E_INVALID, std::string(P) + " out overlaps an input");
+        }
+    }
+    return TROYN_OK;
+}
+
+extern "C" int troyn_dyadic_convolute_accumulate(const troyn_plan* p, uint32_t mod_start, uint32_t nmod,
+                                                 const uint64_t* const* a, const uint64_t* const* b, size_t terms,
+                                                 uint64_t* out, int accumulate, size_t batch, troyn_stream_t stream) {
+    select_device(p);
+    const char* P = "[troyn_dyadic_convolute_accumulate]";
+    if (int rc = check_convolute_accumulate(P, p, mod_start, nmod, a, b, terms, out, batch * 3 * (size_t)nmod * (p ? p->n : 0), batch)) return rc;
+    return launch_convolute_accumulate(p->d_mods, p->n, mod_start, nmod, a, b, terms, (u64*)out, accumulate, batch, (hipStream_t)stream);
+}
+
 extern "C" int troyn_dyadic_square(const troyn_plan* p, uint32_t mod_start, uint32_t nmod,
                                    const uint64_t* a, uint64_t* out, size_t batch, troyn_stream_t stream) {
     select_device(p);
@@ -1821,6 +1875,51 @@ extern "C" int troyn_ckks_multiply_relinearize_rescale(const troyn_plan* p, uint
         joined = hipEventRecord(ms->join[q], ms->s[q]) == hipSuccess && hipStreamWaitEvent(s, ms->join[q], 0) == hipSuccess && joined;
     if (!joined) { for (int q = 0; q < ns; q++) (void)hipStreamSynchronize(ms->s[q]); }
     return rc;
+}
+
+// Dot product of ciphertexts with lazy relinearization (an addition): SUM_t a[t] (x) b[t] into the workspace, then the drivers of troyn_relinearize
+// and troyn_divide_and_round_q_last_ntt on that buffer -- one key switch and one rescale for the whole sum.
+//   workspace: prod3 [batch][3][L][N] | relin2 [batch][2][L][N] | the larger of the two drivers' own workspaces
+struct MarrLayout { size_t prod3, relin2, sub, sub_bytes, total_bytes; };
+static MarrLayout marr_layout(const troyn_plan* p, uint32_t L, size_t batch) {
+    MarrLayout w;
+    const size_t pc = (size_t)L * p->n;
+    w.prod3 = 0;
+    w.relin2 = batch * 3 * pc;
+    w.sub = w.relin2 + batch * 2 * pc;
+    w.sub_bytes = std::max(troyn_relinearize_workspace_bytes(p, L, batch), troyn_divide_and_round_q_last_ntt_workspace_bytes(p, L, 2, batch));
+    w.total_bytes = w.sub * sizeof(u64) + w.sub_bytes;
+    return w;
+}
+
+extern "C" size_t troyn_ckks_multiply_accumulate_relinearize_rescale_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t terms, size_t batch) {
+    if (!plan || terms == 0 || plan->K < 2 || L < 2 || L > plan->K - 1) return 0;     // (the levels the entry itself refuses)
+    return marr_layout(plan, L, batch).total_bytes;     // (the sum is formed in place: the size does not depend on `terms`)
+}
+
+extern "C" int troyn_ckks_multiply_accumulate_relinearize_rescale(const troyn_plan* p, uint32_t L, const uint64_t* const* a, const uint64_t* const* b,
+                                                                  size_t terms, const uint64_t* const* keys, uint64_t* out, void* workspace,
+                                                                  size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(p);
+    const char* P = "[troyn_ckks_multiply_accumulate_relinearize_rescale]";
+    if (!p || !a || !b || !keys) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if (terms == 0) return fail(TROYN_E_INVALID, std::string(P) + " no terms");
+    if (p->K < 2) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] Keyswitching is not supported.");
+    if (L < 2 || L > p->K - 1) return fail(TROYN_E_INVALID, "[Evaluator::mod_switch_scale_to_next_internal] Next context data is not set.");
+    const MarrLayout w = marr_layout(p, L, batch);
+    if ((uintptr_t)workspace & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned workspace");
+    u64* ws = (u64*)workspace;
+    // the operand tables first, as troyn_dyadic_convolute_accumulate does.  The sum is written to the workspace, so that is the buffer no operand
+    // may overlap (`out` is written after the last read of the operands)
+    if (int rc = check_convolute_accumulate(P, p, 0, L, a, b, terms, (const uint64_t*)ws, w.total_bytes / sizeof(u64), batch)) return rc;
+    if (batch == 0) return TROYN_OK;      // as troyn_dyadic_convolute_accumulate: nothing to launch, `out` and the workspace are not looked at
+    if (workspace_bytes < w.total_bytes) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    if (!out) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    int rc;
+    // SUM_t Evaluator::multiply (evaluator.cu:118-145) -> relinearize (evaluator_keyswitching.cu:119-144) -> rescale_to_next (utils/rns_tool.cu:499-694)
+    if ((rc = launch_convolute_accumulate(p->d_mods, p->n, 0, L, a, b, terms, ws + w.prod3, 0, batch, (hipStream_t)stream))) return rc;
+    if ((rc = troyn_relinearize(p, L, 1, 1, (const uint64_t*)(ws + w.prod3), keys, (uint64_t*)(ws + w.relin2), ws + w.sub, w.sub_bytes, batch, stream))) return rc;
+    return troyn_divide_and_round_q_last_ntt(p, L, (const uint64_t*)(ws + w.relin2), 2, out, ws + w.sub, w.sub_bytes, batch, stream);
 }
 
 extern "C" int troyn_mod_switch_drop(const troyn_plan* p, uint32_t L_in, uint32_t L_out, const uint64_t* in, size_t pcount,

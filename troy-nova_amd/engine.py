@@ -315,6 +315,52 @@ class Plan:
                                                                     C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
 
+    # -- dot products of ciphertexts (additions: lazy relinearization) -----------------------------------
+    def _term_ptrs(self, who, a_list, b_list, words_per_item):
+        """two lists of [batch][2][nmod][N] tensors (None stands for a null entry) -> (two host arrays of device pointers, batch); every tensor of
+        both lists must hold the same number of words: the kernel reads `batch` items behind every pointer"""
+        if len(a_list) != len(b_list):
+            raise capi.TroynInvalidArgument("%s the two lists have different lengths" % who)
+        sizes = set()
+        for t in list(a_list) + list(b_list):
+            if t is not None:
+                _ptr(t)
+                sizes.add(t.numel())
+        if len(sizes) > 1:
+            raise capi.TroynInvalidArgument("%s operands of different sizes" % who)
+        words = sizes.pop() if sizes else 0
+        if words_per_item and words % words_per_item:
+            raise capi.TroynInvalidArgument("%s operands are not [batch][2][nmod][N]" % who)
+        arr = lambda ts: (C.c_void_p * max(len(ts), 1))(*[None if t is None else t.data_ptr() for t in ts])
+        return arr(a_list), arr(b_list), (words // words_per_item if words_per_item else 0)      # (an empty slice is the library's to refuse)
+
+    def dyadic_convolute_accumulate(self, a_list, b_list, nmod, mod_start=0, out=None, accumulate=False):
+        """out [batch][3][nmod][N] (+)= SUM_t a_list[t] (x) b_list[t], every operand [batch][2][nmod][N] in NTT form; one pass over the terms"""
+        who = "[troyn_dyadic_convolute_accumulate]"
+        pa, pb, batch = self._term_ptrs(who, a_list, b_list, 2 * nmod * self.n)
+        if out is None:
+            if accumulate:
+                raise capi.TroynInvalidArgument("%s accumulate needs an out tensor" % who)
+            out = torch.empty((batch, 3, nmod, self.n), dtype=torch.int64, device=self.device)
+        elif out.numel() != batch * 3 * nmod * self.n:
+            raise capi.TroynInvalidArgument("%s out is not [batch][3][nmod][N]" % who)
+        capi.check(self.lib.troyn_dyadic_convolute_accumulate(self.h, mod_start, nmod, pa, pb, len(a_list), _ptr(out), int(bool(accumulate)), batch, _stream()))
+        return out
+
+    def ckks_multiply_accumulate_relinearize_rescale(self, L, a_list, b_list, keys, out=None):
+        """rescale_to_next(relinearize(SUM_t multiply(a_list[t], b_list[t]))) -> [batch][2][L-1][N]: one key switch and one rescale for the sum"""
+        who = "[troyn_ckks_multiply_accumulate_relinearize_rescale]"
+        pa, pb, batch = self._term_ptrs(who, a_list, b_list, 2 * L * self.n)
+        if out is None:
+            out = torch.empty((batch, 2, max(L - 1, 0), self.n), dtype=torch.int64, device=self.device)
+        elif out.numel() != batch * 2 * (L - 1) * self.n:
+            raise capi.TroynInvalidArgument("%s out is not [batch][2][L-1][N]" % who)
+        nbytes = self.lib.troyn_ckks_multiply_accumulate_relinearize_rescale_workspace_bytes(self.h, L, len(a_list), batch)
+        ws = self.workspace(nbytes)
+        capi.check(self.lib.troyn_ckks_multiply_accumulate_relinearize_rescale(self.h, L, pa, pb, len(a_list), self._key_ptrs(keys, L), _ptr(out),
+                                                                               C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        return out
+
     # -- modulus switching -------------------------------------------------------------------------
     def divide_and_round_q_last(self, L, x, pcount, out=None):
         batch = x.numel() // (pcount * L * self.n)

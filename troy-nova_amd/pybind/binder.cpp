@@ -459,6 +459,18 @@ PYBIND11_MODULE(pytroy_raw, m) {
                                                       const std::vector<Ciphertext*>& d, PoolArg p) {
         s.multiply_relinearize_rescale_batched(const_ptrs(a), const_ptrs(b), k, d, P(p)); },
            py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    // additions: dot products of ciphertexts with lazy relinearization (troy.h)
+    ev.def("multiply_accumulate", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, Ciphertext& d, PoolArg p) {
+        s.multiply_accumulate(const_ptrs(a), const_ptrs(b), d, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("destination"), POOL);
+    ev.def("multiply_accumulate_new", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, PoolArg p) {
+        return s.multiply_accumulate_new(const_ptrs(a), const_ptrs(b), P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), POOL);
+    ev.def("multiply_accumulate_relinearize_rescale", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, const RelinKeys& k,
+                                                         Ciphertext& d, PoolArg p) {
+        s.multiply_accumulate_relinearize_rescale(const_ptrs(a), const_ptrs(b), k, d, P(p)); },
+           py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    ev.def("multiply_accumulate_relinearize_rescale_new", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, const RelinKeys& k, PoolArg p) {
+        return s.multiply_accumulate_relinearize_rescale_new(const_ptrs(a), const_ptrs(b), k, P(p)); },
+           py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), POOL);
     // Galois
     ev.def("apply_galois", [](const Evaluator& s, const Ciphertext& a, size_t g, const GaloisKeys& k, Ciphertext& d, PoolArg p) { s.apply_galois(a, g, k, d, P(p)); },
            py::arg("encrypted"), py::arg("galois_element"), py::arg("galois_keys"), py::arg("destination"), POOL);

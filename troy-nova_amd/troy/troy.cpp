@@ -1616,6 +1616,88 @@ void Evaluator::multiply_relinearize_rescale(const Ciphertext& e1, const Ciphert
 }
 
 
+// -- dot products with lazy relinearization (additions; the sum of evaluator.cu:118-173's products, then evaluator_keyswitching.cu:119-144 and -----
+// -- evaluator_modswitch.cu:445-461 once) ---------------------------------------------------------------------------------------------------
+void Evaluator::multiply_accumulate_pair_checks(const Ciphertext& e1, const Ciphertext& e2, SchemeType scheme, double& scale, uint64_t& correction_factor) const {
+    check_no_seed("[Evaluator::multiply]", e1); check_no_seed("[Evaluator::multiply]", e2);
+    check_same_parms_id("[Evaluator::multiply]", e1, e2);
+    check_on_device("[Evaluator::multiply]", context_, e1); check_on_device("[Evaluator::multiply]", context_, e2);
+    auto cd = get_context_data("[Evaluator::multiply]", e1.parms_id());
+    const char* P = scheme == SchemeType::CKKS ? "[Evaluator::ckks_multiply_inplace]" : "[Evaluator::bgv_multiply]";
+    check_is_ntt_form(P, e1); check_is_ntt_form(P, e2);
+    if (e1.polynomial_count() != 2 || e2.polynomial_count() != 2) throw std::invalid_argument("[Evaluator::multiply_accumulate] Operands must have two polynomials.");
+    scale = 1.0; correction_factor = 1;
+    if (scheme == SchemeType::CKKS) {
+        scale = e1.scale() * e2.scale();
+        if (!is_scale_within_bounds(scale, cd)) throw std::invalid_argument("[Evaluator::ckks_multiply] Scale out of bounds");
+    } else {
+        const Modulus& t = cd->parms().plain_modulus();
+        correction_factor = (uint64_t)(((unsigned __int128)e1.correction_factor() * e2.correction_factor()) % t.value());
+    }
+}
+
+void Evaluator::multiply_accumulate(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, Ciphertext& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::multiply_accumulate]";
+    if (e1.empty() || e2.empty()) throw std::invalid_argument(std::string(P) + " Empty operand list.");
+    if (e1.size() != e2.size()) throw std::invalid_argument(std::string(P) + " Operand lists have different sizes.");
+    const SchemeType scheme = context_->key_context_data().value()->parms().scheme();
+    if (scheme == SchemeType::BFV) throw std::invalid_argument(std::string(P) + " BFV rounds every product; a sum of products is CKKS / BGV only.");
+    if (scheme != SchemeType::CKKS && scheme != SchemeType::BGV) throw std::logic_error(std::string(P) + " Scheme not implemented.");
+    double scale0 = 1.0; uint64_t cf0 = 1;
+    std::vector<const uint64_t*> a(e1.size()), b(e1.size());
+    for (size_t t = 0; t < e1.size(); t++) {
+        if (!e1[t] || !e2[t]) throw std::invalid_argument(std::string(P) + " Null operand.");
+        double scale = 1.0; uint64_t cf = 1;
+        multiply_accumulate_pair_checks(*e1[t], *e2[t], scheme, scale, cf);
+        if (t == 0) { scale0 = scale; cf0 = cf; }
+        if (e1[t]->parms_id() != e1[0]->parms_id()) throw std::invalid_argument(std::string(P) + " Terms have different parms_id.");
+        if (!are_close_double(scale, scale0)) throw std::invalid_argument(std::string(P) + " Terms have different scales.");
+        if (cf != cf0) throw std::invalid_argument(std::string(P) + " Terms have different correction factors.");
+        a[t] = e1[t]->data().raw_pointer(); b[t] = e2[t]->data().raw_pointer();
+    }
+    Ciphertext out = Ciphertext::like(*e1[0], 3, false, pool);
+    if (scheme == SchemeType::CKKS) out.scale() = scale0; else out.correction_factor() = cf0;
+    const uint32_t L = static_cast<uint32_t>(out.coeff_modulus_size());
+    {
+        detail::LaunchGate gate;
+        troyn_check(troyn_dyadic_convolute_accumulate(context_->plan(), 0, L, a.data(), b.data(), a.size(), out.data().raw_pointer(), 0, 1, current_stream()));
+    }
+    destination = std::move(out);
+}
+
+void Evaluator::multiply_accumulate_relinearize_rescale(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const RelinKeys& relin_keys,
+                                                        Ciphertext& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::multiply_accumulate_relinearize_rescale]";
+    if (e1.empty() || e2.empty()) throw std::invalid_argument(std::string(P) + " Empty operand list.");
+    if (e1.size() != e2.size()) throw std::invalid_argument(std::string(P) + " Operand lists have different sizes.");
+    uint32_t L0 = 0; ParmsID next0; double scale0 = 1.0; std::vector<const uint64_t*> keys0;
+    std::vector<const uint64_t*> a(e1.size()), b(e1.size());
+    for (size_t t = 0; t < e1.size(); t++) {
+        if (!e1[t] || !e2[t]) throw std::invalid_argument(std::string(P) + " Null operand.");
+        uint32_t L = 0; ParmsID next; double scale = 1.0; std::vector<const uint64_t*> keys;
+        if (!multiply_relinearize_rescale_prepare(*e1[t], *e2[t], relin_keys, L, next, scale, keys))
+            throw std::invalid_argument(std::string(P) + " Operands must be two-polynomial CKKS ciphertexts.");
+        if (t == 0) { L0 = L; next0 = next; scale0 = scale; keys0 = std::move(keys); }
+        if (e1[t]->parms_id() != e1[0]->parms_id()) throw std::invalid_argument(std::string(P) + " Terms have different parms_id.");
+        // (the product scales: both were divided by the same dropped modulus)
+        if (!are_close_double(e1[t]->scale() * e2[t]->scale(), e1[0]->scale() * e2[0]->scale())) throw std::invalid_argument(std::string(P) + " Terms have different scales.");
+        a[t] = e1[t]->data().raw_pointer(); b[t] = e2[t]->data().raw_pointer();
+    }
+    Ciphertext out = Ciphertext::like(*e1[0], 2, L0 - 1, false, pool);
+    out.parms_id() = next0;
+    out.scale() = scale0;
+    out.is_ntt_form() = true;
+    const size_t bytes = troyn_ckks_multiply_accumulate_relinearize_rescale_workspace_bytes(context_->plan(), L0, a.size(), 1);
+    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
+    {
+        detail::LaunchGate gate;
+        troyn_check(troyn_ckks_multiply_accumulate_relinearize_rescale(context_->plan(), L0, a.data(), b.data(), a.size(), keys0.data(), out.data().raw_pointer(),
+                                                                       ws.raw_pointer(), bytes, 1, current_stream()));
+    }
+    destination = std::move(out);
+}
+
+
 // -- NTT (evaluator_transform_ntt.cu:469-652) ----------------------------------------------------------------
 void Evaluator::transform_to_ntt_inplace(Ciphertext& encrypted) const {
     check_no_seed("[Evaluator::transform_to_ntt_inplace]", encrypted);

@@ -1422,6 +1422,29 @@ public:
     void multiply_relinearize_rescale_batched(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const RelinKeys& relin_keys,
                                               const std::vector<Ciphertext*>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
 
+    // ADDITION to the reference's interface: dot products of ciphertexts with lazy relinearization.
+    //   multiply_accumulate: destination = SUM_t multiply(e1[t], e2[t]), the three-polynomial sum, formed by ONE launch over all terms
+    //   (troyn_dyadic_convolute_accumulate: one pointer per term, no gather).  CKKS and BGV, two-polynomial NTT-form operands.  Payload, parms_id,
+    //   scale / correction factor are bit-identical to multiply_new per pair folded with add_inplace.  Every pair gets multiply's checks
+    //   (evaluator.cu:118-173) with the reference's messages; all pairs share one parms_id, all product scales (CKKS) are close, all product
+    //   correction factors (BGV) equal, else std::invalid_argument.  BFV throws std::invalid_argument: the BEHZ multiply rounds per product, the
+    //   sum before the rounding is another function.
+    //   multiply_accumulate_relinearize_rescale (CKKS): destination = rescale_to_next(relinearize(that sum)) as one library call
+    //   (troyn_ckks_multiply_accumulate_relinearize_rescale) -- one key switch and one rescale for the whole sum; bit-identical to composing
+    //   multiply_accumulate with evaluator.h's relinearize and rescale_to_next (evaluator_keyswitching.cu:119-144, evaluator_modswitch.cu:445-461).
+    // Call combining does not take part: these methods always launch directly.
+    void multiply_accumulate(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, Ciphertext& destination,
+                             MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext multiply_accumulate_new(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; multiply_accumulate(e1, e2, d, pool); return d;
+    }
+    void multiply_accumulate_relinearize_rescale(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const RelinKeys& relin_keys,
+                                                 Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext multiply_accumulate_relinearize_rescale_new(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const RelinKeys& relin_keys,
+                                                           MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; multiply_accumulate_relinearize_rescale(e1, e2, relin_keys, d, pool); return d;
+    }
+
     // ciphertext x plaintext -- evaluator.h (multiply_plain*, transform_plain_to_ntt*); evaluator_multiply_plain.cu,
     // evaluator_transform_ntt.cu:35-70
     void transform_plain_to_ntt(const Plaintext& plain, const ParmsID& parms_id, Plaintext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -1660,6 +1683,8 @@ private:
     // argument checks + result metadata of multiply -> relinearize -> rescale_to_next; false: the operands do not take the fused entry
     bool multiply_relinearize_rescale_prepare(const Ciphertext& e1, const Ciphertext& e2, const RelinKeys& relin_keys, uint32_t& L, ParmsID& next_parms_id, double& scale,
                                               std::vector<const uint64_t*>& key_ptrs) const;
+    // multiply_prepare's checks for one two-polynomial CKKS / BGV pair of a sum, without the result object; the product's scale and correction factor
+    void multiply_accumulate_pair_checks(const Ciphertext& e1, const Ciphertext& e2, SchemeType scheme, double& scale, uint64_t& correction_factor) const;
     HeContextPointer context_;
 };
 
