@@ -413,6 +413,38 @@ size_t troyn_bfv_multiply_workspace_bytes(const troyn_behz* behz, size_t pa, siz
 int troyn_bfv_multiply(const troyn_behz* behz, const uint64_t* a, size_t pa, const uint64_t* b, size_t pb,
                        uint64_t* out, void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
 
+/* BFV inner product: a sum of BEHZ tensor products with ONE scale-down.  Both entries are ADDITIONS to the reference's surface (the reference
+ * multiplies pair by pair, Evaluator::bfv_multiply, evaluator.cu:29-116, and relinearizes every product, evaluator_keyswitching.cu:119-144).
+ *
+ * troyn_bfv_multiply_accumulate:
+ *     out = floor_step( INTT( SUM_t NTT(lift(a[t])) (x) NTT(lift(b[t])) ) )
+ *   lift        steps (1)-(3) of Evaluator::bfv_multiply: fast_b_conv_m_tilde, sm_mrq, forward transforms in q and in Bsk
+ *   (x)         the two-by-two tensor product; the sums are taken modulo each prime of q and of the auxiliary base
+ *   floor_step  steps (6)-(8): multiply by t, fast_floor, fast_b_conv_sk
+ *   a, b   host arrays of `terms` device pointers, each to u64[batch][2][L][N] in coefficient form, 16-byte aligned; pointers may repeat
+ *          and a[t] == b[t] is allowed
+ *   out    [batch][3][L][N], coefficient form
+ * Contract: every stored word is a canonical residue, so the words depend neither on where reductions happen nor on the auxiliary base the
+ * product works in; with terms == 1 they are bit-identical to troyn_bfv_multiply with pa = pb = 2.  The conversions stay exact while
+ * terms * N * t * q * (1 + rho)^2 < prod(B) * m_sk; both the reference's base and the working base (troyn_behz_working_base_size) leave
+ * 2^31 for terms * N, and the entries accept terms <= 1024 (terms * N <= 2^27 at N = 2^17).
+ *
+ * troyn_bfv_multiply_accumulate_relinearize: out [batch][2][L][N] = troyn_relinearize(L, is_ckks = 0, is_ntt_form = 0) of the sum above,
+ * bit-identical to the two calls; keys as for troyn_switch_key.  One key switch for the whole sum.
+ *
+ * Terms are lifted and accumulated in chunks of at most 32 (every distinct pointer of a chunk is lifted once), so
+ * workspace_bytes(terms) == workspace_bytes(min(terms, 32)).
+ * Errors: TROYN_E_INVALID for terms == 0, terms > 1024, a null table or entry, a misaligned pointer, `out` overlapping an input;
+ * TROYN_E_WORKSPACE for a workspace below the queried size.  batch == 0 returns TROYN_OK, launches nothing and looks at neither `out` nor
+ * the workspace. */
+size_t troyn_bfv_multiply_accumulate_workspace_bytes(const troyn_behz* behz, size_t terms, size_t batch);
+int troyn_bfv_multiply_accumulate(const troyn_behz* behz, const uint64_t* const* a, const uint64_t* const* b, size_t terms,
+                                  uint64_t* out, void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+size_t troyn_bfv_multiply_accumulate_relinearize_workspace_bytes(const troyn_behz* behz, size_t terms, size_t batch);
+int troyn_bfv_multiply_accumulate_relinearize(const troyn_behz* behz, const uint64_t* const* a, const uint64_t* const* b, size_t terms,
+                                              const uint64_t* const* keys, uint64_t* out, void* workspace, size_t workspace_bytes,
+                                              size_t batch, troyn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,10 @@ SYMBOLS = {
     "troyn_extract_lwe": (C.c_int, [vp, u32, vp, vp, vp, vp, sz, vp, sz, vp]),
     "troyn_bfv_multiply_workspace_bytes": (sz, [vp, sz, sz, sz]),
     "troyn_bfv_multiply": (C.c_int, [vp, vp, sz, vp, sz, vp, vp, sz, sz, vp]),
+    "troyn_bfv_multiply_accumulate_workspace_bytes": (sz, [vp, sz, sz]),
+    "troyn_bfv_multiply_accumulate": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
+    "troyn_bfv_multiply_accumulate_relinearize_workspace_bytes": (sz, [vp, sz, sz]),
+    "troyn_bfv_multiply_accumulate_relinearize": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(vp), vp, vp, sz, sz, vp]),
 }
 
 _lib = None

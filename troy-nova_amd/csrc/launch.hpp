@@ -69,6 +69,9 @@ inline bool launch_tensor_f64(unsigned log_n, int stage, const NttArgs& a, const
 inline bool launch_tensor_u64(unsigned log_n, int stage, const NttArgs& a, const NttArgs& b, const NttArgs& d, size_t batch, const LaunchCtx& lc) {
     return log_n <= 13 ? launch_tensor_u64_small(log_n, stage, a, b, d, batch, lc) : launch_tensor_u64_large(log_n, stage, a, b, d, batch, lc);
 }
+// sum of tensor products fused with the transforms (tensor_accumulate_kernel, troyn_tensor_acc.hip; log_n = 15 / 16, limbs of the FP64 class,
+// at most TENSOR_ACC_MAX_TERMS terms); false: no kernel for this size
+bool launch_tensor_accumulate_f64(unsigned log_n, const NttArgs& fa, const TensorAccPtrs& terms, unsigned count, const NttArgs& id, size_t batch, const LaunchCtx& lc);
 // second-generation key-switch inner product (ksmac2_kernel, log_n = 13 / 14 / 15) and its key preparation
 // digits_f64: the digit rows hold doubles (fused chain: NTT_FLAG_STORE_F64) instead of u64 words; wide_digits: some digit limb is 2^50 or
 // wider (mixed chains, a.row_mask selects the rows of moduli < 2^50): digits are reduced with integer arithmetic while loading

@@ -109,6 +109,9 @@ constexpr unsigned NTT_FLAG_STORE_ROUND_HALF = 8u;   // NttArgs::flags: a plain 
 constexpr unsigned NTT_FLAG_TS_U64 = 32u;            // NttArgs::flags: the rows T_s = (s + qk/2) mod qk (special prime) hold u64 words
 constexpr unsigned NTT_FLAG_TL_U64 = 64u;            // NttArgs::flags: the rows T_l = (l + ql/2) mod ql (dropped prime) hold u64 words
 
+// tensor_accumulate_kernel (REGIO 5): the first inverse pass adds its words to the ones its destination holds (both in the form passes hand over)
+constexpr unsigned NTT_FLAG_MID_CARRY = 128u;
+
 enum NttFused {
     NTT_FUSED_MULPAIR = 3,       // inverse: input word = a1 (.) b1 (the product c2 formed while loading)
     NTT_FUSED_LAST_LIMB = 4,     // inverse: input = Q = P qk^-1 + c_k at limb L-1 (from ksmac2); stored word = result - r(s) qk^-1   (= l above)
@@ -403,6 +406,7 @@ struct ArithU64 {
     static __device__ __forceinline__ elem from_lds(u64 raw) { return raw; }
     static __device__ __forceinline__ u64 to_lds(elem x, const Mod&) { return x; }
     static __device__ __forceinline__ elem mid_fix(elem x, const Mod&) { return x; }
+    static __device__ __forceinline__ elem mid_sum(elem x, elem y, const Mod& m) { return csub4(x + y, m); }   // two words between inverse passes, [0, 4q) each
     static __device__ __forceinline__ void fwd(elem& a, elem& b, const tw_t w, const Mod& m) {
         const u64 u = csub4(a, m);
         const u64 v = shoup_lazy3(b, w.x, w.y, m.neg_q);
@@ -588,6 +592,7 @@ struct ArithF64 {
     static __device__ __forceinline__ elem from_lds(u64 raw) { return f64_bits_to_double(raw); }
     static __device__ __forceinline__ u64 to_lds(elem x, const Mod& m) { return f64_double_to_bits(f64_corr(x, m.m)); }
     static __device__ __forceinline__ elem mid_fix(elem x, const Mod& m) { return f64_corr(x, m.m); }
+    static __device__ __forceinline__ elem mid_sum(elem x, elem y, const Mod& m) { return f64_corr(x, m.m) + y; }   // y re-centred (load_mid): |sum| <= p + 1
     // f64_mulq: the quotient comes from the rounded product itself, so no w/p has to be formed per twiddle (w.y is never read and
     // the compiler drops its multiply)
     static __device__ __forceinline__ void fwd(elem& a, elem& b, const tw_t w, const Mod& m) {
@@ -639,6 +644,7 @@ __host__ __device__ constexpr bool ROUNDS_OK(int G, int EB) { return (G + EB - 1
 
 // REGIO (tensor_core_kernel): 1 = a forward last pass leaves its E consecutive outputs per thread in xio (A::keep form) instead of
 // storing them, 2 = an inverse first pass takes its E consecutive inputs per thread from xio (A::inv_in form) instead of loading them.
+// REGIO 5 (tensor_accumulate_kernel): as 2, and under NTT_FLAG_MID_CARRY the pass adds its result to what its destination holds.
 // REGIO 3 / 4 (mrr_tail_kernel, troyn_mrr_tail.hip; FP64 policy, whole-limb tiles): the rows T_s = (s + qk/2) mod qk and T_l = (l + ql/2) mod ql
 // of the fused chain stay in xio[0, E) / xio[E, 2E) instead of passing through memory -- the last inverse round and the first forward round
 // keep the same E words {t + R 2^(TB-EB)} per thread.  3 = an inverse transform ends in xio (IOM 0: T_s; NTT_FUSED_LAST_LIMB: reads T_s, leaves
@@ -650,8 +656,8 @@ template <class A, int LOGN, int LO, int G, int TB, int EB, bool INV, bool FIRST
 __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* keys, u64* lds, unsigned bid, unsigned t, typename A::elem* xio = nullptr) {
     constexpr int C = TB - G;
     static_assert(!HALF || (!KSMAC && REGIO == 0), "half-word LDS tiles: plain and fused transform kernels only");
-    static_assert(REGIO == 0 || REGIO >= 3 || (!KSMAC && IOM == 0 && C == 0 && (G + EB - 1) / EB > 1 && (REGIO == 1 ? (!INV && LAST) : (INV && FIRST))), "register hand-over: last forward / first inverse pass on whole tiles");
-    static_assert(REGIO < 3 || (std::is_same<A, ArithF64>::value && !KSMAC && !HALF && C == 0 && LO == 0 && G == TB && TB == LOGN && (G + EB - 1) / EB > 1 &&
+    static_assert(REGIO == 0 || REGIO == 3 || REGIO == 4 || (!KSMAC && IOM == 0 && C == 0 && (G + EB - 1) / EB > 1 && (REGIO == 1 ? (!INV && LAST) : (INV && FIRST && (REGIO == 2 || !LAST)))), "register hand-over: last forward / first inverse pass on whole tiles");
+    static_assert(REGIO < 3 || REGIO == 5 || (std::is_same<A, ArithF64>::value && !KSMAC && !HALF && C == 0 && LO == 0 && G == TB && TB == LOGN && (G + EB - 1) / EB > 1 &&
                                 (REGIO == 3 ? (INV && (IOM == 0 || IOM == NTT_FUSED_LAST_LIMB)) : (REGIO == 4 && !INV && IOM == NTT_FUSED_TAIL_RESCALE))),
                   "held T rows: whole-limb FP64 transforms of the merged chain tail");
     constexpr int E = 1 << EB;
@@ -837,8 +843,8 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
         constexpr bool PRIVATE_OUT = (r < ROUNDS - 1) && ntt_wave_bits(S, EB, TB) == ntt_wave_bits(S_NEXT, EB, TB);
         (void)PRIVATE_IN;
 
-        if constexpr (REGIO == 2 && r == 0) {
-            static_assert(r != 0 || REGIO != 2 || S == 0, "register hand-over: E consecutive coefficients per thread");
+        if constexpr ((REGIO == 2 || REGIO == 5) && r == 0) {
+            static_assert(r != 0 || (REGIO != 2 && REGIO != 5) || S == 0, "register hand-over: E consecutive coefficients per thread");
             static_for<0, E>([&](auto Rc) { x[decltype(Rc)::value] = xio[decltype(Rc)::value]; });
         } else if constexpr (REGIO == 4 && r == 0) {
             // r_j(s) qk^-1 + f_j(l) from the held T_s, T_l (exact doubles: the bit pattern NTT_FUSED_TAIL_RESCALE's loader reads from the rows)
@@ -1166,7 +1172,10 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
                         // the digits of the key switch are consumed as doubles by ksmac2: convert once here instead of once per output row there
                         if (a.flags & NTT_FLAG_STORE_F64) v = f64_double_to_bits(f64_from_u64(v));
                     }
-                } else v = A::store_mid(x[R], md);
+                } else {
+                    if constexpr (REGIO == 5) { if (a.flags & NTT_FLAG_MID_CARRY) x[R] = A::mid_sum(x[R], A::load_mid(ld_at(gout + GR, gb0), md), md); }
+                    v = A::store_mid(x[R], md);
+                }
                 nt_store_at(gout + GR, gb0, v);
             });
         }   // other rounds: the words stay in registers; the next round starts with the exchange
@@ -1260,6 +1269,79 @@ __global__ __launch_bounds__(1 << (TB - EB), MINB) void tensor_core_kernel(NttAr
     ntt_pass_body<A, LOGN, G1, TB, TB, EB, true, true, WHOLE, false, 0, 2>(id, nullptr, lds, bid(3, 1), t, a0);
     __syncthreads();
     ntt_pass_body<A, LOGN, G1, TB, TB, EB, true, true, WHOLE, false, 0, 2>(id, nullptr, lds, bid(3, 2), t, a1);
+}
+
+// Sum of tensor products (BFV inner product, troyn_bfv_multiply_accumulate): tensor_core_kernel's tile of one limb of one item, over a table
+// of terms.  Per term the workgroup runs the last forward pass of a0, b0, a1, b1 and adds a0 b0, a0 b1 + a1 b0, a1 b1 to three register
+// accumulators; after the last term it reduces them once and runs the first inverse pass of each.  The per-term products never reach HBM:
+// 4 limb reads per term, 3 limb writes per sum.  Two-pass sizes only (the operands arrive after their strided first pass, as for
+// tensor_core_kernel): six E-word arrays next to a transform in flight need more than the 128 registers a whole-limb workgroup has.
+//   fa: forward arguments over [item][2][ncomp][N], `in` taken from the table per term; id: inverse arguments over [item][3][ncomp][N],
+//   NTT_FLAG_MID_CARRY in id.flags: add to the words id.out holds (later chunks of a long sum)
+// FP64 class: a product of two re-centred factors is an exact integer of magnitude <= 0.69 p and d1 takes two per term, so the sums are
+// re-centred every 4 terms (ArithF64::mac_fix): |d| <= 0.5 p + 8 * 0.69 p < 6.1 p < 2^53.  Integer class: reduced sums (A::sum); that
+// instantiation spills (1.2-3 KB of scratch per lane at 8 or 16 coefficients per thread) and is not built: those limbs take the separate launches.
+constexpr int TENSOR_ACC_MAX_TERMS = 32;
+struct TensorAccPtrs { const u64* a[TENSOR_ACC_MAX_TERMS]; const u64* b[TENSOR_ACC_MAX_TERMS]; };
+template <class A, int LOGN, int TB, int EB, int MINB = 1>
+__global__ __launch_bounds__(1 << (TB - EB), MINB) void tensor_accumulate_kernel(NttArgs fa, TensorAccPtrs terms, unsigned count, NttArgs id) {
+    constexpr int G1 = LOGN - TB, E = 1 << EB;
+    static_assert(G1 > 0, "tensor_accumulate_kernel: two-pass sizes");
+    __shared__ u64 lds[ntt_lds_words(TB)];
+    using elem = typename A::elem;
+    unsigned t = threadIdx.x;
+    const unsigned tile = blockIdx.x & ((1u << G1) - 1), lj = blockIdx.x >> G1;
+    const unsigned j = lj % fa.ncomp, b = lj / fa.ncomp;
+    auto bid = [&](unsigned pcount, unsigned k) { return (((b * pcount + k) * fa.ncomp + j) << G1) | tile; };
+    const typename A::Mod md = A::make(fa.mods[ntt_table_index(fa, 0, j)]);
+    elem d0[E], d1[E], d2[E], x[E], y[E], z[E];
+    static_for<0, E>([&](auto Rc) { constexpr int R = decltype(Rc)::value; d0[R] = A::mac_zero(); d1[R] = A::mac_zero(); d2[R] = A::mac_zero(); });
+    NttArgs f = fa;
+    // neither the twiddles nor the LDS addresses depend on the term or the polynomial: keep them from being shared between the transforms
+    // (and spilled) by making both opaque in front of every pass (as ks_mac_kernel does per digit)
+    auto opaque = [&](NttArgs& g, const void* tw) {
+        asm volatile("" : "+v"(t));
+        unsigned tw_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)tw);
+        unsigned tw_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)tw >> 32));
+        asm volatile("" : "+s"(tw_lo), "+s"(tw_hi));
+        g.tw = (const void*)(((unsigned long long)tw_hi << 32) | tw_lo);
+    };
+    for (unsigned it = 0; it < count; ++it) {
+        opaque(f, fa.tw);
+        f.in = terms.a[it];
+        ntt_pass_body<A, LOGN, G1, TB, TB, EB, false, false, true, false, 0, 1>(f, nullptr, lds, bid(2, 0), t, x);           // a0
+        __syncthreads();   // the next transform's first exchange overwrites words other waves read in this one's last round
+        opaque(f, fa.tw);
+        f.in = terms.b[it];
+        ntt_pass_body<A, LOGN, G1, TB, TB, EB, false, false, true, false, 0, 1>(f, nullptr, lds, bid(2, 0), t, y);           // b0
+        __syncthreads();
+        static_for<0, E>([&](auto Rc) { constexpr int R = decltype(Rc)::value; d0[R] = A::sum(d0[R], A::prod(x[R], y[R], md), md); });
+        opaque(f, fa.tw);
+        f.in = terms.a[it];
+        ntt_pass_body<A, LOGN, G1, TB, TB, EB, false, false, true, false, 0, 1>(f, nullptr, lds, bid(2, 1), t, z);           // a1
+        __syncthreads();
+        static_for<0, E>([&](auto Rc) { constexpr int R = decltype(Rc)::value; d1[R] = A::sum(d1[R], A::prod(z[R], y[R], md), md); });
+        opaque(f, fa.tw);
+        f.in = terms.b[it];
+        ntt_pass_body<A, LOGN, G1, TB, TB, EB, false, false, true, false, 0, 1>(f, nullptr, lds, bid(2, 1), t, y);           // b1
+        __syncthreads();
+        static_for<0, E>([&](auto Rc) {
+            constexpr int R = decltype(Rc)::value;
+            d1[R] = A::sum(d1[R], A::prod(x[R], y[R], md), md);
+            d2[R] = A::sum(d2[R], A::prod(z[R], y[R], md), md);
+        });
+        if ((it & 3u) == 3u) static_for<0, E>([&](auto Rc) { constexpr int R = decltype(Rc)::value; A::mac_fix(d0[R], md); A::mac_fix(d1[R], md); A::mac_fix(d2[R], md); });
+    }
+    static_for<0, E>([&](auto Rc) { constexpr int R = decltype(Rc)::value; d0[R] = A::inv_in(d0[R], md); d1[R] = A::inv_in(d1[R], md); d2[R] = A::inv_in(d2[R], md); });
+    NttArgs g = id;
+    opaque(g, id.tw);
+    ntt_pass_body<A, LOGN, G1, TB, TB, EB, true, true, false, false, 0, 5>(g, nullptr, lds, bid(3, 0), t, d0);
+    __syncthreads();
+    opaque(g, id.tw);
+    ntt_pass_body<A, LOGN, G1, TB, TB, EB, true, true, false, false, 0, 5>(g, nullptr, lds, bid(3, 1), t, d1);
+    __syncthreads();
+    opaque(g, id.tw);
+    ntt_pass_body<A, LOGN, G1, TB, TB, EB, true, true, false, false, 0, 5>(g, nullptr, lds, bid(3, 2), t, d2);
 }
 
 // Fused key-switch inner product: grid = (L+1) rows x batch items, one whole-limb workgroup each.

@@ -247,4 +247,17 @@ static bool launch_tensor_class(unsigned log_n, int stage, const NttArgs& a, con
     }
 }
 
+// sum of tensor products at the two-pass sizes (tensor_accumulate_kernel), one 4096-word tile per workgroup: 256 threads x 16 coefficients.
+// Six arrays of 16 words stay in registers next to the transform in flight: one wave per SIMD and its 512 registers (FP64 class: 256 + 75
+// used, no scratch; two workgroups per CU would leave 256 and spill 101).
+template <class A>
+static bool launch_tensor_accumulate_class(unsigned log_n, const NttArgs& fa, const TensorAccPtrs& terms, unsigned count, const NttArgs& id, size_t batch, const LaunchCtx& lc) {
+    if (count == 0 || count > (unsigned)TENSOR_ACC_MAX_TERMS) return false;
+    switch (log_n) {
+        case 15: hipLaunchKernelGGL((tensor_accumulate_kernel<A, 15, 12, 4, 1>), dim3((unsigned)((batch * fa.ncomp) << 3)), dim3(256), 0, lc.s, fa, terms, count, id); return true;
+        case 16: hipLaunchKernelGGL((tensor_accumulate_kernel<A, 16, 12, 4, 1>), dim3((unsigned)((batch * fa.ncomp) << 4)), dim3(256), 0, lc.s, fa, terms, count, id); return true;
+        default: return false;
+    }
+}
+
 }  // namespace troyn

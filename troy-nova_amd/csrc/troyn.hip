@@ -2504,6 +2504,153 @@ extern "C" int troyn_bfv_multiply(const troyn_behz* b, const uint64_t* a_, size_
     return bfv_floor(c, path);
 }
 
+// ---- BFV inner product: SUM_t lift(a[t]) (x) lift(b[t]) in NTT form over both bases, ONE inverse tensor pass, floor and conversion ----
+// (additions to the reference's surface, include/troyn.h).  Every step between the lift and the floor is linear modulo each prime, so the
+// words are those of the per-pair products summed as integers before the floor -- as long as the sum fits the auxiliary base:
+//     T N t q (1 + rho)^2 < prod(B) m_sk,     (1 + rho)^2 < 2  (rho = 2 L / m_tilde, m_tilde = 2^32).
+// The reference's base has prod(B) m_sk > 2^(61 (#B + 1) - 1) >= 2^(32 + bits(t) + bits(q)) > 2^32 t q (its primes are the largest below
+// 2^61), behz_choose_base's working base > 2^(34 + bits(t) + bits(q)): T N < 2^31 holds in either.  The cap of 1024 terms gives
+// T N <= 2^27 at N = 2^17, four bits to spare.
+constexpr size_t BFV_ACC_MAX_TERMS = 1024;
+constexpr size_t BFV_ACC_CHUNK = TENSOR_ACC_MAX_TERMS;      // terms lifted and accumulated at a time (the kernel's pointer table)
+static_assert(BFV_ACC_CHUNK == 32, "include/troyn.h states the chunk");
+
+// workspace: stage_q / stage_bsk: 2 * chunk lifted operands (every distinct pointer of a chunk is lifted once) | d_q, d_bsk: the sum
+// | [prod3: the floor's output | the key switch's own workspace]
+struct BfvAccLayout { BehzLayout w; size_t slots, slot_q, slot_bsk, prod3, sub, sub_bytes, total_bytes; };
+static BfvAccLayout bfv_acc_layout(const troyn_behz* b, size_t terms, size_t batch, bool relin) {
+    const size_t n = b->plan->n, L = b->L, S = b->Bsk;
+    BfvAccLayout y;
+    y.slots = 2 * std::min(terms, BFV_ACC_CHUNK);
+    y.slot_q = batch * 2 * L * n; y.slot_bsk = batch * 2 * S * n;
+    size_t off = 0;
+    y.w.a_q = y.w.b_q = off;     off += y.slots * y.slot_q;
+    y.w.a_bsk = y.w.b_bsk = off; off += y.slots * y.slot_bsk;
+    y.w.d_q = off;   off += batch * 3 * L * n;
+    y.w.d_bsk = off; off += batch * 3 * S * n;
+    y.w.total = off;
+    y.prod3 = off; if (relin) off += batch * 3 * L * n;
+    y.sub = off;
+    y.sub_bytes = relin ? troyn_relinearize_workspace_bytes(b->plan, (uint32_t)L, batch) : 0;
+    y.total_bytes = off * sizeof(u64) + y.sub_bytes;
+    return y;
+}
+
+// one chunk of staged terms into d (one base): tensor_accumulate_kernel
+static int bfv_tensor_accumulate(const troyn_plan* p, unsigned nc, const u64* const* xa, const u64* const* xb, unsigned cnt, u64* d, bool carry, size_t batch, hipStream_t s) {
+    TensorAccPtrs g;
+    for (unsigned t = 0; t < (unsigned)TENSOR_ACC_MAX_TERMS; t++) { g.a[t] = xa[t < cnt ? t : 0]; g.b[t] = xb[t < cnt ? t : 0]; }
+    NttArgs fa = contiguous_args(p, xa[0], nullptr, 2, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
+    NttArgs id = contiguous_args(p, d, d, 3, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
+    prep_direct(p, fa, true, false); prep_direct(p, id, true, true);
+    if (carry) id.flags |= NTT_FLAG_MID_CARRY;
+    if ((batch * 3 * nc) << (p->log_n - 12) > 0x7fffffffull) return fail(TROYN_E_INVALID, "[troyn_bfv_multiply_accumulate] batch too large for one launch");
+    if (!launch_tensor_accumulate_f64(p->log_n, fa, g, cnt, id, batch, launch_ctx(p, s)))
+        return fail(TROYN_E_INVALID, "[troyn_bfv_multiply_accumulate] no accumulating tensor kernel for this size");
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+
+// the sum into out3 [batch][3][L][N] (arguments checked by the entries)
+static int bfv_accumulate(const troyn_behz* b, const uint64_t* const* a, const uint64_t* const* bb, size_t terms, u64* out3, u64* ws,
+                          const BfvAccLayout& y, size_t batch, hipStream_t s) {
+    behz_follow_options(b);
+    BfvCall c{b, b->plan, b->aux, b->L, b->Bsk, (const u64*)a[0], 2, (const u64*)bb[0], 2, out3, ws, y.w, batch, s};
+    BfvPath path = bfv_path(c);
+    // The accumulating kernel exists for the two-pass sizes and the FP64 class.  Whole-limb sizes (tensor_core_kernel is at its register
+    // cap there), limbs of the integer class, TROYN_BFV_TENSOR=split and the small rings: full forward transforms into the staging area,
+    // dyadic_convolute_accumulate_kernel per base, inverse transforms.
+    if (path.tkind != 2 || !use_f64(c.pq, 0, c.L) || !use_f64(c.px, 0, c.S)) { path.tkind = 0; path.lift_fused = false; }
+    const u64* src[2 * BFV_ACC_CHUNK];
+    const u64* xa_q[BFV_ACC_CHUNK]; const u64* xb_q[BFV_ACC_CHUNK]; const u64* xa_x[BFV_ACC_CHUNK]; const u64* xb_x[BFV_ACC_CHUNK];
+    auto tab = [](const u64* const* x) { return reinterpret_cast<const uint64_t* const*>(x); };
+    u64* const stage_q = ws + y.w.a_q;
+    u64* const stage_x = ws + y.w.a_bsk;
+    for (size_t t0 = 0; t0 < terms; t0 += BFV_ACC_CHUNK) {
+        const unsigned cnt = (unsigned)std::min(terms - t0, BFV_ACC_CHUNK);
+        size_t used = 0;
+        // steps (1)-(3) once per distinct operand of the chunk (a[t] == b[t], one ciphertext in several terms)
+        auto staged = [&](const u64* ptr, size_t& slot) -> int {
+            for (slot = 0; slot < used; slot++) if (src[slot] == ptr) return TROYN_OK;
+            src[used++] = ptr;
+            return bfv_lift(c, path, ptr, 2, stage_q + slot * y.slot_q, stage_x + slot * y.slot_bsk);
+        };
+        for (unsigned t = 0; t < cnt; t++) {
+            size_t sa, sb;
+            if (int rc = staged((const u64*)a[t0 + t], sa)) return rc;
+            if (int rc = staged((const u64*)bb[t0 + t], sb)) return rc;
+            xa_q[t] = stage_q + sa * y.slot_q; xa_x[t] = stage_x + sa * y.slot_bsk;
+            xb_q[t] = stage_q + sb * y.slot_q; xb_x[t] = stage_x + sb * y.slot_bsk;
+        }
+        const bool carry = t0 > 0;
+        TimerScope ts(TROYN_TIMER_BFV_TENSOR, s);
+        if (path.tensor()) {
+            if (int rc = bfv_tensor_accumulate(c.pq, c.L, xa_q, xb_q, cnt, ws + y.w.d_q, carry, batch, s)) return rc;
+            if (int rc = bfv_tensor_accumulate(c.px, c.S, xa_x, xb_x, cnt, ws + y.w.d_bsk, carry, batch, s)) return rc;
+        } else {
+            if (int rc = launch_convolute_accumulate(c.pq->d_mods, c.pq->n, 0, c.L, tab(xa_q), tab(xb_q), cnt, ws + y.w.d_q, carry, batch, s)) return rc;
+            if (int rc = launch_convolute_accumulate(c.px->d_mods, c.pq->n, 0, c.S, tab(xa_x), tab(xb_x), cnt, ws + y.w.d_bsk, carry, batch, s)) return rc;
+        }
+    }
+    // the last inverse pass (lift_fused: inside the floor launch) or the inverse transforms, once
+    for (int base = 0; base < 2; base++) {
+        const troyn_plan* p = base ? c.px : c.pq;
+        const unsigned nc = base ? c.S : c.L;
+        u64* xd = ws + (base ? y.w.d_bsk : y.w.d_q);
+        NttArgs id = contiguous_args(p, xd, xd, 3, nc, 0, nc, TROYN_IDX_COMPONENTWISE, 0);
+        if (path.tensor()) { if (!path.lift_fused) if (int rc = tensor_stage(p, 2, id, id, id, batch, s)) return rc; }
+        else if (int rc = launch_ntt(p, id, batch, true, s)) return rc;
+    }
+    return bfv_floor(c, path);
+}
+
+// checks shared by the two entries; out_words: size of `out`
+static int bfv_accumulate_check(const char* P, const troyn_behz* b, const uint64_t* const* a, const uint64_t* const* bb, size_t terms,
+                                const uint64_t* out, size_t out_words, size_t batch) {
+    if (!b || !a || !bb) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if (terms > BFV_ACC_MAX_TERMS) return fail(TROYN_E_INVALID, std::string(P) + " more than 1024 terms");
+    return check_convolute_accumulate(P, b->plan, 0, b->L, a, bb, terms, out, out_words, batch);
+}
+
+extern "C" size_t troyn_bfv_multiply_accumulate_workspace_bytes(const troyn_behz* b, size_t terms, size_t batch) {
+    if (!b || terms == 0 || terms > BFV_ACC_MAX_TERMS) return 0;
+    return bfv_acc_layout(b, terms, batch, false).total_bytes;
+}
+
+extern "C" int troyn_bfv_multiply_accumulate(const troyn_behz* b, const uint64_t* const* a, const uint64_t* const* bb, size_t terms,
+                                             uint64_t* out, void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(b);
+    const char* P = "[troyn_bfv_multiply_accumulate]";
+    if (int rc = bfv_accumulate_check(P, b, a, bb, terms, out, batch * 3 * (size_t)(b ? b->L : 0) * (b ? b->plan->n : 0), batch)) return rc;
+    if (batch == 0) return TROYN_OK;
+    const BfvAccLayout y = bfv_acc_layout(b, terms, batch, false);
+    if (!workspace || workspace_bytes < y.total_bytes) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    if ((uintptr_t)workspace & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned workspace");
+    return bfv_accumulate(b, a, bb, terms, (u64*)out, (u64*)workspace, y, batch, (hipStream_t)stream);
+}
+
+extern "C" size_t troyn_bfv_multiply_accumulate_relinearize_workspace_bytes(const troyn_behz* b, size_t terms, size_t batch) {
+    if (!b || terms == 0 || terms > BFV_ACC_MAX_TERMS) return 0;
+    return bfv_acc_layout(b, terms, batch, true).total_bytes;
+}
+
+extern "C" int troyn_bfv_multiply_accumulate_relinearize(const troyn_behz* b, const uint64_t* const* a, const uint64_t* const* bb, size_t terms,
+                                                         const uint64_t* const* keys, uint64_t* out, void* workspace, size_t workspace_bytes,
+                                                         size_t batch, troyn_stream_t stream) {
+    select_device(b);
+    const char* P = "[troyn_bfv_multiply_accumulate_relinearize]";
+    if (!keys) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if (int rc = bfv_accumulate_check(P, b, a, bb, terms, out, batch * 2 * (size_t)(b ? b->L : 0) * (b ? b->plan->n : 0), batch)) return rc;
+    if (batch == 0) return TROYN_OK;
+    const BfvAccLayout y = bfv_acc_layout(b, terms, batch, true);
+    if (!workspace || workspace_bytes < y.total_bytes) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    if ((uintptr_t)workspace & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned workspace");
+    u64* ws = (u64*)workspace;
+    if (int rc = bfv_accumulate(b, a, bb, terms, ws + y.prod3, ws, y, batch, (hipStream_t)stream)) return rc;
+    // Evaluator::relinearize on coefficient-form BFV data (evaluator_keyswitching.cu:119-144): one key switch for the whole sum
+    return troyn_relinearize(b->plan, b->L, 0, 0, (const uint64_t*)(ws + y.prod3), keys, out, ws + y.sub, y.sub_bytes, batch, stream);
+}
+
 // ---------------------------------------------------------------------------------------
 // context PRNG samplers, BFV plaintext scaling, BFV decryption rounding
 // ---------------------------------------------------------------------------------------

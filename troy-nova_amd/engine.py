@@ -629,3 +629,28 @@ class Behz:
         capi.check(self.plan.lib.troyn_bfv_multiply(self.h, _ptr(a), pa, _ptr(b), pb, _ptr(out),
                                                     C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
+
+    # -- inner product: a sum of tensor products, one scale-down (additions) ------------------------------
+    def bfv_multiply_accumulate(self, a_list, b_list, out=None):
+        """SUM_t a_list[t] x b_list[t] -> [batch][3][L][N]; operands [batch][2][L][N] in coefficient form; one floor for the sum"""
+        n, L = self.plan.n, self.L
+        pa, pb, batch = self.plan._term_ptrs("[troyn_bfv_multiply_accumulate]", a_list, b_list, 2 * L * n)
+        if out is None:
+            out = torch.empty((batch, 3, L, n), dtype=torch.int64, device=self.plan.device)
+        nbytes = self.plan.lib.troyn_bfv_multiply_accumulate_workspace_bytes(self.h, len(a_list), batch)
+        ws = self.plan.workspace(nbytes)
+        capi.check(self.plan.lib.troyn_bfv_multiply_accumulate(self.h, pa, pb, len(a_list), _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                               batch, _stream()))
+        return out
+
+    def bfv_multiply_accumulate_relinearize(self, a_list, b_list, keys, out=None):
+        """relinearize(SUM_t a_list[t] x b_list[t]) -> [batch][2][L][N]: one floor and one key switch for the sum"""
+        n, L = self.plan.n, self.L
+        pa, pb, batch = self.plan._term_ptrs("[troyn_bfv_multiply_accumulate_relinearize]", a_list, b_list, 2 * L * n)
+        if out is None:
+            out = torch.empty((batch, 2, L, n), dtype=torch.int64, device=self.plan.device)
+        nbytes = self.plan.lib.troyn_bfv_multiply_accumulate_relinearize_workspace_bytes(self.h, len(a_list), batch)
+        ws = self.plan.workspace(nbytes)
+        capi.check(self.plan.lib.troyn_bfv_multiply_accumulate_relinearize(self.h, pa, pb, len(a_list), self.plan._key_ptrs(keys, L), _ptr(out),
+                                                                           C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        return out

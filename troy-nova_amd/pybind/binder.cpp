@@ -471,6 +471,18 @@ PYBIND11_MODULE(pytroy_raw, m) {
     ev.def("multiply_accumulate_relinearize_rescale_new", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, const RelinKeys& k, PoolArg p) {
         return s.multiply_accumulate_relinearize_rescale_new(const_ptrs(a), const_ptrs(b), k, P(p)); },
            py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), POOL);
+    // additions: the BFV inner product, one scale-down for the sum (troy.h)
+    ev.def("bfv_multiply_accumulate", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, Ciphertext& d, PoolArg p) {
+        s.bfv_multiply_accumulate(const_ptrs(a), const_ptrs(b), d, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("destination"), POOL);
+    ev.def("bfv_multiply_accumulate_new", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, PoolArg p) {
+        return s.bfv_multiply_accumulate_new(const_ptrs(a), const_ptrs(b), P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), POOL);
+    ev.def("bfv_multiply_accumulate_relinearize", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, const RelinKeys& k,
+                                                     Ciphertext& d, PoolArg p) {
+        s.bfv_multiply_accumulate_relinearize(const_ptrs(a), const_ptrs(b), k, d, P(p)); },
+           py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    ev.def("bfv_multiply_accumulate_relinearize_new", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, const RelinKeys& k, PoolArg p) {
+        return s.bfv_multiply_accumulate_relinearize_new(const_ptrs(a), const_ptrs(b), k, P(p)); },
+           py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), POOL);
     // Galois
     ev.def("apply_galois", [](const Evaluator& s, const Ciphertext& a, size_t g, const GaloisKeys& k, Ciphertext& d, PoolArg p) { s.apply_galois(a, g, k, d, P(p)); },
            py::arg("encrypted"), py::arg("galois_element"), py::arg("galois_keys"), py::arg("destination"), POOL);

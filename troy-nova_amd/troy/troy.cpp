@@ -1641,7 +1641,7 @@ void Evaluator::multiply_accumulate(const std::vector<const Ciphertext*>& e1, co
     if (e1.empty() || e2.empty()) throw std::invalid_argument(std::string(P) + " Empty operand list.");
     if (e1.size() != e2.size()) throw std::invalid_argument(std::string(P) + " Operand lists have different sizes.");
     const SchemeType scheme = context_->key_context_data().value()->parms().scheme();
-    if (scheme == SchemeType::BFV) throw std::invalid_argument(std::string(P) + " BFV rounds every product; a sum of products is CKKS / BGV only.");
+    if (scheme == SchemeType::BFV) throw std::invalid_argument(std::string(P) + " BFV rounds every product; a sum of products is CKKS / BGV only (BFV: bfv_multiply_accumulate).");
     if (scheme != SchemeType::CKKS && scheme != SchemeType::BGV) throw std::logic_error(std::string(P) + " Scheme not implemented.");
     double scale0 = 1.0; uint64_t cf0 = 1;
     std::vector<const uint64_t*> a(e1.size()), b(e1.size());
@@ -1693,6 +1693,62 @@ void Evaluator::multiply_accumulate_relinearize_rescale(const std::vector<const 
         detail::LaunchGate gate;
         troyn_check(troyn_ckks_multiply_accumulate_relinearize_rescale(context_->plan(), L0, a.data(), b.data(), a.size(), keys0.data(), out.data().raw_pointer(),
                                                                        ws.raw_pointer(), bytes, 1, current_stream()));
+    }
+    destination = std::move(out);
+}
+
+
+// -- BFV inner product (addition): the sum of evaluator.cu:29-116's tensor products, scaled down once; evaluator_keyswitching.cu:119-144 once --
+static constexpr size_t BFV_MULTIPLY_ACCUMULATE_MAX_TERMS = 1024;     // include/troyn.h: the bound on terms * N the auxiliary base leaves
+
+void Evaluator::bfv_multiply_accumulate_prepare(const char* P, const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2,
+                                                std::vector<const uint64_t*>& a, std::vector<const uint64_t*>& b) const {
+    if (e1.empty() || e2.empty()) throw std::invalid_argument(std::string(P) + " Empty operand list.");
+    if (e1.size() != e2.size()) throw std::invalid_argument(std::string(P) + " Operand lists have different sizes.");
+    if (e1.size() > BFV_MULTIPLY_ACCUMULATE_MAX_TERMS) throw std::invalid_argument(std::string(P) + " More than 1024 terms.");
+    if (context_->key_context_data().value()->parms().scheme() != SchemeType::BFV) throw std::invalid_argument(std::string(P) + " BFV only (CKKS / BGV: multiply_accumulate).");
+    a.resize(e1.size()); b.resize(e1.size());
+    for (size_t t = 0; t < e1.size(); t++) {
+        if (!e1[t] || !e2[t]) throw std::invalid_argument(std::string(P) + " Null operand.");
+        for (const Ciphertext* x : {e1[t], e2[t]}) {
+            check_no_seed("[Evaluator::multiply]", *x);
+            check_on_device("[Evaluator::multiply]", context_, *x);
+            check_is_not_ntt_form("[Evaluator::bfv_multiply_inplace]", *x);
+            if (x->polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " Operands must have two polynomials.");
+            if (x->parms_id() != e1[0]->parms_id()) throw std::invalid_argument(std::string(P) + " Terms have different parms_id.");
+        }
+        a[t] = e1[t]->data().raw_pointer(); b[t] = e2[t]->data().raw_pointer();
+    }
+    get_context_data("[Evaluator::multiply]", e1[0]->parms_id());
+}
+
+void Evaluator::bfv_multiply_accumulate(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, Ciphertext& destination, MemoryPoolHandle pool) const {
+    std::vector<const uint64_t*> a, b;
+    bfv_multiply_accumulate_prepare("[Evaluator::bfv_multiply_accumulate]", e1, e2, a, b);
+    Ciphertext out = Ciphertext::like(*e1[0], 3, false, pool);
+    const troyn_behz* bz = context_->behz(out.coeff_modulus_size());
+    const size_t bytes = troyn_bfv_multiply_accumulate_workspace_bytes(bz, a.size(), 1);
+    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
+    {
+        detail::LaunchGate gate;
+        troyn_check(troyn_bfv_multiply_accumulate(bz, a.data(), b.data(), a.size(), out.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+    }
+    destination = std::move(out);
+}
+
+void Evaluator::bfv_multiply_accumulate_relinearize(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const RelinKeys& relin_keys,
+                                                    Ciphertext& destination, MemoryPoolHandle pool) const {
+    std::vector<const uint64_t*> a, b, keys;
+    bfv_multiply_accumulate_prepare("[Evaluator::bfv_multiply_accumulate_relinearize]", e1, e2, a, b);
+    // relinearize's checks on the shape of the sum (it is never written: the library keeps the three polynomials in its workspace)
+    Ciphertext sum = Ciphertext::like(*e1[0], 3, false, pool), out;
+    relinearize_prepare(sum, relin_keys, out, keys, pool);
+    const troyn_behz* bz = context_->behz(out.coeff_modulus_size());
+    const size_t bytes = troyn_bfv_multiply_accumulate_relinearize_workspace_bytes(bz, a.size(), 1);
+    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
+    {
+        detail::LaunchGate gate;
+        troyn_check(troyn_bfv_multiply_accumulate_relinearize(bz, a.data(), b.data(), a.size(), keys.data(), out.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
     }
     destination = std::move(out);
 }

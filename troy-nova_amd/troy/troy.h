@@ -1445,6 +1445,24 @@ public:
         Ciphertext d; multiply_accumulate_relinearize_rescale(e1, e2, relin_keys, d, pool); return d;
     }
 
+    // ADDITION to the reference's interface: the BFV inner product.  destination = the BEHZ multiply (evaluator.cu:29-116) with the tensor
+    //   products of all pairs summed BEFORE its scale-down: one floor (and, in the relinearizing form, one key switch,
+    //   evaluator_keyswitching.cu:119-144) for the whole sum (troyn_bfv_multiply_accumulate[_relinearize], include/troyn.h).  It decrypts to
+    //   SUM_t e1[t] * e2[t] with the noise of ONE rounding; with one pair the payload is bit-identical to multiply_new.  BFV context, every
+    //   operand on the device, in coefficient form, two polynomials, no seed, one parms_id, at most 1024 pairs; else std::invalid_argument.
+    // Call combining does not take part: these methods always launch directly.
+    void bfv_multiply_accumulate(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, Ciphertext& destination,
+                                 MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bfv_multiply_accumulate_new(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bfv_multiply_accumulate(e1, e2, d, pool); return d;
+    }
+    void bfv_multiply_accumulate_relinearize(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const RelinKeys& relin_keys,
+                                             Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bfv_multiply_accumulate_relinearize_new(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const RelinKeys& relin_keys,
+                                                       MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bfv_multiply_accumulate_relinearize(e1, e2, relin_keys, d, pool); return d;
+    }
+
     // ciphertext x plaintext -- evaluator.h (multiply_plain*, transform_plain_to_ntt*); evaluator_multiply_plain.cu,
     // evaluator_transform_ntt.cu:35-70
     void transform_plain_to_ntt(const Plaintext& plain, const ParmsID& parms_id, Plaintext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -1685,6 +1703,8 @@ private:
                                               std::vector<const uint64_t*>& key_ptrs) const;
     // multiply_prepare's checks for one two-polynomial CKKS / BGV pair of a sum, without the result object; the product's scale and correction factor
     void multiply_accumulate_pair_checks(const Ciphertext& e1, const Ciphertext& e2, SchemeType scheme, double& scale, uint64_t& correction_factor) const;
+    void bfv_multiply_accumulate_prepare(const char* P, const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2,
+                                         std::vector<const uint64_t*>& a, std::vector<const uint64_t*>& b) const;
     HeContextPointer context_;
 };
 
