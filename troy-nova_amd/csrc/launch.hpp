@@ -3,15 +3,31 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ntt_kernels.hpp"
+#include "ntt_sizes.hpp"
 #include "ksmac_kernels.hpp"
 #include "behz2_kernels.hpp"
 
-// a launch of at most CUs / TROYN_SMALL_LP_FACTOR limb-polynomials counts as small (two-pass transforms at N = 8192 / 16384, merged tails, no split by class)
 #ifndef TROYN_SMALL_LP_FACTOR
 #define TROYN_SMALL_LP_FACTOR 2      // measured 8 | 2 | 1: eight ciphertexts at N = 16384, fused chain 100 | 75 | 75 us; 128: 473 | 469 | 481
 #endif
 
 namespace troyn {
+
+// CUs of the current device (cached per host thread)
+inline unsigned device_cu_count() {
+    static thread_local int cached_dev = -1;
+    static thread_local unsigned cached = 0;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev != cached_dev) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        cached = (unsigned)cus; cached_dev = dev;
+    }
+    return cached;
+}
+// a launch of at most CUs / TROYN_SMALL_LP_FACTOR limb-polynomials counts as small (two-pass transforms at N = 8192 / 16384, merged tails, no split by class)
+inline bool is_small_launch(size_t limb_polys) { return limb_polys * TROYN_SMALL_LP_FACTOR <= device_cu_count(); }
 
 // what a launch of the NTT family needs besides its arguments: the stream and the plan's A/B options that select kernel variants
 // (read once when the plan is created, troyn.hip TroynOptions -- no environment access on the launch path)
@@ -22,56 +38,54 @@ struct LaunchCtx {
     int tensor_wgs;            // TROYN_TENSOR_WGS (8 = default)
 };
 
-// optimised transforms of one arithmetic class (false: no kernel for this size -> ntt_generic); each class is instantiated in two
-// translation units, N <= 8192 and N >= 16384
-#define TROYN_DECL_NTT_UNIT(SUFFIX)                                                                                                   \
-    bool launch_ntt_##SUFFIX(unsigned log_n, const NttArgs& a, size_t limb_polys, bool inverse, const LaunchCtx& lc, u64* scratch);          \
-    bool launch_ks_mac_##SUFFIX(unsigned log_n, const NttArgs& a, const KeyPtrs& kp, size_t blocks, const LaunchCtx& lc);                    \
-    bool launch_tensor_##SUFFIX(unsigned log_n, int stage, const NttArgs& a, const NttArgs& b, const NttArgs& d, size_t batch, const LaunchCtx& lc);
-TROYN_DECL_NTT_UNIT(f64_small) TROYN_DECL_NTT_UNIT(f64_large) TROYN_DECL_NTT_UNIT(u64_small) TROYN_DECL_NTT_UNIT(u64_large)
-#undef TROYN_DECL_NTT_UNIT
+// The NTT-family launches of one arithmetic class and one part of the sizes (ntt_sizes.hpp: ntt_part_of): defined in ntt_launch.inl,
+// instantiated once in each of troyn_ntt_{f64,u64}_{small,large}.hip.  All return false where no kernel exists for the size.
+template <class A, int PART>
+struct NttUnit {
+    static bool transform(unsigned log_n, const NttArgs& a, size_t limb_polys, bool inverse, const LaunchCtx& lc, u64* scratch);
+    static bool small_pass(unsigned log_n, int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc);
+    static bool ks_mac(unsigned log_n, const NttArgs& a, const KeyPtrs& kp, size_t blocks, const LaunchCtx& lc);
+    static bool tensor(unsigned log_n, int stage, const NttArgs& a, const NttArgs& b, const NttArgs& d, size_t batch, const LaunchCtx& lc);
+};
+extern template struct NttUnit<ArithF64, 1>;
+extern template struct NttUnit<ArithF64, 2>;
+extern template struct NttUnit<ArithU64, 1>;
+extern template struct NttUnit<ArithU64, 2>;
+// f(the unit that holds log_n under the FP64 (f64) or the integer policy)
+template <class F>
+inline bool in_ntt_unit(unsigned log_n, bool f64, F&& f) {
+    if (ntt_part_of(log_n) == 1) return f64 ? f(NttUnit<ArithF64, 1>{}) : f(NttUnit<ArithU64, 1>{});
+    return f64 ? f(NttUnit<ArithF64, 2>{}) : f(NttUnit<ArithU64, 2>{});
+}
+
+// optimised transform (false: no kernel for this size -> launch_ntt_generic)
+inline bool launch_transform(unsigned log_n, bool f64, const NttArgs& a, size_t limb_polys, bool inverse, const LaunchCtx& lc, u64* scratch) {
+    return in_ntt_unit(log_n, f64, [&](auto u) { return decltype(u)::transform(log_n, a, limb_polys, inverse, lc, scratch); });
+}
 void launch_ntt_generic(const NttArgs& a, unsigned log_n, bool inverse, size_t limb_polys, const LaunchCtx& lc);
-// single objects through the fused chain at N = 8192 / 16384 (troyn_mrr_small.hip): one pass of a two-pass transform, and the strided passes of the
-// chain's tail (special rows, dropped limb, output limbs) as one launch
-void launch_ntt_f64_pass14(int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc);
-void launch_ntt_f64_pass13(int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc);
-void launch_ntt_u64_pass14(int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc);
-void launch_ntt_u64_pass13(int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc);
-void launch_ntt_f64_pass15(int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc);
-void launch_ntt_u64_pass15(int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc);
-inline void launch_ntt_f64_small_pass(unsigned log_n, int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc) {
-    if (log_n == 13) launch_ntt_f64_pass13(which, a, limb_polys, lc); else if (log_n == 14) launch_ntt_f64_pass14(which, a, limb_polys, lc); else launch_ntt_f64_pass15(which, a, limb_polys, lc);
+// single objects through the fused chain at N = 8192 .. 32768: one pass of the two-pass transform a small launch takes (troyn_mrr_small.hip
+// runs the strided passes between them itself).  which = 0: first inverse pass (the layers inside the contiguous chunks), 1: last forward
+// pass (the same layers + the fused epilogue a.fused_mode selects)
+inline bool launch_small_pass(unsigned log_n, bool f64, int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc) {
+    return in_ntt_unit(log_n, f64, [&](auto u) { return decltype(u)::small_pass(log_n, which, a, limb_polys, lc); });
 }
-inline void launch_ntt_u64_small_pass(unsigned log_n, int which, const NttArgs& a, size_t limb_polys, const LaunchCtx& lc) {
-    if (log_n == 13) launch_ntt_u64_pass13(which, a, limb_polys, lc); else if (log_n == 14) launch_ntt_u64_pass14(which, a, limb_polys, lc); else launch_ntt_u64_pass15(which, a, limb_polys, lc);
-}
+// ... and the strided passes of the chain's tail (special rows, dropped limb, output limbs) as one launch
 void launch_mrr_quartet(unsigned log_n, size_t batch, const NttArgs& sp, const NttArgs& la, const NttArgs& ta, hipStream_t s, bool limb_parallel);
 void launch_mrr_quartet_load(unsigned log_n, size_t groups, const NttArgs& iv, const NttArgs& fw, hipStream_t s, bool f64);
 // the same tail on whole-limb tiles for the batches that fill the chip (troyn_mrr_tail.hip; log_n = 14, all-FP64 chains): one launch for steps (3)-(5)
 void launch_mrr_tail(unsigned log_n, size_t batch, const NttArgs& sp, const NttArgs& la, const NttArgs& ta, hipStream_t s);
-inline bool launch_ntt_f64(unsigned log_n, const NttArgs& a, size_t lp, bool inverse, const LaunchCtx& lc, u64* scratch) {
-    return log_n <= 13 ? launch_ntt_f64_small(log_n, a, lp, inverse, lc, scratch) : launch_ntt_f64_large(log_n, a, lp, inverse, lc, scratch);
-}
-inline bool launch_ntt_u64(unsigned log_n, const NttArgs& a, size_t lp, bool inverse, const LaunchCtx& lc, u64* scratch) {
-    return log_n <= 13 ? launch_ntt_u64_small(log_n, a, lp, inverse, lc, scratch) : launch_ntt_u64_large(log_n, a, lp, inverse, lc, scratch);
-}
 // first-generation fused key-switch inner product (ks_mac_kernel)
-inline bool launch_ks_mac_f64(unsigned log_n, const NttArgs& a, const KeyPtrs& kp, size_t blocks, const LaunchCtx& lc) {
-    return log_n <= 13 ? launch_ks_mac_f64_small(log_n, a, kp, blocks, lc) : launch_ks_mac_f64_large(log_n, a, kp, blocks, lc);
-}
-inline bool launch_ks_mac_u64(unsigned log_n, const NttArgs& a, const KeyPtrs& kp, size_t blocks, const LaunchCtx& lc) {
-    return log_n <= 13 ? launch_ks_mac_u64_small(log_n, a, kp, blocks, lc) : launch_ks_mac_u64_large(log_n, a, kp, blocks, lc);
+inline bool launch_ks_mac(unsigned log_n, bool f64, const NttArgs& a, const KeyPtrs& kp, size_t blocks, const LaunchCtx& lc) {
+    return in_ntt_unit(log_n, f64, [&](auto u) { return decltype(u)::ks_mac(log_n, a, kp, blocks, lc); });
 }
 // tensor product fused with the transforms (tensor_core_kernel); stage 0 / 2: the strided passes of the two-pass sizes
-inline bool launch_tensor_f64(unsigned log_n, int stage, const NttArgs& a, const NttArgs& b, const NttArgs& d, size_t batch, const LaunchCtx& lc) {
-    return log_n <= 13 ? launch_tensor_f64_small(log_n, stage, a, b, d, batch, lc) : launch_tensor_f64_large(log_n, stage, a, b, d, batch, lc);
+inline bool launch_tensor(unsigned log_n, bool f64, int stage, const NttArgs& a, const NttArgs& b, const NttArgs& d, size_t batch, const LaunchCtx& lc) {
+    return in_ntt_unit(log_n, f64, [&](auto u) { return decltype(u)::tensor(log_n, stage, a, b, d, batch, lc); });
 }
-inline bool launch_tensor_u64(unsigned log_n, int stage, const NttArgs& a, const NttArgs& b, const NttArgs& d, size_t batch, const LaunchCtx& lc) {
-    return log_n <= 13 ? launch_tensor_u64_small(log_n, stage, a, b, d, batch, lc) : launch_tensor_u64_large(log_n, stage, a, b, d, batch, lc);
-}
-// sum of tensor products fused with the transforms (tensor_accumulate_kernel, troyn_tensor_acc.hip; log_n = 15 / 16, limbs of the FP64 class,
-// at most TENSOR_ACC_MAX_TERMS terms); false: no kernel for this size
-bool launch_tensor_accumulate_f64(unsigned log_n, const NttArgs& fa, const TensorAccPtrs& terms, unsigned count, const NttArgs& id, size_t batch, const LaunchCtx& lc);
+// sum of tensor products fused with the transforms (tensor_accumulate_kernel, troyn_tensor_acc.hip; log_n = 15 / 16, at most
+// TENSOR_ACC_MAX_TERMS terms).  FP64 class only: false for the integer class (its instantiations spill and are not built) and where no
+// kernel exists for the size
+bool launch_tensor_accumulate(unsigned log_n, bool f64, const NttArgs& fa, const TensorAccPtrs& terms, unsigned count, const NttArgs& id, size_t batch, const LaunchCtx& lc);
 // second-generation key-switch inner product (ksmac2_kernel, log_n = 13 / 14 / 15) and its key preparation
 // digits_f64: the digit rows hold doubles (fused chain: NTT_FLAG_STORE_F64) instead of u64 words; wide_digits: some digit limb is 2^50 or
 // wider (mixed chains, a.row_mask selects the rows of moduli < 2^50): digits are reduced with integer arithmetic while loading

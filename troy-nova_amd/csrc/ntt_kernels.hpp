@@ -279,12 +279,6 @@ __host__ __device__ constexpr unsigned lds_off(unsigned x) { return x + (x >> NT
 
 // Streaming (non-temporal) accesses for the polynomial data: every word is touched once per kernel, while the
 // twiddle tables (same size as one limb, shared by every workgroup of that modulus) should stay in the XCD's L2.
-#ifdef TROYN_NO_NT
-__device__ __forceinline__ u64 nt_load(const u64* p) { return *p; }
-__device__ __forceinline__ ulonglong2 nt_load2(const u64* p) { return *reinterpret_cast<const ulonglong2*>(p); }
-__device__ __forceinline__ void nt_store(u64* p, u64 v) { *p = v; }
-__device__ __forceinline__ void nt_store2(u64* p, u64 a, u64 b) { *reinterpret_cast<ulonglong2*>(p) = make_ulonglong2(a, b); }
-#else
 typedef u64 u64x2_native __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u64 nt_load(const u64* p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ ulonglong2 nt_load2(const u64* p) {
@@ -296,7 +290,6 @@ __device__ __forceinline__ void nt_store2(u64* p, u64 a, u64 b) {
     u64x2_native v; v.x = a; v.y = b;
     __builtin_nontemporal_store(v, reinterpret_cast<u64x2_native*>(p));
 }
-#endif
 
 // store / load of one word at (wave-uniform base) + (32-bit lane byte offset): the scalar-base addressing form, so that E strided
 // words of a thread cost one offset register instead of E 64-bit addresses
@@ -984,24 +977,16 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
                 constexpr int hi = decltype(hc)::value;
                 const unsigned loc0 = twbase | ((unsigned)(hi << (rb + 1)) << S);
                 const unsigned grp = (top << kk) + (loc0 >> (bit + 1));
-#ifdef TROYN_ABLATE_NO_TWIDDLE
-                const tw_t w = tw_load(1u + (grp & 1u));
-#else
                 const tw_t w = tw_load((INV ? N - (2u << l) + 1 + grp : (1u << l) + grp) + tw_dep);
-#endif
                 static_for<0, (1 << rb)>([&](auto oc) {
                     constexpr int R0 = (hi << (rb + 1)) | decltype(oc)::value;
                     constexpr int R1 = R0 | (1 << rb);
-#ifdef TROYN_ABLATE_NO_BUTTERFLY
-                    x[R0] = x[R0] + x[R1]; (void)w;
-#else
                     if constexpr (!INV) A::fwd(x[R0], x[R1], w, md);
                     else {
                         if constexpr (A::FOLD_NINV && LAST && l == 0) { A::inv_fold(x[R0], x[R1], md); (void)w; }
                         else A::inv(x[R0], x[R1], w, md);
                         if constexpr (A::MID_FIX && NLAYERS == 4 && li == 1) x[R0] = A::mid_fix(x[R0], md);
                     }
-#endif
                 });
             });
         });

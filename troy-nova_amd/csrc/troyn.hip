@@ -628,20 +628,6 @@ struct RunOverlap {
 constexpr size_t OVERLAP_MIN_LIMB_POLYS = 512;      // per split launch (all runs together)
 }  // namespace
 
-// CUs of the current device (cached per host thread; the same figure ntt_launch.inl sizes its small launches by)
-static unsigned device_cu_count() {
-    static thread_local int cached_dev = -1;
-    static thread_local unsigned cached = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev != cached_dev) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        cached = (unsigned)cus; cached_dev = dev;
-    }
-    return cached;
-}
-
 static bool use_f64(const troyn_plan* p, unsigned table_start, unsigned table_count) {
     // FP64 butterflies when every modulus this launch can touch is below 2^50
     bool f64 = !force_integer_ntt(p) && p->log_n >= 10;
@@ -701,7 +687,7 @@ static int launch_ntt(const troyn_plan* p, NttArgs a, size_t batch, bool inverse
         a.fused_mode == 0 && p->opt.ntt_split != 0 &&
         // (a launch that cannot fill the chip is latency-bound: one integer launch beats two half-empty ones -- one ciphertext at N = 16384
         // {60,50,50,50,50,60}: relinearize 102 -> 80 us, rescale 51 -> 40 us)
-        (p->opt.ntt_split == 1 || lp * TROYN_SMALL_LP_FACTOR > device_cu_count()) &&
+        (p->opt.ntt_split == 1 || !is_small_launch(lp)) &&
         ((a.load_mode == NTT_LOAD_PLAIN && a.store_mode == NTT_STORE_PLAIN && !two_pass_scratch) || p->log_n >= 14 || p->opt.ntt_split == 1 ||
          (!p->opt.ntt_overlap_off && lp >= OVERLAP_MIN_LIMB_POLYS))) {
         // A component-wise launch over limbs of both size classes ({60,40,40,60}: the reference's default chain): split it into
@@ -727,9 +713,7 @@ static int launch_ntt(const troyn_plan* p, NttArgs a, size_t batch, bool inverse
             });
     }
     a.tw = twiddles(p, f64, inverse);
-    const bool done = f64 ? launch_ntt_f64(p->log_n, a, lp, inverse, launch_ctx(p, s), two_pass_scratch)
-                          : launch_ntt_u64(p->log_n, a, lp, inverse, launch_ctx(p, s), two_pass_scratch);
-    if (!done) {
+    if (!launch_transform(p->log_n, f64, a, lp, inverse, launch_ctx(p, s), two_pass_scratch)) {
         a.tw = twiddles(p, false, inverse);
         launch_ntt_generic(a, p->log_n, inverse, lp, launch_ctx(p, s));
     }
@@ -760,7 +744,7 @@ static int tensor_stage_run(const troyn_plan* p, int stage, NttArgs a, NttArgs b
     const bool f64 = use_f64(p, a.table_start, a.ncomp);
     prep_direct(p, a, f64, stage == 2); prep_direct(p, b, f64, false); prep_direct(p, d, f64, true);
     if ((batch * a.pcount * a.ncomp) << (p->log_n > 12 ? p->log_n - 12 : 0) > 0x7fffffffull) return fail(TROYN_E_INVALID, "[troyn_ntt] batch too large for one launch");
-    if (!(f64 ? launch_tensor_f64(p->log_n, stage, a, b, d, batch, launch_ctx(p, s)) : launch_tensor_u64(p->log_n, stage, a, b, d, batch, launch_ctx(p, s))))
+    if (!launch_tensor(p->log_n, f64, stage, a, b, d, batch, launch_ctx(p, s)))
         return fail(TROYN_E_INVALID, "[troyn_bfv_multiply] no fused tensor kernel for this size");
     LAUNCH_CHECK();
     return TROYN_OK;
@@ -1025,13 +1009,11 @@ static size_t ks_split_words(const troyn_plan* p, size_t batch, unsigned L, unsi
 // shared quartets, troyn_mrr_small.hip), last forward pass with the epilogue of `fw`.  pa: the first inverse pass (in -> out); iv.in = pa.out.
 static bool small_tail_wanted(const troyn_plan* p, size_t limb_polys) {
     // (N = 32768 transforms are two-pass at every size; the merged form is taken for the same small launches)
-    return p->log_n >= 13 && p->log_n <= 15 && !p->opt.mrr_small_off && (p->log_n == 15 || !p->opt.ntt_small_two_pass_off) && limb_polys * TROYN_SMALL_LP_FACTOR <= device_cu_count();
+    return p->log_n >= 13 && p->log_n <= 15 && !p->opt.mrr_small_off && (p->log_n == 15 || !p->opt.ntt_small_two_pass_off) && is_small_launch(limb_polys);
 }
 static int small_tail(const troyn_plan* p, bool f64, NttArgs pa, size_t pa_limb_polys, NttArgs fw, u64* between, size_t groups, hipStream_t s) {
     const LaunchCtx lc = launch_ctx(p, s);
-    auto pass = [&](int which, const NttArgs& x, size_t lp) {
-        if (f64) launch_ntt_f64_small_pass(p->log_n, which, x, lp, lc); else launch_ntt_u64_small_pass(p->log_n, which, x, lp, lc);
-    };
+    auto pass = [&](int which, const NttArgs& x, size_t lp) { launch_small_pass(p->log_n, f64, which, x, lp, lc); };
     prep_direct(p, pa, f64, true);
     pass(0, pa, pa_limb_polys);
     LAUNCH_CHECK();
@@ -1309,8 +1291,7 @@ static int ks_mac_gen1(const KsCall& c, const KeyPtrs& kp) {
         LAUNCH_CHECK();
         a.key_quo = kq; a.key_quo_jstride = 2ll * K * n;
     }
-    if (f64) launch_ks_mac_f64(p->log_n, a, kp, c.batch * (size_t)(L + 1), launch_ctx(p, c.s));
-    else launch_ks_mac_u64(p->log_n, a, kp, c.batch * (size_t)(L + 1), launch_ctx(p, c.s));
+    launch_ks_mac(p->log_n, f64, a, kp, c.batch * (size_t)(L + 1), launch_ctx(p, c.s));
     LAUNCH_CHECK();
     return TROYN_OK;
 }
@@ -1738,7 +1719,7 @@ static int mrr_tail_merged(const MrrCall& c, bool quartet) {
         NttArgs pa = contiguous_args(p, rows, rows, 2, 2, L - 1, K - (L - 1), TROYN_IDX_KS_SKIP_FINALS, 1);
         pa.in_pstride = pa.out_pstride = (long long)(L + 1) * n; pa.in_bstride = pa.out_bstride = 2ll * (L + 1) * n;
         prep_direct(p, pa, true, true);
-        launch_ntt_f64_small_pass(p->log_n, 0, pa, c.batch * 4, lc);
+        launch_small_pass(p->log_n, true, 0, pa, c.batch * 4, lc);
         LAUNCH_CHECK();
     }
     NttArgs sp = special_rows_args(p, c.poly_prod(), nullptr, L);
@@ -1753,12 +1734,12 @@ static int mrr_tail_merged(const MrrCall& c, bool quartet) {
         LAUNCH_CHECK();
         return TROYN_OK;
     }
-    launch_mrr_quartet(p->log_n, c.batch, sp, la, ta, c.s, !p->opt.mrr_small_serial && c.batch * 2 * (size_t)(L - 1) * TROYN_SMALL_LP_FACTOR <= device_cu_count());
+    launch_mrr_quartet(p->log_n, c.batch, sp, la, ta, c.s, !p->opt.mrr_small_serial && is_small_launch(c.batch * 2 * (size_t)(L - 1)));
     LAUNCH_CHECK();
     // last forward pass of the output limbs, in place in `out`, with step (5)'s epilogue
     as_input_of(ta, ta);
     ta.reduce_input = 0;
-    launch_ntt_f64_small_pass(p->log_n, 1, ta, c.batch * 2 * (L - 1), lc);
+    launch_small_pass(p->log_n, true, 1, ta, c.batch * 2 * (L - 1), lc);
     LAUNCH_CHECK();
     return TROYN_OK;
 }
@@ -2545,7 +2526,7 @@ static int bfv_tensor_accumulate(const troyn_plan* p, unsigned nc, const u64* co
     prep_direct(p, fa, true, false); prep_direct(p, id, true, true);
     if (carry) id.flags |= NTT_FLAG_MID_CARRY;
     if ((batch * 3 * nc) << (p->log_n - 12) > 0x7fffffffull) return fail(TROYN_E_INVALID, "[troyn_bfv_multiply_accumulate] batch too large for one launch");
-    if (!launch_tensor_accumulate_f64(p->log_n, fa, g, cnt, id, batch, launch_ctx(p, s)))
+    if (!launch_tensor_accumulate(p->log_n, true, fa, g, cnt, id, batch, launch_ctx(p, s)))
         return fail(TROYN_E_INVALID, "[troyn_bfv_multiply_accumulate] no accumulating tensor kernel for this size");
     LAUNCH_CHECK();
     return TROYN_OK;

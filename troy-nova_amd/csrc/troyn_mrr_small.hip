@@ -142,22 +142,26 @@ static void launch_quartet_load_t(const dim3 grid, const NttArgs& iv, const NttA
     if (t.load_mode == NTT_LOAD_KS_ROUND) hipLaunchKernelGGL((mrr_quartet_load_kernel<A, LOGN, G1, NTT_LOAD_KS_ROUND>), grid, dim3(256), 0, s, iv, t);
     else hipLaunchKernelGGL((mrr_quartet_load_kernel<A, LOGN, G1, NTT_LOAD_RESCALE>), grid, dim3(256), 0, s, iv, t);
 }
-static unsigned strided_words(unsigned log_n) { return log_n == 15 ? 8u : 4u; }
+// f(std::integral_constant<int, log_n>) at the sizes with merged tails (ntt_sizes.hpp); G1 and the words per thread follow the tile of those sizes
+template <class F>
+static void at_merged_tail_size(unsigned log_n, F&& f) {
+    for_ntt_size<0>(log_n, [&](auto n) {
+        if constexpr (ntt_size(decltype(n)::value).merged_tail) f(n);
+        return true;
+    });
+}
+constexpr int strided_layers(int log_n) { return log_n - ntt_merged_tail_tile(log_n).tb; }      // G1 of StridedPass
+static unsigned strided_blocks(unsigned log_n, size_t polys) { return (unsigned)(polys * ((1u << log_n) >> strided_layers((int)log_n)) / 256); }
 void launch_mrr_quartet_load(unsigned log_n, size_t groups, const NttArgs& iv, const NttArgs& fw, hipStream_t s, bool f64) {
-    if (log_n < 13 || log_n > 15) return;
-    const unsigned blocks = (unsigned)(groups * ((1u << log_n) / strided_words(log_n)) / 256);
-    NttArgs t = fw;
-    t.xcd_groups = blocks;
-    const dim3 grid(blocks * fw.ncomp);
-    if (f64) {
-        if (log_n == 13) launch_quartet_load_t<ArithF64, 13, 2>(grid, iv, t, s);
-        else if (log_n == 14) launch_quartet_load_t<ArithF64, 14, 2>(grid, iv, t, s);
-        else launch_quartet_load_t<ArithF64, 15, 3>(grid, iv, t, s);
-    } else {
-        if (log_n == 13) launch_quartet_load_t<ArithU64, 13, 2>(grid, iv, t, s);
-        else if (log_n == 14) launch_quartet_load_t<ArithU64, 14, 2>(grid, iv, t, s);
-        else launch_quartet_load_t<ArithU64, 15, 3>(grid, iv, t, s);
-    }
+    at_merged_tail_size(log_n, [&](auto n) {
+        constexpr int LOGN = decltype(n)::value, G1 = strided_layers(LOGN);
+        const unsigned blocks = strided_blocks(log_n, groups);
+        NttArgs t = fw;
+        t.xcd_groups = blocks;
+        const dim3 grid(blocks * fw.ncomp);
+        if (f64) launch_quartet_load_t<ArithF64, LOGN, G1>(grid, iv, t, s);
+        else launch_quartet_load_t<ArithU64, LOGN, G1>(grid, iv, t, s);
+    });
 }
 
 // sp / la: the pass-A words of the special rows / of limb L - 1 (in, strides, table_start = their modulus, tw = inverse tables; la with the
@@ -168,14 +172,14 @@ static void launch_quartet_t(const QuartetSpecial& qs, const NttArgs& la, const 
     else hipLaunchKernelGGL((mrr_quartet_kernel<LOGN, G1, false>), dim3(blocks), dim3(256), 0, s, qs, la, t);
 }
 void launch_mrr_quartet(unsigned log_n, size_t batch, const NttArgs& sp, const NttArgs& la, const NttArgs& ta, hipStream_t s, bool limb_parallel) {
-    if (log_n < 13 || log_n > 15) return;
-    const unsigned blocks = (unsigned)(batch * 2 * ((1u << log_n) / strided_words(log_n)) / 256);
-    NttArgs t = ta;
-    t.xcd_groups = blocks;        // (the field is free in this kernel: workgroups per output limb)
-    const QuartetSpecial qs{sp.in, sp.in_bstride, sp.in_pstride, sp.table_start};
-    if (log_n == 13) launch_quartet_t<13, 2>(qs, la, t, blocks, s, limb_parallel);
-    else if (log_n == 14) launch_quartet_t<14, 2>(qs, la, t, blocks, s, limb_parallel);
-    else launch_quartet_t<15, 3>(qs, la, t, blocks, s, limb_parallel);
+    at_merged_tail_size(log_n, [&](auto n) {
+        constexpr int LOGN = decltype(n)::value;
+        const unsigned blocks = strided_blocks(log_n, batch * 2);
+        NttArgs t = ta;
+        t.xcd_groups = blocks;        // (the field is free in this kernel: workgroups per output limb)
+        const QuartetSpecial qs{sp.in, sp.in_bstride, sp.in_pstride, sp.table_start};
+        launch_quartet_t<LOGN, strided_layers(LOGN)>(qs, la, t, blocks, s, limb_parallel);
+    });
 }
 
 }  // namespace troyn

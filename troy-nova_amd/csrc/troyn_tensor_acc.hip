@@ -3,8 +3,8 @@
 
 namespace troyn {
 
-bool launch_tensor_accumulate_f64(unsigned log_n, const NttArgs& fa, const TensorAccPtrs& terms, unsigned count, const NttArgs& id, size_t batch, const LaunchCtx& lc) {
-    return launch_tensor_accumulate_class<ArithF64>(log_n, fa, terms, count, id, batch, lc);
+bool launch_tensor_accumulate(unsigned log_n, bool f64, const NttArgs& fa, const TensorAccPtrs& terms, unsigned count, const NttArgs& id, size_t batch, const LaunchCtx& lc) {
+    return f64 && launch_tensor_accumulate_class<ArithF64>(log_n, fa, terms, count, id, batch, lc);
 }
 
 }  // namespace troyn
