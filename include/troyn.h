@@ -296,6 +296,41 @@ int troyn_apply_galois(const troyn_plan* plan, uint32_t mod_start, uint32_t nmod
  * modulus t of a BFV / BGV plaintext (Evaluator::apply_galois_plain, evaluator_keyswitching.cu:235-261). */
 int troyn_apply_galois_plain(const troyn_plan* plan, uint64_t modulus, uint64_t galois_element, const uint64_t* in, uint64_t* out, size_t count,
                              troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Hoisted rotations: many Galois keys applied to ONE ciphertext with one digit decomposition.  Both entries are ADDITIONS to the
+ * reference's surface (the reference applies one automorphism and one complete key switch per rotation, evaluator_keyswitching.cu:147-179).
+ *   ct               [batch][2][L][N] = (c0, c1), NTT form iff is_ntt_form (CKKS: NTT form, BFV: coefficient form, as troyn_switch_key)
+ *   galois_elements  host array of `terms` elements g_t, each odd with 1 < g_t < 2N; duplicates are allowed
+ *   keys             host array of terms * L DEVICE pointers, keys[t * L + j] -> u64[2][K][N] in NTT form (the Galois key of g_t), 16-byte aligned
+ *   out              many: [terms][batch][2][L][N], one ciphertext per term;  sum: [batch][2][L][N];  same form as ct
+ * Contract, per item, on integers (tests/hoist_spec.py; the notation of tests/ks_spec.py):
+ *   d_j          limb j of c1 in coefficient form, an integer in [0, q_j)
+ *   sigma_g      (sigma_g x)[i * g mod N] = (-1)^floor(i * g / N) x[i]
+ *   e_{t,j}      sigma_{g_t}(d_j), signed coefficients in (-q_j, q_j)
+ *   X_c[m]       SUM_{t in S} SUM_j (e_{t,j} mod m) (*) k_{t,j}[c][m]  mod m   for every key modulus m in {q_0 .. q_{L-1}, q_special}
+ *   r_c, result_c[l] = (X_c[q_l] - r_c) * q_special^-1 mod q_l   exactly as in troyn_switch_key (ONE rounded division by the special prime)
+ *   out[0][l] = SUM_{t in S} sigma_{g_t}(c0)[l] + result_0[l]  mod q_l,   out[1][l] = result_1[l]
+ * many: S = {t}, one output per term -- one decomposition, `terms` tails.  sum: S = every term -- one decomposition, ONE tail.
+ * With terms = 1 the words are NOT bit-identical to troyn_apply_galois + troyn_switch_key: the words differ from apply_galois.  Where the
+ * automorphism negates a coefficient x of d_j, the reference decomposes sigma(c1) afresh and its digit under key modulus m is
+ * (q_j - x) mod m; the hoisted digit is (-x) mod m.  The two agree for m = q_j and differ by a multiple of q_j on the other rows.  Both
+ * are key switches with digits bounded by q_j in magnitude, so both decrypt to the same message under the same noise bound; the
+ * contract is the integer specification above, not the reference's words.
+ * Scope: BFV and CKKS.  BGV is left out (its tail divides differently, troyn_bgv_switch_key).
+ * TROYN_E_INVALID: terms == 0, a null table or entry, a misaligned pointer, an element that is even, 1 or >= 2N, L outside [1, K-1],
+ * `out` overlapping `ct`.  TROYN_E_WORKSPACE: a workspace below troyn_apply_galois_hoisted_workspace_bytes(plan, L, terms, batch, sum)
+ * (sum = 0 for _many, 1 for _sum).  batch == 0 returns TROYN_OK, launches nothing and looks at neither `ct`, `out` nor the workspace.  The
+ * tables are read before the call returns.
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_apply_galois_hoisted_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t terms, size_t batch, int sum);
+int troyn_apply_galois_many(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
+                            const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, uint64_t* out,
+                            void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+int troyn_apply_galois_sum(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
+                           const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, uint64_t* out,
+                           void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * BGV.  BGV ciphertexts live in NTT form and reuse troyn_ntt, troyn_dyadic_convolute (bgv_multiply,
  * evaluator.cu:150-173), troyn_add/sub/negate/multiply_scalar, troyn_apply_galois and troyn_plain_centralize unchanged; the

@@ -1,0 +1,144 @@
+// hoist_kernels.hpp -- hoisted rotations (an ADDITION to the reference's kernels: troyn_apply_galois_many / troyn_apply_galois_sum).
+//
+// A key switch decomposes its target ONCE into the transformed digits D[item][L+1][L][N] (row k = the L digits under key modulus m_k,
+// the forward transform with TROYN_IDX_KS_SET_PRODUCTS and reduce_input).  The automorphism X -> X^g commutes with the decomposition,
+// and in NTT form it is the index permutation of galois_kernel (crypto_kernels.hpp):
+//     pi_g(i) = brev_logN(((g * brev_{logN+1}(i + N)) >> 1) mod N)
+// so the digits of sigma_g(c1) under every key modulus are D read at pi_g(i): `terms` Galois keys share one decomposition.
+//
+// Block property of pi_g (g odd): i + 1 for even i adds N to the (logN+1)-bit reversal, g * N / 2 = N / 2 (mod N) flips the top bit of
+// the raw index, which the final reversal turns into the lowest bit: pi_g(i + 1) = pi_g(i) ^ 1.  By the same argument every aligned
+// block of 2^b consecutive outputs reads ONE aligned block of 2^b sources.  A thread owns two adjacent outputs: its two digit words are
+// one aligned 16-byte pair (swapped when pi_g(i) is odd), and a wave's 128 outputs gather from exactly one 1 KiB block of the digit row
+// -- every fetched line is used in full, no LDS staging.
+//
+// hoist_mac_kernel: poly_prod[slot][item][c][k][i] = SUM_{t in S(slot)} SUM_j D[item][k][j][pi_t(i)] * key_{t,j}[c][k][i]  mod m_k
+//   many form: S(slot) = {slot};  sum form: one slot, S = every term.
+//   The keys are the HBM stream (16 L K N bytes per term): 16-byte loads per lane, coalesced; a workgroup carries IB items of the batch
+//   through the same key registers.  Integer arithmetic for every modulus: 64 x 64 -> 128 products in a 128-bit accumulator, L <= 63
+//   products of residues below 2^61 per term, ONE Barrett-128 reduction per term and output word, then an addition modulo m_k -- the
+//   accumulator never runs across terms.  Every output word is written once.
+// hoist_c0_kernel: dest[slot][item][0][l] = SUM_{t in S(slot)} sigma_{g_t}(c0[item][l])  mod q_l, a gather in either form (coefficient
+//   form: the source of output o is i = o * g^-1 mod N, negated when (i * g) & N -- the sign rule of galois_kernel).
+#pragma once
+#include "poly_kernels.hpp"
+
+namespace troyn {
+
+struct HoistArgs {
+    const DevModulus* mods;
+    unsigned K, L, log_n, batch;
+    unsigned groups;               // ceil(batch / IB) (hoist_mac_kernel)
+    unsigned terms_per_slot;       // many: 1, sum: terms
+    int is_ntt_form;
+    const u64* ct;                 // [batch][2][L][N]
+    const u64* digits_ntt;         // D [batch][L+1][L][N]
+    int diag_from_ct;              // NTT form with the diagonal blocks of D not produced (skip_diag): digit k of row k < L is c1's limb k itself
+    const u64* const* keys;        // device table [terms][L] -> u64[2][K][N]
+    const u64* elements;           // device table [terms]
+    const u64* inv_elements;       // device table [terms]: g^-1 mod 2N (coefficient form)
+    u64* poly_prod;                // [slots][batch][2][L+1][N]
+    u64* dest;                     // [slots][batch][2][L][N]
+};
+
+__device__ __forceinline__ unsigned hoist_ntt_source(unsigned i, unsigned g, unsigned log_n) {
+    const unsigned n = 1u << log_n;
+    const unsigned reversed = __brev(i + n) >> (31 - log_n);                   // (log_n + 1)-bit reversal
+    const unsigned index_raw = (unsigned)(((u64)g * reversed) >> 1) & (n - 1);
+    return __brev(index_raw) >> (32 - log_n);
+}
+
+template <int IB>
+__global__ __launch_bounds__(POLY_BLOCK) void hoist_mac_kernel(unsigned chunks, HoistArgs a) {
+    const unsigned L = a.L, K = a.K, n = 1u << a.log_n;
+    const unsigned row = blk_row(chunks);
+    const unsigned k = row % (L + 1);
+    const unsigned grp = (row / (L + 1)) % a.groups;
+    const unsigned slot = row / (L + 1) / a.groups;
+    const unsigned key_index = (k == L) ? K - 1 : k;
+    const DevModulus md = a.mods[key_index];
+    const size_t key_poly = (size_t)K * n;
+    // items past the batch's end recompute the last item and store nothing
+    size_t item[IB];
+    const u64* dp[IB];
+#pragma unroll
+    for (int b = 0; b < IB; ++b) {
+        const unsigned it = grp * IB + b;
+        item[b] = it < a.batch ? it : a.batch - 1;
+        dp[b] = a.digits_ntt + (item[b] * (L + 1) + k) * (size_t)L * n;
+    }
+    const bool diag = a.diag_from_ct && k < L;
+    for (unsigned x = blk_col(chunks) * 2; x < n; x += chunks * blockDim.x * 2) {
+        u64 r[IB][2][2];
+#pragma unroll
+        for (int b = 0; b < IB; ++b) r[b][0][0] = r[b][0][1] = r[b][1][0] = r[b][1][1] = 0;
+        for (unsigned u = 0; u < a.terms_per_slot; ++u) {
+            const size_t t = (size_t)slot * a.terms_per_slot + u;
+            const unsigned src = hoist_ntt_source(x, (unsigned)a.elements[t], a.log_n);
+            const unsigned pair = src & ~1u;
+            const bool swap = src & 1u;
+            u64 lo[IB][2][2], hi[IB][2][2];
+#pragma unroll
+            for (int b = 0; b < IB; ++b)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) lo[b][c][0] = lo[b][c][1] = hi[b][c][0] = hi[b][c][1] = 0;
+            for (unsigned j = 0; j < L; ++j) {
+                const u64* kj = a.keys[t * L + j] + (size_t)key_index * n + x;
+                const u64x2 k0 = ld2(kj), k1 = ld2(kj + key_poly);
+#pragma unroll
+                for (int b = 0; b < IB; ++b) {
+                    const u64* drow = (diag && j == k) ? a.ct + (item[b] * 2 + 1) * (size_t)L * n + (size_t)j * n : dp[b] + (size_t)j * n;
+                    const u64x2 v = ld2(drow + pair);
+                    const u64 d0 = swap ? v.b : v.a, d1 = swap ? v.a : v.b;
+                    mac128(lo[b][0][0], hi[b][0][0], d0, k0.a); mac128(lo[b][0][1], hi[b][0][1], d1, k0.b);
+                    mac128(lo[b][1][0], hi[b][1][0], d0, k1.a); mac128(lo[b][1][1], hi[b][1][1], d1, k1.b);
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < IB; ++b)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    r[b][c][0] = add_mod(r[b][c][0], barrett128(lo[b][c][0], hi[b][c][0], md.q, md.ratio_lo, md.ratio_hi), md.q);
+                    r[b][c][1] = add_mod(r[b][c][1], barrett128(lo[b][c][1], hi[b][c][1], md.q, md.ratio_lo, md.ratio_hi), md.q);
+                }
+        }
+#pragma unroll
+        for (int b = 0; b < IB; ++b) {
+            if (grp * IB + b >= a.batch) break;
+            u64* pp = a.poly_prod + ((size_t)slot * a.batch + item[b]) * 2 * (size_t)(L + 1) * n + (size_t)k * n + x;
+            st2(pp, r[b][0][0], r[b][0][1]);
+            st2(pp + (size_t)(L + 1) * n, r[b][1][0], r[b][1][1]);
+        }
+    }
+}
+
+// one thread per coefficient of (slot, item, limb); rows = slots * batch * L
+__global__ __launch_bounds__(POLY_BLOCK) void hoist_c0_kernel(unsigned chunks, HoistArgs a) {
+    const unsigned L = a.L, n = 1u << a.log_n, mask = n - 1;
+    const unsigned row = blk_row(chunks);
+    const unsigned l = row % L;
+    const size_t item = (row / L) % a.batch;
+    const size_t slot = row / L / a.batch;
+    const u64 q = a.mods[l].q;
+    const u64* ip = a.ct + (item * 2 * L + l) * (size_t)n;
+    u64* op = a.dest + ((slot * a.batch + item) * 2 * L + l) * (size_t)n;
+    for (unsigned x = blk_col(chunks); x < n; x += chunks * blockDim.x) {
+        u64 sum = 0;
+        for (unsigned u = 0; u < a.terms_per_slot; ++u) {
+            const size_t t = slot * a.terms_per_slot + u;
+            const unsigned g = (unsigned)a.elements[t];
+            u64 v;
+            if (a.is_ntt_form) {
+                v = ip[hoist_ntt_source(x, g, a.log_n)];
+            } else {
+                const unsigned i = (unsigned)((u64)x * a.inv_elements[t]) & mask;
+                v = ip[i];
+                if ((((u64)i * g) >> a.log_n) & 1) v = neg_mod(v, q);
+            }
+            sum = add_mod(sum, v, q);
+        }
+        op[x] = sum;
+    }
+}
+
+}  // namespace troyn

@@ -25,6 +25,7 @@
 #include "ksmac_kernels.hpp"
 #include "ksmaci_kernels.hpp"
 #include "poly_kernels.hpp"
+#include "hoist_kernels.hpp"
 
 using namespace troyn;
 
@@ -1295,16 +1296,20 @@ static int ks_mac_gen1(const KsCall& c, const KeyPtrs& kp) {
     LAUNCH_CHECK();
     return TROYN_OK;
 }
-static int ks_mac_two_launch(const KsCall& c, const KeyPtrs& kp, const KsPath& path) {
-    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
-    // (2) digit decomposition fused into the forward NTT (replaces kernel_set_accumulate, fgk/switch_key.cu:6-54,
-    //     + ntt_inplace_ps with key_switching_set_products, :907-908): row i = digits reduced mod q_key(i)
-    NttArgs a = contiguous_args(p, c.digits, c.ws + c.w.temp_ntt, L + 1, L, 0, K, TROYN_IDX_KS_SET_PRODUCTS, L);
+// (2) digit decomposition fused into the forward NTT (replaces kernel_set_accumulate, fgk/switch_key.cu:6-54,
+//     + ntt_inplace_ps with key_switching_set_products, :907-908): temp_ntt [item][L+1][L][N], row i = digits reduced mod q_key(i)
+static int ks_transform_digits(const KsCall& c, bool skip_diag) {
+    const troyn_plan* p = c.p; const unsigned L = c.L;
+    NttArgs a = contiguous_args(p, c.digits, c.ws + c.w.temp_ntt, L + 1, L, 0, p->K, TROYN_IDX_KS_SET_PRODUCTS, L);
     a.in_bstride = (long long)c.digits_bstride;
     a.in_pstride = 0;                 // every row re-reads the same L digits
     a.reduce_input = 1;
-    a.skip_diag = path.fused ? 1 : 0; // row i, digit i is the NTT-form input itself: not recomputed
-    if (int rc = launch_ntt(p, a, c.batch, false, c.s)) return rc;
+    a.skip_diag = skip_diag ? 1 : 0;  // row i, digit i is the NTT-form input itself: not recomputed
+    return launch_ntt(p, a, c.batch, false, c.s);
+}
+static int ks_mac_two_launch(const KsCall& c, const KeyPtrs& kp, const KsPath& path) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    if (int rc = ks_transform_digits(c, path.fused)) return rc;
     // (3) <digits, key> inner product (fgk/switch_key.cu:83-154)
     const unsigned ch = chunks_pairs(n);
     const size_t rows = c.batch * (L + 1);
@@ -1468,6 +1473,125 @@ extern "C" int troyn_relinearize(const troyn_plan* plan, uint32_t L, int is_ckks
     // relinearize_internal (evaluator_keyswitching.cu:119-144): switch_key(target = c2, Overwrite) then += (c0, c1)
     return switch_key_impl(plan, L, is_ckks, is_ntt_form, (const u64*)ct3 + 2 * pc, 3 * pc, keys, TROYN_ASSIGN_OVERWRITE,
                            (u64*)out2, (const u64*)ct3, 3 * pc, workspace, workspace_bytes, batch, (hipStream_t)stream);
+}
+
+// ---- hoisted rotations (an addition to the reference's surface; include/troyn.h, hoist_kernels.hpp) ----
+// One decomposition (ks_digits + ks_transform_digits) serves every term; hoist_mac_kernel forms poly_prod per slot (many: one slot per
+// term, sum: one slot), hoist_c0_kernel the permuted c0, and ks_tail runs unchanged on slots * batch items.
+struct HoistLayout { KsLayout ks; size_t table; };
+
+static HoistLayout hoist_layout(const troyn_plan* p, unsigned L, size_t terms, size_t batch, bool sum) {
+    const size_t n = p->n, items = (sum ? 1 : terms) * batch;
+    HoistLayout h;
+    size_t off = 0;
+    h.ks.target_intt = off; off += batch * L * n;
+    h.ks.temp_ntt = off;    off += batch * (size_t)(L + 1) * L * n;
+    h.ks.poly_prod = off;   off += items * 2 * (size_t)(L + 1) * n;
+    h.ks.prod_intt = off;   off += items * 2 * (size_t)(L + 1) * n;
+    h.ks.temp_last = off;   off += items * 2 * (size_t)L * n;
+    h.ks.keys_f64 = h.ks.split = h.ks.keys_quo = off;      // the inner products of troyn_switch_key do not run here
+    h.table = off;          off += (terms * (L + 2) + 1) & ~(size_t)1;      // key pointers [terms][L], elements [terms], inverse elements [terms]
+    h.ks.total = off;
+    return h;
+}
+
+extern "C" size_t troyn_apply_galois_hoisted_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t terms, size_t batch, int sum) {
+    if (!plan) return 0;
+    return hoist_layout(plan, L, terms, batch, sum != 0).ks.total * sizeof(u64);
+}
+
+static int apply_galois_hoisted(const char* P, const troyn_plan* p, unsigned L, int is_ckks, int is_ntt_form, const u64* ct,
+                                const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, u64* out,
+                                void* workspace, size_t workspace_bytes, size_t batch, hipStream_t s, bool sum) {
+    if (!p) return fail(TROYN_E_INVALID, std::string(P) + " null plan");
+    const unsigned K = p->K, n = p->n;
+    if (K < 2) return fail(TROYN_E_INVALID, std::string(P) + " Keyswitching is not supported.");
+    if (L < 1 || L > K - 1) return fail(TROYN_E_INVALID, std::string(P) + " Invalid target size.");
+    if (terms == 0) return fail(TROYN_E_INVALID, std::string(P) + " no terms");
+    if (!galois_elements || !keys) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    for (size_t t = 0; t < terms; t++) {
+        const uint64_t g = galois_elements[t];
+        if ((g & 1) == 0 || g >= 2ull * n || g == 1) return fail(TROYN_E_INVALID, std::string(P) + " Galois element is not valid.");
+        for (unsigned j = 0; j < L; j++)
+            if (!keys[t * L + j] || ((uintptr_t)keys[t * L + j] & 15)) return fail(TROYN_E_INVALID, std::string(P) + " null or misaligned key pointer");
+    }
+    if (batch == 0) return TROYN_OK;      // nothing to do: neither ct, out nor the workspace is looked at
+    if (!ct || !out || !workspace) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if (((uintptr_t)ct | (uintptr_t)out | (uintptr_t)workspace) & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned pointer");
+    const size_t slots = sum ? 1 : terms, items = slots * batch, ct_words = (size_t)2 * L * n;
+    if ((uintptr_t)out < (uintptr_t)(ct + batch * ct_words) && (uintptr_t)ct < (uintptr_t)(out + items * ct_words))
+        return fail(TROYN_E_INVALID, std::string(P) + " out overlaps ct");
+    const HoistLayout h = hoist_layout(p, L, terms, batch, sum);
+    if (workspace_bytes < h.ks.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    u64* ws = (u64*)workspace;
+    // the tables are read before the call returns: [terms][L] key pointers, the elements, their inverses modulo 2N
+    std::vector<u64> table(terms * (L + 2));
+    for (size_t i = 0; i < terms * L; i++) table[i] = (u64)(uintptr_t)keys[i];
+    for (size_t t = 0; t < terms; t++) {
+        const u64 g = galois_elements[t];
+        u64 inv = g;                                   // g * g = 1 (mod 8); every Newton step doubles the number of correct low bits
+        for (int i = 0; i < 5; i++) inv *= 2 - g * inv;
+        table[terms * L + t] = g;
+        table[terms * (L + 1) + t] = inv & (2ull * n - 1);
+    }
+    if (int rc = upload_host_table(s, ws + h.table, table.data(), table.size() * sizeof(u64))) return rc;
+    // (1) + (2): c1 in coefficient form, then its L digits under every key modulus, once
+    const u64* c1 = ct + (size_t)L * n;
+    KsCall dc{p, L, is_ckks, is_ntt_form != 0, c1, ct_words, TROYN_ASSIGN_OVERWRITE_EXCEPT_FIRST, out, nullptr, 0,
+              ws, h.ks, batch, s, nullptr, c1, ct_words};
+    if (int rc = ks_digits(dc)) return rc;
+    const bool skip_diag = dc.is_ntt_form && p->log_n >= 10;      // as ks_path's `fused`: the transform leaves the diagonal blocks to the consumer
+    if (int rc = ks_transform_digits(dc, skip_diag)) return rc;
+    HoistArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.mods = p->d_mods; a.K = K; a.L = L; a.log_n = p->log_n; a.batch = (unsigned)batch;
+    a.terms_per_slot = (unsigned)(sum ? terms : 1); a.is_ntt_form = dc.is_ntt_form ? 1 : 0;
+    a.ct = ct; a.digits_ntt = ws + h.ks.temp_ntt; a.diag_from_ct = skip_diag ? 1 : 0;
+    a.keys = reinterpret_cast<const u64* const*>(ws + h.table);
+    a.elements = ws + h.table + terms * L; a.inv_elements = a.elements + terms;
+    a.poly_prod = ws + h.ks.poly_prod; a.dest = out;
+    if (batch > 0xffffffffull || terms > 0xffffffffull) return fail(TROYN_E_INVALID, std::string(P) + " batch too large for one launch");
+    // (3) the permuted c0 (summed over the terms in the sum form) into component 0 of the destination
+    {
+        const unsigned ch = chunks_single(n);
+        const size_t rows = items * L;
+        if (int rc = check_rows(rows, ch)) return rc;
+        hipLaunchKernelGGL(hoist_c0_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s, ch, a);
+        LAUNCH_CHECK();
+    }
+    // (4) <permuted digits, keys>: a workgroup carries up to four items of the batch through the same key words
+    {
+        const unsigned ib = batch >= 4 ? 4u : batch >= 2 ? 2u : 1u;
+        a.groups = (unsigned)((batch + ib - 1) / ib);
+        const unsigned ch = chunks_pairs(n);
+        const size_t rows = slots * a.groups * (size_t)(L + 1);
+        if (int rc = check_rows(rows, ch)) return rc;
+        TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, s);
+        const dim3 grid((unsigned)(rows * ch)), block(POLY_BLOCK);
+        if (ib == 4) hipLaunchKernelGGL((hoist_mac_kernel<4>), grid, block, 0, s, ch, a);
+        else if (ib == 2) hipLaunchKernelGGL((hoist_mac_kernel<2>), grid, block, 0, s, ch, a);
+        else hipLaunchKernelGGL((hoist_mac_kernel<1>), grid, block, 0, s, ch, a);
+        LAUNCH_CHECK();
+    }
+    // (5) the tail of troyn_switch_key on slots * batch items: dest[.][0] += result_0, dest[.][1] = result_1
+    KsCall tc = dc;
+    tc.batch = items;
+    return ks_tail(tc, ks_path(p, L, items, tc.is_ntt_form, false));
+}
+
+extern "C" int troyn_apply_galois_many(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
+                                       const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, uint64_t* out,
+                                       void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(plan);
+    return apply_galois_hoisted("[troyn_apply_galois_many]", plan, L, is_ckks, is_ntt_form, (const u64*)ct, galois_elements, keys, terms,
+                                (u64*)out, workspace, workspace_bytes, batch, (hipStream_t)stream, false);
+}
+extern "C" int troyn_apply_galois_sum(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
+                                      const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, uint64_t* out,
+                                      void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(plan);
+    return apply_galois_hoisted("[troyn_apply_galois_sum]", plan, L, is_ckks, is_ntt_form, (const u64*)ct, galois_elements, keys, terms,
+                                (u64*)out, workspace, workspace_bytes, batch, (hipStream_t)stream, true);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -216,6 +216,44 @@ class Plan:
                         is_ckks=is_ckks, is_ntt_form=is_ntt_form)
         return out
 
+    # -- hoisted rotations (additions: one digit decomposition for many Galois keys) ----------------
+    def _apply_galois_hoisted(self, summed, L, ct, elements, keys_per_element, is_ckks, is_ntt_form, out):
+        who = "[troyn_apply_galois_sum]" if summed else "[troyn_apply_galois_many]"
+        terms = len(elements)
+        if len(keys_per_element) != terms:
+            raise capi.TroynInvalidArgument("%s one key per Galois element is needed" % who)
+        words = 2 * L * self.n
+        if L < 1 or ct.numel() % words:
+            raise capi.TroynInvalidArgument("%s ct is not [batch][2][L][N]" % who)
+        batch = ct.numel() // words
+        ptrs = []
+        for keys in keys_per_element:
+            if len(keys) < L:
+                raise capi.TroynInvalidArgument("%s Key switch keys index out of range." % who)
+            ptrs += [None if k is None else k.data_ptr() for k in keys[:L]]      # (a null entry is the library's to refuse)
+        karr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        earr = (C.c_uint64 * max(terms, 1))(*[int(e) for e in elements])
+        shape = (batch, 2, L, self.n) if summed else (terms, batch, 2, L, self.n)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=self.device)
+        elif out.numel() != int(np.prod(shape)):
+            raise capi.TroynInvalidArgument("%s out is not %s" % (who, "[batch][2][L][N]" if summed else "[terms][batch][2][L][N]"))
+        ws = self.workspace(self.lib.troyn_apply_galois_hoisted_workspace_bytes(self.h, L, terms, batch, int(summed)))
+        fn = self.lib.troyn_apply_galois_sum if summed else self.lib.troyn_apply_galois_many
+        capi.check(fn(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(ct), earr, karr, terms, _ptr(out),
+                      C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        return out
+
+    def apply_galois_many(self, L, ct, elements, keys_per_element, is_ckks=True, is_ntt_form=True, out=None):
+        """ct [batch][2][L][N] -> [terms][batch][2][L][N]: the key-switched automorphism X -> X^elements[t] of ct for every t, with ONE digit
+        decomposition of ct; keys_per_element[t]: the L tensors [2][K][N] of the Galois key of elements[t] (include/troyn.h states the contract)"""
+        return self._apply_galois_hoisted(False, L, ct, elements, keys_per_element, is_ckks, is_ntt_form, out)
+
+    def apply_galois_sum(self, L, ct, elements, keys_per_element, is_ckks=True, is_ntt_form=True, out=None):
+        """ct [batch][2][L][N] -> [batch][2][L][N]: the SUM over t of the key-switched automorphisms, one decomposition and ONE division by the
+        special prime"""
+        return self._apply_galois_hoisted(True, L, ct, elements, keys_per_element, is_ckks, is_ntt_form, out)
+
     # -- RLWE / LWE packing (evaluator_lwes.cu) -----------------------------------------------------
     def negacyclic_shift(self, x, nmod, shift, mod_start=0):
         """x [count][nmod][N] * X^shift (utils::negacyclic_shift_ps), any shift (modulo 2N)"""

@@ -501,6 +501,29 @@ PYBIND11_MODULE(pytroy_raw, m) {
            py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), POOL);
     ev.def("complex_conjugate_new", [](const Evaluator& s, const Ciphertext& a, const GaloisKeys& k, PoolArg p) { return s.complex_conjugate_new(a, k, P(p)); },
            py::arg("encrypted"), py::arg("galois_keys"), POOL);
+    // additions: hoisted rotations -- one digit decomposition for many Galois keys (troy.h)
+    ev.def("apply_galois_many", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& g, const GaloisKeys& k, const std::vector<Ciphertext*>& d, PoolArg p) {
+        std::vector<Ciphertext> out = s.apply_galois_many_new(a, g, k, P(p));
+        if (d.size() != out.size()) throw std::invalid_argument("[Evaluator::apply_galois_many] destination needs one ciphertext per element.");
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },
+           py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("apply_galois_many_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& g, const GaloisKeys& k, PoolArg p) {
+        return s.apply_galois_many_new(a, g, k, P(p)); }, py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), POOL);
+    ev.def("apply_galois_sum", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& g, const GaloisKeys& k, Ciphertext& d, PoolArg p) {
+        s.apply_galois_sum(a, g, k, d, P(p)); }, py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("apply_galois_sum_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& g, const GaloisKeys& k, PoolArg p) {
+        return s.apply_galois_sum_new(a, g, k, P(p)); }, py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), POOL);
+    ev.def("rotate_many", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, const std::vector<Ciphertext*>& d, PoolArg p) {
+        std::vector<Ciphertext> out = s.rotate_many_new(a, st, k, P(p));
+        if (d.size() != out.size()) throw std::invalid_argument("[Evaluator::rotate_many] destination needs one ciphertext per step.");
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },
+           py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("rotate_many_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, PoolArg p) {
+        return s.rotate_many_new(a, st, k, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), POOL);
+    ev.def("rotate_sum", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, Ciphertext& d, PoolArg p) {
+        s.rotate_sum(a, st, k, d, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("rotate_sum_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, PoolArg p) {
+        return s.rotate_sum_new(a, st, k, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), POOL);
     // ciphertext +/- plaintext
 #define EV_PLAIN(name)                                                                                                           \
     ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const Plaintext& w, Ciphertext& d, PoolArg p) { s.name(a, w, d, P(p)); },  \

@@ -2112,6 +2112,88 @@ void Evaluator::rotate_columns(const Ciphertext& encrypted, const GaloisKeys& ga
     apply_galois(encrypted, utils::galois_element_from_step(cd->parms().poly_modulus_degree(), 0), galois_keys, destination, pool);
 }
 
+// -- hoisted rotations (addition; troy.h): one digit decomposition of `encrypted` for every Galois key, troyn_apply_galois_many / _sum --
+void Evaluator::apply_galois_hoisted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, bool allow_identity,
+                                     const GaloisKeys& galois_keys, bool sum, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const {
+    if (galois_elements.empty()) throw std::invalid_argument(std::string(P) + " Empty element list.");
+    auto cd = get_context_data(P, encrypted.parms_id());
+    const SchemeType scheme = cd->parms().scheme();
+    if (scheme == SchemeType::BGV) throw std::invalid_argument(std::string(P) + " BGV is not supported: its key switch divides by the special prime differently.");
+    if (encrypted.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " Ciphertext size must be 2.");
+    const size_t n = cd->parms().poly_modulus_degree();
+    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
+    const size_t words = 2 * static_cast<size_t>(L) * n;
+    // apply_galois's checks per element; the terms the library sees are the elements other than the identity
+    std::vector<uint64_t> elements;
+    std::vector<const uint64_t*> keys;
+    std::vector<Ciphertext> shells;      // one allocated result per keyed term (the many form moves them out)
+    size_t identities = 0;
+    for (size_t g : galois_elements) {
+        if (allow_identity && g == 1) { identities++; continue; }
+        Ciphertext shell;
+        std::vector<const uint64_t*> ptrs;
+        apply_galois_prepare(encrypted, g, galois_keys, shell, ptrs, pool);
+        if (ptrs.size() < L) throw std::invalid_argument(std::string(P) + " Key switching key has too few components for this level.");
+        elements.push_back(g);
+        keys.insert(keys.end(), ptrs.begin(), ptrs.begin() + L);
+        if (!sum || shells.empty()) shells.push_back(std::move(shell));
+    }
+    check_no_seed(P, encrypted);
+    check_on_device(P, context_, encrypted);
+    const size_t terms = elements.size();
+    utils::DynamicArray flat(sum || terms == 0 ? 2 : terms * words, true, pool);     // many form: [terms][2][L][N], copied out per term
+    if (terms) {
+        const size_t bytes = troyn_apply_galois_hoisted_workspace_bytes(context_->plan(), L, terms, 1, sum ? 1 : 0);
+        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
+        detail::LaunchGate gate;
+        const int is_ckks = scheme == SchemeType::CKKS, is_ntt = encrypted.is_ntt_form() ? 1 : 0;
+        if (sum)
+            troyn_check(troyn_apply_galois_sum(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), elements.data(), keys.data(), terms,
+                                               shells[0].data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+        else
+            troyn_check(troyn_apply_galois_many(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), elements.data(), keys.data(), terms,
+                                                flat.raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+    }
+    out.clear();
+    if (sum) {
+        // the identity terms: the ciphertext itself, added once per occurrence
+        Ciphertext acc = terms ? std::move(shells[0]) : encrypted.clone(pool);
+        for (size_t i = terms ? 0 : 1; i < identities; i++)
+            troyn_check(troyn_add(context_->plan(), 0, L, acc.data().raw_pointer(), encrypted.data().raw_pointer(), acc.data().raw_pointer(), 2, current_stream()));
+        out.push_back(std::move(acc));
+        return;
+    }
+    size_t t = 0;
+    for (size_t g : galois_elements) {
+        if (allow_identity && g == 1) { out.push_back(encrypted.clone(pool)); continue; }
+        hip_check(hipMemcpyAsync(shells[t].data().raw_pointer(), flat.raw_pointer() + t * words, words * 8, hipMemcpyDeviceToDevice, current_stream()), "copy_device_to_device");
+        out.push_back(std::move(shells[t]));
+        t++;
+    }
+}
+
+std::vector<size_t> Evaluator::hoisted_elements_from_steps(const char* P, const Ciphertext& encrypted, const std::vector<int>& steps) const {
+    auto cd = get_context_data(P, encrypted.parms_id());
+    const size_t n = cd->parms().poly_modulus_degree();
+    std::vector<size_t> elements;
+    for (int st : steps) elements.push_back(st == 0 ? size_t(1) : utils::galois_element_from_step(n, st));      // a step of 0: the ciphertext itself
+    return elements;
+}
+
+void Evaluator::rotate_many(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, std::vector<Ciphertext>& destination,
+                            MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::rotate_many]";
+    apply_galois_hoisted(P, encrypted, hoisted_elements_from_steps(P, encrypted, steps), true, galois_keys, false, destination, pool);
+}
+
+void Evaluator::rotate_sum(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, Ciphertext& destination,
+                           MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::rotate_sum]";
+    std::vector<Ciphertext> d;
+    apply_galois_hoisted(P, encrypted, hoisted_elements_from_steps(P, encrypted, steps), true, galois_keys, true, d, pool);
+    destination = std::move(d[0]);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Serialization  (utils/serialize.h, ciphertext.cu:93-210, plaintext.cu:20-70, kswitch_keys.cu:5-55,
 // encryption_parameters.cu:53-112): raw little-endian fields in the reference's order, so files are interchangeable.

@@ -1463,6 +1463,48 @@ public:
         Ciphertext d; bfv_multiply_accumulate_relinearize(e1, e2, relin_keys, d, pool); return d;
     }
 
+    // ADDITION to the reference's interface: hoisted rotations -- many Galois keys applied to ONE ciphertext with one digit decomposition
+    //   (troyn_apply_galois_many / troyn_apply_galois_sum, include/troyn.h states the contract on integers).
+    //   apply_galois_many: destination[t] = the key-switched automorphism X -> X^elements[t] of `encrypted`; one decomposition, one tail per term.
+    //   apply_galois_sum:  destination = SUM_t of those, summed BEFORE the division by the special prime: one decomposition, ONE tail.
+    //   rotate_many / rotate_sum: the same for rotation steps (rotate_rows for BFV, rotate_vector for CKKS); a step of 0 contributes the
+    //   ciphertext itself (a copy in the many form, an addition in the sum form); duplicates are allowed.
+    //   Every result decrypts to what apply_galois / rotate_* per term (and add_inplace for the sum) decrypt to, under the same noise bound; the
+    //   payload words are NOT those of apply_galois (the digits of a negated coefficient differ by multiples of q_j).  Checks are those of
+    //   apply_galois; a missing key throws "Galois key not present." -- there is no NAF chain (a chain is sequential, nothing to hoist).  BFV and
+    //   CKKS; BGV throws std::invalid_argument (its key switch divides differently).
+    // Call combining does not take part: these methods always launch directly.
+    void apply_galois_many(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys, std::vector<Ciphertext>& destination,
+                           MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        apply_galois_hoisted("[Evaluator::apply_galois_many]", encrypted, galois_elements, false, galois_keys, false, destination, pool);
+    }
+    std::vector<Ciphertext> apply_galois_many_new(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                                  MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; apply_galois_many(encrypted, galois_elements, galois_keys, d, pool); return d;
+    }
+    void apply_galois_sum(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys, Ciphertext& destination,
+                          MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d;
+        apply_galois_hoisted("[Evaluator::apply_galois_sum]", encrypted, galois_elements, false, galois_keys, true, d, pool);
+        destination = std::move(d[0]);
+    }
+    Ciphertext apply_galois_sum_new(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                    MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; apply_galois_sum(encrypted, galois_elements, galois_keys, d, pool); return d;
+    }
+    void rotate_many(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, std::vector<Ciphertext>& destination,
+                     MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::vector<Ciphertext> rotate_many_new(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                                            MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; rotate_many(encrypted, steps, galois_keys, d, pool); return d;
+    }
+    void rotate_sum(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, Ciphertext& destination,
+                    MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext rotate_sum_new(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                              MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; rotate_sum(encrypted, steps, galois_keys, d, pool); return d;
+    }
+
     // ciphertext x plaintext -- evaluator.h (multiply_plain*, transform_plain_to_ntt*); evaluator_multiply_plain.cu,
     // evaluator_transform_ntt.cu:35-70
     void transform_plain_to_ntt(const Plaintext& plain, const ParmsID& parms_id, Plaintext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -1691,6 +1733,10 @@ private:
     SchemeType mod_switch_scale_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
     void apply_galois_prepare(const Ciphertext& encrypted, size_t galois_element, const GaloisKeys& galois_keys, Ciphertext& out, std::vector<const uint64_t*>& key_ptrs,
                               MemoryPoolHandle pool) const;
+    // the hoisted rotations (addition): out = one ciphertext per element, or their sum in out[0]; element 1 (allow_identity: a step of 0) is the ciphertext itself
+    void apply_galois_hoisted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, bool allow_identity, const GaloisKeys& galois_keys,
+                              bool sum, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const;
+    std::vector<size_t> hoisted_elements_from_steps(const char* P, const Ciphertext& encrypted, const std::vector<int>& steps) const;
     void switch_key_internal(const Ciphertext& encrypted, const uint64_t* target, const KSwitchKeys& kswitch_keys, size_t kswitch_keys_index,
                              SwitchKeyDestinationAssignMethod assign_method, Ciphertext& destination, MemoryPoolHandle pool) const;
     void relinearize_inplace_internal(Ciphertext& encrypted, const RelinKeys& relin_keys, size_t destination_size, MemoryPoolHandle pool) const;
