@@ -1,12 +1,17 @@
 // C++ driver for tests/test_gpu_cpp_api.py::test_batched_ops_cpp_api: every Evaluator x_batched form returns, bit for bit, what
 // the per-object call returns -- for operands that are scattered allocations (staged by the gather launch), for operands that are
-// adjacent windows of one buffer (used in place), for in-place calls, and for mixed batches (per-object path).
-// usage: batched_ops_driver <bfv|ckks> <count>
+// adjacent windows of one buffer (used in place), for in-place calls, and for mixed batches (per-object path).  In bgv mode relinearize,
+// apply_galois, apply_keyswitching and mod_switch_to_next take their per-object fallbacks.  A last pass repeats the combinable per-object
+// calls with call combining on (one thread: the shared stream; two threads in step: batches through the rendezvous) and compares with the
+// results computed before it was on.
+// usage: batched_ops_driver <bfv|ckks|bgv> <count>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <thread>
 
 #include "../../troy-nova_amd/troy/troy.h"
 
@@ -33,10 +38,12 @@ static std::vector<Ciphertext*> mptr(std::vector<Ciphertext>& v) { std::vector<C
 int main(int argc, char** argv) {
     try {
         const bool ckks = argc > 1 && std::strcmp(argv[1], "ckks") == 0;
+        const bool bgv = argc > 1 && std::strcmp(argv[1], "bgv") == 0;
+        const bool ntt_ct = ckks || bgv;                                     // CKKS and BGV ciphertexts live in NTT form
         const size_t count = argc > 2 ? std::strtoull(argv[2], nullptr, 0) : 6;
         const size_t n = 4096;
         const uint64_t t = 65537;
-        EncryptionParameters params(ckks ? SchemeType::CKKS : SchemeType::BFV);
+        EncryptionParameters params(ckks ? SchemeType::CKKS : bgv ? SchemeType::BGV : SchemeType::BFV);
         params.set_poly_modulus_degree(n);
         params.set_coeff_modulus(CoeffModulus::create(n, {40, 40, 40, 40}));
         if (!ckks) params.set_plain_modulus(t);
@@ -85,7 +92,7 @@ int main(int argc, char** argv) {
             w_relin.push_back(ev.relinearize_new(w_mul[i], rk));
             w_ms.push_back(ckks ? ev.rescale_to_next_new(w_relin[i]) : ev.mod_switch_to_next_new(w_relin[i]));
             w_gal.push_back(ev.apply_galois_new(a[i], 3, gk));
-            w_ntt.push_back(ckks ? ev.transform_from_ntt_new(a[i]) : ev.transform_to_ntt_new(a[i]));
+            w_ntt.push_back(ntt_ct ? ev.transform_from_ntt_new(a[i]) : ev.transform_to_ntt_new(a[i]));
         }
         std::vector<Ciphertext> g(count);
         ev.add_batched(cptr(a), cptr(b), mptr(g)); report("add_batched", g, w_add);
@@ -98,10 +105,10 @@ int main(int argc, char** argv) {
         if (ckks) ev.rescale_to_next_batched(cptr(gr), mptr(gs)); else ev.mod_switch_to_next_batched(cptr(gr), mptr(gs));
         report(ckks ? "rescale_to_next_batched" : "mod_switch_to_next_batched", gs, w_ms);
         ev.apply_galois_batched(cptr(a), 3, gk, mptr(gg)); report("apply_galois_batched", gg, w_gal);
-        if (ckks) ev.transform_from_ntt_batched(cptr(a), mptr(gn)); else ev.transform_to_ntt_batched(cptr(a), mptr(gn));
+        if (ntt_ct) ev.transform_from_ntt_batched(cptr(a), mptr(gn)); else ev.transform_to_ntt_batched(cptr(a), mptr(gn));
         report("transform_ntt_batched", gn, w_ntt);
         // round trip in place: back to the inputs
-        if (ckks) ev.transform_to_ntt_inplace_batched(mptr(gn)); else ev.transform_from_ntt_inplace_batched(mptr(gn));
+        if (ntt_ct) ev.transform_to_ntt_inplace_batched(mptr(gn)); else ev.transform_from_ntt_inplace_batched(mptr(gn));
         report("transform_ntt_inplace_batched(round trip)", gn, a);
         // in place: destination objects are the operands
         std::vector<Ciphertext> ip;
@@ -120,7 +127,7 @@ int main(int argc, char** argv) {
             std::vector<Ciphertext> an;
             std::vector<Plaintext> pn;
             for (size_t i = 0; i < count; i++) {
-                an.push_back(ckks ? a[i].clone() : ev.transform_to_ntt_new(a[i]));
+                an.push_back(ntt_ct ? a[i].clone() : ev.transform_to_ntt_new(a[i]));
                 pn.push_back(ckks ? plains[i].clone() : ev.transform_plain_to_ntt_new(plains[i], context->first_parms_id()));
             }
             std::vector<const Plaintext*> pnp;
@@ -164,13 +171,15 @@ int main(int argc, char** argv) {
             report("mod_switch_to_new_batched(last level)", ev.mod_switch_to_new_batched(cptr(a), last), w_to);
             report("mod_switch_to_next_new_batched", ev.mod_switch_to_next_new_batched(cptr(a)), w_next);
             if (!ckks) {                                                       // the shift works on coefficient-form ciphertexts
-                for (auto& c : a) w_shift.push_back(ev.negacyclic_shift_new(c, 37));
-                report("negacyclic_shift_new_batched", ev.negacyclic_shift_new_batched(cptr(a), 37), w_shift);
-            }
-            if (!ckks) {
+                std::vector<Ciphertext> coeff;
+                for (auto& c : a) coeff.push_back(bgv ? ev.transform_from_ntt_new(c) : c.clone());
+                for (auto& c : coeff) w_shift.push_back(ev.negacyclic_shift_new(c, 37));
+                report("negacyclic_shift_new_batched", ev.negacyclic_shift_new_batched(cptr(coeff), 37), w_shift);
                 std::vector<Ciphertext> w_mpn;
                 for (size_t i = 0; i < count; i++) w_mpn.push_back(ev.multiply_plain_new(a[i], plains[i]));
                 report("multiply_plain_new_batched", ev.multiply_plain_new_batched(cptr(a), pp), w_mpn);
+            }
+            if (!ntt_ct) {
                 // plaintext side: bfv_centralize + NTT == transform_plain_to_ntt; its inverse returns the centred lift; bfv_scale_up == BatchEncoder::scale_up
                 BatchEncoder benc(context);
                 const ParmsID first = context->first_parms_id();
@@ -191,7 +200,7 @@ int main(int argc, char** argv) {
             Ciphertext e2 = ckks ? encryptor.encrypt_zero_symmetric_new(true, std::nullopt, &g2) : encryptor.encrypt_symmetric_new(plains[0], true, &g2);
             const bool seeded = e1.seed() != 0 && e1.seed() == e2.seed();
             std::vector<Ciphertext> zs = encryptor.encrypt_zero_symmetric_new_batched(3, true);
-            const bool zeros = zs.size() == 3 && zs[0].seed() != 0 && zs[0].seed() != zs[1].seed() && zs[0].is_ntt_form() == ckks;
+            const bool zeros = zs.size() == 3 && zs[0].seed() != 0 && zs[0].seed() != zs[1].seed() && zs[0].is_ntt_form() == ntt_ct;
             std::printf("u_prng_seed %d zero_batched %d\n", seeded ? 1 : 0, zeros ? 1 : 0);
             failures += !seeded + !zeros;
         }
@@ -202,6 +211,54 @@ int main(int argc, char** argv) {
             std::vector<Ciphertext> want, got(count);
             for (auto& c : mix) want.push_back(ev.negate_new(c));
             ev.negate_batched(cptr(mix), mptr(got)); report("negate_batched(mixed)", got, want);
+        }
+        // ---- call combining: the per-object calls that have a combined form, repeated with combining on ----
+        {
+            std::vector<Ciphertext> want;
+            for (size_t i = 0; i < count; i++) {
+                want.push_back(w_mul[i].clone()); want.push_back(w_relin[i].clone()); want.push_back(w_ms[i].clone()); want.push_back(w_gal[i].clone());
+                if (ckks) want.push_back(ev.multiply_relinearize_rescale_new(a[i], b[i], rk));
+            }
+            // `step()` runs before every call: the two threads of the second pass enter each call together, so that the rendezvous sees both
+            auto pass = [&](std::vector<Ciphertext>& out, size_t& bad, auto step) {
+                try {
+                    Evaluator evt(context);
+                    for (size_t i = 0; i < count; i++) {
+                        step(); out.push_back(evt.multiply_new(a[i], b[i]));
+                        step(); out.push_back(evt.relinearize_new(w_mul[i], rk));
+                        step(); out.push_back(ckks ? evt.rescale_to_next_new(w_relin[i]) : evt.mod_switch_to_next_new(w_relin[i]));
+                        step(); out.push_back(evt.apply_galois_new(a[i], 3, gk));
+                        if (ckks) { step(); out.push_back(evt.multiply_relinearize_rescale_new(a[i], b[i], rk)); }
+                    }
+                } catch (const std::exception& e) {
+                    std::printf("combined pass EXCEPTION %s\n", e.what());
+                    bad++;
+                }
+            };
+            combining::set_enabled(true);
+            std::vector<Ciphertext> one, two[2];
+            size_t bad[3] = {0, 0, 0};
+            pass(one, bad[0], [] {});
+            combining::reset_stats();
+            const unsigned window = combining::window_us();
+            combining::set_window_us(2000);      // the two threads enter each call together; a wide window takes a loaded host's skew out of "did a batch form"
+            std::atomic<size_t> arrived{0};
+            std::vector<std::thread> threads;
+            for (size_t k = 0; k < 2; k++)
+                threads.emplace_back([&, k] {
+                    size_t round = 0;
+                    pass(two[k], bad[1 + k], [&] { round++; arrived.fetch_add(1); while (arrived.load() < 2 * round) std::this_thread::yield(); });
+                    arrived.fetch_add(1000000);       // a thread that stopped early must not hold the other one back
+                });
+            for (auto& th : threads) th.join();
+            const combining::Stats st = combining::stats();
+            combining::set_window_us(window);
+            combining::set_enabled(false);
+            report("combined(one thread)", one, want);
+            report("combined(two threads, first)", two[0], want);
+            report("combined(two threads, second)", two[1], want);
+            std::printf("combined batches %llu calls %llu: none formed %d\n", (unsigned long long)st.batches, (unsigned long long)st.calls, st.batches == 0 ? 1 : 0);
+            failures += bad[0] + bad[1] + bad[2] + (st.batches == 0);
         }
         // size mismatch throws what the reference throws
         bool threw = false;

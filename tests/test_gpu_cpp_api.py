@@ -201,17 +201,18 @@ def test_batched_encrypt_decrypt_cpp_api(dev, n, count):
     assert "encrypt_mismatches 0 of" in r.stdout and "decrypt_mismatches 0 of" in r.stdout and "ntt_form_rejected 1" in r.stdout
 
 
-@pytest.mark.parametrize("scheme,count", [("bfv", 6), ("ckks", 5), ("bfv", 2)])
+@pytest.mark.parametrize("scheme,count", [("bfv", 6), ("ckks", 5), ("bfv", 2), ("bgv", 5)])
 def test_batched_ops_cpp_api(dev, scheme, count):
     """every Evaluator x_batched form equals the per-object call bit for bit (scattered operands, adjacent windows, in place,
-    mixed batches, below the batching threshold)"""
+    mixed batches, below the batching threshold, the per-object fallbacks of BGV), and so do the per-object calls with call
+    combining on (one thread, and two threads whose calls run as batches)"""
     drv = os.path.join(ROOT, "tests", "cpp", "batched_ops_driver")
     if not os.path.exists(drv):
         pytest.fail("tests/cpp/batched_ops_driver is not built (python -c 'import __graft_entry__ as g; g.build()')")
     r = subprocess.run([drv, scheme, str(count)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln and ln not in ("OK",)]
-    assert len(lines) >= 26 and all(ln.endswith(" 0") or ln in ("size_mismatch_rejected 1", "u_prng_seed 1 zero_batched 1") for ln in lines), r.stdout
+    assert len(lines) >= 30 and all(ln.endswith(" 0") or ln in ("size_mismatch_rejected 1", "u_prng_seed 1 zero_batched 1") for ln in lines), r.stdout
 
 
 def test_bgv_cpp_api(dev):

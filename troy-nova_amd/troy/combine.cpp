@@ -27,6 +27,7 @@
 #include <thread>
 
 #include "troy.h"
+#include "device_steps.h"
 
 namespace troy {
 
@@ -96,90 +97,31 @@ static_assert(sizeof(std::atomic<int>) == sizeof(int), "futex word");
 void futex_wait(std::atomic<int>* a, int expected) { (void)syscall(SYS_futex, reinterpret_cast<int*>(a), FUTEX_WAIT_PRIVATE, expected, nullptr, nullptr, 0); }
 void futex_wake(std::atomic<int>* a) { (void)syscall(SYS_futex, reinterpret_cast<int*>(a), FUTEX_WAKE_PRIVATE, INT_MAX, nullptr, nullptr, 0); }
 
-// operands of the batch as [count][words]: in place when they happen to be consecutive windows of one buffer, else one gather launch
-const uint64_t* stage(const std::vector<detail::CombineRequest*>& batch, bool second, utils::DynamicArray& staged, void* table, size_t table_bytes,
-                      MemoryPoolHandle pool, hipStream_t s) {
-    const size_t count = batch.size();
-    const size_t words = second ? batch[0]->words2 : batch[0]->words1;
-    const uint64_t* base = second ? batch[0]->in2 : batch[0]->in1;
-    bool adjacent = true;
-    for (size_t i = 0; i < count && adjacent; i++) adjacent = (second ? batch[i]->in2 : batch[i]->in1) == base + i * words;
-    if (adjacent) return base;
-    staged = utils::DynamicArray(count * words, true, pool);
-    std::vector<const uint64_t*> src(count);
-    for (size_t i = 0; i < count; i++) src[i] = second ? batch[i]->in2 : batch[i]->in1;
-    lib_ok(troyn_gather(src.data(), count, words, staged.raw_pointer(), table, table_bytes, (troyn_stream_t)s));
-    return staged.raw_pointer();
-}
-
+// the batch as one device step (device_steps.h) between a gather of the callers' operands and a scatter to their destinations
 void execute(std::vector<detail::CombineRequest*>& batch, MemoryPoolHandle pool) {
     using detail::CombineKind;
     const detail::CombineRequest& h = *batch[0];
     const size_t count = batch.size();
-    hipStream_t s = (hipStream_t)troyn_current_stream();   // the shared stream
-    {
-        utils::DynamicArray s1, s2, block, ws;
-        const size_t table_bytes = troyn_gather_workspace_bytes(count);
-        utils::DynamicArray table((table_bytes + 7) / 8, true, pool);
-        const uint64_t* a = stage(batch, false, s1, table.raw_pointer(), table_bytes, pool, s);
-        const uint64_t* b = h.in2 ? stage(batch, true, s2, table.raw_pointer(), table_bytes, pool, s) : nullptr;
-        block = utils::DynamicArray(count * h.out_words, true, pool);
-        uint64_t* out = block.raw_pointer();
-        switch (h.kind) {
-            case CombineKind::DyadicMultiply: {
-                const troyn_plan* plan = static_cast<const troyn_plan*>(h.handle);
-                lib_ok(troyn_dyadic_convolute(plan, 0, h.L, a, h.p1, b, h.p2, out, count, (troyn_stream_t)s));
-                break;
-            }
-            case CombineKind::BfvMultiply: {
-                const troyn_behz* bz = static_cast<const troyn_behz*>(h.handle);
-                const size_t bytes = troyn_bfv_multiply_workspace_bytes(bz, h.p1, h.p2, count);
-                ws = utils::DynamicArray((bytes + 7) / 8, true, pool);
-                lib_ok(troyn_bfv_multiply(bz, a, h.p1, b, h.p2, out, ws.raw_pointer(), bytes, count, (troyn_stream_t)s));
-                break;
-            }
-            case CombineKind::Relinearize: {
-                const troyn_plan* plan = static_cast<const troyn_plan*>(h.handle);
-                const size_t bytes = troyn_relinearize_workspace_bytes(plan, h.L, count);
-                ws = utils::DynamicArray((bytes + 7) / 8, true, pool);
-                lib_ok(troyn_relinearize(plan, h.L, h.ckks, h.ntt_form, a, h.keys->data(), out, ws.raw_pointer(), bytes, count, (troyn_stream_t)s));
-                break;
-            }
-            case CombineKind::Rescale: {
-                const troyn_plan* plan = static_cast<const troyn_plan*>(h.handle);
-                const size_t bytes = troyn_divide_and_round_q_last_ntt_workspace_bytes(plan, h.L, h.p1, count);
-                ws = utils::DynamicArray((bytes + 7) / 8, true, pool);
-                lib_ok(troyn_divide_and_round_q_last_ntt(plan, h.L, a, h.p1, out, ws.raw_pointer(), bytes, count, (troyn_stream_t)s));
-                break;
-            }
-            case CombineKind::ApplyGalois: {
-                // Evaluator::apply_galois (evaluator_keyswitching.cu:147-179) over the batch: permute (c0, c1) of every item, take the permuted c1s
-                // as key-switch targets, overwrite them with the switched result (c0 += ks0, c1 = ks1)
-                const troyn_plan* plan = static_cast<const troyn_plan*>(h.handle);
-                const size_t pc = h.words1 / 2;
-                lib_ok(troyn_apply_galois(plan, 0, h.L, h.ntt_form ? 1 : 0, h.p2, a, out, count * 2, (troyn_stream_t)s));
-                s2 = utils::DynamicArray(count * pc, true, pool);
-                if (hipMemcpy2DAsync(s2.raw_pointer(), pc * 8, out + pc, 2 * pc * 8, pc * 8, count, hipMemcpyDeviceToDevice, s) != hipSuccess)
-                    throw std::runtime_error("[kernel_provider::copy_device_to_device] failed");
-                const size_t bytes = troyn_switch_key_workspace_bytes(plan, h.L, count);
-                ws = utils::DynamicArray((bytes + 7) / 8, true, pool);
-                lib_ok(troyn_switch_key(plan, h.L, h.ckks, h.ntt_form, s2.raw_pointer(), h.keys->data(), TROYN_ASSIGN_OVERWRITE_EXCEPT_FIRST, out, ws.raw_pointer(), bytes, count,
-                                        (troyn_stream_t)s));
-                break;
-            }
-            case CombineKind::MultiplyRelinearizeRescale: {
-                const troyn_plan* plan = static_cast<const troyn_plan*>(h.handle);
-                const size_t bytes = troyn_ckks_multiply_relinearize_rescale_workspace_bytes(plan, h.L, count);
-                ws = utils::DynamicArray((bytes + 7) / 8, true, pool);
-                lib_ok(troyn_ckks_multiply_relinearize_rescale(plan, h.L, a, b, h.keys->data(), out, ws.raw_pointer(), bytes, count, (troyn_stream_t)s));
-                break;
-            }
-        }
-        std::vector<uint64_t*> dst(count);
-        for (size_t i = 0; i < count; i++) dst[i] = batch[i]->out;
-        lib_ok(troyn_scatter(out, dst.data(), count, h.out_words, table.raw_pointer(), table_bytes, (troyn_stream_t)s));
-    }   // staging, block, workspace go back to the pool here: whoever takes them next uses them behind this batch (one stream)
-}
+    const detail::StepEnv env{pool, detail::current_stream(), lib_ok};   // the shared stream
+    const troyn_plan* plan = static_cast<const troyn_plan*>(h.handle);  // (BfvMultiply: a troyn_behz)
+    std::vector<const uint64_t*> src1(count), src2(count);
+    std::vector<uint64_t*> dst(count);
+    for (size_t i = 0; i < count; i++) { src1[i] = batch[i]->in1; src2[i] = batch[i]->in2; dst[i] = batch[i]->out; }
+    utils::DynamicArray s1, s2, table;
+    const uint64_t* a = detail::stage(env, src1, h.words1, s1, table);
+    const uint64_t* b = h.in2 ? detail::stage(env, src2, h.words2, s2, table) : nullptr;
+    utils::DynamicArray block(count * h.out_words, true, pool);
+    uint64_t* out = block.raw_pointer();
+    switch (h.kind) {
+        case CombineKind::DyadicMultiply: detail::multiply_dyadic_step(env, plan, h.L, a, h.p1, b, h.p2, out, count); break;
+        case CombineKind::BfvMultiply: detail::multiply_bfv_step(env, static_cast<const troyn_behz*>(h.handle), a, h.p1, b, h.p2, out, count); break;
+        case CombineKind::Relinearize: detail::relinearize_step(env, plan, nullptr, h.L, h.ckks, h.ntt_form, a, h.keys->data(), out, count); break;
+        case CombineKind::Rescale: detail::rescale_step(env, plan, h.L, a, h.p1, out, count); break;
+        case CombineKind::ApplyGalois: detail::apply_galois_step(env, plan, nullptr, h.L, h.words1 / 2 / h.L, h.ckks, h.ntt_form, h.p2, a, h.keys->data(), out, count); break;
+        case CombineKind::MultiplyRelinearizeRescale: detail::multiply_relinearize_rescale_step(env, plan, h.L, a, b, h.keys->data(), out, count); break;
+    }
+    detail::scatter(env, out, dst, h.out_words, table);
+}   // staging, block, table go back to the pool here: whoever takes them next uses them behind this batch (one stream)
 
 }  // namespace
 

@@ -1,0 +1,149 @@
+// The Evaluator's device steps (device_steps.h): workspace from the pool, then the C-ABI entry.  No argument checks, no Ciphertext.
+#include "device_steps.h"
+
+#include <hip/hip_runtime.h>
+
+namespace troy {
+namespace detail {
+
+void hip_check(hipError_t e, const char* what) {
+    if (e != hipSuccess) throw std::runtime_error(std::string("[kernel_provider::") + what + "] " + hipGetErrorString(e));
+}
+
+namespace {
+
+// a workspace of `bytes` from the step's pool; it returns to the pool when the step ends and is reused in stream order (MemoryPool)
+utils::DynamicArray workspace(const StepEnv& env, size_t bytes) { return utils::DynamicArray((bytes + 7) / 8, true, env.pool); }
+
+void gather_table(const StepEnv& env, size_t count, utils::DynamicArray& table) {
+    if (table.size() == 0) table = workspace(env, troyn_gather_workspace_bytes(count));
+}
+
+// the c1 of every (c0, c1) of `pairs` as [count][words]: the key-switch targets
+void extract_c1(const StepEnv& env, const uint64_t* pairs, size_t words, uint64_t* target, size_t count) {
+    if (count == 1) hip_check(hipMemcpyAsync(target, pairs + words, words * 8, hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
+    else hip_check(hipMemcpy2DAsync(target, words * 8, pairs + words, 2 * words * 8, words * 8, count, hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
+}
+
+}  // namespace
+
+const uint64_t* stage(const StepEnv& env, const std::vector<const uint64_t*>& src, size_t words, utils::DynamicArray& staged, utils::DynamicArray& table) {
+    const size_t count = src.size();
+    bool adjacent = true;
+    for (size_t i = 0; i < count && adjacent; i++) adjacent = src[i] == src[0] + i * words;
+    if (adjacent) return src[0];
+    staged = utils::DynamicArray(count * words, true, env.pool);
+    gather_table(env, count, table);
+    env.check(troyn_gather(src.data(), count, words, staged.raw_pointer(), table.raw_pointer(), troyn_gather_workspace_bytes(count), env.stream));   // (`src` is consumed by the call)
+    return staged.raw_pointer();
+}
+
+void scatter(const StepEnv& env, const uint64_t* block, const std::vector<uint64_t*>& dst, size_t words, utils::DynamicArray& table) {
+    gather_table(env, dst.size(), table);
+    env.check(troyn_scatter(block, dst.data(), dst.size(), words, table.raw_pointer(), troyn_gather_workspace_bytes(dst.size()), env.stream));
+}
+
+void multiply_dyadic_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* a, size_t p1, const uint64_t* b, size_t p2, uint64_t* out, size_t count) {
+    env.check(troyn_dyadic_convolute(plan, 0, L, a, p1, b, p2, out, count, env.stream));
+}
+
+void multiply_bfv_step(const StepEnv& env, const troyn_behz* behz, const uint64_t* a, size_t p1, const uint64_t* b, size_t p2, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_bfv_multiply_workspace_bytes(behz, p1, p2, count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    env.check(troyn_bfv_multiply(behz, a, p1, b, p2, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void square_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t count) {
+    env.check(troyn_dyadic_square(plan, 0, L, in, out, count, env.stream));
+}
+
+void relinearize_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* in,
+                      const uint64_t* const* keys, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_relinearize_workspace_bytes(plan, L, count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    if (bgv) env.check(troyn_bgv_relinearize(bgv, L, in, keys, out, ws.raw_pointer(), bytes, count, env.stream));
+    else env.check(troyn_relinearize(plan, L, ckks, ntt_form, in, keys, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void switch_key_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* target,
+                     const uint64_t* const* keys, int assign, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_switch_key_workspace_bytes(plan, L, count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    // BGV: the ski_util5 tail needs the key level's q_special^-1 mod t (evaluator_keyswitching_core.cu:930-932)
+    if (bgv) env.check(troyn_bgv_switch_key(bgv, L, target, keys, assign, out, ws.raw_pointer(), bytes, count, env.stream));
+    else env.check(troyn_switch_key(plan, L, ckks, ntt_form, target, keys, assign, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, size_t polys, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_divide_and_round_q_last_ntt_workspace_bytes(plan, L, polys, count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_divide_and_round_q_last_ntt(plan, L, in, polys, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void divide_round_q_last_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, size_t polys, uint64_t* out, size_t count) {
+    env.check(troyn_divide_and_round_q_last(plan, L, in, polys, out, count, env.stream));
+}
+
+void bgv_mod_t_divide_step(const StepEnv& env, const troyn_bgv* bgv, const uint64_t* in, size_t polys, uint64_t* out, size_t count) {
+    // RNSTool::mod_t_and_divide_q_last_ntt
+    const size_t bytes = troyn_bgv_mod_switch_workspace_bytes(bgv, polys, count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    env.check(troyn_bgv_mod_t_and_divide_q_last_ntt(bgv, in, polys, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void mod_switch_drop_step(const StepEnv& env, const troyn_plan* plan, uint32_t L_in, uint32_t L_out, const uint64_t* in, size_t polys, uint64_t* out, size_t count) {
+    env.check(troyn_mod_switch_drop(plan, L_in, L_out, in, polys, out, count, env.stream));
+}
+
+void negate_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t polys) {
+    env.check(troyn_negate(plan, 0, L, in, out, polys, env.stream));
+}
+
+void add_sub_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, bool subtract, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t polys) {
+    env.check((subtract ? troyn_sub : troyn_add)(plan, 0, L, a, b, out, polys, env.stream));
+}
+
+void ntt_step(const StepEnv& env, const troyn_plan* plan, bool inverse, const uint64_t* in, uint64_t* out, size_t count, size_t polys, uint32_t L) {
+    env.check(troyn_ntt(plan, inverse ? 1 : 0, in, out, count, polys, L, 0, L, TROYN_IDX_COMPONENTWISE, 0, env.stream));
+}
+
+void apply_galois_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, size_t n, bool ckks, bool ntt_form, size_t galois_element,
+                       const uint64_t* in, const uint64_t* const* keys, uint64_t* out, size_t count) {
+    // Evaluator::apply_galois (evaluator_keyswitching.cu:147-179) over the batch: the permuted c1s are the targets, the switched result overwrites them
+    const size_t words = static_cast<size_t>(L) * n;
+    env.check(troyn_apply_galois(plan, 0, L, ntt_form ? 1 : 0, galois_element, in, out, count * 2, env.stream));
+    utils::DynamicArray target(count * words, true, env.pool);
+    extract_c1(env, out, words, target.raw_pointer(), count);
+    switch_key_step(env, plan, bgv, L, ckks, ntt_form, target.raw_pointer(), keys, TROYN_ASSIGN_OVERWRITE_EXCEPT_FIRST, out, count);
+}
+
+void apply_keyswitching_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, size_t n, bool ckks, bool ntt_form, const uint64_t* in,
+                             const uint64_t* const* keys, uint64_t* out, size_t count) {
+    // evaluator_keyswitching.cu:11-93: the result starts as a copy of the operands
+    const size_t words = static_cast<size_t>(L) * n;
+    hip_check(hipMemcpyAsync(out, in, count * 2 * words * sizeof(uint64_t), hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
+    if (count == 1) {   // the one c1 is its own [1][words]
+        switch_key_step(env, plan, bgv, L, ckks, ntt_form, in + words, keys, TROYN_ASSIGN_OVERWRITE_EXCEPT_FIRST, out, 1);
+        return;
+    }
+    utils::DynamicArray target(count * words, true, env.pool);
+    extract_c1(env, in, words, target.raw_pointer(), count);
+    switch_key_step(env, plan, bgv, L, ckks, ntt_form, target.raw_pointer(), keys, TROYN_ASSIGN_OVERWRITE_EXCEPT_FIRST, out, count);
+}
+
+void negacyclic_shift_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t shift, size_t polys) {
+    env.check(troyn_negacyclic_shift(plan, 0, L, in, out, shift, polys, env.stream));
+}
+
+void multiply_relinearize_rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* a, const uint64_t* b, const uint64_t* const* keys,
+                                       uint64_t* out, size_t count) {
+    const size_t bytes = troyn_ckks_multiply_relinearize_rescale_workspace_bytes(plan, L, count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_ckks_multiply_relinearize_rescale(plan, L, a, b, keys, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+}  // namespace detail
+}  // namespace troy

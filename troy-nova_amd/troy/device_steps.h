@@ -1,0 +1,78 @@
+// The device steps of the Evaluator: ONE function per operation sizes the workspace, takes it from the pool and calls the C-ABI
+// (include/troyn.h).  The per-object methods (troy.cpp, lwe.cpp) call a step with count = 1 on the calling thread's stream, the
+// *_batched forms (batched.cpp) with the batch's count, the call-combining rendezvous (combine.cpp) on the shared stream.  A step
+// checks no Ciphertext and touches none: the callers' *_prepare functions have done the checks and shaped the result.
+//
+// Rule: each C-ABI entry named below is called from exactly one function of the mirror -- its step.  A change to an entry's
+// workspace contract is a change to one function.
+//
+// Operands are [count][...] contiguous words on the device; `out` may alias an input only where the entry allows it.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include "troy.h"
+
+namespace troy {
+namespace detail {
+#pragma GCC visibility push(hidden)   // internal to libtroy_amd.so: direct calls, nothing here is part of the library's surface
+
+// where a step runs and who hears about a failure: the pool its workspace comes from, the stream, and the caller's checker of a C-ABI
+// return code (troyn_check_public for the methods and the batched forms; the rendezvous has its own)
+struct StepEnv {
+    const MemoryPoolHandle& pool;   // the CALLER's handle, by reference (no reference count per call): an environment is built in the argument list of a
+                                    // step or as a local next to the handle it names, and never outlives that handle
+    hipStream_t stream;
+    void (*check)(int);
+    bool gated = false;             // the caller's decision: a step that takes a workspace holds the stream gate around its C-ABI call only
+};
+
+// The threads that share a stream enter the library one at a time (troy.cpp).  A per-object caller that gates a step without a workspace
+// holds one around the step; around a step with a workspace it sets StepEnv::gated, so that the pool is not used under the gate.
+struct LaunchGate {
+    std::mutex* m = nullptr;
+    explicit LaunchGate(bool take = true);
+    ~LaunchGate();
+    LaunchGate(const LaunchGate&) = delete;
+    LaunchGate& operator=(const LaunchGate&) = delete;
+};
+
+hipStream_t current_stream();                      // the calling thread's stream (troy.cpp)
+void hip_check(hipError_t e, const char* what);   // kernel_provider.h:11-16: std::runtime_error with the runtime's message
+inline StepEnv on_current_stream(const MemoryPoolHandle& pool, bool gated = false) { return StepEnv{pool, current_stream(), troyn_check_public, gated}; }
+
+// `src[i]` as [count][words]: in place when the operands are consecutive windows, else one gather launch into `staged`.
+// `table` is the gather's pointer table: taken from the pool here when the caller has not sized it already.
+const uint64_t* stage(const StepEnv& env, const std::vector<const uint64_t*>& src, size_t words, utils::DynamicArray& staged, utils::DynamicArray& table);
+// the inverse of a gather: [count][words] to `dst[i]`
+void scatter(const StepEnv& env, const uint64_t* block, const std::vector<uint64_t*>& dst, size_t words, utils::DynamicArray& table);
+
+void multiply_dyadic_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* a, size_t p1, const uint64_t* b, size_t p2, uint64_t* out, size_t count);
+void multiply_bfv_step(const StepEnv& env, const troyn_behz* behz, const uint64_t* a, size_t p1, const uint64_t* b, size_t p2, uint64_t* out, size_t count);
+void square_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t count);
+// 3 -> 2 components; `bgv` (the key level's handle) selects the BGV tail
+void relinearize_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* in,
+                      const uint64_t* const* keys, uint64_t* out, size_t count);
+// `target` is [count][L][N]; `assign` a TROYN_ASSIGN_* value applied to out = [count][2][L][N]
+void switch_key_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* target,
+                     const uint64_t* const* keys, int assign, uint64_t* out, size_t count);
+void rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, size_t polys, uint64_t* out, size_t count);   // divide_and_round_q_last_ntt
+void divide_round_q_last_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, size_t polys, uint64_t* out, size_t count);   // BFV
+void bgv_mod_t_divide_step(const StepEnv& env, const troyn_bgv* bgv, const uint64_t* in, size_t polys, uint64_t* out, size_t count);
+void mod_switch_drop_step(const StepEnv& env, const troyn_plan* plan, uint32_t L_in, uint32_t L_out, const uint64_t* in, size_t polys, uint64_t* out, size_t count);
+void negate_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t polys);
+void add_sub_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, bool subtract, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t polys);
+void ntt_step(const StepEnv& env, const troyn_plan* plan, bool inverse, const uint64_t* in, uint64_t* out, size_t count, size_t polys, uint32_t L);
+// (c0, c1) permuted by the element, the permuted c1s switched back: c0 += ks0, c1 = ks1
+void apply_galois_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, size_t n, bool ckks, bool ntt_form, size_t galois_element,
+                       const uint64_t* in, const uint64_t* const* keys, uint64_t* out, size_t count);
+// (c0, c1) -> (c0 + ks0, ks1) with the c1s as key-switch targets
+void apply_keyswitching_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, size_t n, bool ckks, bool ntt_form, const uint64_t* in,
+                             const uint64_t* const* keys, uint64_t* out, size_t count);
+void negacyclic_shift_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t shift, size_t polys);
+void multiply_relinearize_rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* a, const uint64_t* b, const uint64_t* const* keys,
+                                       uint64_t* out, size_t count);
+
+#pragma GCC visibility pop
+}  // namespace detail
+}  // namespace troy

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "troy.h"
+#include "device_steps.h"
 
 namespace troy {
 
@@ -218,16 +219,21 @@ void Evaluator::divide_by_poly_modulus_degree_inplace(Ciphertext& encrypted, uin
     troyn_sync_current_stream();
 }
 
-void Evaluator::negacyclic_shift(const Ciphertext& encrypted, size_t shift, Ciphertext& destination, MemoryPoolHandle pool) const {
+// the argument checks of negacyclic_shift and the result object WITHOUT the device work
+void Evaluator::negacyclic_shift_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const {
     const char* P = "[Evaluator::negacyclic_shift]";
     no_seed(P, encrypted);
     need_device(P, context_, encrypted);
-    ContextDataPointer cd = level(P, context_, encrypted.parms_id());
-    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
+    level(P, context_, encrypted.parms_id());
     if (encrypted.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Ciphertext is in NTT form.");
-    Ciphertext out = Ciphertext::like(encrypted, false, pool);
-    troyn_check_public(troyn_negacyclic_shift(context_->plan(), 0, L, encrypted.data().raw_pointer(), out.data().raw_pointer(), shift,
-                                              encrypted.polynomial_count(), stream()));
+    out = Ciphertext::like(encrypted, false, pool);
+}
+
+void Evaluator::negacyclic_shift(const Ciphertext& encrypted, size_t shift, Ciphertext& destination, MemoryPoolHandle pool) const {
+    Ciphertext out;
+    negacyclic_shift_prepare(encrypted, out, pool);
+    detail::negacyclic_shift_step(detail::on_current_stream(pool), context_->plan(), static_cast<uint32_t>(out.coeff_modulus_size()), encrypted.data().raw_pointer(),
+                                  out.data().raw_pointer(), shift, encrypted.polynomial_count());
     troyn_sync_current_stream();
     destination = std::move(out);
 }
@@ -284,7 +290,7 @@ void Evaluator::mod_switch_plain_to(const Plaintext& plain, const ParmsID& parms
     Plaintext out;
     out.data() = utils::DynamicArray(0, true, pool);
     out.resize_rns(*context_, parms_id);
-    troyn_check_public(troyn_mod_switch_drop(context_->plan(), L_in, L_out, plain.poly(), 1, out.poly(), 1, stream()));
+    detail::mod_switch_drop_step(detail::on_current_stream(pool), context_->plan(), L_in, L_out, plain.poly(), 1, out.poly(), 1);
     troyn_sync_current_stream();
     out.is_ntt_form() = true;
     out.scale() = plain.scale();
@@ -446,8 +452,7 @@ void Evaluator::pack_rlwe_ciphertexts_batched(const std::vector<std::vector<cons
         troyn_check_public(troyn_pack_layer(plan, L, g, input_interval >> (layer + 1), current->raw_pointer(), next->raw_pointer(), target.raw_pointer(), pairs, s));
         const std::vector<const uint64_t*> keys = automorphism_keys.get_data_ptrs(GaloisKeys::get_index(g));
         if (keys.size() < L) throw std::invalid_argument("[Evaluator::switch_key_inplace_internal] Key switching key has too few components for this level.");
-        const size_t bytes = troyn_switch_key_workspace_bytes(plan, L, pairs);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
+        const detail::StepEnv env{pool, s, troyn_check_public};
         if (scheme == SchemeType::BGV) {
             // BGV key switching is defined on NTT-form operands (its tail removes the special prime AND keeps the result a multiple of t:
             // ski_util5, evaluator_keyswitching_core.cu:998-1030), so the reference transforms the odd member around apply_galois
@@ -456,13 +461,12 @@ void Evaluator::pack_rlwe_ciphertexts_batched(const std::vector<std::vector<cons
             const size_t K = context_->key_context_data().value()->parms().coeff_modulus().size();
             utils::DynamicArray switched(pairs * words, true, pool);
             troyn_check_public(troyn_ntt(plan, 0, target.raw_pointer(), target.raw_pointer(), pairs, 1, L, 0, L, TROYN_IDX_COMPONENTWISE, 0, s));
-            troyn_check_public(troyn_bgv_switch_key(context_->bgv(K), L, target.raw_pointer(), keys.data(), TROYN_ASSIGN_OVERWRITE, switched.raw_pointer(), ws.raw_pointer(), bytes, pairs, s));
+            detail::switch_key_step(env, plan, context_->bgv(K), L, false, true, target.raw_pointer(), keys.data(), TROYN_ASSIGN_OVERWRITE, switched.raw_pointer(), pairs);
             troyn_check_public(troyn_ntt(plan, 1, switched.raw_pointer(), switched.raw_pointer(), pairs, 2, L, 0, L, TROYN_IDX_COMPONENTWISE, 0, s));
             troyn_check_public(troyn_add(plan, 0, L, next->raw_pointer(), switched.raw_pointer(), next->raw_pointer(), pairs * 2, s));
         } else
-        troyn_check_public(troyn_switch_key(plan, L, scheme == SchemeType::CKKS, 0, target.raw_pointer(), keys.data(), TROYN_ASSIGN_ADD_INPLACE, next->raw_pointer(),
-                                            ws.raw_pointer(), bytes, pairs, s));
-        // `target`, `ws` and the previous buffer return to the pool here: stream order protects them (same thread, same stream), no wait per layer
+        detail::switch_key_step(env, plan, nullptr, L, scheme == SchemeType::CKKS, false, target.raw_pointer(), keys.data(), TROYN_ASSIGN_ADD_INPLACE, next->raw_pointer(), pairs);
+        // `target`, the step's workspace and the previous buffer return to the pool here: stream order protects them (same thread, same stream), no wait per layer
         current = std::move(next);
         count = pairs;
     }

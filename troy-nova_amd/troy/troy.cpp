@@ -2,6 +2,7 @@
 // operation goes through the C-ABI (include/troyn.h).  Reference file:line citations name the
 // function whose behaviour (checks, metadata updates, error text) is mirrored.
 #include "troy.h"
+#include "device_steps.h"
 
 #include <atomic>
 #include <unordered_set>
@@ -22,10 +23,7 @@ namespace troy {
 // ------------------------------------------------------------------------------------------------
 // helpers
 // ------------------------------------------------------------------------------------------------
-static void hip_check(hipError_t e, const char* what) {
-    // kernel_provider.h:11-16: runtime failures are std::runtime_error with the runtime's message
-    if (e != hipSuccess) throw std::runtime_error(std::string("[kernel_provider::") + what + "] " + hipGetErrorString(e));
-}
+using detail::hip_check;   // device_steps.cpp
 
 static void troyn_check(int rc) {
     if (rc == 0) return;
@@ -146,23 +144,24 @@ static inline hipStream_t pooled_stream(int q, int* slot_out = nullptr) {
 namespace detail {
 static bool stream_gate_on() { static const bool on = [] { const char* e = std::getenv("TROY_STREAM_GATE"); return !(e && e[0] == '0'); }(); return on; }
 static std::mutex* stream_gates() { static std::mutex* g = new std::mutex[MAX_POOL_DEVICES * MAX_POOL_STREAMS]; return g; }
-struct LaunchGate {
-    std::mutex* m = nullptr;
-    LaunchGate() {
-        if (!stream_gate_on() || combining_on()) return;
-        const int q = stream_pool_size();
-        int slot = 0;
-        if (q != 0 && pooled_stream(q, &slot)) { m = &stream_gates()[slot]; m->lock(); }
-    }
-    ~LaunchGate() { if (m) m->unlock(); }
-};
+LaunchGate::LaunchGate(bool take) {
+    if (!take || !stream_gate_on() || combining_on()) return;
+    const int q = stream_pool_size();
+    int slot = 0;
+    if (q != 0 && pooled_stream(q, &slot)) { m = &stream_gates()[slot]; m->lock(); }
+}
+LaunchGate::~LaunchGate() { if (m) m->unlock(); }
 }  // namespace detail
 
-static inline hipStream_t current_stream() {
-    if (detail::combining_on()) if (hipStream_t s = detail::shared_stream()) if (on_shared_device()) return s;
-    if (const int q = detail::stream_pool_size()) if (hipStream_t s = detail::pooled_stream(q)) return s;
+namespace detail {
+hipStream_t current_stream() {
+    if (combining_on()) if (hipStream_t s = shared_stream()) if (on_shared_device()) return s;
+    if (const int q = stream_pool_size()) if (hipStream_t s = pooled_stream(q)) return s;
     return hipStreamPerThread;
 }
+}  // namespace detail
+using detail::current_stream;
+using detail::on_current_stream;
 
 namespace detail { bool on_combining_stream() { return combining_on() && g_shared_stream && current_stream() == g_shared_stream; } }
 
@@ -1106,14 +1105,18 @@ ContextDataPointer Evaluator::get_context_data(const char* prompt, const ParmsID
 }
 
 // -- negate ------------------------------------------------------------------------------------
-void Evaluator::negate(const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const {
+// every argument check of negate and the result object WITHOUT the device work (multiply_prepare is the pattern of every *_prepare)
+void Evaluator::negate_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const {
     check_no_seed("[Evaluator::negate]", encrypted);
     check_on_device("[Evaluator::negate]", context_, encrypted);
-    auto cd = get_context_data("[Evaluator::negate]", encrypted.parms_id());
-    destination = Ciphertext::like(encrypted, false, pool);
-    const size_t L = cd->parms().coeff_modulus().size();
-    troyn_check(troyn_negate(context_->plan(), 0, static_cast<uint32_t>(L), encrypted.data().raw_pointer(), destination.data().raw_pointer(),
-                             encrypted.polynomial_count(), current_stream()));
+    get_context_data("[Evaluator::negate]", encrypted.parms_id());
+    out = Ciphertext::like(encrypted, false, pool);
+}
+
+void Evaluator::negate(const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const {
+    negate_prepare(encrypted, destination, pool);
+    detail::negate_step(on_current_stream(pool), context_->plan(), static_cast<uint32_t>(destination.coeff_modulus_size()), encrypted.data().raw_pointer(),
+                        destination.data().raw_pointer(), encrypted.polynomial_count());
 }
 
 void Evaluator::negate_inplace(Ciphertext& encrypted) const {
@@ -1121,8 +1124,8 @@ void Evaluator::negate_inplace(Ciphertext& encrypted) const {
     check_on_device("[Evaluator::negate_inplace]", context_, encrypted);
     auto cd = get_context_data("[Evaluator::negate_inplace]", encrypted.parms_id());
     const size_t L = cd->parms().coeff_modulus().size();
-    troyn_check(troyn_negate(context_->plan(), 0, static_cast<uint32_t>(L), encrypted.data().raw_pointer(), encrypted.data().raw_pointer(),
-                             encrypted.polynomial_count(), current_stream()));
+    detail::negate_step(on_current_stream(MemoryPool::GlobalPool()), context_->plan(), static_cast<uint32_t>(L), encrypted.data().raw_pointer(), encrypted.data().raw_pointer(),
+                        encrypted.polynomial_count());
 }
 
 
@@ -1163,7 +1166,9 @@ static void balance_correction_factors(uint64_t factor1, uint64_t factor2, uint6
 }
 
 // -- add / sub (evaluator_translate.cu:12-118) ------------------------------------------------------
-void Evaluator::translate(const Ciphertext& e1, const Ciphertext& e2, Ciphertext& destination, bool subtract, MemoryPoolHandle pool) const {
+// every argument check of add / sub and the result object WITHOUT the device work; false (no result object): BGV operands whose correction
+// factors have to be balanced first
+bool Evaluator::translate_prepare(const Ciphertext& e1, const Ciphertext& e2, Ciphertext& out, MemoryPoolHandle pool) const {
     const char* P = "[Evaluator::translate_inplace]";
     check_no_seed(P, e1); check_no_seed(P, e2);
     check_same_parms_id(P, e1, e2);
@@ -1172,8 +1177,20 @@ void Evaluator::translate(const Ciphertext& e1, const Ciphertext& e2, Ciphertext
     check_on_device(P, context_, e1); check_on_device(P, context_, e2);
     auto cd = get_context_data(P, e1.parms_id());
     if (e1.correction_factor() != e2.correction_factor()) {
-        // evaluator_translate.cu:84-98: bring both operands to a common correction factor first
         if (cd->parms().scheme() != SchemeType::BGV) throw std::invalid_argument(std::string(P) + " Correction factors differ outside BGV.");
+        return false;
+    }
+    out = Ciphertext::like(e1, std::max(e1.polynomial_count(), e2.polynomial_count()), false, pool);
+    return true;
+}
+
+void Evaluator::translate(const Ciphertext& e1, const Ciphertext& e2, Ciphertext& destination, bool subtract, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::translate_inplace]";
+    Ciphertext out;
+    const bool balanced = translate_prepare(e1, e2, out, pool);
+    auto cd = get_context_data(P, e1.parms_id());
+    if (!balanced) {
+        // evaluator_translate.cu:84-98: bring both operands to a common correction factor first
         uint64_t f0 = 1, f1 = 1, f2 = 1;
         balance_correction_factors(e1.correction_factor(), e2.correction_factor(), cd->parms().plain_modulus().value(), f0, f1, f2);
         const uint32_t Lb = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
@@ -1189,15 +1206,12 @@ void Evaluator::translate(const Ciphertext& e1, const Ciphertext& e2, Ciphertext
     const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
     const size_t n = cd->parms().poly_modulus_degree();
     const size_t s1 = e1.polynomial_count(), s2 = e2.polynomial_count();
-    const size_t mx = std::max(s1, s2), mn = std::min(s1, s2);
-    Ciphertext out = Ciphertext::like(e1, mx, false, pool);
     const troyn_plan* plan = context_->plan();
-    if (!subtract) troyn_check(troyn_add(plan, 0, L, e1.data().raw_pointer(), e2.data().raw_pointer(), out.data().raw_pointer(), mn, current_stream()));
-    else troyn_check(troyn_sub(plan, 0, L, e1.data().raw_pointer(), e2.data().raw_pointer(), out.data().raw_pointer(), mn, current_stream()));
+    detail::add_sub_step(on_current_stream(pool), plan, L, subtract, e1.data().raw_pointer(), e2.data().raw_pointer(), out.data().raw_pointer(), std::min(s1, s2));
     const size_t pc = static_cast<size_t>(L) * n;
     if (s1 < s2) {
         if (!subtract) hip_check(hipMemcpyAsync(out.poly(s1), e2.poly(s1), (s2 - s1) * pc * 8, hipMemcpyDeviceToDevice, current_stream()), "copy_device_to_device");
-        else troyn_check(troyn_negate(plan, 0, L, e2.poly(s1), out.poly(s1), s2 - s1, current_stream()));
+        else detail::negate_step(on_current_stream(pool), plan, L, e2.poly(s1), out.poly(s1), s2 - s1);
     } else if (s1 > s2) {
         hip_check(hipMemcpyAsync(out.poly(s2), e1.poly(s2), (s1 - s2) * pc * 8, hipMemcpyDeviceToDevice, current_stream()), "copy_device_to_device");
     }
@@ -1260,13 +1274,10 @@ void Evaluator::multiply(const Ciphertext& e1, const Ciphertext& e2, Ciphertext&
         if (detail::combine_submit(rq, pool)) { destination = std::move(out); return; }
     }
     if (scheme == SchemeType::BFV) {
-        const troyn_behz* bz = context_->behz(L);
-        size_t bytes = troyn_bfv_multiply_workspace_bytes(bz, p1, p2, 1);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-        troyn_check(troyn_bfv_multiply(bz, e1.data().raw_pointer(), p1, e2.data().raw_pointer(), p2, out.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+        detail::multiply_bfv_step(on_current_stream(pool), context_->behz(L), e1.data().raw_pointer(), p1, e2.data().raw_pointer(), p2, out.data().raw_pointer(), 1);
     } else {
         detail::LaunchGate gate;
-        troyn_check(troyn_dyadic_convolute(context_->plan(), 0, L, e1.data().raw_pointer(), p1, e2.data().raw_pointer(), p2, out.data().raw_pointer(), 1, current_stream()));
+        detail::multiply_dyadic_step(on_current_stream(pool), context_->plan(), L, e1.data().raw_pointer(), p1, e2.data().raw_pointer(), p2, out.data().raw_pointer(), 1);
     }
     destination = std::move(out);
 }
@@ -1280,7 +1291,7 @@ void Evaluator::square(const Ciphertext& encrypted, Ciphertext& destination, Mem
     check_is_ntt_form("[Evaluator::ckks_square_inplace]", encrypted);
     const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
     Ciphertext out = Ciphertext::like(encrypted, 3, false, pool);
-    troyn_check(troyn_dyadic_square(context_->plan(), 0, L, encrypted.data().raw_pointer(), out.data().raw_pointer(), 1, current_stream()));
+    detail::square_step(on_current_stream(pool), context_->plan(), L, encrypted.data().raw_pointer(), out.data().raw_pointer(), 1);
     if (scheme == SchemeType::CKKS) {
         out.scale() = encrypted.scale() * encrypted.scale();
         if (!is_scale_within_bounds(out.scale(), cd)) throw std::invalid_argument("[Evaluator::ckks_multiply_inplace] Scale out of bounds");   // evaluator.cu:308-311
@@ -1326,28 +1337,34 @@ void Evaluator::switch_key_internal(const Ciphertext& encrypted, const uint64_t*
     if (destination.polynomial_count() > 2 && assign_method != SwitchKeyDestinationAssignMethod::AddInplace)
         hip_check(hipMemsetAsync(destination.poly(2), 0, (destination.polynomial_count() - 2) * L * n * 8, current_stream()), "memset");
     std::vector<const uint64_t*> ptrs = kswitch_keys.get_data_ptrs(kswitch_keys_index);
-    size_t bytes = troyn_switch_key_workspace_bytes(context_->plan(), L, 1);
-    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-    if (scheme == SchemeType::BGV) {
-        // the ski_util5 tail needs the key level's q_special^-1 mod t (evaluator_keyswitching_core.cu:930-932)
-        const size_t K = context_->key_context_data().value()->parms().coeff_modulus().size();
-        troyn_check(troyn_bgv_switch_key(context_->bgv(K), L, target, ptrs.data(), static_cast<int>(assign_method), destination.data().raw_pointer(), ws.raw_pointer(), bytes, 1,
-                                         current_stream()));
-    } else
-    troyn_check(troyn_switch_key(context_->plan(), L, scheme == SchemeType::CKKS, encrypted.is_ntt_form(), target, ptrs.data(),
-                                 static_cast<int>(assign_method), destination.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+    detail::switch_key_step(on_current_stream(pool), context_->plan(), key_level_bgv(scheme), L, scheme == SchemeType::CKKS, encrypted.is_ntt_form(), target, ptrs.data(),
+                            static_cast<int>(assign_method), destination.data().raw_pointer(), 1);
+}
+
+// the BGV handle of the key level for the key-switching steps; null for the other schemes
+const troyn_bgv* Evaluator::key_level_bgv(SchemeType scheme) const {
+    return scheme == SchemeType::BGV ? context_->bgv(context_->key_context_data().value()->parms().coeff_modulus().size()) : nullptr;
+}
+
+// every argument check of apply_keyswitching (evaluator_keyswitching.cu:11-50 and the key-switch checks behind it), the key pointers and the
+// result object WITHOUT the device work
+void Evaluator::apply_keyswitching_prepare(const Ciphertext& encrypted, const KSwitchKeys& kswitch_keys, Ciphertext& out, std::vector<const uint64_t*>& key_ptrs,
+                                           MemoryPoolHandle pool) const {
+    if (kswitch_keys.data().size() != 1) throw std::invalid_argument("[Evaluator::apply_keyswitching_inplace] Key switch keys size must be 1.");
+    if (encrypted.polynomial_count() != 2) throw std::invalid_argument("[Evaluator::apply_keyswitching_inplace] Ciphertext polynomial count must be 2.");
+    get_context_data("[Evaluator::apply_keyswitching_inplace]", encrypted.parms_id());
+    out = Ciphertext::like(encrypted, false, pool);
+    switch_key_checks(encrypted, kswitch_keys, 0, out);
+    key_ptrs = kswitch_keys.get_data_ptrs(0);
 }
 
 void Evaluator::apply_keyswitching(const Ciphertext& encrypted, const KSwitchKeys& kswitch_keys, Ciphertext& destination, MemoryPoolHandle pool) const {
-    // evaluator_keyswitching.cu:11-50
-    if (kswitch_keys.data().size() != 1) throw std::invalid_argument("[Evaluator::apply_keyswitching_inplace] Key switch keys size must be 1.");
-    if (encrypted.polynomial_count() != 2) throw std::invalid_argument("[Evaluator::apply_keyswitching_inplace] Ciphertext polynomial count must be 2.");
-    auto cd = get_context_data("[Evaluator::apply_keyswitching_inplace]", encrypted.parms_id());
-    Ciphertext out = Ciphertext::like(encrypted, false, pool);
-    switch_key_internal(encrypted, encrypted.poly(1), kswitch_keys, 0, SwitchKeyDestinationAssignMethod::Overwrite, out, pool);
-    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
-    // c0' = c0 + ks0
-    troyn_check(troyn_add(context_->plan(), 0, L, out.poly(0), encrypted.poly(0), out.poly(0), 1, current_stream()));
+    Ciphertext out;
+    std::vector<const uint64_t*> ptrs;
+    apply_keyswitching_prepare(encrypted, kswitch_keys, out, ptrs, pool);
+    const SchemeType scheme = get_context_data("[Evaluator::apply_keyswitching_inplace]", encrypted.parms_id())->parms().scheme();
+    detail::apply_keyswitching_step(on_current_stream(pool), context_->plan(), key_level_bgv(scheme), static_cast<uint32_t>(out.coeff_modulus_size()), out.poly_modulus_degree(),
+                                    scheme == SchemeType::CKKS, encrypted.is_ntt_form(), encrypted.data().raw_pointer(), ptrs.data(), out.data().raw_pointer(), 1);
     destination = std::move(out);
 }
 
@@ -1404,15 +1421,12 @@ void Evaluator::relinearize_internal(const Ciphertext& encrypted, const RelinKey
             rq.out = out.data().raw_pointer(); rq.out_words = out.data().size();
             if (detail::combine_submit(rq, pool)) { destination = std::move(out); return; }
         }
-        size_t bytes = troyn_relinearize_workspace_bytes(context_->plan(), L, 1);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
         if (scheme == SchemeType::BGV) {
-            const size_t K = context_->key_context_data().value()->parms().coeff_modulus().size();
-            troyn_check(troyn_bgv_relinearize(context_->bgv(K), L, encrypted.data().raw_pointer(), ptrs.data(), out.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+            detail::relinearize_step(on_current_stream(pool), context_->plan(), key_level_bgv(scheme), L, false, true, encrypted.data().raw_pointer(), ptrs.data(),
+                                     out.data().raw_pointer(), 1);
         } else {
-        detail::LaunchGate gate;
-        troyn_check(troyn_relinearize(context_->plan(), L, scheme == SchemeType::CKKS, encrypted.is_ntt_form(), encrypted.data().raw_pointer(), ptrs.data(),
-                                      out.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+            detail::relinearize_step(on_current_stream(pool, true), context_->plan(), nullptr, L, scheme == SchemeType::CKKS, encrypted.is_ntt_form(), encrypted.data().raw_pointer(),
+                                     ptrs.data(), out.data().raw_pointer(), 1);
         }
         destination = std::move(out);
         return;
@@ -1424,7 +1438,7 @@ void Evaluator::relinearize_internal(const Ciphertext& encrypted, const RelinKey
                             i == 0 ? SwitchKeyDestinationAssignMethod::Overwrite : SwitchKeyDestinationAssignMethod::AddInplace, out, pool);
         encrypted_size -= 1;
     }
-    troyn_check(troyn_add(context_->plan(), 0, L, out.data().raw_pointer(), encrypted.data().raw_pointer(), out.data().raw_pointer(), destination_size, current_stream()));
+    detail::add_sub_step(on_current_stream(pool), context_->plan(), L, false, out.data().raw_pointer(), encrypted.data().raw_pointer(), out.data().raw_pointer(), destination_size);
     destination = std::move(out);
 }
 
@@ -1458,7 +1472,12 @@ SchemeType Evaluator::mod_switch_scale_prepare(const Ciphertext& encrypted, Ciph
 void Evaluator::mod_switch_scale_to_next_internal(const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const {
     // evaluator_modswitch.cu:14-74
     Ciphertext out;
-    const SchemeType scheme = mod_switch_scale_prepare(encrypted, out, pool);
+    mod_switch_scale_run(mod_switch_scale_prepare(encrypted, out, pool), encrypted, out, pool);
+    destination = std::move(out);
+}
+
+// the division into the prepared `out` (one object: through the rendezvous when call combining wants it)
+void Evaluator::mod_switch_scale_run(SchemeType scheme, const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const {
     const uint32_t L = static_cast<uint32_t>(encrypted.coeff_modulus_size());
     const size_t pc = encrypted.polynomial_count();
     if (scheme == SchemeType::CKKS && detail::combining_wanted()) {
@@ -1466,30 +1485,23 @@ void Evaluator::mod_switch_scale_to_next_internal(const Ciphertext& encrypted, C
         rq.kind = detail::CombineKind::Rescale; rq.handle = context_->plan(); rq.L = L; rq.p1 = static_cast<uint32_t>(pc); rq.ckks = true; rq.ntt_form = true;
         rq.in1 = encrypted.data().raw_pointer(); rq.words1 = encrypted.data().size();
         rq.out = out.data().raw_pointer(); rq.out_words = out.data().size();
-        if (detail::combine_submit(rq, pool)) { destination = std::move(out); return; }
+        if (detail::combine_submit(rq, pool)) return;
     }
     if (scheme == SchemeType::BFV) {
-        troyn_check(troyn_divide_and_round_q_last(context_->plan(), L, encrypted.data().raw_pointer(), pc, out.data().raw_pointer(), 1, current_stream()));
+        detail::divide_round_q_last_step(on_current_stream(pool), context_->plan(), L, encrypted.data().raw_pointer(), pc, out.data().raw_pointer(), 1);
     } else if (scheme == SchemeType::BGV) {
-        // RNSTool::mod_t_and_divide_q_last_ntt; the plaintext is multiplied by q_last^-1 mod t (evaluator_modswitch.cu:62-72)
+        // the plaintext is multiplied by q_last^-1 mod t (evaluator_modswitch.cu:62-72)
         const troyn_bgv* bg = context_->bgv(L);
-        const size_t bytes = troyn_bgv_mod_switch_workspace_bytes(bg, pc, 1);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-        troyn_check(troyn_bgv_mod_t_and_divide_q_last_ntt(bg, encrypted.data().raw_pointer(), pc, out.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+        detail::bgv_mod_t_divide_step(on_current_stream(pool), bg, encrypted.data().raw_pointer(), pc, out.data().raw_pointer(), 1);
         const uint64_t t = context_->get_context_data(out.parms_id()).value()->parms().plain_modulus().value();
         out.correction_factor() = static_cast<uint64_t>((static_cast<unsigned __int128>(encrypted.correction_factor()) * troyn_bgv_inv_q_last_mod_t(bg)) % t);
     } else {
-        size_t bytes = troyn_divide_and_round_q_last_ntt_workspace_bytes(context_->plan(), L, pc, 1);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-        detail::LaunchGate gate;
-        troyn_check(troyn_divide_and_round_q_last_ntt(context_->plan(), L, encrypted.data().raw_pointer(), pc, out.data().raw_pointer(),
-                                                      ws.raw_pointer(), bytes, 1, current_stream()));
+        detail::rescale_step(on_current_stream(pool, true), context_->plan(), L, encrypted.data().raw_pointer(), pc, out.data().raw_pointer(), 1);
     }
-    destination = std::move(out);
 }
 
-void Evaluator::mod_switch_drop_to_internal(const Ciphertext& encrypted, Ciphertext& destination, const ParmsID& target, MemoryPoolHandle pool) const {
-    // evaluator_modswitch.cu:173-220
+// the argument checks of mod_switch_drop_to_internal (evaluator_modswitch.cu:173-220) and the result object at `target` WITHOUT the device work
+void Evaluator::mod_switch_drop_prepare(const Ciphertext& encrypted, Ciphertext& out, const ParmsID& target, MemoryPoolHandle pool) const {
     const char* P = "[Evaluator::mod_switch_drop_to_internal]";
     auto cd = get_context_data(P, encrypted.parms_id());
     if (cd->parms().scheme() == SchemeType::CKKS) check_is_ntt_form(P, encrypted);
@@ -1497,29 +1509,46 @@ void Evaluator::mod_switch_drop_to_internal(const Ciphertext& encrypted, Ciphert
     auto tcd = get_context_data("[Evaluator::mod_switch_drop_to_next_internal]", target);
     if (!is_scale_within_bounds(encrypted.scale(), tcd)) throw std::invalid_argument("[Evaluator::mod_switch_drop_to_internal] Scale out of bounds.");   // evaluator_modswitch.cu:186-188
     check_on_device(P, context_, encrypted);
-    const uint32_t L_in = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
-    const uint32_t L_out = static_cast<uint32_t>(tcd->parms().coeff_modulus().size());
-    const size_t pc = encrypted.polynomial_count();
-    Ciphertext out = Ciphertext::like(encrypted, pc, L_out, false, pool);
+    out = Ciphertext::like(encrypted, encrypted.polynomial_count(), tcd->parms().coeff_modulus().size(), false, pool);
     out.parms_id() = target;
-    troyn_check(troyn_mod_switch_drop(context_->plan(), L_in, L_out, encrypted.data().raw_pointer(), pc, out.data().raw_pointer(), 1, current_stream()));
+}
+
+void Evaluator::mod_switch_drop_run(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const {
+    detail::mod_switch_drop_step(on_current_stream(pool), context_->plan(), static_cast<uint32_t>(encrypted.coeff_modulus_size()), static_cast<uint32_t>(out.coeff_modulus_size()),
+                                 encrypted.data().raw_pointer(), encrypted.polynomial_count(), out.data().raw_pointer(), 1);
+}
+
+void Evaluator::mod_switch_drop_to_internal(const Ciphertext& encrypted, Ciphertext& destination, const ParmsID& target, MemoryPoolHandle pool) const {
+    Ciphertext out;
+    mod_switch_drop_prepare(encrypted, out, target, pool);
+    mod_switch_drop_run(encrypted, out, pool);
     destination = std::move(out);
 }
 
-void Evaluator::mod_switch_to_next(const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const {
-    // evaluator_modswitch.cu:275-300
+// the argument checks of mod_switch_to_next (evaluator_modswitch.cu:275-300) and of the branch it takes, and the result object WITHOUT the
+// device work; the scheme tells the branch: BFV / BGV scale down (mod_switch_scale_prepare), CKKS drops the last prime (mod_switch_drop_prepare)
+SchemeType Evaluator::mod_switch_to_next_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const {
     check_no_seed("[Evaluator::mod_switch_to_next]", encrypted);
     if (context_->last_parms_id() == encrypted.parms_id()) throw std::invalid_argument("[Evaluator::mod_switch_to_next] End of modulus switching chain reached.");
-    SchemeType scheme = context_->first_context_data().value()->parms().scheme();
+    const SchemeType scheme = context_->first_context_data().value()->parms().scheme();
     switch (scheme) {
-        case SchemeType::BFV: case SchemeType::BGV: mod_switch_scale_to_next_internal(encrypted, destination, pool); break;
+        case SchemeType::BFV: case SchemeType::BGV: mod_switch_scale_prepare(encrypted, out, pool); break;
         case SchemeType::CKKS: {
             auto cd = get_context_data("[Evaluator::mod_switch_to_next]", encrypted.parms_id());
-            mod_switch_drop_to_internal(encrypted, destination, cd->next_context_data().value()->parms_id(), pool);
+            mod_switch_drop_prepare(encrypted, out, cd->next_context_data().value()->parms_id(), pool);
             break;
         }
         default: throw std::logic_error("[Evaluator::mod_switch_to_next] Scheme not implemented.");
     }
+    return scheme;
+}
+
+void Evaluator::mod_switch_to_next(const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const {
+    Ciphertext out;
+    const SchemeType scheme = mod_switch_to_next_prepare(encrypted, out, pool);
+    if (scheme == SchemeType::CKKS) mod_switch_drop_run(encrypted, out, pool);
+    else mod_switch_scale_run(scheme, encrypted, out, pool);
+    destination = std::move(out);
 }
 
 
@@ -1605,13 +1634,8 @@ void Evaluator::multiply_relinearize_rescale(const Ciphertext& e1, const Ciphert
         rq.out = out.data().raw_pointer(); rq.out_words = out.data().size();
         if (detail::combine_submit(rq, pool)) { destination = std::move(out); return; }
     }
-    const size_t bytes = troyn_ckks_multiply_relinearize_rescale_workspace_bytes(context_->plan(), L, 1);
-    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-    {
-        detail::LaunchGate gate;
-        troyn_check(troyn_ckks_multiply_relinearize_rescale(context_->plan(), L, e1.data().raw_pointer(), e2.data().raw_pointer(), keys.data(), out.data().raw_pointer(),
-                                                            ws.raw_pointer(), bytes, 1, current_stream()));
-    }
+    detail::multiply_relinearize_rescale_step(on_current_stream(pool, true), context_->plan(), L, e1.data().raw_pointer(), e2.data().raw_pointer(), keys.data(),
+                                              out.data().raw_pointer(), 1);
     destination = std::move(out);
 }
 
@@ -1755,53 +1779,40 @@ void Evaluator::bfv_multiply_accumulate_relinearize(const std::vector<const Ciph
 
 
 // -- NTT (evaluator_transform_ntt.cu:469-652) ----------------------------------------------------------------
-void Evaluator::transform_to_ntt_inplace(Ciphertext& encrypted) const {
-    check_no_seed("[Evaluator::transform_to_ntt_inplace]", encrypted);
-    check_is_not_ntt_form("[Evaluator::transform_to_ntt_inplace]", encrypted);
-    check_on_device("[Evaluator::transform_to_ntt_inplace]", context_, encrypted);
-    auto cd = get_context_data("[Evaluator::transform_to_ntt_inplace]", encrypted.parms_id());
-    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
-    troyn_check(troyn_ntt(context_->plan(), 0, encrypted.data().raw_pointer(), encrypted.data().raw_pointer(), 1, encrypted.polynomial_count(), L,
-                          0, L, TROYN_IDX_COMPONENTWISE, 0, current_stream()));
-    encrypted.is_ntt_form() = true;
+// the argument checks of the four transforms under the caller's prompt; the level's limb count
+uint32_t Evaluator::transform_checks(const char* P, bool inverse, const Ciphertext& encrypted) const {
+    check_no_seed(P, encrypted);
+    if (inverse) check_is_ntt_form(P, encrypted); else check_is_not_ntt_form(P, encrypted);
+    check_on_device(P, context_, encrypted);
+    return static_cast<uint32_t>(get_context_data(P, encrypted.parms_id())->parms().coeff_modulus().size());
 }
 
-void Evaluator::transform_to_ntt(const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const {
-    check_no_seed("[Evaluator::transform_to_ntt]", encrypted);
-    check_is_not_ntt_form("[Evaluator::transform_to_ntt]", encrypted);
-    check_on_device("[Evaluator::transform_to_ntt]", context_, encrypted);
-    auto cd = get_context_data("[Evaluator::transform_to_ntt]", encrypted.parms_id());
-    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
-    Ciphertext out = Ciphertext::like(encrypted, false, pool);
-    troyn_check(troyn_ntt(context_->plan(), 0, encrypted.data().raw_pointer(), out.data().raw_pointer(), 1, encrypted.polynomial_count(), L,
-                          0, L, TROYN_IDX_COMPONENTWISE, 0, current_stream()));
-    out.is_ntt_form() = true;
+// the checks of transform_to_ntt / transform_from_ntt and the result object WITHOUT the device work
+void Evaluator::transform_prepare(bool inverse, const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const {
+    transform_checks(inverse ? "[Evaluator::transform_from_ntt]" : "[Evaluator::transform_to_ntt]", inverse, encrypted);
+    out = Ciphertext::like(encrypted, false, pool);
+    out.is_ntt_form() = !inverse;
+}
+
+void Evaluator::transform(bool inverse, const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const {
+    Ciphertext out;
+    transform_prepare(inverse, encrypted, out, pool);
+    detail::ntt_step(on_current_stream(pool), context_->plan(), inverse, encrypted.data().raw_pointer(), out.data().raw_pointer(), 1, encrypted.polynomial_count(),
+                     static_cast<uint32_t>(out.coeff_modulus_size()));
     destination = std::move(out);
 }
 
-void Evaluator::transform_from_ntt_inplace(Ciphertext& encrypted) const {
-    check_no_seed("[Evaluator::transform_from_ntt_inplace]", encrypted);
-    check_is_ntt_form("[Evaluator::transform_from_ntt_inplace]", encrypted);
-    check_on_device("[Evaluator::transform_from_ntt_inplace]", context_, encrypted);
-    auto cd = get_context_data("[Evaluator::transform_from_ntt_inplace]", encrypted.parms_id());
-    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
-    troyn_check(troyn_ntt(context_->plan(), 1, encrypted.data().raw_pointer(), encrypted.data().raw_pointer(), 1, encrypted.polynomial_count(), L,
-                          0, L, TROYN_IDX_COMPONENTWISE, 0, current_stream()));
-    encrypted.is_ntt_form() = false;
+void Evaluator::transform_inplace(const char* P, bool inverse, Ciphertext& encrypted) const {
+    const uint32_t L = transform_checks(P, inverse, encrypted);
+    detail::ntt_step(on_current_stream(MemoryPool::GlobalPool()), context_->plan(), inverse, encrypted.data().raw_pointer(), encrypted.data().raw_pointer(), 1,
+                     encrypted.polynomial_count(), L);
+    encrypted.is_ntt_form() = !inverse;
 }
 
-void Evaluator::transform_from_ntt(const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const {
-    check_no_seed("[Evaluator::transform_from_ntt]", encrypted);
-    check_is_ntt_form("[Evaluator::transform_from_ntt]", encrypted);
-    check_on_device("[Evaluator::transform_from_ntt]", context_, encrypted);
-    auto cd = get_context_data("[Evaluator::transform_from_ntt]", encrypted.parms_id());
-    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
-    Ciphertext out = Ciphertext::like(encrypted, false, pool);
-    troyn_check(troyn_ntt(context_->plan(), 1, encrypted.data().raw_pointer(), out.data().raw_pointer(), 1, encrypted.polynomial_count(), L,
-                          0, L, TROYN_IDX_COMPONENTWISE, 0, current_stream()));
-    out.is_ntt_form() = false;
-    destination = std::move(out);
-}
+void Evaluator::transform_to_ntt_inplace(Ciphertext& encrypted) const { transform_inplace("[Evaluator::transform_to_ntt_inplace]", false, encrypted); }
+void Evaluator::transform_from_ntt_inplace(Ciphertext& encrypted) const { transform_inplace("[Evaluator::transform_from_ntt_inplace]", true, encrypted); }
+void Evaluator::transform_to_ntt(const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const { transform(false, encrypted, destination, pool); }
+void Evaluator::transform_from_ntt(const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const { transform(true, encrypted, destination, pool); }
 
 
 // ------------------------------------------------------------------------------------------------
@@ -2070,13 +2081,9 @@ void Evaluator::apply_galois(const Ciphertext& encrypted, size_t galois_element,
         rq.out = out.data().raw_pointer(); rq.out_words = out.data().size();
         if (detail::combine_submit(rq, pool)) { destination = std::move(out); return; }
     }
-    troyn_check(troyn_apply_galois(context_->plan(), 0, L, encrypted.is_ntt_form() ? 1 : 0, galois_element,
-                                   encrypted.data().raw_pointer(), out.data().raw_pointer(), 2, current_stream()));
-    // the permuted c1 is the key-switch target; the result overwrites it (c0 += ks0, c1 = ks1)
-    utils::DynamicArray target(static_cast<size_t>(L) * n, true, pool);
-    hip_check(hipMemcpyAsync(target.raw_pointer(), out.poly(1), static_cast<size_t>(L) * n * 8, hipMemcpyDeviceToDevice, current_stream()), "copy_device_to_device");
-    switch_key_internal(encrypted, target.raw_pointer(), galois_keys, GaloisKeys::get_index(galois_element),
-                        SwitchKeyDestinationAssignMethod::OverwriteExceptFirst, out, pool);
+    const SchemeType scheme = cd->parms().scheme();
+    detail::apply_galois_step(on_current_stream(pool), context_->plan(), key_level_bgv(scheme), L, n, scheme == SchemeType::CKKS, encrypted.is_ntt_form(), galois_element,
+                              encrypted.data().raw_pointer(), ptrs.data(), out.data().raw_pointer(), 1);
     // (no stream wait: the temporaries return to the pool in stream order, the call is asynchronous like the reference's)
     destination = std::move(out);
 }
@@ -3038,22 +3045,17 @@ void Encryptor::encrypt_zero_internal(const ParmsID& parms_id, bool is_ntt_form,
     out.data() = utils::DynamicArray(0, true, pool);
     out.resize(context_, parms_id, pc, true, false);
     hipStream_t s = current_stream();
+    const detail::StepEnv env{pool, s, troyn_check_public};
     if (cd->parms().scheme() == SchemeType::BGV) {
         // encryptor.cu:65-84
         if (!is_ntt_form) throw std::invalid_argument(std::string(P) + " BGV - Plaintext is not in NTT form.");
-        const troyn_bgv* bg = context_->bgv(Lp);
-        const size_t wsb = troyn_bgv_mod_switch_workspace_bytes(bg, pc, 1);
-        utils::DynamicArray ws((wsb + 7) / 8, true, pool);
-        troyn_check(troyn_bgv_mod_t_and_divide_q_last_ntt(bg, temp.data().raw_pointer(), pc, out.data().raw_pointer(), ws.raw_pointer(), wsb, 1, s));
+        detail::bgv_mod_t_divide_step(env, context_->bgv(Lp), temp.data().raw_pointer(), pc, out.data().raw_pointer(), 1);
         hip_check(hipStreamSynchronize(s), "stream_sync");
     } else if (is_ntt_form) {
-        const size_t wsb = troyn_divide_and_round_q_last_ntt_workspace_bytes(context_->plan(), Lp, pc, 1);
-        utils::DynamicArray ws((wsb + 7) / 8, true, pool);
-        troyn_check(troyn_divide_and_round_q_last_ntt(context_->plan(), Lp, temp.data().raw_pointer(), pc, out.data().raw_pointer(),
-                                                      ws.raw_pointer(), wsb, 1, s));
+        detail::rescale_step(env, context_->plan(), Lp, temp.data().raw_pointer(), pc, out.data().raw_pointer(), 1);
         hip_check(hipStreamSynchronize(s), "stream_sync");
     } else {
-        troyn_check(troyn_divide_and_round_q_last(context_->plan(), Lp, temp.data().raw_pointer(), pc, out.data().raw_pointer(), 1, s));
+        detail::divide_round_q_last_step(env, context_->plan(), Lp, temp.data().raw_pointer(), pc, out.data().raw_pointer(), 1);
     }
     (void)n;
     out.is_ntt_form() = is_ntt_form;

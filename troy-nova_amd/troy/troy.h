@@ -1727,12 +1727,30 @@ private:
     void translate_batched(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const std::vector<Ciphertext*>& d, bool subtract,
                            MemoryPoolHandle pool) const;
     void switch_key_checks(const Ciphertext& encrypted, const KSwitchKeys& kswitch_keys, size_t kswitch_keys_index, const Ciphertext& destination) const;
-    // argument checks + result object (allocated, metadata set) of the three methods, without the device work (troy.cpp)
+    // argument checks + result object (allocated, metadata set) of a method, without the device work: the method is its prepare + the device step
+    // (device_steps.h) with count 1, the *_batched form the prepare of item 0 + the step with the batch's count
     SchemeType multiply_prepare(const Ciphertext& e1, const Ciphertext& e2, Ciphertext& out, MemoryPoolHandle pool) const;
     void relinearize_prepare(const Ciphertext& encrypted, const RelinKeys& relin_keys, Ciphertext& out, std::vector<const uint64_t*>& key_ptrs, MemoryPoolHandle pool) const;
     SchemeType mod_switch_scale_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
+    void mod_switch_drop_prepare(const Ciphertext& encrypted, Ciphertext& out, const ParmsID& target, MemoryPoolHandle pool) const;
+    SchemeType mod_switch_to_next_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
     void apply_galois_prepare(const Ciphertext& encrypted, size_t galois_element, const GaloisKeys& galois_keys, Ciphertext& out, std::vector<const uint64_t*>& key_ptrs,
                               MemoryPoolHandle pool) const;
+    void apply_keyswitching_prepare(const Ciphertext& encrypted, const KSwitchKeys& kswitch_keys, Ciphertext& out, std::vector<const uint64_t*>& key_ptrs,
+                                    MemoryPoolHandle pool) const;
+    void negate_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
+    bool translate_prepare(const Ciphertext& e1, const Ciphertext& e2, Ciphertext& out, MemoryPoolHandle pool) const;
+    void transform_prepare(bool inverse, const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
+    void negacyclic_shift_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
+    uint32_t transform_checks(const char* P, bool inverse, const Ciphertext& encrypted) const;
+    void transform(bool inverse, const Ciphertext& encrypted, Ciphertext& destination, MemoryPoolHandle pool) const;
+    void transform_inplace(const char* P, bool inverse, Ciphertext& encrypted) const;
+    void transform_batched(bool inverse, const std::vector<const Ciphertext*>& encrypted, const std::vector<Ciphertext*>& destination, MemoryPoolHandle pool) const;
+    void conjugate_batched(const std::vector<const Ciphertext*>& e, const GaloisKeys& k, const std::vector<Ciphertext*>& d, MemoryPoolHandle pool) const;
+    // the device work of the two mod-switch branches into a prepared result
+    void mod_switch_scale_run(SchemeType scheme, const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
+    void mod_switch_drop_run(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
+    const troyn_bgv* key_level_bgv(SchemeType scheme) const;
     // the hoisted rotations (addition): out = one ciphertext per element, or their sum in out[0]; element 1 (allow_identity: a step of 0) is the ciphertext itself
     void apply_galois_hoisted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, bool allow_identity, const GaloisKeys& galois_keys,
                               bool sum, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const;
