@@ -398,6 +398,7 @@ struct ArithU64 {
     static __device__ __forceinline__ u64 store_mid(elem x, const Mod&) { return x; }
     static __device__ __forceinline__ elem from_lds(u64 raw) { return raw; }
     static __device__ __forceinline__ u64 to_lds(elem x, const Mod&) { return x; }
+    static __device__ __forceinline__ u64 to_lds_raw(elem x, const Mod&) { return x; }
     static __device__ __forceinline__ elem mid_fix(elem x, const Mod&) { return x; }
     static __device__ __forceinline__ elem mid_sum(elem x, elem y, const Mod& m) { return csub4(x + y, m); }   // two words between inverse passes, [0, 4q) each
     static __device__ __forceinline__ void fwd(elem& a, elem& b, const tw_t w, const Mod& m) {
@@ -415,7 +416,10 @@ struct ArithU64 {
         return shoup_lazy(final_fwd(v, m), m.ninv_op, m.ninv_quo, m.q);   // the reference's lazy N^-1 multiply
     }
     static __device__ __forceinline__ void inv_fold(elem&, elem&, const Mod&) {}   // FOLD_NINV is false: never used
-    static __device__ __forceinline__ elem held_t(elem x, bool, const Mod&) { return x; }   // held T rows are an FP64 form (REGIO 3): never used
+    static __device__ __forceinline__ elem held_c(elem x, bool, const Mod&) { return x; }   // held rows are an FP64 form (REGIO 3 / 4): never used
+    static __device__ __forceinline__ elem held_last(const NttIo&, elem x, bool, elem, const Mod&) { return x; }
+    static __device__ __forceinline__ elem held_tail_in(const NttIo&, elem x, elem, const Mod&) { return x; }
+    static __device__ __forceinline__ u64 digit_word(elem x, bool, double, unsigned, const Mod&) { return x; }   // LEAN is an FP64 form: never used
     // register hand-over between a forward and an inverse transform (tensor_core_kernel): canonical residues
     static __device__ __forceinline__ elem keep(elem x, const Mod& m) { return final_fwd(x, m); }
     static __device__ __forceinline__ elem prod(elem x, elem y, const Mod& m) {
@@ -542,11 +546,41 @@ struct ArithF64 {
         const double t = x_canon + 0.5 * (m.m.p - 1.0);
         return t >= m.m.p ? t - m.m.p : t;
     }
-    // T of the last inverse round's word for a row that stays in registers (ntt_pass_body REGIO 3): final_inv (scaled: the folded layer applied
-    // N^-1 already) and round_half without the u64 round trip -- the canonical value in [0, p) is an exact double either way
-    static __device__ __forceinline__ double held_t(elem x, bool scaled, const Mod& m) {
-        const double c = f64_corr(scaled ? x : f64_mulc(x, m.ninv, m.ninv_p, m.m.p), m.m);
-        return round_half(c < 0.0 ? c + m.m.p : c, m);
+    // Rows that stay in registers (mrr_tail_kernel, ntt_pass_body REGIO 3 / 4) are handed over as the CENTRED representative c(x) of a
+    // coefficient x of the dropped prime `aux` (odd): the one integer in [-(aux-1)/2, (aux-1)/2] congruent to x.  With half = (aux-1)/2,
+    // T = (x + half) mod aux lies in [0, aux) and T - half is that integer, so
+    //     r_j(x) = T - (half mod q_j) = c(x)  (mod q_j)   for every limb modulus q_j:
+    // the rounding fix of a consumer limb is c(x) itself, with the half-rounding offset carried exactly and no per-limb constant or reduction.
+    // Magnitudes (every modulus of an all-FP64 chain is below 2^50): |c| <= (aux-1)/2 < 2^49, so f64_mulq(c, w) is exact with |result| <=
+    // (0.5 + 1.5 * 2^49 * 2^-52) p = 0.6875 p for ANY limb modulus p, whatever aux / p is (dev_math_f64.hpp: the bound needs |y| < 2^53 only).
+    // f64_corr leaves |c| <= aux/2 + 1, i.e. at most one step of aux away from the centred range: one conditional step puts it there.
+    static __device__ __forceinline__ double centred(double x, const Mod& m) {
+        const double c = f64_corr(x, m.m);
+        const double step = __builtin_fabs(c) > 0.5 * (m.m.p - 1.0) ? __builtin_copysign(m.m.p, c) : 0.0;
+        return c - step;
+    }
+    // c(s) of the last inverse round's word (scaled: the folded final layer applied N^-1 already); |x| <= 2 p there (two layers from 0.5 p + 1)
+    static __device__ __forceinline__ double held_c(elem x, bool scaled, const Mod& m) {
+        return centred(scaled ? x : f64_mulc(x, m.ninv, m.ninv_p, m.m.p), m);
+    }
+    // c(l), l = INTT(Q) - r(s) qk^-1 under the dropped limb's modulus m = ql, from the held c(s): |ys| <= 1.25 p, |c(s) qk^-1| <= 0.6875 p
+    static __device__ __forceinline__ double held_last(const NttIo& io, elem xr, bool scaled, double cs, const Mod& m) {
+        const elem ys = scaled ? xr : f64_mulc(xr, m.ninv, m.ninv_p, m.m.p);
+        return centred(ys - scale_by(cs, io.inv_d, m), m);
+    }
+    // r_j(s) qk^-1 + f_j(l) from the held c(s), c(l): |x| <= 0.6875 p + 2^49.  A 4-layer forward block grows by |x'| <= |x| + (0.5 + 1.5 |x| 2^-52) p;
+    // the start and every step increase with p, and at p = 2^50 the block goes 1.1875 -> 2.133 -> 3.433 -> 5.220 -> 7.678 (x 2^50) < 8 x 2^50 = 2^53
+    // (tools/fp64_lean_check.cpp replays it for the ends of the modulus range with the +1 terms).
+    static __device__ __forceinline__ elem held_tail_in(const NttIo& io, double cs, double cl, const Mod& m) {
+        return scale_by(cs, io.inv_d, m) + cl;
+    }
+    // a digit of the key switch from the last inverse round's word: its canonical value c in [0, p) as a double, stored either as that double
+    // (NTT_FLAG_STORE_F64, what ksmac2 reads: add = 0, mask_hi = all ones; c >= +0, so c + 0 keeps its bits) or as the word f64_to_u64(c)
+    // (add = 2^52, mask_hi = 0x000fffff) -- no u64 round trip in front of the double, and one instruction sequence for both
+    static __device__ __forceinline__ u64 digit_word(elem x, bool scaled, double add, unsigned mask_hi, const Mod& m) {
+        double c = f64_corr(scaled ? x : f64_mulc(x, m.ninv, m.ninv_p, m.m.p), m.m);
+        c = c < 0.0 ? c + m.m.p : c;
+        return f64_double_to_bits(c + add) & (((u64)mask_hi << 32) | 0xffffffffull);
     }
     static __device__ __forceinline__ elem round_fix_t(u64 t_bits, double hm, const Mod& m) { return f64_corr(f64_bits_to_double(t_bits) - hm, m.m); }
     // the same for a T row that may hold u64 words of a prime of 2^50 or more (NTT_FUSED_*_W): T < 2^61 = hi 2^30 + lo, hi 2^30 is exact in a
@@ -584,6 +618,12 @@ struct ArithF64 {
     static __device__ __forceinline__ u64 store_mid(elem x, const Mod&) { return f64_double_to_bits(x); }
     static __device__ __forceinline__ elem from_lds(u64 raw) { return f64_bits_to_double(raw); }
     static __device__ __forceinline__ u64 to_lds(elem x, const Mod& m) { return f64_double_to_bits(f64_corr(x, m.m)); }
+    // a word that passes through the tile as it is, where the consumer's own bound has room for it (|x| < 2^53 either way):
+    //   a1 (.) b1 in front of the first inverse round: |x| <= 0.875 p instead of 0.5 p + 1; the block (sums re-centred after 2 layers) then
+    //     reaches 2 * 2 * (0.5 + 0.375 * 2 * 0.875 * 2) p = 7.25 p at p = 2^50 and less below (tools/fp64_lean_check.cpp);
+    //   the last forward round's outputs in front of TAIL_RESCALE's epilogue: at most 4 layers from 0.5 p + 1, |y| <= 5.3 p, and tail_out
+    //     re-centres Q - y (|.| <= 6.3 p) in one step instead of y and Q - y in two.
+    static __device__ __forceinline__ u64 to_lds_raw(elem x, const Mod&) { return f64_double_to_bits(x); }
     static __device__ __forceinline__ elem mid_fix(elem x, const Mod& m) { return f64_corr(x, m.m); }
     static __device__ __forceinline__ elem mid_sum(elem x, elem y, const Mod& m) { return f64_corr(x, m.m) + y; }   // y re-centred (load_mid): |sum| <= p + 1
     // f64_mulq: the quotient comes from the rounded product itself, so no w/p has to be formed per twiddle (w.y is never read and
@@ -638,10 +678,11 @@ __host__ __device__ constexpr bool ROUNDS_OK(int G, int EB) { return (G + EB - 1
 // REGIO (tensor_core_kernel): 1 = a forward last pass leaves its E consecutive outputs per thread in xio (A::keep form) instead of
 // storing them, 2 = an inverse first pass takes its E consecutive inputs per thread from xio (A::inv_in form) instead of loading them.
 // REGIO 5 (tensor_accumulate_kernel): as 2, and under NTT_FLAG_MID_CARRY the pass adds its result to what its destination holds.
-// REGIO 3 / 4 (mrr_tail_kernel, troyn_mrr_tail.hip; FP64 policy, whole-limb tiles): the rows T_s = (s + qk/2) mod qk and T_l = (l + ql/2) mod ql
-// of the fused chain stay in xio[0, E) / xio[E, 2E) instead of passing through memory -- the last inverse round and the first forward round
-// keep the same E words {t + R 2^(TB-EB)} per thread.  3 = an inverse transform ends in xio (IOM 0: T_s; NTT_FUSED_LAST_LIMB: reads T_s, leaves
-// T_l), 4 = NTT_FUSED_TAIL_RESCALE takes its input from both.  The values are the doubles the separate launches store and load.
+// REGIO 3 / 4 (mrr_tail_kernel, troyn_mrr_tail.hip; FP64 policy, whole-limb tiles): the INTT s of the special row and l of the dropped limb
+// stay in xio[0, E) / xio[E, 2E) instead of passing through memory as the rows T_s, T_l -- the last inverse round and the first forward round
+// keep the same E words {t + R 2^(TB-EB)} per thread.  3 = an inverse transform ends in xio (IOM 0: c(s); NTT_FUSED_LAST_LIMB: reads c(s), leaves
+// c(l)), 4 = NTT_FUSED_TAIL_RESCALE takes its input from both.  The values are centred representatives (ArithF64::centred), congruent to the
+// rows the separate launches store and load minus aux/2; NTT_FLAG_STORE_ROUND_HALF and the constants hm_d / hm2_d play no part here.
 // HALF: the LDS tile holds 32-bit words (half the bytes): every exchange moves the low halves, then the high halves of its E words
 // (three barriers instead of one).  A whole-limb N = 16384 tile then takes 66 KB instead of 132 KB and TWO 1024-thread workgroups
 // share a CU, so one can load / store while the other computes -- what N = 8192 gets for free.
@@ -652,7 +693,7 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
     static_assert(REGIO == 0 || REGIO == 3 || REGIO == 4 || (!KSMAC && IOM == 0 && C == 0 && (G + EB - 1) / EB > 1 && (REGIO == 1 ? (!INV && LAST) : (INV && FIRST && (REGIO == 2 || !LAST)))), "register hand-over: last forward / first inverse pass on whole tiles");
     static_assert(REGIO < 3 || REGIO == 5 || (std::is_same<A, ArithF64>::value && !KSMAC && !HALF && C == 0 && LO == 0 && G == TB && TB == LOGN && (G + EB - 1) / EB > 1 &&
                                 (REGIO == 3 ? (INV && (IOM == 0 || IOM == NTT_FUSED_LAST_LIMB)) : (REGIO == 4 && !INV && IOM == NTT_FUSED_TAIL_RESCALE))),
-                  "held T rows: whole-limb FP64 transforms of the merged chain tail");
+                  "held rows: whole-limb FP64 transforms of the merged chain tail");
     constexpr int E = 1 << EB;
     constexpr unsigned N = 1u << LOGN;
     constexpr int TILE_BITS = LOGN - TB;               // tiles per limb-polynomial = 2^TILE_BITS
@@ -727,6 +768,11 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
     constexpr bool TW = IOM == NTT_FUSED_LAST_LIMB_W || IOM == NTT_FUSED_TAIL_RESCALE_W;     // FP64 policy: the T rows may hold u64 words
     constexpr bool F_LAST_LD = F_LAST && FIRST, F_LAST_ST = F_LAST && LAST;
     constexpr bool F_TR_LD = F_TR && FIRST, F_TR_ST = F_TR && LAST;
+    // the all-FP64 chain's whole-limb kernels (MULPAIR, TAIL_RESCALE on full-word tiles: the batches that fill the chip) hand their words to the
+    // tile without a re-centring where the consumer's bound has room (ArithF64::to_lds_raw) and store digits without the u64 round trip; the
+    // half-word tiles and the two-pass forms run at their register limits and keep the longer sequences
+    // (N = 16384 only: the other sizes' kernels are left as they are)
+    constexpr bool LEAN = std::is_same<A, ArithF64>::value && LOGN == 14 && !HALF && FIRST && LAST && C == 0 && (IOM == NTT_FUSED_MULPAIR || IOM == NTT_FUSED_TAIL_RESCALE);
     // coefficient-form key-switch tail (BFV): the inverse transform of a data row ends with ski_util6_merged + ski_util7_merged
     // (evaluator_keyswitching_core.cu:570-658) -- the rounding fix is formed from the INTT of the special-prime row (in2) at the same
     // coefficient, then (this + lift - fix) qk^-1 [+ dest] [+ addend] is stored
@@ -840,11 +886,11 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
             static_assert(r != 0 || (REGIO != 2 && REGIO != 5) || S == 0, "register hand-over: E consecutive coefficients per thread");
             static_for<0, E>([&](auto Rc) { x[decltype(Rc)::value] = xio[decltype(Rc)::value]; });
         } else if constexpr (REGIO == 4 && r == 0) {
-            // r_j(s) qk^-1 + f_j(l) from the held T_s, T_l (exact doubles: the bit pattern NTT_FUSED_TAIL_RESCALE's loader reads from the rows)
-            static_assert(r != 0 || REGIO != 4 || S == TB - EB, "held T rows: the first forward round keeps the words the last inverse round left");
+            // r_j(s) qk^-1 + f_j(l) from the held centred rows c(s), c(l) (ArithF64::centred)
+            static_assert(r != 0 || REGIO != 4 || S == TB - EB, "held rows: the first forward round keeps the words the last inverse round left");
             static_for<0, E>([&](auto Rc) {
                 constexpr int R = decltype(Rc)::value;
-                x[R] = A::template tail_in<false>(io, f64_double_to_bits(xio[R]), f64_double_to_bits(xio[E + R]), md);
+                x[R] = A::held_tail_in(io, xio[R], xio[E + R], md);
             });
         } else if constexpr (r == 0 && INV && S == 0 && C == 0 && ROUNDS > 1) {
             // Mirror image of the forward store transpose: a thread starts with E consecutive coefficients.  Loading
@@ -861,8 +907,13 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
                 if constexpr (F_MULPAIR) {
                     // c2 = a1 (.) b1 formed while loading (the tensor product is never written to HBM)
                     const ulonglong2 va = ld2_at(io.a1 + mul_off + gbase + m * 128u, lane * 16u, true), vb = ld2_at(io.b1 + mul_off + gbase + m * 128u, lane * 16u, true);
-                    wv[2 * m] = A::to_lds(A::prod_in(va.x, vb.x, md), md);
-                    wv[2 * m + 1] = A::to_lds(A::prod_in(va.y, vb.y, md), md);
+                    if constexpr (LEAN) {       // |.| <= 0.875 p: within the first block's bound as it is
+                        wv[2 * m] = A::to_lds_raw(A::prod_in(va.x, vb.x, md), md);
+                        wv[2 * m + 1] = A::to_lds_raw(A::prod_in(va.y, vb.y, md), md);
+                    } else {
+                        wv[2 * m] = A::to_lds(A::prod_in(va.x, vb.x, md), md);
+                        wv[2 * m + 1] = A::to_lds(A::prod_in(va.y, vb.y, md), md);
+                    }
                 } else if constexpr (F_LAST_LD) {
                     // Q = P qk^-1 + c_k at the dropped limb, as ksmac2 left it (KsMacArgs::ten_a)
                     const ulonglong2 vp = nt_load2(gin + gbase + idx);
@@ -880,7 +931,7 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
             static_for<0, E>([&](auto Rc) {
                 constexpr int R = decltype(Rc)::value;
                 const u64 raw = wv[R];
-                if constexpr (F_MULPAIR || F_LAST_LD) x[R] = A::from_lds(raw);     // re-centred when it was parked
+                if constexpr (F_MULPAIR || F_LAST_LD) x[R] = A::from_lds(raw);     // re-centred when it was parked (LEAN MULPAIR: |x| <= 0.875 p)
                 else if constexpr (FIRST) x[R] = A::load_first(raw, a.reduce_input != 0, md);
                 else x[R] = A::load_mid(raw, md);
             });
@@ -995,14 +1046,14 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
             static_assert(r != ROUNDS - 1 || REGIO != 1 || S == 0, "register hand-over: E consecutive coefficients per thread");
             static_for<0, E>([&](auto Rc) { xio[decltype(Rc)::value] = A::keep(x[decltype(Rc)::value], md); });
         } else if constexpr (REGIO == 3 && r == ROUNDS - 1) {
-            static_assert(r != ROUNDS - 1 || REGIO != 3 || S == TB - EB, "held T rows: the last inverse round leaves the words the first forward round keeps");
+            static_assert(r != ROUNDS - 1 || REGIO != 3 || S == TB - EB, "held rows: the last inverse round leaves the words the first forward round keeps");
             static_for<0, E>([&](auto Rc) {
                 constexpr int R = decltype(Rc)::value;
                 constexpr bool scaled = A::FOLD_NINV && ((R >> (EB - 1)) & 1);      // the folded final layer applied N^-1 already
-                // T_l from the held T_s (the epilogue of NTT_FUSED_LAST_LIMB), or T_s itself (NTT_FLAG_STORE_ROUND_HALF's epilogue; the canonical
-                // value stays a double: 0 <= . < p < 2^50, exact)
-                if constexpr (F_LAST_ST) xio[E + R] = f64_bits_to_double(A::template last_out<false>(io, x[R], scaled, f64_double_to_bits(xio[R]), md));
-                else xio[R] = A::held_t(x[R], scaled, md);
+                // c(l) from the held c(s) (the epilogue of NTT_FUSED_LAST_LIMB), or c(s) itself: the rows the separate launches store as
+                // T = (x + aux/2) mod aux, minus aux/2 -- every consumer limb takes them as they are
+                if constexpr (F_LAST_ST) xio[E + R] = A::held_last(io, x[R], scaled, xio[R], md);
+                else xio[R] = A::held_c(x[R], scaled, md);
             });
         } else if constexpr (KSMAC && r == ROUNDS - 1) {
             // transpose inside the wave's own LDS slice (see the store path below), then multiply-accumulate with
@@ -1062,7 +1113,8 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
             u64 wv[E];
             static_for<0, E>([&](auto Rc) {
                 constexpr int R = decltype(Rc)::value;
-                if constexpr (F_TR_ST) wv[R] = A::to_lds(x[R], md);       // stays a re-centred double through the transpose
+                if constexpr (F_TR_ST && LEAN) wv[R] = A::to_lds_raw(x[R], md);   // stays a double through the transpose; tail_out re-centres Q - y
+                else if constexpr (F_TR_ST) wv[R] = A::to_lds(x[R], md);          // stays a re-centred double through the transpose
                 else wv[R] = A::template store_prep<SM>(x[R], md);
             });
             const unsigned gbase = gindex(wbase);
@@ -1125,12 +1177,21 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
             });
         } else if constexpr (r == ROUNDS - 1) {
             const unsigned gi0 = gindex(locbase), gb0 = gi0 * 8u;
+            // LEAN MULPAIR: the digits leave as the doubles ksmac2 reads (NTT_FLAG_STORE_F64, a launch-wide choice) or as words -- one loop, the
+            // two forms differ in two wave-uniform constants (ArithF64::digit_word)
+            constexpr bool LEAN_DIGITS = LEAN && INV && IOM == NTT_FUSED_MULPAIR;
+            const bool digits_f64 = LEAN_DIGITS && (a.flags & NTT_FLAG_STORE_F64) != 0;
+            const double dg_add = digits_f64 ? 0.0 : F64_TWO52;
+            const unsigned dg_mask_hi = digits_f64 ? 0xffffffffu : 0x000fffffu;
+            (void)dg_add; (void)dg_mask_hi;
             static_for<0, E>([&](auto Rc) {
                 constexpr int R = decltype(Rc)::value;
                 u64 v;
                 constexpr unsigned GR = gpart((unsigned)R << S);     // this register's share of the index
                 const unsigned gi = gi0 + GR;
-                if constexpr (F_LAST_ST) {
+                if constexpr (LEAN_DIGITS) {
+                    v = A::digit_word(x[R], A::FOLD_NINV && ((R >> (EB - 1)) & 1), dg_add, dg_mask_hi, md);
+                } else if constexpr (F_LAST_ST) {
                     // l = INTT(P qk^-1 + c) - r(s) qk^-1: the INTT of relinearize's last limb without ever forming that limb
                     constexpr bool scaled = A::FOLD_NINV && ((R >> (EB - 1)) & 1);      // the folded final layer applied N^-1 already
                     v = A::template last_out<TW>(io, x[R], scaled, io.in2[gi], md);
@@ -1153,7 +1214,7 @@ __device__ __forceinline__ void ntt_pass_body(const NttArgs& a, const KeyPtrs* k
                     if constexpr (INV && IOM == 0 && std::is_same<A, ArithU64>::value) {
                         if (a.flags & NTT_FLAG_STORE_ROUND_HALF) v = add_mod(v, md.q >> 1, md.q);      // the same T as a u64 word (NTT_FLAG_TS_U64)
                     }
-                    if constexpr (INV && IOM == NTT_FUSED_MULPAIR && std::is_same<A, ArithF64>::value) {
+                    if constexpr (!LEAN && INV && IOM == NTT_FUSED_MULPAIR && std::is_same<A, ArithF64>::value) {
                         // the digits of the key switch are consumed as doubles by ksmac2: convert once here instead of once per output row there
                         if (a.flags & NTT_FLAG_STORE_F64) v = f64_double_to_bits(f64_from_u64(v));
                     }

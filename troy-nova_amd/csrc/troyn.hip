@@ -1847,7 +1847,6 @@ static int mrr_tail_merged(const MrrCall& c, bool quartet) {
         LAUNCH_CHECK();
     }
     NttArgs sp = special_rows_args(p, c.poly_prod(), nullptr, L);
-    if (!quartet) sp.flags = NTT_FLAG_STORE_ROUND_HALF;
     prep_direct(p, sp, true, true);
     NttArgs la = mrr_last_args(c);
     prep_direct(p, la, true, true);
