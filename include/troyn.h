@@ -332,6 +332,46 @@ int troyn_apply_galois_sum(const troyn_plan* plan, uint32_t L, int is_ckks, int 
                            void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Plaintext-weighted hoisted rotations: out[s] = SUM_t w_{s,t} (.) rot_t(ct), the diagonal method of a plaintext matrix times an
+ * encrypted vector (with baby-step/giant-step: several such sums over the same rotations of one ciphertext).  An ADDITION to the
+ * reference's surface, built on the hoisted entries above: one digit decomposition per ciphertext, ONE division by the special prime
+ * per slot -- the weight is applied BEFORE the division, on the extended basis q_0 .. q_{L-1}, q_special.
+ *   ct               [batch][2][L][N], NTT form iff is_ntt_form (CKKS: NTT form, BFV: coefficient form, as troyn_switch_key)
+ *   galois_elements  host array of `terms` elements g_t, each odd and < 2N; duplicates are allowed.  The element 1 IS allowed here: the
+ *                    unrotated ciphertext (the main diagonal); its L key entries are ignored and may be NULL
+ *   keys             host array of terms * L DEVICE pointers, keys[t * L + j] -> u64[2][K][N] in NTT form, 16-byte aligned
+ *   weights          host array of slots * terms DEVICE pointers, weights[s * terms + t] -> u64[K][N] in NTT form and KEY-LEVEL layout:
+ *                    rows 0 .. K-2 under q_0 .. q_{K-2}, row K-1 under the special prime; only rows 0 .. L-1 and K-1 are read; words are
+ *                    canonical (below their modulus); 16-byte aligned; NULL = the term is absent from that slot.  Shared by the batch.
+ *   out              [slots][batch][2][L][N], same form as ct
+ * Contract, per item and slot s, on integers (tests/weighted_hoist_spec.py; the notation of the block above).  T_s = {t : weight (s, t)
+ * non-NULL}; (*) is the negacyclic product = the pointwise product of the NTT-form words as given:
+ *   e_{t,j}      sigma_{g_t}(d_j), signed
+ *   X_c[m]       SUM_{t in T_s, g_t != 1} w_{s,t}[m] (*) SUM_j (e_{t,j} mod m) (*) k_{t,j}[c][m]  mod m,  m in {q_0 .. q_{L-1}, q_special}
+ *   r_c, result_c[l]   exactly as in troyn_switch_key (ONE rounded division by the special prime per slot)
+ *   out[s][0][l] = SUM_{t in T_s}          w_{s,t}[q_l] (*) sigma_{g_t}(c0)[l] + result_0[l]  mod q_l
+ *   out[s][1][l] = SUM_{t in T_s, g_t = 1} w_{s,t}[q_l] (*) c1[l]              + result_1[l]  mod q_l
+ * The unkeyed contributions y (c0 of every term, c1 of the identity terms) may be added after the division, as written, or injected
+ * before it as (q_special mod q_l) * y on the rows q_l and nothing on the special row; the output WORDS are the same either way: the
+ * special row and hence r_c is unchanged, and ((X + q_special * y) - r) * q_special^-1 = (X - r) * q_special^-1 + y  mod q_l.  The
+ * implementation injects before the division (one tail with TROYN_ASSIGN_OVERWRITE serves both components and both forms).
+ * With every weight the constant 1 and no identity term the words equal troyn_apply_galois_sum's.  As stated above, the words are NOT
+ * those of troyn_apply_galois + troyn_switch_key + a plaintext multiplication: the digits of a negated coefficient differ by multiples
+ * of q_j, and the reference would round once per term; both decrypt to the same message under the same kind of noise bound.
+ * Scope: BFV and CKKS.  BGV is left out (its tail divides differently).
+ * TROYN_E_INVALID: terms == 0, slots == 0, a slot with no weight, a null table, a null or misaligned key entry of a term with g != 1, a
+ * misaligned pointer (ct, out, workspace, a weight), an element that is even or >= 2N, L outside [1, K-1], `out` overlapping `ct`.
+ * TROYN_E_WORKSPACE: a workspace below troyn_apply_galois_weighted_workspace_bytes(plan, L, terms, slots, batch, is_ntt_form).
+ * batch == 0 returns TROYN_OK, launches nothing and looks at neither `ct`, `out` nor the workspace.  The tables are read before the
+ * call returns.
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_apply_galois_weighted_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t terms, size_t slots, size_t batch, int is_ntt_form);
+int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
+                                     const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms,
+                                     const uint64_t* const* weights, size_t slots, uint64_t* out,
+                                     void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * BGV.  BGV ciphertexts live in NTT form and reuse troyn_ntt, troyn_dyadic_convolute (bgv_multiply,
  * evaluator.cu:150-173), troyn_add/sub/negate/multiply_scalar, troyn_apply_galois and troyn_plain_centralize unchanged; the
  * entries below are the steps where BGV differs.  troyn_bgv holds the constants of ONE level's RNSTool that only BGV reads

@@ -20,6 +20,16 @@
 //   accumulator never runs across terms.  Every output word is written once.
 // hoist_c0_kernel: dest[slot][item][0][l] = SUM_{t in S(slot)} sigma_{g_t}(c0[item][l])  mod q_l, a gather in either form (coefficient
 //   form: the source of output o is i = o * g^-1 mod N, negated when (i * g) & N -- the sign rule of galois_kernel).
+//
+// hoist_weighted_kernel (troyn_apply_galois_weighted_sums): the same rows, pairs and gather with a plaintext weight between the per-term
+//   Barrett reduction and the addition across terms,
+//     poly_prod[slot][item][c][k][i] = SUM_{t in T(slot)} w_{slot,t}[m_k][i] * ( SUM_j D[item][k][j][pi_t(i)] * key_{t,j}[c][k][i]          (g_t != 1)
+//                                                                            + (q_special mod q_k) * u_{t,c}[item][k][pi_t(i)] )  mod m_k   (k < L)
+//   u_{t,0} = the NTT-form limbs of c0, u_{t,1} = those of c1 for the identity terms and nothing otherwise: the unkeyed contributions enter
+//   BEFORE the division by the special prime, scaled by q_special on the data rows and absent from the special row, so the tail's
+//   (X - r) * q_special^-1 returns them unscaled and r is untouched (include/troyn.h states the argument).  The slot is a grid dimension;
+//   a term whose weight pointer is null in this slot is skipped without touching its keys; the keys of an identity term are never read.
+//   One 16-byte weight load per thread and term serves the IB items.
 #pragma once
 #include "poly_kernels.hpp"
 
@@ -138,6 +148,115 @@ __global__ __launch_bounds__(POLY_BLOCK) void hoist_c0_kernel(unsigned chunks, H
             sum = add_mod(sum, v, q);
         }
         op[x] = sum;
+    }
+}
+
+struct HoistWeightedArgs {
+    const DevModulus* mods;
+    unsigned K, L, log_n, batch;
+    unsigned groups;               // ceil(batch / IB)
+    unsigned terms;
+    const u64* digits_ntt;         // D [batch][L+1][L][N]
+    const u64* c0_ntt;             // NTT-form limbs of c0: item b, limb l at c0_ntt + b * c0_bstride + l * N
+    size_t c0_bstride;
+    const u64* c1_ntt;             // NTT-form limb l of c1 at c1_ntt + b * c1_bstride + l * c1_lstride (the ciphertext, or the diagonal block D[l][l])
+    size_t c1_bstride, c1_lstride;
+    int diag_from_c1;              // skip_diag: digit k of row k < L was not produced, it is c1's NTT-form limb k
+    const u64* const* keys;        // device table [terms][L] -> u64[2][K][N]; the entries of an identity term are not read
+    const u64* elements;           // device table [terms]
+    const u64* const* weights;     // device table [slots][terms] -> u64[K][N], null = the term is absent from the slot
+    const u64* special_mod;        // device table [L]: q_special mod q_l
+    u64* poly_prod;                // [slots][batch][2][L+1][N]
+};
+
+template <int IB>
+__global__ __launch_bounds__(POLY_BLOCK) void hoist_weighted_kernel(unsigned chunks, HoistWeightedArgs a) {
+    const unsigned L = a.L, K = a.K, n = 1u << a.log_n;
+    const unsigned row = blk_row(chunks);
+    const unsigned k = row % (L + 1);
+    const unsigned grp = (row / (L + 1)) % a.groups;
+    const unsigned slot = row / (L + 1) / a.groups;
+    const unsigned key_index = (k == L) ? K - 1 : k;
+    const DevModulus md = a.mods[key_index];
+    const size_t key_poly = (size_t)K * n;
+    const bool data_row = k < L;
+    const u64 special = data_row ? a.special_mod[k] : 0;
+    // items past the batch's end recompute the last item and store nothing
+    size_t item[IB];
+    const u64 *dp[IB], *c0p[IB], *c1p[IB];
+#pragma unroll
+    for (int b = 0; b < IB; ++b) {
+        const unsigned it = grp * IB + b;
+        item[b] = it < a.batch ? it : a.batch - 1;
+        dp[b] = a.digits_ntt + (item[b] * (L + 1) + k) * (size_t)L * n;
+        c0p[b] = a.c0_ntt + item[b] * a.c0_bstride + (size_t)(data_row ? k : 0) * n;
+        c1p[b] = a.c1_ntt + item[b] * a.c1_bstride + (size_t)(data_row ? k : 0) * a.c1_lstride;
+    }
+    const bool diag = a.diag_from_c1 && data_row;
+    const u64* const* wrow = a.weights + (size_t)slot * a.terms;
+    for (unsigned x = blk_col(chunks) * 2; x < n; x += chunks * blockDim.x * 2) {
+        u64 r[IB][2][2];
+#pragma unroll
+        for (int b = 0; b < IB; ++b) r[b][0][0] = r[b][0][1] = r[b][1][0] = r[b][1][1] = 0;
+        for (unsigned t = 0; t < a.terms; ++t) {
+            const u64* w = wrow[t];
+            if (!w) continue;                                           // uniform over the grid row: the term is absent from this slot
+            const u64x2 wv = ld2(w + (size_t)key_index * n + x);
+            const unsigned g = (unsigned)a.elements[t];
+            const unsigned src = hoist_ntt_source(x, g, a.log_n);
+            const unsigned pair = src & ~1u;
+            const bool swap = src & 1u;
+            if (g != 1) {
+                u64 lo[IB][2][2], hi[IB][2][2];
+#pragma unroll
+                for (int b = 0; b < IB; ++b)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) lo[b][c][0] = lo[b][c][1] = hi[b][c][0] = hi[b][c][1] = 0;
+                for (unsigned j = 0; j < L; ++j) {
+                    const u64* kj = a.keys[(size_t)t * L + j] + (size_t)key_index * n + x;
+                    const u64x2 k0 = ld2(kj), k1 = ld2(kj + key_poly);
+#pragma unroll
+                    for (int b = 0; b < IB; ++b) {
+                        const u64* drow = (diag && j == k) ? c1p[b] : dp[b] + (size_t)j * n;
+                        const u64x2 v = ld2(drow + pair);
+                        const u64 d0 = swap ? v.b : v.a, d1 = swap ? v.a : v.b;
+                        mac128(lo[b][0][0], hi[b][0][0], d0, k0.a); mac128(lo[b][0][1], hi[b][0][1], d1, k0.b);
+                        mac128(lo[b][1][0], hi[b][1][0], d0, k1.a); mac128(lo[b][1][1], hi[b][1][1], d1, k1.b);
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < IB; ++b)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const u64 p0 = barrett128(lo[b][c][0], hi[b][c][0], md.q, md.ratio_lo, md.ratio_hi);
+                        const u64 p1 = barrett128(lo[b][c][1], hi[b][c][1], md.q, md.ratio_lo, md.ratio_hi);
+                        r[b][c][0] = add_mod(r[b][c][0], mul_mod(p0, wv.a, md), md.q);
+                        r[b][c][1] = add_mod(r[b][c][1], mul_mod(p1, wv.b, md), md.q);
+                    }
+            }
+            if (data_row) {
+                // the unkeyed contributions, scaled by q_special: c0 under every term, c1 under the identity
+                const u64 ws0 = mul_mod(wv.a, special, md), ws1 = mul_mod(wv.b, special, md);
+#pragma unroll
+                for (int b = 0; b < IB; ++b) {
+                    const u64x2 v = ld2(c0p[b] + pair);
+                    r[b][0][0] = add_mod(r[b][0][0], mul_mod(swap ? v.b : v.a, ws0, md), md.q);
+                    r[b][0][1] = add_mod(r[b][0][1], mul_mod(swap ? v.a : v.b, ws1, md), md.q);
+                    if (g == 1) {
+                        const u64x2 v1 = ld2(c1p[b] + x);
+                        r[b][1][0] = add_mod(r[b][1][0], mul_mod(v1.a, ws0, md), md.q);
+                        r[b][1][1] = add_mod(r[b][1][1], mul_mod(v1.b, ws1, md), md.q);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < IB; ++b) {
+            if (grp * IB + b >= a.batch) break;
+            u64* pp = a.poly_prod + ((size_t)slot * a.batch + item[b]) * 2 * (size_t)(L + 1) * n + (size_t)k * n + x;
+            st2(pp, r[b][0][0], r[b][0][1]);
+            st2(pp + (size_t)(L + 1) * n, r[b][1][0], r[b][1][1]);
+        }
     }
 }
 

@@ -1480,8 +1480,9 @@ extern "C" int troyn_relinearize(const troyn_plan* plan, uint32_t L, int is_ckks
 // term, sum: one slot), hoist_c0_kernel the permuted c0, and ks_tail runs unchanged on slots * batch items.
 struct HoistLayout { KsLayout ks; size_t table; };
 
-static HoistLayout hoist_layout(const troyn_plan* p, unsigned L, size_t terms, size_t batch, bool sum) {
-    const size_t n = p->n, items = (sum ? 1 : terms) * batch;
+// `slots` results per item of the batch (many: one per term, sum: one, weighted sums: the caller's count)
+static HoistLayout hoist_layout(const troyn_plan* p, unsigned L, size_t terms, size_t batch, size_t slots) {
+    const size_t n = p->n, items = slots * batch;
     HoistLayout h;
     size_t off = 0;
     h.ks.target_intt = off; off += batch * L * n;
@@ -1497,12 +1498,13 @@ static HoistLayout hoist_layout(const troyn_plan* p, unsigned L, size_t terms, s
 
 extern "C" size_t troyn_apply_galois_hoisted_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t terms, size_t batch, int sum) {
     if (!plan) return 0;
-    return hoist_layout(plan, L, terms, batch, sum != 0).ks.total * sizeof(u64);
+    return hoist_layout(plan, L, terms, batch, sum ? 1 : terms).ks.total * sizeof(u64);
 }
 
-static int apply_galois_hoisted(const char* P, const troyn_plan* p, unsigned L, int is_ckks, int is_ntt_form, const u64* ct,
-                                const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, u64* out,
-                                void* workspace, size_t workspace_bytes, size_t batch, hipStream_t s, bool sum) {
+// what every hoisted entry checks before it looks at the batch: the plan, the level, the element and key tables.  The identity element
+// (no key: its L entries are not looked at) is the weighted entry's alone.
+static int hoist_check_tables(const char* P, const troyn_plan* p, unsigned L, const uint64_t* galois_elements, const uint64_t* const* keys,
+                              size_t terms, bool allow_identity) {
     if (!p) return fail(TROYN_E_INVALID, std::string(P) + " null plan");
     const unsigned K = p->K, n = p->n;
     if (K < 2) return fail(TROYN_E_INVALID, std::string(P) + " Keyswitching is not supported.");
@@ -1511,37 +1513,64 @@ static int apply_galois_hoisted(const char* P, const troyn_plan* p, unsigned L, 
     if (!galois_elements || !keys) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
     for (size_t t = 0; t < terms; t++) {
         const uint64_t g = galois_elements[t];
-        if ((g & 1) == 0 || g >= 2ull * n || g == 1) return fail(TROYN_E_INVALID, std::string(P) + " Galois element is not valid.");
+        if ((g & 1) == 0 || g >= 2ull * n || (g == 1 && !allow_identity)) return fail(TROYN_E_INVALID, std::string(P) + " Galois element is not valid.");
+        if (g == 1) continue;
         for (unsigned j = 0; j < L; j++)
             if (!keys[t * L + j] || ((uintptr_t)keys[t * L + j] & 15)) return fail(TROYN_E_INVALID, std::string(P) + " null or misaligned key pointer");
     }
-    if (batch == 0) return TROYN_OK;      // nothing to do: neither ct, out nor the workspace is looked at
+    return TROYN_OK;
+}
+// the buffers of a non-empty batch: `out` holds `items` ciphertexts and may not overlap the `batch` ciphertexts of `ct`
+static int hoist_check_buffers(const char* P, const troyn_plan* p, unsigned L, const u64* ct, const u64* out, const void* workspace,
+                               size_t batch, size_t items) {
     if (!ct || !out || !workspace) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
     if (((uintptr_t)ct | (uintptr_t)out | (uintptr_t)workspace) & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned pointer");
-    const size_t slots = sum ? 1 : terms, items = slots * batch, ct_words = (size_t)2 * L * n;
+    const size_t ct_words = (size_t)2 * L * p->n;
     if ((uintptr_t)out < (uintptr_t)(ct + batch * ct_words) && (uintptr_t)ct < (uintptr_t)(out + items * ct_words))
         return fail(TROYN_E_INVALID, std::string(P) + " out overlaps ct");
-    const HoistLayout h = hoist_layout(p, L, terms, batch, sum);
-    if (workspace_bytes < h.ks.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
-    u64* ws = (u64*)workspace;
-    // the tables are read before the call returns: [terms][L] key pointers, the elements, their inverses modulo 2N
+    return TROYN_OK;
+}
+// the host tables of one call, [terms][L] key pointers, the elements, their inverses modulo 2N, followed by `extra`: one upload
+static int hoist_upload_tables(const troyn_plan* p, unsigned L, const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms,
+                               const std::vector<u64>& extra, u64* dev, hipStream_t s) {
     std::vector<u64> table(terms * (L + 2));
-    for (size_t i = 0; i < terms * L; i++) table[i] = (u64)(uintptr_t)keys[i];
     for (size_t t = 0; t < terms; t++) {
         const u64 g = galois_elements[t];
+        for (unsigned j = 0; j < L; j++) table[t * L + j] = g == 1 ? 0 : (u64)(uintptr_t)keys[t * L + j];
         u64 inv = g;                                   // g * g = 1 (mod 8); every Newton step doubles the number of correct low bits
         for (int i = 0; i < 5; i++) inv *= 2 - g * inv;
         table[terms * L + t] = g;
-        table[terms * (L + 1) + t] = inv & (2ull * n - 1);
+        table[terms * (L + 1) + t] = inv & (2ull * p->n - 1);
     }
-    if (int rc = upload_host_table(s, ws + h.table, table.data(), table.size() * sizeof(u64))) return rc;
-    // (1) + (2): c1 in coefficient form, then its L digits under every key modulus, once
+    table.insert(table.end(), extra.begin(), extra.end());
+    return upload_host_table(s, dev, table.data(), table.size() * sizeof(u64));
+}
+// (1) + (2): c1 in coefficient form, then its L digits under every key modulus, once.  `dc` is also the call the tail later runs with (on
+// slots * batch items); skip_diag: the transform left the diagonal blocks to the consumer.
+static int hoist_decompose(KsCall& dc, bool& skip_diag) {
+    if (int rc = ks_digits(dc)) return rc;
+    skip_diag = dc.is_ntt_form && dc.p->log_n >= 10;      // as ks_path's `fused`
+    return ks_transform_digits(dc, skip_diag);
+}
+
+static int apply_galois_hoisted(const char* P, const troyn_plan* p, unsigned L, int is_ckks, int is_ntt_form, const u64* ct,
+                                const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, u64* out,
+                                void* workspace, size_t workspace_bytes, size_t batch, hipStream_t s, bool sum) {
+    if (int rc = hoist_check_tables(P, p, L, galois_elements, keys, terms, false)) return rc;
+    const unsigned K = p->K, n = p->n;
+    if (batch == 0) return TROYN_OK;      // nothing to do: neither ct, out nor the workspace is looked at
+    const size_t slots = sum ? 1 : terms, items = slots * batch, ct_words = (size_t)2 * L * n;
+    if (int rc = hoist_check_buffers(P, p, L, ct, out, workspace, batch, items)) return rc;
+    const HoistLayout h = hoist_layout(p, L, terms, batch, slots);
+    if (workspace_bytes < h.ks.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    u64* ws = (u64*)workspace;
+    // the tables are read before the call returns
+    if (int rc = hoist_upload_tables(p, L, galois_elements, keys, terms, {}, ws + h.table, s)) return rc;
     const u64* c1 = ct + (size_t)L * n;
     KsCall dc{p, L, is_ckks, is_ntt_form != 0, c1, ct_words, TROYN_ASSIGN_OVERWRITE_EXCEPT_FIRST, out, nullptr, 0,
               ws, h.ks, batch, s, nullptr, c1, ct_words};
-    if (int rc = ks_digits(dc)) return rc;
-    const bool skip_diag = dc.is_ntt_form && p->log_n >= 10;      // as ks_path's `fused`: the transform leaves the diagonal blocks to the consumer
-    if (int rc = ks_transform_digits(dc, skip_diag)) return rc;
+    bool skip_diag = false;
+    if (int rc = hoist_decompose(dc, skip_diag)) return rc;
     HoistArgs a;
     std::memset(&a, 0, sizeof(a));
     a.mods = p->d_mods; a.K = K; a.L = L; a.log_n = p->log_n; a.batch = (unsigned)batch;
@@ -1592,6 +1621,110 @@ extern "C" int troyn_apply_galois_sum(const troyn_plan* plan, uint32_t L, int is
     select_device(plan);
     return apply_galois_hoisted("[troyn_apply_galois_sum]", plan, L, is_ckks, is_ntt_form, (const u64*)ct, galois_elements, keys, terms,
                                 (u64*)out, workspace, workspace_bytes, batch, (hipStream_t)stream, true);
+}
+
+// ---- plaintext-weighted hoisted rotations (an addition; include/troyn.h, hoist_weighted_kernel) ----
+// out[s] = SUM_t w_{s,t} (.) sigma_{g_t}(ct): the weight enters between the per-term reduction and the sum, on the extended basis, and the
+// unkeyed contributions are injected there scaled by q_special -- so ONE tail per slot (TROYN_ASSIGN_OVERWRITE) finishes both components.
+struct WeightedLayout { HoistLayout h; size_t weights, special_mod, c0_ntt, total; };
+
+static WeightedLayout weighted_layout(const troyn_plan* p, unsigned L, size_t terms, size_t slots, size_t batch, bool is_ntt_form) {
+    WeightedLayout w;
+    w.h = hoist_layout(p, L, terms, batch, slots);
+    size_t off = w.h.table + terms * (L + 2);           // the extra tables follow the hoisted ones: one upload
+    w.weights = off;     off += slots * terms;
+    w.special_mod = off; off += L;
+    off = (off + 1) & ~(size_t)1;
+    w.c0_ntt = off;      off += is_ntt_form ? 0 : batch * L * (size_t)p->n;      // coefficient form: the forward transform of c0
+    w.total = off;
+    return w;
+}
+
+extern "C" size_t troyn_apply_galois_weighted_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t terms, size_t slots, size_t batch,
+                                                              int is_ntt_form) {
+    if (!plan) return 0;
+    return weighted_layout(plan, L, terms, slots, batch, is_ntt_form != 0).total * sizeof(u64);
+}
+
+extern "C" int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
+                                                const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms,
+                                                const uint64_t* const* weights, size_t slots, uint64_t* out_,
+                                                void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(plan);
+    const char* P = "[troyn_apply_galois_weighted_sums]";
+    const troyn_plan* p = plan;
+    const u64* ct = (const u64*)ct_;
+    u64* out = (u64*)out_;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = hoist_check_tables(P, p, L, galois_elements, keys, terms, true)) return rc;
+    if (slots == 0) return fail(TROYN_E_INVALID, std::string(P) + " no slots");
+    if (!weights) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    for (size_t sl = 0; sl < slots; sl++) {
+        bool any = false;
+        for (size_t t = 0; t < terms; t++) {
+            const uint64_t* w = weights[sl * terms + t];
+            if ((uintptr_t)w & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned weight pointer");
+            any = any || w;
+        }
+        if (!any) return fail(TROYN_E_INVALID, std::string(P) + " a slot has no weight");
+    }
+    const unsigned K = p->K, n = p->n;
+    if (batch == 0) return TROYN_OK;      // nothing to do: neither ct, out nor the workspace is looked at
+    const size_t items = slots * batch, ct_words = (size_t)2 * L * n;
+    if (int rc = hoist_check_buffers(P, p, L, ct, out, workspace, batch, items)) return rc;
+    const bool ntt = is_ntt_form != 0;
+    const WeightedLayout w = weighted_layout(p, L, terms, slots, batch, ntt);
+    if (workspace_bytes < w.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    if (batch > 0xffffffffull || terms > 0xffffffffull || slots > 0xffffffffull) return fail(TROYN_E_INVALID, std::string(P) + " batch too large for one launch");
+    u64* ws = (u64*)workspace;
+    // the tables are read before the call returns: the hoisted tables, then [slots][terms] weight pointers and q_special mod q_l
+    std::vector<u64> extra(slots * terms + L);
+    for (size_t i = 0; i < slots * terms; i++) extra[i] = (u64)(uintptr_t)weights[i];
+    for (unsigned l = 0; l < L; l++) extra[slots * terms + l] = p->moduli[K - 1] % p->moduli[l];
+    if (int rc = hoist_upload_tables(p, L, galois_elements, keys, terms, extra, ws + w.h.table, s)) return rc;
+    const u64* c1 = ct + (size_t)L * n;
+    KsCall dc{p, L, is_ckks, ntt, c1, ct_words, TROYN_ASSIGN_OVERWRITE, out, nullptr, 0,
+              ws, w.h.ks, batch, s, nullptr, c1, ct_words};
+    bool skip_diag = false;
+    if (int rc = hoist_decompose(dc, skip_diag)) return rc;
+    HoistWeightedArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.mods = p->d_mods; a.K = K; a.L = L; a.log_n = p->log_n; a.batch = (unsigned)batch; a.terms = (unsigned)terms;
+    a.digits_ntt = ws + w.h.ks.temp_ntt; a.diag_from_c1 = skip_diag ? 1 : 0;
+    if (ntt) {
+        a.c0_ntt = ct; a.c0_bstride = ct_words;
+        a.c1_ntt = c1; a.c1_bstride = ct_words; a.c1_lstride = n;
+    } else {
+        // the NTT-form limbs of c0: one forward transform; those of c1 are the diagonal blocks D[l][l], present in coefficient form
+        NttArgs f = contiguous_args(p, ct, ws + w.c0_ntt, 1, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
+        f.in_bstride = (long long)ct_words;
+        if (int rc = launch_ntt(p, f, batch, false, s)) return rc;
+        a.c0_ntt = ws + w.c0_ntt; a.c0_bstride = (size_t)L * n;
+        a.c1_ntt = a.digits_ntt; a.c1_bstride = (size_t)(L + 1) * L * n; a.c1_lstride = (size_t)(L + 1) * n;
+    }
+    a.keys = reinterpret_cast<const u64* const*>(ws + w.h.table);
+    a.elements = ws + w.h.table + terms * L;
+    a.weights = reinterpret_cast<const u64* const*>(ws + w.weights);
+    a.special_mod = ws + w.special_mod;
+    a.poly_prod = ws + w.h.ks.poly_prod;
+    // <permuted digits, keys>, the weight, the sum over the slot's terms and the scaled unkeyed contributions in one launch
+    {
+        const unsigned ib = batch >= 4 ? 4u : batch >= 2 ? 2u : 1u;
+        a.groups = (unsigned)((batch + ib - 1) / ib);
+        const unsigned ch = chunks_pairs(n);
+        const size_t rows = slots * a.groups * (size_t)(L + 1);
+        if (int rc = check_rows(rows, ch)) return rc;
+        TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, s);
+        const dim3 grid((unsigned)(rows * ch)), block(POLY_BLOCK);
+        if (ib == 4) hipLaunchKernelGGL((hoist_weighted_kernel<4>), grid, block, 0, s, ch, a);
+        else if (ib == 2) hipLaunchKernelGGL((hoist_weighted_kernel<2>), grid, block, 0, s, ch, a);
+        else hipLaunchKernelGGL((hoist_weighted_kernel<1>), grid, block, 0, s, ch, a);
+        LAUNCH_CHECK();
+    }
+    // the tail of troyn_switch_key on slots * batch items, both components overwritten
+    KsCall tc = dc;
+    tc.batch = items;
+    return ks_tail(tc, ks_path(p, L, items, tc.is_ntt_form, false));
 }
 
 // ---------------------------------------------------------------------------------------

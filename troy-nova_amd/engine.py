@@ -254,6 +254,47 @@ class Plan:
         special prime"""
         return self._apply_galois_hoisted(True, L, ct, elements, keys_per_element, is_ckks, is_ntt_form, out)
 
+    def apply_galois_weighted_sums(self, L, ct, elements, keys_per_element, weights, is_ckks=True, is_ntt_form=True, out=None):
+        """ct [batch][2][L][N] -> [slots][batch][2][L][N]: out[s] = SUM_t weights[s][t] (.) (key-switched automorphism X -> X^elements[t] of ct),
+        one digit decomposition and ONE division by the special prime per slot (the diagonal method; include/troyn.h states the contract).
+        weights[s][t]: a tensor [K][N] in NTT form and key-level layout (special prime last), or None = the term is absent from slot s.
+        The element 1 is the unrotated ciphertext; its entry of keys_per_element may be None."""
+        who = "[troyn_apply_galois_weighted_sums]"
+        terms, slots = len(elements), len(weights)
+        if len(keys_per_element) != terms:
+            raise capi.TroynInvalidArgument("%s one key per Galois element is needed" % who)
+        words = 2 * L * self.n
+        if L < 1 or ct.numel() % words:
+            raise capi.TroynInvalidArgument("%s ct is not [batch][2][L][N]" % who)
+        batch = ct.numel() // words
+        ptrs = []
+        for e, keys in zip(elements, keys_per_element):
+            if keys is None and int(e) == 1:
+                keys = [None] * L
+            if keys is None or len(keys) < L:
+                raise capi.TroynInvalidArgument("%s Key switch keys index out of range." % who)
+            ptrs += [None if k is None else k.data_ptr() for k in keys[:L]]      # (a null entry is the library's to refuse)
+        wptrs = []
+        for row in weights:
+            if len(row) != terms:
+                raise capi.TroynInvalidArgument("%s one weight (or None) per slot and term is needed" % who)
+            for w in row:
+                if w is not None and w.numel() != self.K * self.n:
+                    raise capi.TroynInvalidArgument("%s a weight is not [K][N]" % who)
+                wptrs.append(None if w is None else w.data_ptr())
+        karr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        warr = (C.c_void_p * max(len(wptrs), 1))(*wptrs)
+        earr = (C.c_uint64 * max(terms, 1))(*[int(e) for e in elements])
+        shape = (slots, batch, 2, L, self.n)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=self.device)
+        elif out.numel() != int(np.prod(shape)):
+            raise capi.TroynInvalidArgument("%s out is not [slots][batch][2][L][N]" % who)
+        ws = self.workspace(self.lib.troyn_apply_galois_weighted_workspace_bytes(self.h, L, terms, slots, batch, int(is_ntt_form)))
+        capi.check(self.lib.troyn_apply_galois_weighted_sums(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(ct), earr, karr, terms, warr, slots,
+                                                             _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        return out
+
     # -- RLWE / LWE packing (evaluator_lwes.cu) -----------------------------------------------------
     def negacyclic_shift(self, x, nmod, shift, mod_start=0):
         """x [count][nmod][N] * X^shift (utils::negacyclic_shift_ps), any shift (modulo 2N)"""

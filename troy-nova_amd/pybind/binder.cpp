@@ -524,6 +524,32 @@ PYBIND11_MODULE(pytroy_raw, m) {
         s.rotate_sum(a, st, k, d, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("destination"), POOL);
     ev.def("rotate_sum_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, PoolArg p) {
         return s.rotate_sum_new(a, st, k, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), POOL);
+    // additions: plaintext-weighted hoisted rotations -- the diagonal method; weights [slot][term], None = the term is absent from the slot (troy.h)
+    typedef std::vector<const Plaintext*> WeightRow;
+    ev.def("apply_galois_weighted_sums", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& g, const GaloisKeys& k, const std::vector<WeightRow>& w,
+                                            const std::vector<Ciphertext*>& d, PoolArg p) {
+        std::vector<Ciphertext> out = s.apply_galois_weighted_sums_new(a, g, k, w, P(p));
+        if (d.size() != out.size()) throw std::invalid_argument("[Evaluator::apply_galois_weighted_sums] destination needs one ciphertext per slot.");
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },
+           py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);
+    ev.def("apply_galois_weighted_sums_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& g, const GaloisKeys& k, const std::vector<WeightRow>& w, PoolArg p) {
+        return s.apply_galois_weighted_sums_new(a, g, k, w, P(p)); }, py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), py::arg("weights"), POOL);
+    ev.def("apply_galois_weighted_sum", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& g, const GaloisKeys& k, const WeightRow& w, Ciphertext& d, PoolArg p) {
+        s.apply_galois_weighted_sum(a, g, k, w, d, P(p)); }, py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);
+    ev.def("apply_galois_weighted_sum_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& g, const GaloisKeys& k, const WeightRow& w, PoolArg p) {
+        return s.apply_galois_weighted_sum_new(a, g, k, w, P(p)); }, py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), py::arg("weights"), POOL);
+    ev.def("rotate_weighted_sums", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, const std::vector<WeightRow>& w,
+                                      const std::vector<Ciphertext*>& d, PoolArg p) {
+        std::vector<Ciphertext> out = s.rotate_weighted_sums_new(a, st, k, w, P(p));
+        if (d.size() != out.size()) throw std::invalid_argument("[Evaluator::rotate_weighted_sums] destination needs one ciphertext per slot.");
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },
+           py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);
+    ev.def("rotate_weighted_sums_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, const std::vector<WeightRow>& w, PoolArg p) {
+        return s.rotate_weighted_sums_new(a, st, k, w, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("weights"), POOL);
+    ev.def("rotate_weighted_sum", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, const WeightRow& w, Ciphertext& d, PoolArg p) {
+        s.rotate_weighted_sum(a, st, k, w, d, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);
+    ev.def("rotate_weighted_sum_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, const WeightRow& w, PoolArg p) {
+        return s.rotate_weighted_sum_new(a, st, k, w, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("weights"), POOL);
     // ciphertext +/- plaintext
 #define EV_PLAIN(name)                                                                                                           \
     ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const Plaintext& w, Ciphertext& d, PoolArg p) { s.name(a, w, d, P(p)); },  \

@@ -2201,6 +2201,89 @@ void Evaluator::rotate_sum(const Ciphertext& encrypted, const std::vector<int>& 
     destination = std::move(d[0]);
 }
 
+// -- plaintext-weighted hoisted rotations (addition; troy.h): troyn_apply_galois_weighted_sums, one launch chain for every slot --
+void Evaluator::apply_galois_weighted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                      const std::vector<std::vector<const Plaintext*>>& weights, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const {
+    if (galois_elements.empty()) throw std::invalid_argument(std::string(P) + " Empty element list.");
+    if (weights.empty()) throw std::invalid_argument(std::string(P) + " Empty slot list.");
+    auto cd = get_context_data(P, encrypted.parms_id());
+    const SchemeType scheme = cd->parms().scheme();
+    if (scheme == SchemeType::BGV) throw std::invalid_argument(std::string(P) + " BGV is not supported: its key switch divides by the special prime differently.");
+    if (encrypted.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " Ciphertext size must be 2.");
+    check_no_seed(P, encrypted);
+    check_on_device(P, context_, encrypted);
+    const size_t n = cd->parms().poly_modulus_degree();
+    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
+    const size_t words = 2 * static_cast<size_t>(L) * n, terms = galois_elements.size(), slots = weights.size();
+    std::vector<uint64_t> elements;
+    std::vector<const uint64_t*> keys;
+    Ciphertext shell;
+    for (size_t g : galois_elements) {
+        elements.push_back(g);
+        if (g == 1) { keys.insert(keys.end(), L, nullptr); continue; }      // the ciphertext itself: no key
+        if ((g & 1) && g < 2 * n && !galois_keys.has_key(g)) throw std::invalid_argument(std::string(P) + " Galois key not present.");
+        std::vector<const uint64_t*> ptrs;
+        apply_galois_prepare(encrypted, g, galois_keys, shell, ptrs, pool);
+        if (ptrs.size() < L) throw std::invalid_argument(std::string(P) + " Key switching key has too few components for this level.");
+        keys.insert(keys.end(), ptrs.begin(), ptrs.begin() + L);
+    }
+    // the weights: NTT form at the key level (the layout of the Galois keys), one scale
+    std::vector<const uint64_t*> wptrs;
+    const size_t key_words = context_->key_context_data().value()->parms().coeff_modulus().size() * n;
+    double weight_scale = 1.0;
+    bool have_scale = false;
+    for (const auto& row : weights) {
+        if (row.size() != terms) throw std::invalid_argument(std::string(P) + " One weight (or null) per slot and term is needed.");
+        bool any = false;
+        for (const Plaintext* w : row) {
+            wptrs.push_back(w ? w->data().raw_pointer() : nullptr);
+            if (!w) continue;
+            any = true;
+            if (!w->on_device()) throw std::invalid_argument(std::string(P) + " Operand is on host; the evaluator runs on the GPU only.");
+            if (!w->is_ntt_form()) throw std::invalid_argument(std::string(P) + " Weight is not in NTT form.");
+            if (w->parms_id() != context_->key_parms_id()) throw std::invalid_argument(std::string(P) + " Weight is not at the key level.");
+            if (w->data().size() != key_words) throw std::invalid_argument(std::string(P) + " Weight is not a full key-level polynomial.");
+            if (scheme == SchemeType::CKKS) {
+                if (have_scale && !are_close_double(w->scale(), weight_scale)) throw std::invalid_argument(std::string(P) + " Weights have different scales.");
+                weight_scale = w->scale(); have_scale = true;
+            }
+        }
+        if (!any) throw std::invalid_argument(std::string(P) + " A slot has no weight.");
+    }
+    const double scale = scheme == SchemeType::CKKS ? encrypted.scale() * weight_scale : encrypted.scale();
+    if (scheme == SchemeType::CKKS && !is_scale_within_bounds(scale, cd)) throw std::invalid_argument(std::string(P) + " Scale out of bounds.");
+    utils::DynamicArray flat(slots * words, true, pool);     // [slots][2][L][N], copied out per slot
+    {
+        const int is_ckks = scheme == SchemeType::CKKS, is_ntt = encrypted.is_ntt_form() ? 1 : 0;
+        const size_t bytes = troyn_apply_galois_weighted_workspace_bytes(context_->plan(), L, terms, slots, 1, is_ntt);
+        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
+        detail::LaunchGate gate;
+        troyn_check(troyn_apply_galois_weighted_sums(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), elements.data(), keys.data(), terms,
+                                                     wptrs.data(), slots, flat.raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+    }
+    out.clear();
+    for (size_t sl = 0; sl < slots; sl++) {
+        Ciphertext d = Ciphertext::like(encrypted, false, pool);
+        d.scale() = scale;
+        hip_check(hipMemcpyAsync(d.data().raw_pointer(), flat.raw_pointer() + sl * words, words * 8, hipMemcpyDeviceToDevice, current_stream()), "copy_device_to_device");
+        out.push_back(std::move(d));
+    }
+}
+
+void Evaluator::rotate_weighted_sums(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights,
+                                     std::vector<Ciphertext>& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::rotate_weighted_sums]";
+    apply_galois_weighted(P, encrypted, hoisted_elements_from_steps(P, encrypted, steps), galois_keys, weights, destination, pool);
+}
+
+void Evaluator::rotate_weighted_sum(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const WeightRow& weights,
+                                    Ciphertext& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::rotate_weighted_sum]";
+    std::vector<Ciphertext> d;
+    apply_galois_weighted(P, encrypted, hoisted_elements_from_steps(P, encrypted, steps), galois_keys, {weights}, d, pool);
+    destination = std::move(d[0]);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Serialization  (utils/serialize.h, ciphertext.cu:93-210, plaintext.cu:20-70, kswitch_keys.cu:5-55,
 // encryption_parameters.cu:53-112): raw little-endian fields in the reference's order, so files are interchangeable.

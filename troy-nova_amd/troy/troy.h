@@ -1505,6 +1505,51 @@ public:
         Ciphertext d; rotate_sum(encrypted, steps, galois_keys, d, pool); return d;
     }
 
+    // ADDITION to the reference's interface: plaintext-weighted hoisted rotations -- the diagonal method of a plaintext matrix times an
+    //   encrypted vector (troyn_apply_galois_weighted_sums, include/troyn.h states the contract on integers).
+    //   rotate_weighted_sum:   destination = SUM_k weights[k] * rotate(encrypted, steps[k]); one digit decomposition and ONE division by the
+    //                          special prime, the weights applied before it.  A step of 0 is the unrotated ciphertext (the main diagonal).
+    //   rotate_weighted_sums:  destination[s] = SUM_k weights[s][k] * rotate(encrypted, steps[k]) for every slot s -- the baby steps of a
+    //                          baby-step/giant-step product, one slot per giant step; a null weights[s][k] leaves step k out of slot s.
+    //   apply_galois_weighted_sum(s): the same for Galois elements (the element 1 is the unrotated ciphertext).
+    //   Weights are Plaintexts in NTT form whose parms_id() is the context's KEY parms id (CKKS: encoder.encode_*(..., key_parms_id, scale);
+    //   BFV: transform_plain_to_ntt(plain, key_parms_id)), whatever the level of `encrypted`.  CKKS: the weights' scales must be close to
+    //   each other, the destination's scale is encrypted.scale() * the weight scale.  The destination has the parms id and form of `encrypted`.
+    //   Every result decrypts to what rotate_* + multiply_plain + add per term decrypt to; the payload words are NOT theirs.  A missing key
+    //   throws "Galois key not present." (no NAF chain); BFV and CKKS, BGV throws std::invalid_argument.
+    // Call combining does not take part: these methods always launch directly.
+    typedef std::vector<const Plaintext*> WeightRow;
+    void apply_galois_weighted_sums(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                    const std::vector<WeightRow>& weights, std::vector<Ciphertext>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        apply_galois_weighted("[Evaluator::apply_galois_weighted_sums]", encrypted, galois_elements, galois_keys, weights, destination, pool);
+    }
+    std::vector<Ciphertext> apply_galois_weighted_sums_new(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                                           const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; apply_galois_weighted_sums(encrypted, galois_elements, galois_keys, weights, d, pool); return d;
+    }
+    void apply_galois_weighted_sum(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                   const WeightRow& weights, Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d;
+        apply_galois_weighted("[Evaluator::apply_galois_weighted_sum]", encrypted, galois_elements, galois_keys, {weights}, d, pool);
+        destination = std::move(d[0]);
+    }
+    Ciphertext apply_galois_weighted_sum_new(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                             const WeightRow& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; apply_galois_weighted_sum(encrypted, galois_elements, galois_keys, weights, d, pool); return d;
+    }
+    void rotate_weighted_sums(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights,
+                              std::vector<Ciphertext>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::vector<Ciphertext> rotate_weighted_sums_new(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                                                     const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; rotate_weighted_sums(encrypted, steps, galois_keys, weights, d, pool); return d;
+    }
+    void rotate_weighted_sum(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const WeightRow& weights,
+                             Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext rotate_weighted_sum_new(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const WeightRow& weights,
+                                       MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; rotate_weighted_sum(encrypted, steps, galois_keys, weights, d, pool); return d;
+    }
+
     // ciphertext x plaintext -- evaluator.h (multiply_plain*, transform_plain_to_ntt*); evaluator_multiply_plain.cu,
     // evaluator_transform_ntt.cu:35-70
     void transform_plain_to_ntt(const Plaintext& plain, const ParmsID& parms_id, Plaintext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -1755,6 +1800,9 @@ private:
     void apply_galois_hoisted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, bool allow_identity, const GaloisKeys& galois_keys,
                               bool sum, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const;
     std::vector<size_t> hoisted_elements_from_steps(const char* P, const Ciphertext& encrypted, const std::vector<int>& steps) const;
+    // the weighted sums (addition): out[s] = SUM_t weights[s][t] * sigma_{elements[t]}(encrypted); element 1 is the ciphertext itself
+    void apply_galois_weighted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                               const std::vector<std::vector<const Plaintext*>>& weights, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const;
     void switch_key_internal(const Ciphertext& encrypted, const uint64_t* target, const KSwitchKeys& kswitch_keys, size_t kswitch_keys_index,
                              SwitchKeyDestinationAssignMethod assign_method, Ciphertext& destination, MemoryPoolHandle pool) const;
     void relinearize_inplace_internal(Ciphertext& encrypted, const RelinKeys& relin_keys, size_t destination_size, MemoryPoolHandle pool) const;
