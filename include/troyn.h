@@ -420,6 +420,60 @@ int troyn_ring2k_centralize(const troyn_ring2k* h, const void* src, size_t count
 int troyn_ring2k_scale_down(const troyn_ring2k* h, const uint64_t* in, void* dst, troyn_stream_t stream);
 int troyn_ring2k_decentralize(const troyn_ring2k* h, const uint64_t* in, void* dst, uint64_t correction_lo, uint64_t correction_hi, troyn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * CKKS encoder on the device (src/ckks_encoder.cu: kernel_set_conjugate_values, kernel_fft_transform_{from,to}_rev_layer,
+ * kernel_set_plaintext_value_array_*, decode_internal).  One handle per plan; it holds the slot index map (Galois generator 3,
+ * bit-reversed) and the root powers of both FFT directions, built on the host with the formulas of CKKSEncoder::CKKSEncoder and
+ * uploaded: their contents never depend on the device.  Rows 0..L-1 of a plaintext are under the plan's moduli 0..L-1; L = the plan's
+ * modulus count gives the key-level layout that troyn_apply_galois_weighted_sums reads.
+ *
+ * ENCODING CONTRACT: the words equal those of the host path (troy/troy.cpp), which is the specification:
+ *   encode_complex64_simd   a[0..N) = 0; a[index_map[i]] = values[i], a[index_map[i + N/2]] = conj(values[i]) for i < count;
+ *                           Gentleman-Sande layers, gap 1, 2, .., N/2, root_index counting up from 1 across the layers:
+ *                             r = inv_root_powers[root_index++]; u = a[j], v = a[j + gap]; d = u - v; a[j] = u + v;
+ *                             a[j + gap] = (d.re * r.re - d.im * r.im, d.re * r.im + d.im * r.re);
+ *                           coefficient j = a[j].re * (scale / N)
+ *   encode_float64_polynomial  coefficient j = coeffs[j] * scale, zero for j >= count
+ *   set_plaintext           v = nearbyint(coefficient) (half to even); a = |v|; hi = (uint64)(a / 2^64), lo = (uint64)(a - hi * 2^64);
+ *                           residue_i = (hi * 2^64 + lo) mod q_i, negated modulo q_i for v < 0; then the forward NTT of every row
+ * Both transforms use only IEEE double +, -, * in that order and association (no fused multiply-add on either side), so a device kernel
+ * that runs the same butterflies on the same table entries gives the same bits however it divides the layers.
+ * |v| >= 2^128 (or a NaN) sets too_large[item] = 1 (0 otherwise); that item's rows are unspecified, every other item is unaffected; with too_large ==
+ * NULL such an item is silently unspecified.
+ *
+ * DECODING CONTRACT (the host path's long double Horner has no device counterpart, so this is defined exactly):
+ *   1. inverse NTT of the L rows;  2. x = the centred representative in (-Q/2, Q/2] of the residues, Q = q_0 ... q_{L-1};
+ *   3. coefficient j = (x correctly rounded to the nearest double, ties to even) / scale, IEEE division;
+ *   4. troyn_ckks_decode_simd continues with the Cooley-Tukey layers of decode_complex64_simd on (coefficient, 0), gap N/2, .., 1:
+ *        r = root_powers[root_index++]; u = a[j], w = a[j + gap]; v = (w.re * r.re - w.im * r.im, w.re * r.im + w.im * r.re);
+ *        a[j] = u + v; a[j + gap] = u - v;      slot i = a[index_map[i]]
+ *   L <= 16; above that TROYN_E_UNSUPPORTED.
+ *
+ * values [batch][count][2] (re, im; 16-byte aligned), coeffs [batch][count], out u64 [batch][L][N] in NTT form / double [batch][N] /
+ * double [batch][N/2][2], too_large u32 [batch]: all device memory.  The encoders need troyn_ckks_encode_workspace_bytes(h, batch) bytes (the points
+ * between the two FFT passes at N >= 16384; nothing below, where the workspace may be null), the decoders troyn_ckks_workspace_bytes(h, L, batch),
+ * which is never the smaller of the two.
+ * TROYN_E_INVALID: a null handle or pointer, a misaligned pointer (16 bytes; 8 for coeffs, 4 for too_large), L outside [1, n_moduli],
+ * count above N/2 (N for polynomials), an encoding scale that is not positive or has log2(scale) + 1 >= the total bit count of the L
+ * primes.  TROYN_E_WORKSPACE: a workspace below the entry's size.  batch == 0 returns TROYN_OK and touches nothing; only the handle and L
+ * are looked at before.  count == 0 encodes zero (the source may then be null).  Everything is enqueued on the caller's stream; no entry synchronises or
+ * touches the default stream.  troyn_ckks_get_tables copies the host tables out (index_map [N], root_powers / inv_root_powers [N][2]).
+ * ------------------------------------------------------------------------------------- */
+typedef struct troyn_ckks troyn_ckks;
+int troyn_ckks_create(troyn_ckks** out, const troyn_plan* plan);
+int troyn_ckks_destroy(troyn_ckks* h);
+int troyn_ckks_get_tables(const troyn_ckks* h, uint32_t* index_map, double* root_powers, double* inv_root_powers);
+size_t troyn_ckks_workspace_bytes(const troyn_ckks* h, uint32_t L, size_t batch);
+size_t troyn_ckks_encode_workspace_bytes(const troyn_ckks* h, size_t batch);
+int troyn_ckks_encode_simd(const troyn_ckks* h, uint32_t L, const double* values, size_t count, double scale, uint64_t* out, uint32_t* too_large,
+                           void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+int troyn_ckks_encode_polynomial(const troyn_ckks* h, uint32_t L, const double* coeffs, size_t count, double scale, uint64_t* out, uint32_t* too_large,
+                                 void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+int troyn_ckks_decode_polynomial(const troyn_ckks* h, uint32_t L, const uint64_t* plain, double scale, double* out, void* workspace, size_t workspace_bytes,
+                                 size_t batch, troyn_stream_t stream);
+int troyn_ckks_decode_simd(const troyn_ckks* h, uint32_t L, const uint64_t* plain, double scale, double* out, void* workspace, size_t workspace_bytes,
+                           size_t batch, troyn_stream_t stream);
+
 /* RLWE / LWE packing (evaluator_lwes.cu):
  *   troyn_negacyclic_shift     utils::negacyclic_shift_ps (utils/poly_small_mod.cu:927-968): multiply `count` RNS polynomials by
  *                              X^shift, any shift (taken modulo 2N as the reference does); out of place

@@ -96,6 +96,15 @@ SYMBOLS = {
     "troyn_ring2k_centralize": (C.c_int, [vp, vp, sz, vp, vp]),
     "troyn_ring2k_scale_down": (C.c_int, [vp, vp, vp, vp]),
     "troyn_ring2k_decentralize": (C.c_int, [vp, vp, vp, u64, u64, vp]),
+    "troyn_ckks_create": (C.c_int, [C.POINTER(vp), vp]),
+    "troyn_ckks_destroy": (C.c_int, [vp]),
+    "troyn_ckks_get_tables": (C.c_int, [vp, vp, vp, vp]),
+    "troyn_ckks_workspace_bytes": (sz, [vp, u32, sz]),
+    "troyn_ckks_encode_workspace_bytes": (sz, [vp, sz]),
+    "troyn_ckks_encode_simd": (C.c_int, [vp, u32, vp, sz, C.c_double, vp, vp, vp, sz, sz, vp]),
+    "troyn_ckks_encode_polynomial": (C.c_int, [vp, u32, vp, sz, C.c_double, vp, vp, vp, sz, sz, vp]),
+    "troyn_ckks_decode_polynomial": (C.c_int, [vp, u32, vp, C.c_double, vp, vp, sz, sz, vp]),
+    "troyn_ckks_decode_simd": (C.c_int, [vp, u32, vp, C.c_double, vp, vp, sz, sz, vp]),
     "troyn_gather_workspace_bytes": (sz, [sz]),
     "troyn_gather": (C.c_int, [vp, sz, sz, vp, vp, sz, vp]),
     "troyn_scatter": (C.c_int, [vp, vp, sz, sz, vp, sz, vp]),

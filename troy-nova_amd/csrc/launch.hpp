@@ -109,4 +109,14 @@ bool launch_behz2_floor_pass2(unsigned L, size_t items, hipStream_t s, const Beh
                               const double* tw_q, const double* tw_aux, const DevModulus* q_mods, const DevModulus* aux_mods);
 void launch_behz2_floor(unsigned L, bool smallq, unsigned grid, hipStream_t s, unsigned chunks, const Behz2Dev& c, const u64* in_q, const u64* in_bsk, u64* out, bool aux50 = false);
 
+// CKKS encoder (troyn_ckks.hip, ckks_kernels.hpp): the FP64 canonical-embedding FFT with its fused first loads / last stores (every pass of the
+// size's form, ntt_sizes.hpp column fft), the coefficient-wise encoding, and the CRT composition of a decoded plaintext (L <= CKKS_MAX_L)
+struct CkksFftArgs;
+struct CkksComposeArgs;
+bool ckks_fft_two_pass(unsigned log_n);
+bool launch_ckks_fft(unsigned log_n, bool decode, const CkksFftArgs& a, size_t batch, hipStream_t s);
+void launch_ckks_encode_polynomial(const double* coeffs, unsigned count, double scale, unsigned n, const DevModulus* mods, unsigned L, u64* residues,
+                                   unsigned* too_large, size_t batch, hipStream_t s);
+bool launch_ckks_compose(const CkksComposeArgs& a, size_t batch, hipStream_t s);
+
 }  // namespace troyn

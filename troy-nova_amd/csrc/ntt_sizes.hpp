@@ -22,6 +22,7 @@ struct NttSize {
     int ks_mac_eb;       // first-generation ks_mac_kernel (0: not built -- N >= 8192 takes ksmac2_kernel / ksmaci_kernel)
     bool tensor_acc;     // tensor_accumulate_kernel is built
     bool merged_tail;    // mrr_quartet_kernel / mrr_quartet_load_kernel are built: single passes of the two-pass form can be launched alone
+    NttTile fft;         // FP64 complex FFT of the CKKS encoder (ckks_kernels.hpp): a point is 16 bytes, so a whole transform fits one workgroup's LDS up to N = 8192
 };
 
 // N = 4096 / 8192: 8 coefficients per thread (EB = 3) doubles the waves per tile, so a CU holds 32 waves instead of 16; measured 5-14 %
@@ -30,15 +31,15 @@ struct NttSize {
 // has); launches that leave most of the chip idle take the two-pass form of the larger rings -- 4 workgroups per limb and pass, ~3x shorter.
 constexpr int NTT_LOG_N_MIN = 10, NTT_LOG_N_MAX = 17;
 constexpr NttSize NTT_SIZES[] = {
-    // log_n  full      small                  tensor    ks_mac  acc    merged tail
-    {10,      {10, 4},  {0, 0},                {10, 4},  4,      false, false},
-    {11,      {11, 4},  {0, 0},                {11, 4},  4,      false, false},
-    {12,      {12, 3},  {0, 0},                {12, 3},  4,      false, false},
-    {13,      {13, 3},  {11, TROYN_SMALL_EB},  {13, 3},  0,      false, true},
-    {14,      {14, 4},  {12, TROYN_SMALL_EB},  {14, 4},  0,      false, true},
-    {15,      {12, 4},  {0, 0},                {12, 4},  0,      true,  true},
-    {16,      {12, 4},  {0, 0},                {12, 4},  0,      true,  false},
-    {17,      {12, 4},  {0, 0},                {0, 0},   0,      false, false},
+    // log_n  full      small                  tensor    ks_mac  acc    merged tail  fft
+    {10,      {10, 4},  {0, 0},                {10, 4},  4,      false, false,     {10, 3}},
+    {11,      {11, 4},  {0, 0},                {11, 4},  4,      false, false,     {11, 3}},
+    {12,      {12, 3},  {0, 0},                {12, 3},  4,      false, false,     {12, 3}},
+    {13,      {13, 3},  {11, TROYN_SMALL_EB},  {13, 3},  0,      false, true,      {13, 3}},
+    {14,      {14, 4},  {12, TROYN_SMALL_EB},  {14, 4},  0,      false, true,      {12, 3}},
+    {15,      {12, 4},  {0, 0},                {12, 4},  0,      true,  true,      {12, 3}},
+    {16,      {12, 4},  {0, 0},                {12, 4},  0,      true,  false,     {12, 3}},
+    {17,      {12, 4},  {0, 0},                {0, 0},   0,      false, false,     {12, 3}},
 };
 constexpr const NttSize& ntt_size(int log_n) { return NTT_SIZES[log_n - NTT_LOG_N_MIN]; }
 static_assert(ntt_size(NTT_LOG_N_MIN).log_n == NTT_LOG_N_MIN && ntt_size(13).log_n == 13 && ntt_size(NTT_LOG_N_MAX).log_n == NTT_LOG_N_MAX, "row i holds log_n = NTT_LOG_N_MIN + i");

@@ -4,6 +4,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
+#include <complex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +28,8 @@
 #include "ksmaci_kernels.hpp"
 #include "poly_kernels.hpp"
 #include "hoist_kernels.hpp"
+#include "ckks_kernels.hpp"
+#include "ckks_tables.hpp"
 
 using namespace troyn;
 
@@ -3328,6 +3332,199 @@ extern "C" int troyn_ring2k_decentralize(const troyn_ring2k* h, const uint64_t* 
     hipLaunchKernelGGL(ring2k_decentralize_kernel, dim3((h->dev.n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->dev, (const u64*)in, dst, (u64)fix, (u64)(fix >> 64));
     LAUNCH_CHECK();
     return TROYN_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// CKKS encoder (src/ckks_encoder.cu): canonical-embedding FFT, RNS reduction and CRT composition on the device
+// ---------------------------------------------------------------------------------------
+struct troyn_ckks {
+    const troyn_plan* plan = nullptr;
+    std::vector<uint32_t> index_map;                            // host copies (KAT hook)
+    std::vector<std::complex<double>> roots, inv_roots;
+    unsigned* d_slot_of = nullptr;                              // [N] inverse of index_map
+    double2* d_roots = nullptr;                                 // [N]
+    double2* d_inv_roots = nullptr;                             // [N]
+    ulonglong2* d_garner = nullptr;                             // [K][K] q_j^-1 mod q_i, j < i
+    u64* d_q_words = nullptr;                                   // [min(K, CKKS_MAX_L)][2][CKKS_MAX_L]: Q_L, floor(Q_L / 2)
+};
+
+extern "C" int troyn_ckks_destroy(troyn_ckks* h) {
+    if (!h) return TROYN_OK;
+    for (void* p : {(void*)h->d_slot_of, (void*)h->d_roots, (void*)h->d_inv_roots, (void*)h->d_garner, (void*)h->d_q_words})
+        if (p) (void)hipFree(p);
+    delete h;
+    return TROYN_OK;
+}
+
+extern "C" int troyn_ckks_create(troyn_ckks** out, const troyn_plan* plan) {
+    const char* P = "[CKKSEncoder::CKKSEncoder]";
+    if (!out || !plan) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    *out = nullptr;
+    select_device(plan);
+    std::unique_ptr<troyn_ckks, int (*)(troyn_ckks*)> h(new troyn_ckks, troyn_ckks_destroy);
+    h->plan = plan;
+    const size_t n = plan->n, K = plan->K;
+    ckks_tables::build(plan->log_n, h->index_map, h->roots, h->inv_roots);
+    std::vector<unsigned> slot_of(n);
+    for (size_t i = 0; i < n; i++) slot_of[h->index_map[i]] = (unsigned)i;
+    std::vector<double2> fwd(n), inv(n);
+    for (size_t i = 0; i < n; i++) { fwd[i] = make_double2(h->roots[i].real(), h->roots[i].imag()); inv[i] = make_double2(h->inv_roots[i].real(), h->inv_roots[i].imag()); }
+    std::vector<ulonglong2> garner(K * K, make_ulonglong2(0, 0));
+    for (size_t i = 0; i < K; i++) for (size_t j = 0; j < i; j++) {
+        const u64 qi = plan->moduli[i];
+        u64 w = 0;
+        if (!host::invmod(plan->moduli[j] % qi, qi, w)) return fail(TROYN_E_MODULUS, std::string(P) + " coeff_modulus is not pairwise coprime");
+        garner[i * K + j] = shoup_pair(w, qi);
+    }
+    const size_t levels = std::min<size_t>(K, CKKS_MAX_L);
+    std::vector<u64> words(levels * 2 * CKKS_MAX_L, 0);
+    for (size_t L = 1; L <= levels; L++) {
+        const std::vector<u64> big = host::big_product(std::vector<u64>(plan->moduli.begin(), plan->moduli.begin() + L));
+        u64* qw = &words[(L - 1) * 2 * CKKS_MAX_L];
+        for (size_t w = 0; w < big.size(); w++) qw[w] = big[w];
+        for (size_t w = 0; w < (size_t)CKKS_MAX_L; w++) qw[CKKS_MAX_L + w] = (qw[w] >> 1) | (w + 1 < (size_t)CKKS_MAX_L ? qw[w + 1] << 63 : 0);
+    }
+    if (int rc = upload_vector(&h->d_slot_of, slot_of)) return rc;
+    if (int rc = upload_vector(&h->d_roots, fwd)) return rc;
+    if (int rc = upload_vector(&h->d_inv_roots, inv)) return rc;
+    if (int rc = upload_vector(&h->d_garner, garner)) return rc;
+    if (int rc = upload_vector(&h->d_q_words, words)) return rc;
+    *out = h.release();
+    return TROYN_OK;
+}
+
+extern "C" int troyn_ckks_get_tables(const troyn_ckks* h, uint32_t* index_map, double* root_powers, double* inv_root_powers) {
+    if (!h || !index_map || !root_powers || !inv_root_powers) return fail(TROYN_E_INVALID, "[troyn_ckks_get_tables] null argument");
+    const size_t n = h->plan->n;
+    for (size_t i = 0; i < n; i++) {
+        index_map[i] = h->index_map[i];
+        root_powers[2 * i] = h->roots[i].real(); root_powers[2 * i + 1] = h->roots[i].imag();
+        inv_root_powers[2 * i] = h->inv_roots[i].real(); inv_root_powers[2 * i + 1] = h->inv_roots[i].imag();
+    }
+    return TROYN_OK;
+}
+
+namespace {
+// the points between the two FFT passes come first (all an encoding needs: nothing at the one-pass sizes); decoding adds the residues of the inverse
+// NTT and the real coefficients
+struct CkksWorkspace { size_t work, residues, coeffs, total; };
+inline size_t ckks_align(size_t b) { return (b + 255) & ~(size_t)255; }
+CkksWorkspace ckks_workspace(const troyn_plan* p, size_t L, size_t batch, bool decode) {
+    CkksWorkspace w;
+    w.work = 0;
+    w.residues = ckks_fft_two_pass(p->log_n) ? ckks_align(batch * p->n * sizeof(double2)) : 0;
+    w.coeffs = w.residues + ckks_align(batch * L * p->n * sizeof(u64));
+    w.total = decode ? w.coeffs + ckks_align(batch * p->n * sizeof(double)) : w.residues;
+    return w;
+}
+}  // namespace
+
+extern "C" size_t troyn_ckks_workspace_bytes(const troyn_ckks* h, uint32_t L, size_t batch) {
+    if (!h || L < 1 || L > h->plan->K) return 0;
+    return ckks_workspace(h->plan, L, batch, true).total;
+}
+extern "C" size_t troyn_ckks_encode_workspace_bytes(const troyn_ckks* h, size_t batch) {
+    if (!h) return 0;
+    return ckks_workspace(h->plan, 1, batch, false).total;
+}
+
+// what every entry checks the same way; 1: nothing to do (batch == 0)
+static int ckks_check(const char* P, const troyn_ckks* h, uint32_t L, const void* in, const void* out, const void* ws, size_t ws_bytes, size_t batch, unsigned in_align, bool decode) {
+    if (!h) return fail(TROYN_E_INVALID, std::string(P) + " null handle");
+    if (L < 1 || L > h->plan->K) return fail(TROYN_E_INVALID, std::string(P) + " modulus count out of range");
+    if (batch == 0) return 1;
+    if (!in || !out) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if (((uintptr_t)in & (in_align - 1)) || ((uintptr_t)out & 15) || ((uintptr_t)ws & 15)) return fail(TROYN_E_INVALID, std::string(P) + " misaligned pointer");
+    if (batch << (h->plan->log_n - 8) > 0x7fffffffull || batch * L > 0x7fffffffull) return fail(TROYN_E_INVALID, std::string(P) + " batch too large for one launch");
+    const size_t need = ckks_workspace(h->plan, L, batch, decode).total;
+    if (ws_bytes < need || (need && !ws)) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    return TROYN_OK;
+}
+
+static int ckks_encode(const troyn_ckks* h, bool simd, uint32_t L, const double* src, size_t count, double scale, uint64_t* out, uint32_t* too_large,
+                       void* ws, size_t ws_bytes, size_t batch, troyn_stream_t stream) {
+    const char* P = simd ? "[CKKSEncoder::encode_internal_complex_array]" : "[CKKSEncoder::encode_internal_double_polynomial]";
+    select_device(h);
+    // count == 0 reads nothing: a null source is then allowed
+    alignas(16) static const double none[2] = {0, 0};
+    const int rc = ckks_check(P, h, L, count ? (const void*)src : (const void*)none, out, ws, ws_bytes, batch, simd ? 16 : 8, false);
+    if (rc < 0) return rc;
+    if (rc == 1) return TROYN_OK;
+    const troyn_plan* p = h->plan;
+    if (count > (simd ? p->n / 2 : p->n)) return fail(TROYN_E_INVALID, std::string(P) + " Too many input values.");
+    size_t total_bits = 0;
+    for (uint32_t i = 0; i < L; i++) total_bits += 64 - (size_t)__builtin_clzll(p->moduli[i]);
+    if (!(scale > 0) || std::log2(scale) + 1.0 >= static_cast<double>(total_bits)) return fail(TROYN_E_INVALID, std::string(P) + " scale out of bounds.");
+    if (too_large && ((uintptr_t)too_large & 3)) return fail(TROYN_E_INVALID, std::string(P) + " misaligned pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (too_large) HIP_TRY(hipMemsetAsync(too_large, 0, batch * sizeof(uint32_t), s));
+    if (simd) {
+        CkksFftArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.roots = h->d_inv_roots; a.slot_of = h->d_slot_of;
+        a.values = reinterpret_cast<const double2*>(src); a.count = (unsigned)count;
+        a.work = reinterpret_cast<double2*>((char*)ws + ckks_workspace(p, L, batch, false).work);
+        a.residues = (u64*)out; a.mods = p->d_mods; a.L = L;
+        a.fix = scale / static_cast<double>(p->n);
+        a.too_large = too_large;
+        if (!launch_ckks_fft(p->log_n, false, a, batch, s)) return fail(TROYN_E_UNSUPPORTED, std::string(P) + " no FFT kernel for this size");
+    } else {
+        launch_ckks_encode_polynomial(src, (unsigned)count, scale, p->n, p->d_mods, L, (u64*)out, too_large, batch, s);
+    }
+    LAUNCH_CHECK();
+    NttArgs na = contiguous_args(p, (const u64*)out, (u64*)out, 1, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
+    return launch_ntt(p, na, batch, false, s);
+}
+
+extern "C" int troyn_ckks_encode_simd(const troyn_ckks* h, uint32_t L, const double* values, size_t count, double scale, uint64_t* out, uint32_t* too_large,
+                                      void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    return ckks_encode(h, true, L, values, count, scale, out, too_large, workspace, workspace_bytes, batch, stream);
+}
+extern "C" int troyn_ckks_encode_polynomial(const troyn_ckks* h, uint32_t L, const double* coeffs, size_t count, double scale, uint64_t* out, uint32_t* too_large,
+                                            void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    return ckks_encode(h, false, L, coeffs, count, scale, out, too_large, workspace, workspace_bytes, batch, stream);
+}
+
+static int ckks_decode(const troyn_ckks* h, bool simd, uint32_t L, const uint64_t* plain, double scale, double* out, void* ws, size_t ws_bytes, size_t batch,
+                       troyn_stream_t stream) {
+    const char* P = "[CKKSEncoder::decode_internal]";
+    select_device(h);
+    const int rc = ckks_check(P, h, L, plain, out, ws, ws_bytes, batch, 16, true);
+    if (rc < 0) return rc;
+    if (rc == 1) return TROYN_OK;
+    if (L > (uint32_t)CKKS_MAX_L) return fail(TROYN_E_UNSUPPORTED, std::string(P) + " more than 16 moduli");
+    const troyn_plan* p = h->plan;
+    hipStream_t s = (hipStream_t)stream;
+    const CkksWorkspace w = ckks_workspace(p, L, batch, true);
+    u64* residues = reinterpret_cast<u64*>((char*)ws + w.residues);
+    double* coeffs = simd ? reinterpret_cast<double*>((char*)ws + w.coeffs) : out;
+    NttArgs na = contiguous_args(p, (const u64*)plain, residues, 1, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
+    if (int r = launch_ntt(p, na, batch, true, s)) return r;
+    CkksComposeArgs c;
+    std::memset(&c, 0, sizeof(c));
+    c.residues = residues; c.mods = p->d_mods; c.garner = h->d_garner; c.K = p->K; c.L = L; c.n = p->n;
+    c.q_words = h->d_q_words + (size_t)(L - 1) * 2 * CKKS_MAX_L; c.half_words = c.q_words + CKKS_MAX_L;
+    c.scale = scale; c.out = coeffs;
+    if (!launch_ckks_compose(c, batch, s)) return fail(TROYN_E_UNSUPPORTED, std::string(P) + " more than 16 moduli");
+    if (simd) {
+        CkksFftArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.roots = h->d_roots; a.slot_of = h->d_slot_of; a.coeffs = coeffs;
+        a.work = reinterpret_cast<double2*>((char*)ws + w.work);
+        a.slots = reinterpret_cast<double2*>(out);
+        if (!launch_ckks_fft(p->log_n, true, a, batch, s)) return fail(TROYN_E_UNSUPPORTED, std::string(P) + " no FFT kernel for this size");
+    }
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+
+extern "C" int troyn_ckks_decode_polynomial(const troyn_ckks* h, uint32_t L, const uint64_t* plain, double scale, double* out, void* workspace, size_t workspace_bytes,
+                                            size_t batch, troyn_stream_t stream) {
+    return ckks_decode(h, false, L, plain, scale, out, workspace, workspace_bytes, batch, stream);
+}
+extern "C" int troyn_ckks_decode_simd(const troyn_ckks* h, uint32_t L, const uint64_t* plain, double scale, double* out, void* workspace, size_t workspace_bytes,
+                                      size_t batch, troyn_stream_t stream) {
+    return ckks_decode(h, true, L, plain, scale, out, workspace, workspace_bytes, batch, stream);
 }
 
 extern "C" size_t troyn_gather_workspace_bytes(size_t count) { return (count + 1) * sizeof(u64); }

@@ -1,0 +1,51 @@
+// troyn_ckks.hip -- the instantiations and launches of the CKKS encoder kernels (ckks_kernels.hpp); troyn.hip (the C-ABI) only calls these.
+#include "ckks_kernels.hpp"
+#include "launch.hpp"
+
+namespace troyn {
+
+bool ckks_fft_two_pass(unsigned log_n) {
+    return log_n >= (unsigned)NTT_LOG_N_MIN && log_n <= (unsigned)NTT_LOG_N_MAX && ntt_size((int)log_n).fft.tb < (int)log_n;
+}
+
+template <int LOGN, bool DEC>
+static void ckks_fft_passes(const CkksFftArgs& a, size_t batch, hipStream_t s) {
+    constexpr int TB = ntt_size(LOGN).fft.tb;
+    static_assert(ntt_size(LOGN).fft.eb == 3, "ckks_fft_kernel holds 8 points per thread");
+    const dim3 grid((unsigned)(batch << (LOGN - TB))), block(1u << (TB - 3));
+    if constexpr (TB == LOGN) {
+        hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, DEC, false>), grid, block, 0, s, a);
+    } else if constexpr (DEC) {          // gap N/2 downwards: the strided layers first
+        hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, true, true>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, true, false>), grid, block, 0, s, a);
+    } else {                             // gap 1 upwards: the contiguous tiles first
+        hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, false, false>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, false, true>), grid, block, 0, s, a);
+    }
+}
+
+bool launch_ckks_fft(unsigned log_n, bool decode, const CkksFftArgs& a, size_t batch, hipStream_t s) {
+    return for_ntt_size<0>(log_n, [&](auto size) {
+        constexpr int LOGN = decltype(size)::value;
+        if (decode) ckks_fft_passes<LOGN, true>(a, batch, s);
+        else ckks_fft_passes<LOGN, false>(a, batch, s);
+        return true;
+    });
+}
+
+void launch_ckks_encode_polynomial(const double* coeffs, unsigned count, double scale, unsigned n, const DevModulus* mods, unsigned L, u64* residues,
+                                   unsigned* too_large, size_t batch, hipStream_t s) {
+    hipLaunchKernelGGL(ckks_encode_polynomial_kernel, dim3((unsigned)(batch * (n / 256))), dim3(256), 0, s, coeffs, count, scale, n, mods, L, residues, too_large);
+}
+
+bool launch_ckks_compose(const CkksComposeArgs& a, size_t batch, hipStream_t s) {
+    const dim3 grid((unsigned)(batch * (a.n / 256))), block(256);
+    if (a.L <= 2) hipLaunchKernelGGL(ckks_compose_kernel<2>, grid, block, 0, s, a);
+    else if (a.L <= 4) hipLaunchKernelGGL(ckks_compose_kernel<4>, grid, block, 0, s, a);
+    else if (a.L <= 8) hipLaunchKernelGGL(ckks_compose_kernel<8>, grid, block, 0, s, a);
+    else if (a.L <= (unsigned)CKKS_MAX_L) hipLaunchKernelGGL(ckks_compose_kernel<CKKS_MAX_L>, grid, block, 0, s, a);
+    else return false;
+    return true;
+}
+
+}  // namespace troyn

@@ -5,6 +5,7 @@ layout [batch][poly][limb][N] (ciphertext.h:211-247).  Every method only enqueue
 current torch stream; nothing is computed on the CPU.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -59,6 +60,9 @@ class Plan:
         self._ws = None
 
     def close(self):
+        if getattr(self, "_ckks", None) is not None:
+            self._ckks.close()
+            self._ckks = None
         if getattr(self, "h", None):
             self.lib.troyn_plan_destroy(self.h)
             self.h = None
@@ -68,6 +72,12 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+    def ckks_handle(self):
+        """the plan's CkksEncoder (troyn_ckks), created on first use"""
+        if getattr(self, "_ckks", None) is None:
+            self._ckks = CkksEncoder(self)
+        return self._ckks
 
     def set_option(self, name, value=None):
         """an A/B switch of this plan (the library reads the TROYN_* environment variables once, in troyn_plan_create; never on a call)"""
@@ -640,6 +650,84 @@ class Ring2k:
         capi.check(self.plan.lib.troyn_ring2k_decentralize(self.h, _ptr(plain), _ptr(out), cf & ((1 << 64) - 1), (cf >> 64) & ((1 << 64) - 1), _stream()))
         raw = out.cpu().numpy().tobytes()
         return [int.from_bytes(raw[i * self.elem_bytes:(i + 1) * self.elem_bytes], "little") for i in range(self.plan.n)]
+
+
+class CkksEncoder:
+    """troyn_ckks: the CKKS encoder on the device (src/ckks_encoder.cu).  Values are torch.float64 CUDA tensors (complex values as [..][2] = re, im),
+    plaintexts int64 tensors [batch][L][N] in NTT form under the plan's first L moduli."""
+
+    def __init__(self, plan):
+        self._plan = weakref.ref(plan)       # the plan may own this object (Plan.ckks_handle): no cycle between two objects with __del__
+        self.lib = plan.lib
+        h = C.c_void_p()
+        capi.check(plan.lib.troyn_ckks_create(C.byref(h), plan.h))
+        self.h = h
+
+    @property
+    def plan(self):
+        plan = self._plan()
+        if plan is None or not plan.h:
+            raise capi.TroynError("[troyn] the plan of this CkksEncoder is gone")
+        return plan
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.troyn_ckks_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def tables(self):
+        """host copies: index_map uint32 [N], root_powers and inv_root_powers float64 [N][2]"""
+        n = self.plan.n
+        index_map, roots, inv_roots = np.zeros(n, dtype=np.uint32), np.zeros((n, 2), dtype=np.float64), np.zeros((n, 2), dtype=np.float64)
+        capi.check(self.plan.lib.troyn_ckks_get_tables(self.h, C.c_void_p(index_map.ctypes.data), C.c_void_p(roots.ctypes.data), C.c_void_p(inv_roots.ctypes.data)))
+        return index_map, roots, inv_roots
+
+    def _f64(self, t):
+        if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda:
+            raise capi.TroynInvalidArgument("[troyn] values must be contiguous float64 CUDA tensors")
+        return C.c_void_p(t.data_ptr())
+
+    def _ws(self, nbytes):
+        ws = self.plan.workspace(nbytes)
+        return C.c_void_p(ws.data_ptr()), ws.numel()
+
+    def _encode(self, fn, L, values, batch, count, scale, flags):
+        out = torch.empty((batch, L, self.plan.n), dtype=torch.int64, device=self.plan.device)
+        too_large = torch.empty(max(batch, 1), dtype=torch.int32, device=self.plan.device) if flags else None
+        ws, ws_bytes = self._ws(self.lib.troyn_ckks_encode_workspace_bytes(self.h, batch))
+        capi.check(fn(self.h, L, self._f64(values), count, float(scale), _ptr(out), C.c_void_p(too_large.data_ptr()) if flags else None, ws, ws_bytes, batch, _stream()))
+        return (out, too_large[:batch]) if flags else out
+
+    def encode_simd(self, L, values, scale, flags=False):
+        """values [batch][count][2] -> [batch][L][N] (and the too_large flags, int32 [batch], with flags=True)"""
+        batch, count = values.shape[0], values.shape[1]
+        return self._encode(self.plan.lib.troyn_ckks_encode_simd, L, values, batch, count, scale, flags)
+
+    def encode_polynomial(self, L, coeffs, scale, flags=False):
+        """coeffs [batch][count] -> [batch][L][N]"""
+        batch, count = coeffs.shape[0], coeffs.shape[1]
+        return self._encode(self.plan.lib.troyn_ckks_encode_polynomial, L, coeffs, batch, count, scale, flags)
+
+    def _decode(self, fn, L, plain, scale, shape):
+        batch = plain.numel() // (L * self.plan.n)
+        out = torch.empty((batch,) + shape, dtype=torch.float64, device=self.plan.device)
+        ws, ws_bytes = self._ws(self.lib.troyn_ckks_workspace_bytes(self.h, L, batch))
+        capi.check(fn(self.h, L, _ptr(plain), float(scale), C.c_void_p(out.data_ptr()), ws, ws_bytes, batch, _stream()))
+        return out
+
+    def decode_polynomial(self, L, plain, scale):
+        """plain [batch][L][N] NTT form -> float64 [batch][N]"""
+        return self._decode(self.plan.lib.troyn_ckks_decode_polynomial, L, plain, scale, (self.plan.n,))
+
+    def decode_simd(self, L, plain, scale):
+        """plain [batch][L][N] NTT form -> float64 [batch][N/2][2]"""
+        return self._decode(self.plan.lib.troyn_ckks_decode_simd, L, plain, scale, (self.plan.n // 2, 2))
 
 
 class Behz:

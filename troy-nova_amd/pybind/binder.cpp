@@ -366,7 +366,32 @@ PYBIND11_MODULE(pytroy_raw, m) {
         .def("encode_integer64_polynomial", [](const CKKSEncoder& s, const std::vector<int64_t>& v, std::optional<ParmsID> id, Plaintext& d, PoolArg p) { s.encode_integer64_polynomial(v, id, d, P(p)); },
              py::arg("values"), py::arg("parms_id"), py::arg("destination"), POOL)
         .def("encode_integer64_polynomial_new", [](const CKKSEncoder& s, const std::vector<int64_t>& v, std::optional<ParmsID> id, PoolArg p) { return s.encode_integer64_polynomial_new(v, id, P(p)); },
-             py::arg("values"), py::arg("parms_id"), POOL);
+             py::arg("values"), py::arg("parms_id"), POOL)
+        // batched, on the device (additions to the reference's surface).  The slice forms take (address, length, on_device) views, e.g. of a torch tensor
+        .def("encode_complex64_simd_new_batched", [](const CKKSEncoder& s, const std::vector<std::vector<std::complex<double>>>& v, std::optional<ParmsID> id, double scale, PoolArg p) {
+            return s.encode_complex64_simd_new_batched(v, id, scale, P(p)); }, py::arg("values"), py::arg("parms_id"), py::arg("scale"), POOL)
+        .def("encode_float64_polynomial_new_batched", [](const CKKSEncoder& s, const std::vector<std::vector<double>>& v, std::optional<ParmsID> id, double scale, PoolArg p) {
+            return s.encode_float64_polynomial_new_batched(v, id, scale, P(p)); }, py::arg("values"), py::arg("parms_id"), py::arg("scale"), POOL)
+        .def("encode_complex64_simd_batched", [](const CKKSEncoder& s, const std::vector<std::vector<std::complex<double>>>& v, std::optional<ParmsID> id, double scale, const std::vector<Plaintext*>& d, PoolArg p) {
+            s.encode_complex64_simd_batched(v, id, scale, d, P(p)); }, py::arg("values"), py::arg("parms_id"), py::arg("scale"), py::arg("destinations"), POOL)
+        .def("encode_float64_polynomial_batched", [](const CKKSEncoder& s, const std::vector<std::vector<double>>& v, std::optional<ParmsID> id, double scale, const std::vector<Plaintext*>& d, PoolArg p) {
+            s.encode_float64_polynomial_batched(v, id, scale, d, P(p)); }, py::arg("values"), py::arg("parms_id"), py::arg("scale"), py::arg("destinations"), POOL)
+        .def("encode_complex64_simd_slice_new_batched", [](const CKKSEncoder& s, const std::vector<std::tuple<uintptr_t, size_t, bool>>& v, std::optional<ParmsID> id, double scale, PoolArg p) {
+            utils::ConstSliceVec<std::complex<double>> views;
+            for (const auto& [address, length, on_device] : v) views.emplace_back(reinterpret_cast<const std::complex<double>*>(address), length, on_device);
+            return s.encode_complex64_simd_slice_new_batched(views, id, scale, P(p)); }, py::arg("values"), py::arg("parms_id"), py::arg("scale"), POOL)
+        .def("encode_float64_polynomial_slice_new_batched", [](const CKKSEncoder& s, const std::vector<std::tuple<uintptr_t, size_t, bool>>& v, std::optional<ParmsID> id, double scale, PoolArg p) {
+            utils::ConstSliceVec<double> views;
+            for (const auto& [address, length, on_device] : v) views.emplace_back(reinterpret_cast<const double*>(address), length, on_device);
+            return s.encode_float64_polynomial_slice_new_batched(views, id, scale, P(p)); }, py::arg("values"), py::arg("parms_id"), py::arg("scale"), POOL)
+        .def("decode_complex64_simd_batched", [](const CKKSEncoder& s, const std::vector<const Plaintext*>& pl, PoolArg p) {
+            std::vector<py::array_t<std::complex<double>>> out;
+            for (const auto& v : s.decode_complex64_simd_batched(pl, P(p))) out.emplace_back(v.size(), v.data());
+            return out; }, py::arg("sources"), POOL)
+        .def("decode_float64_polynomial_batched", [](const CKKSEncoder& s, const std::vector<const Plaintext*>& pl, PoolArg p) {
+            std::vector<py::array_t<double>> out;
+            for (const auto& v : s.decode_float64_polynomial_batched(pl, P(p))) out.emplace_back(v.size(), v.data());
+            return out; }, py::arg("sources"), POOL);
 
     // PolynomialEncoderRing2k32 / 64 (pybind/src/polynomial_encoder_ring2k.cu); 128-bit elements have no numpy dtype and stay C++-only
     auto register_ring2k = [&m](auto tag, const char* name) {

@@ -3,6 +3,7 @@
 // function whose behaviour (checks, metadata updates, error text) is mirrored.
 #include "troy.h"
 #include "device_steps.h"
+#include "../csrc/ckks_tables.hpp"
 
 #include <atomic>
 #include <unordered_set>
@@ -936,6 +937,7 @@ HeContextPointer HeContext::create(EncryptionParameters parms, bool expand_mod_c
 HeContext::~HeContext() {
     for (auto& kv : behz_) troyn_behz_destroy(kv.second);
     for (auto& kv : bgv_) troyn_bgv_destroy(kv.second);
+    if (ckks_) troyn_ckks_destroy(ckks_);
     if (plain_plan_) troyn_plan_destroy(plain_plan_);
     if (plan_) troyn_plan_destroy(plan_);
 }
@@ -986,6 +988,14 @@ const troyn_bgv* HeContext::bgv(size_t L) const {
     troyn_check(troyn_bgv_create(&b, plan_, static_cast<uint32_t>(L), kp.plain_modulus().value()));
     bgv_[L] = b;
     return b;
+}
+
+const troyn_ckks* HeContext::ckks() const {
+    std::lock_guard<std::mutex> lock(behz_mutex_);
+    if (ckks_) return ckks_;
+    if (!plan_) throw std::invalid_argument("[HeContext::ckks] HeContext is not on device (call to_device_inplace).");
+    troyn_check(troyn_ckks_create(&ckks_, plan_));
+    return ckks_;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3691,23 +3701,8 @@ CKKSEncoder::CKKSEncoder(HeContextPointer context) : context_(std::move(context)
     slots_ = n / 2;
     size_t logn = 0;
     while ((size_t(1) << logn) < n) logn++;
-    matrix_reps_index_map_.resize(n);
-    const size_t m = n << 1;
-    size_t pos = 1;
-    for (size_t i = 0; i < slots_; i++) {
-        matrix_reps_index_map_[i] = reverse_bits_sz((pos - 1) >> 1, logn);
-        matrix_reps_index_map_[i + slots_] = reverse_bits_sz((m - pos - 1) >> 1, logn);
-        pos = (pos * 3) & (m - 1);
-    }
-    // psi = exp(2 pi i / m); root_powers[i] = psi^bitrev(i), inv_root_powers[i] = conj(psi^(bitrev(i-1)+1))
-    const double pi = 3.14159265358979323846264338327950288;
-    auto root = [&](size_t k) { const double ang = 2.0 * pi * static_cast<double>(k % m) / static_cast<double>(m); return std::complex<double>(std::cos(ang), std::sin(ang)); };
-    root_powers_.assign(n, {0, 0});
-    inv_root_powers_.assign(n, {0, 0});
-    for (size_t i = 1; i < n; i++) {
-        root_powers_[i] = root(reverse_bits_sz(i, logn));
-        inv_root_powers_[i] = std::conj(root(reverse_bits_sz(i - 1, logn) + 1));
-    }
+    // index map and root powers: the builder the device handle (troyn_ckks_create) uses too, so both sides transform with the same doubles
+    troyn::ckks_tables::build(logn, matrix_reps_index_map_, root_powers_, inv_root_powers_);
 }
 
 void CKKSEncoder::set_plaintext(const std::vector<double>& coeffs, const ParmsID& parms_id, double scale, Plaintext& destination, MemoryPoolHandle pool) const {
@@ -3888,6 +3883,156 @@ void CKKSEncoder::decode_complex64_simd(const Plaintext& plain, std::vector<std:
     }
     destination.resize(slots_);
     for (size_t i = 0; i < slots_; i++) destination[i] = a[matrix_reps_index_map_[i]];
+}
+
+// ---- batched, on the device (troyn_ckks_*) ------------------------------------------------------------------------------------------
+std::vector<Plaintext> CKKSEncoder::encode_batched(bool simd, const std::vector<BatchItem>& items, std::optional<ParmsID> parms_id, double scale, MemoryPoolHandle pool) const {
+    const char* P = simd ? "[CKKSEncoder::encode_internal_complex_array]" : "[CKKSEncoder::encode_internal_double_polynomial]";
+    if (!context_->on_device()) throw std::invalid_argument(std::string(P) + " HeContext is not on device (call to_device_inplace).");
+    const ParmsID pid = parms_id.value_or(context_->first_parms_id());
+    auto cdo = context_->get_context_data(pid);
+    if (!cdo.has_value()) throw std::invalid_argument(std::string(P) + " parms_id not valid for context.");
+    const size_t n = slots_ * 2, L = cdo.value()->parms().coeff_modulus().size(), batch = items.size(), per = simd ? 2 : 1;
+    size_t doubles = 0;                                              // of the longest item: the row length of the staged values
+    for (const BatchItem& it : items) doubles = std::max(doubles, it.doubles);
+    if (doubles > n) throw std::invalid_argument(std::string(P) + " Too many input values.");
+    size_t total_bits = 0;                                           // the bound of set_plaintext, before anything is queued
+    for (const Modulus& mdl : cdo.value()->parms().coeff_modulus()) total_bits += mdl.bit_count();
+    if (scale <= 0 || std::log2(scale) + 1.0 >= static_cast<double>(total_bits))
+        throw std::invalid_argument("[CKKSEncoder::encode_internal_complex_array] scale out of bounds.");
+    if (batch == 0) return {};
+    hipStream_t s = current_stream();
+    // staged values [batch][doubles], then the too-large flags
+    const size_t value_words = batch * doubles, flag_words = (batch + 1) / 2;
+    utils::DynamicArray staged(value_words + flag_words + 2, true, pool);
+    double* d_values = reinterpret_cast<double*>(staged.raw_pointer());
+    uint32_t* d_flags = reinterpret_cast<uint32_t*>(staged.raw_pointer() + ((value_words + 1) & ~size_t(1)));
+    bool ragged = false, any_host = false;
+    for (const BatchItem& it : items) { ragged |= it.doubles != doubles; any_host |= !it.device && it.doubles; }
+    if (ragged) hip_check(hipMemsetAsync(d_values, 0, value_words * sizeof(double), s), "memset");
+    PinnedImage& img = pinned_image();
+    if (!any_host) img.reserve((value_words + flag_words) * sizeof(double));
+    if (any_host) {
+        // the host items leave through the pinned image by one copy (all on the host: one copy for the whole batch), device items by a device copy each
+        // (the flags come back into the words behind the values: one reservation, no wait between the upload and the call)
+        double* host = reinterpret_cast<double*>(img.reserve((value_words + flag_words) * sizeof(double)));
+        bool all_host = true;
+        for (const BatchItem& it : items) all_host &= !it.device;
+        for (size_t i = 0; i < batch; i++) {
+            if (items[i].device) continue;
+            std::memcpy(host + i * doubles, items[i].ptr, items[i].doubles * sizeof(double));
+            if (all_host && items[i].doubles < doubles) std::memset(host + i * doubles + items[i].doubles, 0, (doubles - items[i].doubles) * sizeof(double));
+        }
+        if (all_host) hip_check(hipMemcpyAsync(d_values, host, value_words * sizeof(double), hipMemcpyHostToDevice, s), "copy_host_to_device");
+        else for (size_t i = 0; i < batch; i++)
+            if (!items[i].device && items[i].doubles)
+                hip_check(hipMemcpyAsync(d_values + i * doubles, host + i * doubles, items[i].doubles * sizeof(double), hipMemcpyHostToDevice, s), "copy_host_to_device");
+        img.mark(s);
+    }
+    for (size_t i = 0; i < batch; i++)
+        if (items[i].device && items[i].doubles)
+            hip_check(hipMemcpyAsync(d_values + i * doubles, items[i].ptr, items[i].doubles * sizeof(double), hipMemcpyDeviceToDevice, s), "copy_device_to_device");
+    const troyn_ckks* h = context_->ckks();
+    const size_t ws_bytes = troyn_ckks_encode_workspace_bytes(h, batch);
+    utils::DynamicArray ws((ws_bytes + 7) / 8 + 2, true, pool);
+    auto shared = std::make_shared<utils::DynamicArray>(batch * L * n, true, pool);
+    const int rc = simd ? troyn_ckks_encode_simd(h, static_cast<uint32_t>(L), d_values, doubles / per, scale, shared->raw_pointer(), d_flags, ws.raw_pointer(), ws_bytes, batch, s)
+                        : troyn_ckks_encode_polynomial(h, static_cast<uint32_t>(L), d_values, doubles, scale, shared->raw_pointer(), d_flags, ws.raw_pointer(), ws_bytes, batch, s);
+    if (rc != TROYN_OK) {
+        (void)stream_wait();             // copies into `staged` may be queued: it returns to the pool only after them
+        troyn_check(rc);
+    }
+    // the flags: the only wait of the call (the staged values and the workspace return to the pool after it)
+    uint32_t* h_flags = reinterpret_cast<uint32_t*>(img.p + value_words * sizeof(double));
+    hip_check(hipMemcpyAsync(h_flags, d_flags, batch * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy_device_to_host");
+    hip_check(stream_wait(), "copy_device_to_host");
+    img.pending = false;                 // the wait covered the upload that read the image
+    for (size_t i = 0; i < batch; i++)
+        if (h_flags[i]) throw std::invalid_argument("[CKKSEncoder::encode_internal_complex_array] encoded values are too large.");
+    std::vector<Plaintext> out(batch);
+    for (size_t i = 0; i < batch; i++) {
+        Plaintext& p = out[i];
+        p.data() = utils::DynamicArray::device_view(shared->raw_pointer() + i * L * n, L * n, shared);
+        p.parms_id() = pid;
+        p.coeff_count() = n;
+        p.coeff_modulus_size() = L;
+        p.poly_modulus_degree() = n;
+        p.scale() = scale;
+        p.is_ntt_form() = true;
+    }
+    return out;
+}
+
+std::vector<Plaintext> CKKSEncoder::encode_complex64_simd_slice_new_batched(const utils::ConstSliceVec<std::complex<double>>& values, std::optional<ParmsID> parms_id, double scale,
+                                                                            MemoryPoolHandle pool) const {
+    std::vector<BatchItem> items;
+    for (const auto& v : values) {
+        if (v.size() > slots_) throw std::invalid_argument("[CKKSEncoder::encode_internal_complex_array] Too many input values.");
+        items.push_back(BatchItem{reinterpret_cast<const double*>(v.raw_pointer()), v.size() * 2, v.on_device()});
+    }
+    return encode_batched(true, items, parms_id, scale, pool);
+}
+
+std::vector<Plaintext> CKKSEncoder::encode_float64_polynomial_slice_new_batched(const utils::ConstSliceVec<double>& values, std::optional<ParmsID> parms_id, double scale,
+                                                                                MemoryPoolHandle pool) const {
+    std::vector<BatchItem> items;
+    for (const auto& v : values) {
+        if (v.size() > slots_ * 2) throw std::invalid_argument("[CKKSEncoder::encode_internal_double_polynomial] Too many input values.");
+        items.push_back(BatchItem{v.raw_pointer(), v.size(), v.on_device()});
+    }
+    return encode_batched(false, items, parms_id, scale, pool);
+}
+
+std::vector<double> CKKSEncoder::decode_batched(bool simd, const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool) const {
+    const char* P = "[CKKSEncoder::decode_internal]";
+    if (!context_->on_device()) throw std::invalid_argument(std::string(P) + " HeContext is not on device (call to_device_inplace).");
+    const size_t batch = plains.size(), n = slots_ * 2;
+    if (batch == 0) return {};
+    for (const Plaintext* p : plains) {
+        if (!p->is_ntt_form()) throw std::invalid_argument(std::string(P) + " Plaintext is not in NTT form.");
+        if (!(p->parms_id() == plains[0]->parms_id()) || p->scale() != plains[0]->scale())
+            throw std::invalid_argument(std::string(P) + " the plaintexts of one batched call share parms_id and scale.");
+    }
+    auto cdo = context_->get_context_data(plains[0]->parms_id());
+    if (!cdo.has_value()) throw std::invalid_argument(std::string(P) + " Plaintext parms_id is not valid.");
+    const size_t L = cdo.value()->parms().coeff_modulus().size(), words = L * n;
+    hipStream_t s = current_stream();
+    // consecutive windows of one buffer (what the batched encoders return) are read where they are; anything else is gathered by device copies
+    bool contiguous = true;
+    for (size_t i = 0; i < batch; i++) contiguous &= plains[i]->on_device() && plains[i]->poly().raw_pointer() == plains[0]->poly().raw_pointer() + i * words;
+    utils::DynamicArray gathered(contiguous ? 0 : batch * words, true, pool);
+    if (!contiguous)
+        for (size_t i = 0; i < batch; i++)
+            hip_check(hipMemcpyAsync(gathered.raw_pointer() + i * words, plains[i]->poly().raw_pointer(), words * sizeof(uint64_t),
+                                     plains[i]->on_device() ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s), "copy");
+    const uint64_t* src = contiguous ? plains[0]->poly().raw_pointer() : gathered.raw_pointer();
+    const troyn_ckks* h = context_->ckks();
+    const size_t ws_bytes = troyn_ckks_workspace_bytes(h, static_cast<uint32_t>(L), batch);
+    utils::DynamicArray ws((ws_bytes + 7) / 8 + 2, true, pool), out(batch * n, true, pool);
+    double* d_out = reinterpret_cast<double*>(out.raw_pointer());
+    troyn_check(simd ? troyn_ckks_decode_simd(h, static_cast<uint32_t>(L), src, plains[0]->scale(), d_out, ws.raw_pointer(), ws_bytes, batch, s)
+                     : troyn_ckks_decode_polynomial(h, static_cast<uint32_t>(L), src, plains[0]->scale(), d_out, ws.raw_pointer(), ws_bytes, batch, s));
+    PinnedImage& img = pinned_image();
+    const double* host = reinterpret_cast<const double*>(img.reserve(batch * n * sizeof(double)));
+    hip_check(hipMemcpyAsync(const_cast<double*>(host), d_out, batch * n * sizeof(double), hipMemcpyDeviceToHost, s), "copy_device_to_host");
+    hip_check(stream_wait(), "copy_device_to_host");
+    return std::vector<double>(host, host + batch * n);
+}
+
+std::vector<std::vector<std::complex<double>>> CKKSEncoder::decode_complex64_simd_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool) const {
+    const std::vector<double> flat = decode_batched(true, plains, pool);
+    std::vector<std::vector<std::complex<double>>> out(plains.size(), std::vector<std::complex<double>>(slots_));
+    for (size_t i = 0; i < plains.size(); i++)
+        for (size_t j = 0; j < slots_; j++) out[i][j] = std::complex<double>(flat[(i * slots_ + j) * 2], flat[(i * slots_ + j) * 2 + 1]);
+    return out;
+}
+
+std::vector<std::vector<double>> CKKSEncoder::decode_float64_polynomial_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool) const {
+    const std::vector<double> flat = decode_batched(false, plains, pool);
+    const size_t n = slots_ * 2;
+    std::vector<std::vector<double>> out(plains.size());
+    for (size_t i = 0; i < plains.size(); i++) out[i].assign(flat.begin() + i * n, flat.begin() + (i + 1) * n);
+    return out;
 }
 
 }  // namespace troy

@@ -595,6 +595,7 @@ public:
     const troyn_behz* behz(size_t coeff_modulus_size) const;   // created on first use
     const troyn_bgv* bgv(size_t coeff_modulus_size) const;     // BGV-only constants of the level with that many primes
     const troyn_plan* plain_plan() const;                      // NTT tables mod t (ContextData::plain_ntt_tables), first use
+    const troyn_ckks* ckks() const;                            // the CKKS encoder's device tables, first use
 private:
     HeContext() = default;
     std::unordered_map<ParmsID, std::shared_ptr<ContextData>, ParmsIDHash> map_;
@@ -608,6 +609,7 @@ private:
     mutable std::map<size_t, troyn_behz*> behz_;
     mutable std::map<size_t, troyn_bgv*> bgv_;
     mutable troyn_plan* plain_plan_ = nullptr;
+    mutable troyn_ckks* ckks_ = nullptr;
     mutable utils::RandomGenerator random_generator_;
 };
 
@@ -1162,9 +1164,11 @@ private:
 };
 
 // ----------------------------------------------------------------------------------------------
-// CKKSEncoder  (src/ckks_encoder.h, ckks_encoder.cu).  The canonical-embedding FFT and the RNS conversion of the
-// scaled coefficients are floating-point / host work outside the integer hot path: they run on the host in double
-// precision (same slot order as the reference: Galois generator 3, bit-reversed), the NTT on the device.
+// CKKSEncoder  (src/ckks_encoder.h, ckks_encoder.cu).  Same slot order as the reference: Galois generator 3, bit-reversed.
+// The per-plaintext methods (encode_* / decode_* on one Plaintext) run the canonical-embedding FFT and the RNS conversion of the
+// scaled coefficients on the host in double precision and only the NTT on the device.  The *_batched methods run everything on the
+// device (troyn_ckks_*, csrc/ckks_kernels.hpp): one upload of the values, one C-ABI call, one read of the too-large flags; the
+// encoded words equal the per-plaintext methods' (include/troyn.h, ENCODING CONTRACT), decoding follows the DECODING CONTRACT there.
 // ----------------------------------------------------------------------------------------------
 class CKKSEncoder {
 public:
@@ -1243,7 +1247,52 @@ public:
     utils::Array<double> decode_float64_polynomial_slice_new(const Plaintext& plain, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
         return utils::located(utils::Array<double>(decode_float64_polynomial_new(plain, pool)), plain.on_device(), pool);
     }
+    // batched, on the device.  Items shorter than the longest are zero-extended (an absent slot and a zero slot encode alike).  The plaintexts
+    // of one call are windows of one buffer.  The slice forms take host or device views; device views are read in place of an upload.
+    std::vector<Plaintext> encode_complex64_simd_slice_new_batched(const utils::ConstSliceVec<std::complex<double>>& values, std::optional<ParmsID> parms_id, double scale,
+                                                                   MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::vector<Plaintext> encode_float64_polynomial_slice_new_batched(const utils::ConstSliceVec<double>& values, std::optional<ParmsID> parms_id, double scale,
+                                                                       MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    void encode_complex64_simd_slice_batched(const utils::ConstSliceVec<std::complex<double>>& values, std::optional<ParmsID> parms_id, double scale,
+                                             const std::vector<Plaintext*>& destinations, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        assign_batched("[CKKSEncoder::encode_complex64_simd_slice_batched]", encode_complex64_simd_slice_new_batched(values, parms_id, scale, pool), destinations);
+    }
+    void encode_float64_polynomial_slice_batched(const utils::ConstSliceVec<double>& values, std::optional<ParmsID> parms_id, double scale,
+                                                 const std::vector<Plaintext*>& destinations, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        assign_batched("[CKKSEncoder::encode_float64_polynomial_slice_batched]", encode_float64_polynomial_slice_new_batched(values, parms_id, scale, pool), destinations);
+    }
+    std::vector<Plaintext> encode_complex64_simd_new_batched(const std::vector<std::vector<std::complex<double>>>& values, std::optional<ParmsID> parms_id, double scale,
+                                                             MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        utils::ConstSliceVec<std::complex<double>> views;
+        for (const auto& v : values) views.emplace_back(v.data(), v.size(), false);
+        return encode_complex64_simd_slice_new_batched(views, parms_id, scale, pool);
+    }
+    std::vector<Plaintext> encode_float64_polynomial_new_batched(const std::vector<std::vector<double>>& values, std::optional<ParmsID> parms_id, double scale,
+                                                                 MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        utils::ConstSliceVec<double> views;
+        for (const auto& v : values) views.emplace_back(v.data(), v.size(), false);
+        return encode_float64_polynomial_slice_new_batched(views, parms_id, scale, pool);
+    }
+    void encode_complex64_simd_batched(const std::vector<std::vector<std::complex<double>>>& values, std::optional<ParmsID> parms_id, double scale,
+                                       const std::vector<Plaintext*>& destinations, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        assign_batched("[CKKSEncoder::encode_complex64_simd_batched]", encode_complex64_simd_new_batched(values, parms_id, scale, pool), destinations);
+    }
+    void encode_float64_polynomial_batched(const std::vector<std::vector<double>>& values, std::optional<ParmsID> parms_id, double scale,
+                                           const std::vector<Plaintext*>& destinations, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        assign_batched("[CKKSEncoder::encode_float64_polynomial_batched]", encode_float64_polynomial_new_batched(values, parms_id, scale, pool), destinations);
+    }
+    // the plaintexts of one call share their parms_id and scale: one C-ABI call, one download
+    std::vector<std::vector<std::complex<double>>> decode_complex64_simd_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::vector<std::vector<double>> decode_float64_polynomial_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
 private:
+    static void assign_batched(const char* prompt, std::vector<Plaintext> encoded, const std::vector<Plaintext*>& destinations) {
+        if (encoded.size() != destinations.size()) throw std::invalid_argument(std::string(prompt) + " values and destinations size mismatch.");
+        for (size_t i = 0; i < encoded.size(); i++) *destinations[i] = std::move(encoded[i]);
+    }
+    // items: (pointer, doubles, on_device) of every item; words_per_value = 2 (complex) or 1
+    struct BatchItem { const double* ptr; size_t doubles; bool device; };
+    std::vector<Plaintext> encode_batched(bool simd, const std::vector<BatchItem>& items, std::optional<ParmsID> parms_id, double scale, MemoryPoolHandle pool) const;
+    std::vector<double> decode_batched(bool simd, const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool) const;   // [batch][N] doubles either way
     void set_plaintext(const std::vector<double>& coeffs, const ParmsID& parms_id, double scale, Plaintext& destination, MemoryPoolHandle pool) const;
     std::vector<double> plaintext_coefficients(const Plaintext& plain, MemoryPoolHandle pool) const;   // centred, as doubles (not yet / scale)
     HeContextPointer context_;
