@@ -372,6 +372,70 @@ int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t L, int is_
                                      void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The sum of key-switched automorphisms of DIFFERENT ciphertexts, and the baby-step/giant-step (BSGS) linear transform on top of it.  Both
+ * entries are ADDITIONS to the reference's surface, built on the two blocks above.
+ *
+ * troyn_apply_galois_sum_each: out = SUM_t sigma_{g_t}(cts[t]) with ONE division by the special prime.
+ *   cts              [terms][batch][2][L][N], one ciphertext PER TERM (exactly the layout of troyn_apply_galois_weighted_sums' `out`),
+ *                    NTT form iff is_ntt_form
+ *   galois_elements  host array of `terms` elements g_t, each odd and < 2N; duplicates are allowed.  The element 1 IS allowed: the term is
+ *                    added unrotated; its L key entries are ignored and may be NULL
+ *   keys             host array of terms * L DEVICE pointers, keys[t * L + j] -> u64[2][K][N] in NTT form, 16-byte aligned
+ *   out              [batch][2][L][N], same form as cts
+ * Contract, per item, on integers (tests/bsgs_spec.py; the notation of the two blocks above):
+ *   d_{t,j}      limb j of c1 of term t in coefficient form, an integer in [0, q_j)
+ *   e_{t,j}      sigma_{g_t}(d_{t,j}), signed
+ *   X_c[m]       SUM_{t, g_t != 1} SUM_j (e_{t,j} mod m) (*) k_{t,j}[c][m]  mod m,  m in {q_0 .. q_{L-1}, q_special}
+ *   r_c, result_c[l]   exactly as in troyn_switch_key (ONE rounded division by the special prime)
+ *   out[0][l] = SUM_t            sigma_{g_t}(c0_t)[l] + result_0[l]  mod q_l
+ *   out[1][l] = SUM_{t, g_t = 1} c1_t[l]              + result_1[l]  mod q_l
+ * The unkeyed contributions y (c0 of every term, c1 of the identity terms) may be added after the division, as written, or injected
+ * before it as (q_special mod q_l) * y on the rows q_l and nothing on the special row; the WORDS are the same either way (the argument of
+ * the block above).  The implementation injects before the division, in both forms: in coefficient form (BFV) after one forward
+ * transform of the terms' c0 into the workspace.  With every cts[t] the same ciphertext and no identity term the words equal
+ * troyn_apply_galois_sum's; with only identity terms the result is the plain sum.
+ * The transformed digits of at most TROYN_HOIST_EACH_GROUP terms are resident at once; later groups add into the extended-basis sum
+ * modulo each key modulus.  Modular addition is associative: the words do not depend on the grouping, and the workspace does not grow
+ * with `terms` beyond one group.
+ * Scope: BFV and CKKS.  BGV is left out (its tail divides differently).
+ * TROYN_E_INVALID: terms == 0, a null table, a null or misaligned key entry of a term with g != 1, a misaligned pointer (cts, out,
+ * workspace), an element that is even or >= 2N, L outside [1, K-1], `out` overlapping `cts`.  TROYN_E_WORKSPACE: a workspace below
+ * troyn_apply_galois_sum_each_workspace_bytes(plan, L, terms, batch, is_ntt_form).  batch == 0 returns TROYN_OK, launches nothing and
+ * looks at neither `cts`, `out` nor the workspace.  The tables are read before the call returns.
+ *
+ * troyn_linear_transform_bsgs: out = SUM_g sigma_{G_g}( SUM_b w_{g,b} (.) sigma_{B_b}(ct) ).
+ *   ct               [batch][2][L][N], NTT form iff is_ntt_form
+ *   baby_elements    host array of `babies` elements B_b, odd, < 2N, 1 allowed;   baby_keys   host array of babies * L device pointers
+ *   giant_elements   host array of `giants` elements G_g, odd, < 2N, 1 allowed;   giant_keys  host array of giants * L device pointers
+ *   weights          host array of giants * babies DEVICE pointers, weights[g * babies + b] -> u64[K][N] in NTT form and key-level layout
+ *                    (as in the block above), NULL = absent; a giant step with no weight is invalid.  The caller supplies the weights
+ *                    ALREADY ROTATED BACK by the giant step: for the matrix diagonal diag_{g,b} that multiplies rot_{G_g + B_b}(v),
+ *                    w_{g,b} = rot_{-G_g}(diag_{g,b}), so that rot_{G_g}(w_{g,b} (.) rot_{B_b}(v)) = diag_{g,b} (.) rot_{G_g + B_b}(v)
+ *   out              [batch][2][L][N], same form as ct
+ * Contract: the words are those of troyn_apply_galois_weighted_sums(ct, baby_*, weights, slots = giants) followed by
+ * troyn_apply_galois_sum_each on that result with the giant elements and keys: one decomposition of ct, `giants` divisions for the inner
+ * sums, ONE division for the outer sum.  One workspace, one table upload per stage (per group of TROYN_HOIST_EACH_GROUP giant steps in
+ * the second); the inner results live in the workspace and are never visible.
+ * Out of scope: "double hoisting", keeping the inner c0 component on the extended basis and skipping its division.  It changes the words
+ * of the inner stage and is a separate step.
+ * TROYN_E_INVALID: babies == 0, giants == 0, a giant step with no weight, a misaligned weight, and what the two entries refuse for their
+ * tables and buffers (`out` may not overlap `ct`).  TROYN_E_WORKSPACE: a workspace below
+ * troyn_linear_transform_bsgs_workspace_bytes(plan, L, babies, giants, batch, is_ntt_form).  batch == 0 returns TROYN_OK and launches
+ * nothing.  The tables are read before the call returns.
+ * ------------------------------------------------------------------------------------- */
+#define TROYN_HOIST_EACH_GROUP 8
+size_t troyn_apply_galois_sum_each_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t terms, size_t batch, int is_ntt_form);
+int troyn_apply_galois_sum_each(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* cts,
+                                const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, uint64_t* out,
+                                void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+size_t troyn_linear_transform_bsgs_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t babies, size_t giants, size_t batch, int is_ntt_form);
+int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
+                                const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                                const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                const uint64_t* const* weights, uint64_t* out,
+                                void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * BGV.  BGV ciphertexts live in NTT form and reuse troyn_ntt, troyn_dyadic_convolute (bgv_multiply,
  * evaluator.cu:150-173), troyn_add/sub/negate/multiply_scalar, troyn_apply_galois and troyn_plain_centralize unchanged; the
  * entries below are the steps where BGV differs.  troyn_bgv holds the constants of ONE level's RNSTool that only BGV reads

@@ -71,6 +71,11 @@ SYMBOLS = {
     "troyn_apply_galois_sum": (C.c_int, [vp, u32, C.c_int, C.c_int, vp, p64, C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
     "troyn_apply_galois_weighted_workspace_bytes": (sz, [vp, u32, sz, sz, sz, C.c_int]),
     "troyn_apply_galois_weighted_sums": (C.c_int, [vp, u32, C.c_int, C.c_int, vp, p64, C.POINTER(vp), sz, C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
+    "troyn_apply_galois_sum_each_workspace_bytes": (sz, [vp, u32, sz, sz, C.c_int]),
+    "troyn_apply_galois_sum_each": (C.c_int, [vp, u32, C.c_int, C.c_int, vp, p64, C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
+    "troyn_linear_transform_bsgs_workspace_bytes": (sz, [vp, u32, sz, sz, sz, C.c_int]),
+    "troyn_linear_transform_bsgs": (C.c_int, [vp, u32, C.c_int, C.c_int, vp, p64, C.POINTER(vp), sz, p64, C.POINTER(vp), sz, C.POINTER(vp), vp,
+                                              vp, sz, sz, vp]),
     "troyn_behz_gamma": (u64, [vp]),
     "troyn_bfv_scale_up": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, sz, C.c_int, sz, vp]),
     "troyn_bfv_decrypt_scale_and_round": (C.c_int, [vp, vp, vp, sz, vp]),

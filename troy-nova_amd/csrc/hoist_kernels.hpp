@@ -260,4 +260,119 @@ __global__ __launch_bounds__(POLY_BLOCK) void hoist_weighted_kernel(unsigned chu
     }
 }
 
+// hoist_each_kernel (troyn_apply_galois_sum_each): the rows, pairs and gather of hoist_mac_kernel with ONE CIPHERTEXT PER TERM,
+//     poly_prod[item][c][k][i] (+)= SUM_t ( SUM_j D[t][item][k][j][pi_t(i)] * key_{t,j}[c][k][i]                                  (g_t != 1)
+//                                         + (q_special mod q_k) * u_{t,c}[item][k][pi_t(i)] )  mod m_k                            (k < L)
+//   u_{t,0} = the NTT-form limbs of c0 of term t, u_{t,1} = those of c1 of an identity term and nothing otherwise, injected as
+//   hoist_weighted_kernel injects them.  The digit row pointer depends on the term: every term streams its own digits, 8 L (L+1) N bytes
+//   per item and term next to 16 L (L+1) N bytes of keys per term -- at IB = 4 about twice the key stream.  The 128-bit accumulator runs
+//   over the L digits of a term, one Barrett-128 per term and word, then an addition modulo m_k.  The host resides the digits of at most
+//   TROYN_HOIST_EACH_GROUP terms at once; `accumulate` makes a later group add into poly_prod modulo m_k (modular addition is associative:
+//   the words do not depend on the grouping).  The keys of an identity term are never read.  No LDS, no scratch.
+struct HoistEachArgs {
+    const DevModulus* mods;
+    unsigned K, L, log_n, batch;
+    unsigned groups;               // ceil(batch / IB)
+    unsigned terms;                // the terms of this launch (one group)
+    int accumulate;                // a later group: add into poly_prod
+    const u64* digits_ntt;         // D [terms][batch][L+1][L][N]
+    const u64* c0_ntt;             // NTT-form limbs of c0: term t, item b, limb l at c0_ntt + (t * batch + b) * c0_bstride + l * N
+    size_t c0_bstride;
+    const u64* c1_ntt;             // NTT-form limb l of c1 at c1_ntt + (t * batch + b) * c1_bstride + l * c1_lstride (the ciphertext, or D[l][l])
+    size_t c1_bstride, c1_lstride;
+    int diag_from_c1;              // skip_diag: digit k of row k < L was not produced, it is c1's NTT-form limb k
+    const u64* const* keys;        // device table [terms][L] -> u64[2][K][N]; the entries of an identity term are not read
+    const u64* elements;           // device table [terms]
+    const u64* special_mod;        // device table [L]: q_special mod q_l
+    u64* poly_prod;                // [batch][2][L+1][N]
+};
+
+template <int IB>
+__global__ __launch_bounds__(POLY_BLOCK) void hoist_each_kernel(unsigned chunks, HoistEachArgs a) {
+    const unsigned L = a.L, K = a.K, n = 1u << a.log_n;
+    const unsigned row = blk_row(chunks);
+    const unsigned k = row % (L + 1);
+    const unsigned grp = row / (L + 1);
+    const unsigned key_index = (k == L) ? K - 1 : k;
+    const DevModulus md = a.mods[key_index];
+    const size_t key_poly = (size_t)K * n;
+    const size_t digit_item = (size_t)(L + 1) * L * n;
+    const bool data_row = k < L;
+    const u64 special = data_row ? a.special_mod[k] : 0;
+    const bool diag = a.diag_from_c1 && data_row;
+    // items past the batch's end recompute the last item and store nothing
+    size_t item[IB];
+#pragma unroll
+    for (int b = 0; b < IB; ++b) {
+        const unsigned it = grp * IB + b;
+        item[b] = it < a.batch ? it : a.batch - 1;
+    }
+    for (unsigned x = blk_col(chunks) * 2; x < n; x += chunks * blockDim.x * 2) {
+        u64 r[IB][2][2];
+#pragma unroll
+        for (int b = 0; b < IB; ++b) {
+            if (a.accumulate) {
+                const u64* pp = a.poly_prod + item[b] * 2 * (size_t)(L + 1) * n + (size_t)k * n + x;
+                const u64x2 p0 = ld2(pp), p1 = ld2(pp + (size_t)(L + 1) * n);
+                r[b][0][0] = p0.a; r[b][0][1] = p0.b; r[b][1][0] = p1.a; r[b][1][1] = p1.b;
+            } else r[b][0][0] = r[b][0][1] = r[b][1][0] = r[b][1][1] = 0;
+        }
+        for (unsigned t = 0; t < a.terms; ++t) {
+            const unsigned g = (unsigned)a.elements[t];
+            const unsigned src = hoist_ntt_source(x, g, a.log_n);
+            const unsigned pair = src & ~1u;
+            const bool swap = src & 1u;
+            const size_t first = (size_t)t * a.batch;      // the term's first ciphertext
+            if (g != 1) {
+                u64 lo[IB][2][2], hi[IB][2][2];
+#pragma unroll
+                for (int b = 0; b < IB; ++b)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) lo[b][c][0] = lo[b][c][1] = hi[b][c][0] = hi[b][c][1] = 0;
+                for (unsigned j = 0; j < L; ++j) {
+                    const u64* kj = a.keys[(size_t)t * L + j] + (size_t)key_index * n + x;
+                    const u64x2 k0 = ld2(kj), k1 = ld2(kj + key_poly);
+#pragma unroll
+                    for (int b = 0; b < IB; ++b) {
+                        const u64* drow = (diag && j == k) ? a.c1_ntt + (first + item[b]) * a.c1_bstride + (size_t)k * a.c1_lstride
+                                                           : a.digits_ntt + (first + item[b]) * digit_item + ((size_t)k * L + j) * n;
+                        const u64x2 v = ld2(drow + pair);
+                        const u64 d0 = swap ? v.b : v.a, d1 = swap ? v.a : v.b;
+                        mac128(lo[b][0][0], hi[b][0][0], d0, k0.a); mac128(lo[b][0][1], hi[b][0][1], d1, k0.b);
+                        mac128(lo[b][1][0], hi[b][1][0], d0, k1.a); mac128(lo[b][1][1], hi[b][1][1], d1, k1.b);
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < IB; ++b)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        r[b][c][0] = add_mod(r[b][c][0], barrett128(lo[b][c][0], hi[b][c][0], md.q, md.ratio_lo, md.ratio_hi), md.q);
+                        r[b][c][1] = add_mod(r[b][c][1], barrett128(lo[b][c][1], hi[b][c][1], md.q, md.ratio_lo, md.ratio_hi), md.q);
+                    }
+            }
+            if (data_row) {
+                // the unkeyed contributions, scaled by q_special: c0 under every term, c1 under the identity
+#pragma unroll
+                for (int b = 0; b < IB; ++b) {
+                    const u64x2 v = ld2(a.c0_ntt + (first + item[b]) * a.c0_bstride + (size_t)k * n + pair);
+                    r[b][0][0] = add_mod(r[b][0][0], mul_mod(swap ? v.b : v.a, special, md), md.q);
+                    r[b][0][1] = add_mod(r[b][0][1], mul_mod(swap ? v.a : v.b, special, md), md.q);
+                    if (g == 1) {
+                        const u64x2 v1 = ld2(a.c1_ntt + (first + item[b]) * a.c1_bstride + (size_t)k * a.c1_lstride + x);
+                        r[b][1][0] = add_mod(r[b][1][0], mul_mod(v1.a, special, md), md.q);
+                        r[b][1][1] = add_mod(r[b][1][1], mul_mod(v1.b, special, md), md.q);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < IB; ++b) {
+            if (grp * IB + b >= a.batch) break;
+            u64* pp = a.poly_prod + item[b] * 2 * (size_t)(L + 1) * n + (size_t)k * n + x;
+            st2(pp, r[b][0][0], r[b][0][1]);
+            st2(pp + (size_t)(L + 1) * n, r[b][1][0], r[b][1][1]);
+        }
+    }
+}
+
 }  // namespace troyn

@@ -1731,6 +1731,166 @@ extern "C" int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t
     return ks_tail(tc, ks_path(p, L, items, tc.is_ntt_form, false));
 }
 
+// ---- the sum of key-switched automorphisms of DIFFERENT ciphertexts (an addition; include/troyn.h, hoist_each_kernel) ----
+// out = SUM_t sigma_{g_t}(cts[t]): the decomposition runs with terms * batch as its batch, hoist_each_kernel sums the terms on the extended
+// basis (the unkeyed contributions scaled by q_special, as in the weighted entry), ONE tail on `batch` items finishes both components.  The
+// digits of at most TROYN_HOIST_EACH_GROUP terms are resident at once; later groups add into poly_prod.
+struct EachLayout { KsLayout ks; size_t table, c0_ntt, total; };
+
+static EachLayout each_layout(const troyn_plan* p, unsigned L, size_t terms, size_t batch, bool is_ntt_form) {
+    const size_t n = p->n, resident = std::min<size_t>(terms, TROYN_HOIST_EACH_GROUP) * batch;
+    EachLayout e;
+    size_t off = 0;
+    e.ks.target_intt = off; off += resident * L * n;
+    e.ks.temp_ntt = off;    off += resident * (size_t)(L + 1) * L * n;
+    e.ks.poly_prod = off;   off += batch * 2 * (size_t)(L + 1) * n;
+    e.ks.prod_intt = off;   off += batch * 2 * (size_t)(L + 1) * n;
+    e.ks.temp_last = off;   off += batch * 2 * (size_t)L * n;
+    e.ks.keys_f64 = e.ks.split = e.ks.keys_quo = off;      // the inner products of troyn_switch_key do not run here
+    e.table = off;          off += std::min<size_t>(terms, TROYN_HOIST_EACH_GROUP) * (L + 2) + L;      // one group's hoisted tables, then q_special mod q_l
+    off = (off + 1) & ~(size_t)1;
+    e.c0_ntt = off;         off += is_ntt_form ? 0 : resident * L * n;      // coefficient form: the forward transform of the group's c0
+    e.total = e.ks.total = off;
+    return e;
+}
+
+extern "C" size_t troyn_apply_galois_sum_each_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t terms, size_t batch, int is_ntt_form) {
+    if (!plan) return 0;
+    return each_layout(plan, L, terms, batch, is_ntt_form != 0).total * sizeof(u64);
+}
+
+// the entry's work once the element and key tables have passed hoist_check_tables
+static int apply_galois_sum_each(const char* P, const troyn_plan* p, unsigned L, int is_ckks, int is_ntt_form, const u64* cts,
+                                 const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, u64* out,
+                                 void* workspace, size_t workspace_bytes, size_t batch, hipStream_t s) {
+    const unsigned K = p->K, n = p->n;
+    if (batch == 0) return TROYN_OK;      // nothing to do: neither cts, out nor the workspace is looked at
+    const size_t ct_words = (size_t)2 * L * n;
+    if (terms > 0xffffffffull || batch > 0xffffffffull || terms * batch > 0xffffffffull)
+        return fail(TROYN_E_INVALID, std::string(P) + " batch too large for one launch");
+    if (int rc = hoist_check_buffers(P, p, L, cts, out, workspace, terms * batch, batch)) return rc;
+    const bool ntt = is_ntt_form != 0;
+    const EachLayout e = each_layout(p, L, terms, batch, ntt);
+    if (workspace_bytes < e.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    u64* ws = (u64*)workspace;
+    std::vector<u64> special(L);
+    for (unsigned l = 0; l < L; l++) special[l] = p->moduli[K - 1] % p->moduli[l];
+    const unsigned ib = batch >= 4 ? 4u : batch >= 2 ? 2u : 1u;
+    const unsigned ch = chunks_pairs(n);
+    const size_t groups = (batch + ib - 1) / ib, rows = groups * (size_t)(L + 1);
+    if (int rc = check_rows(rows, ch)) return rc;
+    for (size_t t0 = 0; t0 < terms; t0 += TROYN_HOIST_EACH_GROUP) {
+        const size_t gt = std::min<size_t>(terms - t0, TROYN_HOIST_EACH_GROUP);
+        const u64* ct = cts + t0 * batch * ct_words;      // the group's ciphertexts: gt * batch items, ct_words apart
+        // the tables are read before the call returns (a group's upload waits on the stream for the launch that read the last one)
+        if (int rc = hoist_upload_tables(p, L, galois_elements + t0, keys + t0 * L, gt, special, ws + e.table, s)) return rc;
+        const u64* c1 = ct + (size_t)L * n;
+        KsCall dc{p, L, is_ckks, ntt, c1, ct_words, TROYN_ASSIGN_OVERWRITE, out, nullptr, 0,
+                  ws, e.ks, gt * batch, s, nullptr, c1, ct_words};
+        bool skip_diag = false;
+        if (int rc = hoist_decompose(dc, skip_diag)) return rc;
+        HoistEachArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.mods = p->d_mods; a.K = K; a.L = L; a.log_n = p->log_n; a.batch = (unsigned)batch; a.groups = (unsigned)groups;
+        a.terms = (unsigned)gt; a.accumulate = t0 ? 1 : 0;
+        a.digits_ntt = ws + e.ks.temp_ntt; a.diag_from_c1 = skip_diag ? 1 : 0;
+        if (ntt) {
+            a.c0_ntt = ct; a.c0_bstride = ct_words;
+            a.c1_ntt = c1; a.c1_bstride = ct_words; a.c1_lstride = n;
+        } else {
+            // BFV: the unkeyed contributions are injected after ONE forward transform of the group's c0 into the workspace; the NTT-form limbs
+            // of c1 (identity terms) are the diagonal blocks D[l][l], present in coefficient form
+            NttArgs f = contiguous_args(p, ct, ws + e.c0_ntt, 1, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
+            f.in_bstride = (long long)ct_words;
+            if (int rc = launch_ntt(p, f, gt * batch, false, s)) return rc;
+            a.c0_ntt = ws + e.c0_ntt; a.c0_bstride = (size_t)L * n;
+            a.c1_ntt = a.digits_ntt; a.c1_bstride = (size_t)(L + 1) * L * n; a.c1_lstride = (size_t)(L + 1) * n;
+        }
+        a.keys = reinterpret_cast<const u64* const*>(ws + e.table);
+        a.elements = ws + e.table + gt * L;
+        a.special_mod = ws + e.table + gt * (L + 2);
+        a.poly_prod = ws + e.ks.poly_prod;
+        {
+            TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, s);
+            const dim3 grid((unsigned)(rows * ch)), block(POLY_BLOCK);
+            if (ib == 4) hipLaunchKernelGGL((hoist_each_kernel<4>), grid, block, 0, s, ch, a);
+            else if (ib == 2) hipLaunchKernelGGL((hoist_each_kernel<2>), grid, block, 0, s, ch, a);
+            else hipLaunchKernelGGL((hoist_each_kernel<1>), grid, block, 0, s, ch, a);
+            LAUNCH_CHECK();
+        }
+    }
+    // the tail of troyn_switch_key on `batch` items, both components overwritten
+    const u64* c1 = cts + (size_t)L * n;
+    KsCall tc{p, L, is_ckks, ntt, c1, ct_words, TROYN_ASSIGN_OVERWRITE, out, nullptr, 0,
+              ws, e.ks, batch, s, nullptr, c1, ct_words};
+    return ks_tail(tc, ks_path(p, L, batch, ntt, false));
+}
+
+extern "C" int troyn_apply_galois_sum_each(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* cts,
+                                           const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, uint64_t* out,
+                                           void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(plan);
+    const char* P = "[troyn_apply_galois_sum_each]";
+    if (int rc = hoist_check_tables(P, plan, L, galois_elements, keys, terms, true)) return rc;
+    return apply_galois_sum_each(P, plan, L, is_ckks, is_ntt_form, (const u64*)cts, galois_elements, keys, terms, (u64*)out,
+                                 workspace, workspace_bytes, batch, (hipStream_t)stream);
+}
+
+// ---- baby-step/giant-step linear transform (an addition; include/troyn.h): the weighted sums over the baby steps, one per giant step, into
+// the workspace, then the sum of their giant-step automorphisms with ONE division ----
+struct BsgsLayout { size_t inner, stage, stage_words, total; };
+
+static BsgsLayout bsgs_layout(const troyn_plan* p, unsigned L, size_t babies, size_t giants, size_t batch, bool is_ntt_form) {
+    BsgsLayout b;
+    b.inner = 0;                                                       // [giants][batch][2][L][N], never visible to the caller
+    b.stage = giants * batch * 2 * (size_t)L * p->n;                   // one workspace, used by the stages one after the other
+    b.stage_words = std::max(weighted_layout(p, L, babies, giants, batch, is_ntt_form).total, each_layout(p, L, giants, batch, is_ntt_form).total);
+    b.total = b.stage + b.stage_words;
+    return b;
+}
+
+extern "C" size_t troyn_linear_transform_bsgs_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t babies, size_t giants, size_t batch,
+                                                              int is_ntt_form) {
+    if (!plan) return 0;
+    return bsgs_layout(plan, L, babies, giants, batch, is_ntt_form != 0).total * sizeof(u64);
+}
+
+extern "C" int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
+                                           const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                                           const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                           const uint64_t* const* weights, uint64_t* out_,
+                                           void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(plan);
+    const char* P = "[troyn_linear_transform_bsgs]";
+    const troyn_plan* p = plan;
+    const u64* ct = (const u64*)ct_;
+    u64* out = (u64*)out_;
+    if (int rc = hoist_check_tables(P, p, L, baby_elements, baby_keys, babies, true)) return rc;
+    if (int rc = hoist_check_tables(P, p, L, giant_elements, giant_keys, giants, true)) return rc;
+    if (!weights) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    for (size_t g = 0; g < giants; g++) {
+        bool any = false;
+        for (size_t b = 0; b < babies; b++) {
+            const uint64_t* w = weights[g * babies + b];
+            if ((uintptr_t)w & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned weight pointer");
+            any = any || w;
+        }
+        if (!any) return fail(TROYN_E_INVALID, std::string(P) + " a giant step has no weight");
+    }
+    if (batch == 0) return TROYN_OK;      // nothing to do: neither ct, out nor the workspace is looked at
+    if (int rc = hoist_check_buffers(P, p, L, ct, out, workspace, batch, batch)) return rc;
+    const BsgsLayout b = bsgs_layout(p, L, babies, giants, batch, is_ntt_form != 0);
+    if (workspace_bytes < b.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    u64* ws = (u64*)workspace;
+    u64* inner = ws + b.inner;
+    // stage 1: one decomposition of ct, `giants` divisions -- inner[g] = SUM_b w_{g,b} (.) sigma_{B_b}(ct)
+    if (int rc = troyn_apply_galois_weighted_sums(plan, L, is_ckks, is_ntt_form, ct_, baby_elements, baby_keys, babies, weights, giants,
+                                                  (uint64_t*)inner, ws + b.stage, b.stage_words * sizeof(u64), batch, stream)) return rc;
+    // stage 2: out = SUM_g sigma_{G_g}(inner[g]), ONE division
+    return apply_galois_sum_each(P, p, L, is_ckks, is_ntt_form, inner, giant_elements, giant_keys, giants, out,
+                                 ws + b.stage, b.stage_words * sizeof(u64), batch, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------
 // modulus switching
 // ---------------------------------------------------------------------------------------

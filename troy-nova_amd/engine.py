@@ -305,6 +305,81 @@ class Plan:
                                                              _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
 
+    # -- sums over different ciphertexts and the baby-step/giant-step transform (additions) ---------
+    def _keyed_tables(self, who, L, elements, keys_per_element):
+        """the element and key-pointer tables of one stage; the entry of the element 1 may be None"""
+        if len(keys_per_element) != len(elements):
+            raise capi.TroynInvalidArgument("%s one key per Galois element is needed" % who)
+        ptrs = []
+        for e, keys in zip(elements, keys_per_element):
+            if keys is None and int(e) == 1:
+                keys = [None] * L
+            if keys is None or len(keys) < L:
+                raise capi.TroynInvalidArgument("%s Key switch keys index out of range." % who)
+            ptrs += [None if k is None else k.data_ptr() for k in keys[:L]]      # (a null entry is the library's to refuse)
+        karr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        earr = (C.c_uint64 * max(len(elements), 1))(*[int(e) for e in elements])
+        return earr, karr
+
+    def apply_galois_sum_each(self, L, cts, elements, keys_per_element, is_ckks=True, is_ntt_form=True, out=None):
+        """cts [terms][batch][2][L][N] -> [batch][2][L][N]: the SUM over t of the key-switched automorphism X -> X^elements[t] of cts[t], one
+        ciphertext PER TERM, summed before ONE division by the special prime (include/troyn.h states the contract).  The element 1 adds the
+        term unrotated; its entry of keys_per_element may be None."""
+        who = "[troyn_apply_galois_sum_each]"
+        terms = len(elements)
+        earr, karr = self._keyed_tables(who, L, elements, keys_per_element)
+        words = 2 * L * self.n
+        if terms == 0:
+            raise capi.TroynInvalidArgument("%s no terms" % who)
+        if L < 1 or cts.numel() % (terms * words):
+            raise capi.TroynInvalidArgument("%s cts is not [terms][batch][2][L][N]" % who)
+        batch = cts.numel() // (terms * words)
+        shape = (batch, 2, L, self.n)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=self.device)
+        elif out.numel() != int(np.prod(shape)):
+            raise capi.TroynInvalidArgument("%s out is not [batch][2][L][N]" % who)
+        ws = self.workspace(self.lib.troyn_apply_galois_sum_each_workspace_bytes(self.h, L, terms, batch, int(is_ntt_form)))
+        capi.check(self.lib.troyn_apply_galois_sum_each(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(cts), earr, karr, terms, _ptr(out),
+                                                        C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        return out
+
+    def linear_transform_bsgs(self, L, ct, baby_elements, baby_keys, giant_elements, giant_keys, weights, is_ckks=True, is_ntt_form=True,
+                              out=None):
+        """ct [batch][2][L][N] -> [batch][2][L][N]: SUM_g sigma_G[g]( SUM_b weights[g][b] (.) sigma_B[b](ct) ), the baby-step/giant-step form of
+        a plaintext matrix times an encrypted vector: one digit decomposition of ct, one division per giant step for the inner sums and ONE
+        for the outer sum.  weights[g][b]: a tensor [K][N] in NTT form and key-level layout, ALREADY rotated back by the giant step, or None;
+        every giant step needs a weight.  The element 1 is the identity in either list; its keys may be None."""
+        who = "[troyn_linear_transform_bsgs]"
+        babies, giants = len(baby_elements), len(giant_elements)
+        bearr, bkarr = self._keyed_tables(who, L, baby_elements, baby_keys)
+        gearr, gkarr = self._keyed_tables(who, L, giant_elements, giant_keys)
+        words = 2 * L * self.n
+        if L < 1 or ct.numel() % words:
+            raise capi.TroynInvalidArgument("%s ct is not [batch][2][L][N]" % who)
+        batch = ct.numel() // words
+        if len(weights) != giants:
+            raise capi.TroynInvalidArgument("%s one weight row per giant step is needed" % who)
+        wptrs = []
+        for row in weights:
+            if len(row) != babies:
+                raise capi.TroynInvalidArgument("%s one weight (or None) per giant and baby step is needed" % who)
+            for w in row:
+                if w is not None and w.numel() != self.K * self.n:
+                    raise capi.TroynInvalidArgument("%s a weight is not [K][N]" % who)
+                wptrs.append(None if w is None else w.data_ptr())
+        warr = (C.c_void_p * max(len(wptrs), 1))(*wptrs)
+        shape = (batch, 2, L, self.n)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=self.device)
+        elif out.numel() != int(np.prod(shape)):
+            raise capi.TroynInvalidArgument("%s out is not [batch][2][L][N]" % who)
+        ws = self.workspace(self.lib.troyn_linear_transform_bsgs_workspace_bytes(self.h, L, babies, giants, batch, int(is_ntt_form)))
+        capi.check(self.lib.troyn_linear_transform_bsgs(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(ct), bearr, bkarr, babies,
+                                                        gearr, gkarr, giants, warr, _ptr(out),
+                                                        C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        return out
+
     # -- RLWE / LWE packing (evaluator_lwes.cu) -----------------------------------------------------
     def negacyclic_shift(self, x, nmod, shift, mod_start=0):
         """x [count][nmod][N] * X^shift (utils::negacyclic_shift_ps), any shift (modulo 2N)"""

@@ -575,8 +575,30 @@ PYBIND11_MODULE(pytroy_raw, m) {
         s.rotate_weighted_sum(a, st, k, w, d, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);
     ev.def("rotate_weighted_sum_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& st, const GaloisKeys& k, const WeightRow& w, PoolArg p) {
         return s.rotate_weighted_sum_new(a, st, k, w, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("weights"), POOL);
+    // additions: the sum of rotations of DIFFERENT ciphertexts with one division, and the baby-step/giant-step transform; weights [giant][baby] (troy.h)
+    typedef std::vector<const Ciphertext*> CtRow;
+    ev.def("apply_galois_sum_each", [](const Evaluator& s, const CtRow& a, const std::vector<size_t>& g, const GaloisKeys& k, Ciphertext& d, PoolArg p) {
+        s.apply_galois_sum_each(a, g, k, d, P(p)); }, py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("apply_galois_sum_each_new", [](const Evaluator& s, const CtRow& a, const std::vector<size_t>& g, const GaloisKeys& k, PoolArg p) {
+        return s.apply_galois_sum_each_new(a, g, k, P(p)); }, py::arg("encrypted"), py::arg("galois_elements"), py::arg("galois_keys"), POOL);
+    ev.def("rotate_sum_each", [](const Evaluator& s, const CtRow& a, const std::vector<int>& st, const GaloisKeys& k, Ciphertext& d, PoolArg p) {
+        s.rotate_sum_each(a, st, k, d, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("rotate_sum_each_new", [](const Evaluator& s, const CtRow& a, const std::vector<int>& st, const GaloisKeys& k, PoolArg p) {
+        return s.rotate_sum_each_new(a, st, k, P(p)); }, py::arg("encrypted"), py::arg("steps"), py::arg("galois_keys"), POOL);
+    ev.def("apply_galois_bsgs_sum", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& b, const std::vector<size_t>& g, const GaloisKeys& k,
+                                       const std::vector<WeightRow>& w, Ciphertext& d, PoolArg p) { s.apply_galois_bsgs_sum(a, b, g, k, w, d, P(p)); },
+           py::arg("encrypted"), py::arg("baby_elements"), py::arg("giant_elements"), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);
+    ev.def("apply_galois_bsgs_sum_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& b, const std::vector<size_t>& g, const GaloisKeys& k,
+                                           const std::vector<WeightRow>& w, PoolArg p) { return s.apply_galois_bsgs_sum_new(a, b, g, k, w, P(p)); },
+           py::arg("encrypted"), py::arg("baby_elements"), py::arg("giant_elements"), py::arg("galois_keys"), py::arg("weights"), POOL);
+    ev.def("rotate_bsgs_sum", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& b, const std::vector<int>& g, const GaloisKeys& k,
+                                 const std::vector<WeightRow>& w, Ciphertext& d, PoolArg p) { s.rotate_bsgs_sum(a, b, g, k, w, d, P(p)); },
+           py::arg("encrypted"), py::arg("baby_steps"), py::arg("giant_steps"), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);
+    ev.def("rotate_bsgs_sum_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& b, const std::vector<int>& g, const GaloisKeys& k,
+                                     const std::vector<WeightRow>& w, PoolArg p) { return s.rotate_bsgs_sum_new(a, b, g, k, w, P(p)); },
+           py::arg("encrypted"), py::arg("baby_steps"), py::arg("giant_steps"), py::arg("galois_keys"), py::arg("weights"), POOL);
     // ciphertext +/- plaintext
-#define EV_PLAIN(name)                                                                                                           \
+#define EV_PLAIN(name)                                                                                                          \
     ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const Plaintext& w, Ciphertext& d, PoolArg p) { s.name(a, w, d, P(p)); },  \
            py::arg("encrypted"), py::arg("plain"), py::arg("destination"), POOL);                                               \
     ev.def(#name "_inplace", [](const Evaluator& s, Ciphertext& a, const Plaintext& w, PoolArg p) { s.name##_inplace(a, w, P(p)); }, \

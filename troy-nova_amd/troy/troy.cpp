@@ -2211,6 +2211,49 @@ void Evaluator::rotate_sum(const Ciphertext& encrypted, const std::vector<int>& 
     destination = std::move(d[0]);
 }
 
+// the element and key-pointer tables of one stage over ciphertexts shaped like `like`: apply_galois's checks per element; the element 1 has no key
+void Evaluator::hoisted_key_table(const char* P, const Ciphertext& like, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys, uint32_t L,
+                                  std::vector<uint64_t>& elements, std::vector<const uint64_t*>& keys, MemoryPoolHandle pool) const {
+    const size_t n = get_context_data(P, like.parms_id())->parms().poly_modulus_degree();
+    Ciphertext shell;
+    for (size_t g : galois_elements) {
+        elements.push_back(g);
+        if (g == 1) { keys.insert(keys.end(), L, nullptr); continue; }      // the ciphertext itself: no key
+        if ((g & 1) && g < 2 * n && !galois_keys.has_key(g)) throw std::invalid_argument(std::string(P) + " Galois key not present.");
+        std::vector<const uint64_t*> ptrs;
+        apply_galois_prepare(like, g, galois_keys, shell, ptrs, pool);
+        if (ptrs.size() < L) throw std::invalid_argument(std::string(P) + " Key switching key has too few components for this level.");
+        keys.insert(keys.end(), ptrs.begin(), ptrs.begin() + L);
+    }
+}
+
+// the weight pointers [rows][terms]: NTT form at the key level (the layout of the Galois keys), one scale, which is returned (CKKS; 1 otherwise)
+double Evaluator::weight_table(const char* P, SchemeType scheme, size_t n, const std::vector<std::vector<const Plaintext*>>& weights, size_t terms,
+                               const char* row_name, std::vector<const uint64_t*>& wptrs) const {
+    const size_t key_words = context_->key_context_data().value()->parms().coeff_modulus().size() * n;
+    double weight_scale = 1.0;
+    bool have_scale = false;
+    for (const auto& row : weights) {
+        if (row.size() != terms) throw std::invalid_argument(std::string(P) + " One weight (or null) per " + row_name + " and term is needed.");
+        bool any = false;
+        for (const Plaintext* w : row) {
+            wptrs.push_back(w ? w->data().raw_pointer() : nullptr);
+            if (!w) continue;
+            any = true;
+            if (!w->on_device()) throw std::invalid_argument(std::string(P) + " Operand is on host; the evaluator runs on the GPU only.");
+            if (!w->is_ntt_form()) throw std::invalid_argument(std::string(P) + " Weight is not in NTT form.");
+            if (w->parms_id() != context_->key_parms_id()) throw std::invalid_argument(std::string(P) + " Weight is not at the key level.");
+            if (w->data().size() != key_words) throw std::invalid_argument(std::string(P) + " Weight is not a full key-level polynomial.");
+            if (scheme == SchemeType::CKKS) {
+                if (have_scale && !are_close_double(w->scale(), weight_scale)) throw std::invalid_argument(std::string(P) + " Weights have different scales.");
+                weight_scale = w->scale(); have_scale = true;
+            }
+        }
+        if (!any) throw std::invalid_argument(std::string(P) + " A " + row_name + " has no weight.");
+    }
+    return weight_scale;
+}
+
 // -- plaintext-weighted hoisted rotations (addition; troy.h): troyn_apply_galois_weighted_sums, one launch chain for every slot --
 void Evaluator::apply_galois_weighted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
                                       const std::vector<std::vector<const Plaintext*>>& weights, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const {
@@ -2226,40 +2269,9 @@ void Evaluator::apply_galois_weighted(const char* P, const Ciphertext& encrypted
     const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
     const size_t words = 2 * static_cast<size_t>(L) * n, terms = galois_elements.size(), slots = weights.size();
     std::vector<uint64_t> elements;
-    std::vector<const uint64_t*> keys;
-    Ciphertext shell;
-    for (size_t g : galois_elements) {
-        elements.push_back(g);
-        if (g == 1) { keys.insert(keys.end(), L, nullptr); continue; }      // the ciphertext itself: no key
-        if ((g & 1) && g < 2 * n && !galois_keys.has_key(g)) throw std::invalid_argument(std::string(P) + " Galois key not present.");
-        std::vector<const uint64_t*> ptrs;
-        apply_galois_prepare(encrypted, g, galois_keys, shell, ptrs, pool);
-        if (ptrs.size() < L) throw std::invalid_argument(std::string(P) + " Key switching key has too few components for this level.");
-        keys.insert(keys.end(), ptrs.begin(), ptrs.begin() + L);
-    }
-    // the weights: NTT form at the key level (the layout of the Galois keys), one scale
-    std::vector<const uint64_t*> wptrs;
-    const size_t key_words = context_->key_context_data().value()->parms().coeff_modulus().size() * n;
-    double weight_scale = 1.0;
-    bool have_scale = false;
-    for (const auto& row : weights) {
-        if (row.size() != terms) throw std::invalid_argument(std::string(P) + " One weight (or null) per slot and term is needed.");
-        bool any = false;
-        for (const Plaintext* w : row) {
-            wptrs.push_back(w ? w->data().raw_pointer() : nullptr);
-            if (!w) continue;
-            any = true;
-            if (!w->on_device()) throw std::invalid_argument(std::string(P) + " Operand is on host; the evaluator runs on the GPU only.");
-            if (!w->is_ntt_form()) throw std::invalid_argument(std::string(P) + " Weight is not in NTT form.");
-            if (w->parms_id() != context_->key_parms_id()) throw std::invalid_argument(std::string(P) + " Weight is not at the key level.");
-            if (w->data().size() != key_words) throw std::invalid_argument(std::string(P) + " Weight is not a full key-level polynomial.");
-            if (scheme == SchemeType::CKKS) {
-                if (have_scale && !are_close_double(w->scale(), weight_scale)) throw std::invalid_argument(std::string(P) + " Weights have different scales.");
-                weight_scale = w->scale(); have_scale = true;
-            }
-        }
-        if (!any) throw std::invalid_argument(std::string(P) + " A slot has no weight.");
-    }
+    std::vector<const uint64_t*> keys, wptrs;
+    hoisted_key_table(P, encrypted, galois_elements, galois_keys, L, elements, keys, pool);
+    const double weight_scale = weight_table(P, scheme, n, weights, terms, "slot", wptrs);
     const double scale = scheme == SchemeType::CKKS ? encrypted.scale() * weight_scale : encrypted.scale();
     if (scheme == SchemeType::CKKS && !is_scale_within_bounds(scale, cd)) throw std::invalid_argument(std::string(P) + " Scale out of bounds.");
     utils::DynamicArray flat(slots * words, true, pool);     // [slots][2][L][N], copied out per slot
@@ -2292,6 +2304,95 @@ void Evaluator::rotate_weighted_sum(const Ciphertext& encrypted, const std::vect
     std::vector<Ciphertext> d;
     apply_galois_weighted(P, encrypted, hoisted_elements_from_steps(P, encrypted, steps), galois_keys, {weights}, d, pool);
     destination = std::move(d[0]);
+}
+
+// -- the sum of key-switched automorphisms of different ciphertexts (addition; troy.h): troyn_apply_galois_sum_each, ONE division --
+void Evaluator::apply_galois_each(const char* P, const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements,
+                                  const GaloisKeys& galois_keys, Ciphertext& destination, MemoryPoolHandle pool) const {
+    if (galois_elements.empty()) throw std::invalid_argument(std::string(P) + " Empty element list.");
+    if (encrypted.size() != galois_elements.size()) throw std::invalid_argument(std::string(P) + " One ciphertext per element is needed.");
+    for (const Ciphertext* c : encrypted) if (!c) throw std::invalid_argument(std::string(P) + " Null ciphertext.");
+    const Ciphertext& first = *encrypted[0];
+    auto cd = get_context_data(P, first.parms_id());
+    const SchemeType scheme = cd->parms().scheme();
+    if (scheme == SchemeType::BGV) throw std::invalid_argument(std::string(P) + " BGV is not supported: its key switch divides by the special prime differently.");
+    for (const Ciphertext* c : encrypted) {
+        if (c->polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " Ciphertext size must be 2.");
+        check_no_seed(P, *c);
+        check_on_device(P, context_, *c);
+        if (c->parms_id() != first.parms_id()) throw std::invalid_argument(std::string(P) + " Operands are at different levels.");
+        if (c->is_ntt_form() != first.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Operands are in different forms.");
+        if (scheme == SchemeType::CKKS && !are_close_double(c->scale(), first.scale())) throw std::invalid_argument(std::string(P) + " Operands have different scales.");
+    }
+    const size_t n = cd->parms().poly_modulus_degree();
+    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
+    const size_t words = 2 * static_cast<size_t>(L) * n, terms = galois_elements.size();
+    std::vector<uint64_t> elements;
+    std::vector<const uint64_t*> keys;
+    hoisted_key_table(P, first, galois_elements, galois_keys, L, elements, keys, pool);
+    utils::DynamicArray flat(terms * words, true, pool);     // [terms][2][L][N]: the library's layout, one ciphertext per term
+    for (size_t t = 0; t < terms; t++)
+        hip_check(hipMemcpyAsync(flat.raw_pointer() + t * words, encrypted[t]->data().raw_pointer(), words * 8, hipMemcpyDeviceToDevice, current_stream()), "copy_device_to_device");
+    Ciphertext d = Ciphertext::like(first, false, pool);
+    {
+        const int is_ckks = scheme == SchemeType::CKKS, is_ntt = first.is_ntt_form() ? 1 : 0;
+        const size_t bytes = troyn_apply_galois_sum_each_workspace_bytes(context_->plan(), L, terms, 1, is_ntt);
+        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
+        detail::LaunchGate gate;
+        troyn_check(troyn_apply_galois_sum_each(context_->plan(), L, is_ckks, is_ntt, flat.raw_pointer(), elements.data(), keys.data(), terms,
+                                                d.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
+    }
+    destination = std::move(d);
+}
+
+void Evaluator::rotate_sum_each(const std::vector<const Ciphertext*>& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                                Ciphertext& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::rotate_sum_each]";
+    if (encrypted.empty() || !encrypted[0]) throw std::invalid_argument(std::string(P) + " Empty ciphertext list.");
+    apply_galois_each(P, encrypted, hoisted_elements_from_steps(P, *encrypted[0], steps), galois_keys, destination, pool);
+}
+
+// -- baby-step/giant-step linear transform (addition; troy.h): troyn_linear_transform_bsgs, one decomposition, giants + 1 divisions --
+void Evaluator::apply_galois_bsgs(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
+                                  const GaloisKeys& galois_keys, const std::vector<std::vector<const Plaintext*>>& weights, Ciphertext& destination,
+                                  MemoryPoolHandle pool) const {
+    if (baby_elements.empty() || giant_elements.empty()) throw std::invalid_argument(std::string(P) + " Empty element list.");
+    if (weights.size() != giant_elements.size()) throw std::invalid_argument(std::string(P) + " One weight row per giant step is needed.");
+    auto cd = get_context_data(P, encrypted.parms_id());
+    const SchemeType scheme = cd->parms().scheme();
+    if (scheme == SchemeType::BGV) throw std::invalid_argument(std::string(P) + " BGV is not supported: its key switch divides by the special prime differently.");
+    if (encrypted.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " Ciphertext size must be 2.");
+    check_no_seed(P, encrypted);
+    check_on_device(P, context_, encrypted);
+    const size_t n = cd->parms().poly_modulus_degree();
+    const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
+    const size_t babies = baby_elements.size(), giants = giant_elements.size();
+    std::vector<uint64_t> belements, gelements;
+    std::vector<const uint64_t*> bkeys, gkeys, wptrs;
+    hoisted_key_table(P, encrypted, baby_elements, galois_keys, L, belements, bkeys, pool);
+    hoisted_key_table(P, encrypted, giant_elements, galois_keys, L, gelements, gkeys, pool);
+    const double weight_scale = weight_table(P, scheme, n, weights, babies, "giant step", wptrs);
+    const double scale = scheme == SchemeType::CKKS ? encrypted.scale() * weight_scale : encrypted.scale();
+    if (scheme == SchemeType::CKKS && !is_scale_within_bounds(scale, cd)) throw std::invalid_argument(std::string(P) + " Scale out of bounds.");
+    Ciphertext d = Ciphertext::like(encrypted, false, pool);
+    d.scale() = scale;
+    {
+        const int is_ckks = scheme == SchemeType::CKKS, is_ntt = encrypted.is_ntt_form() ? 1 : 0;
+        const size_t bytes = troyn_linear_transform_bsgs_workspace_bytes(context_->plan(), L, babies, giants, 1, is_ntt);
+        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
+        detail::LaunchGate gate;
+        troyn_check(troyn_linear_transform_bsgs(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), belements.data(), bkeys.data(), babies,
+                                                gelements.data(), gkeys.data(), giants, wptrs.data(), d.data().raw_pointer(), ws.raw_pointer(), bytes, 1,
+                                                current_stream()));
+    }
+    destination = std::move(d);
+}
+
+void Evaluator::rotate_bsgs_sum(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps, const GaloisKeys& galois_keys,
+                                const std::vector<WeightRow>& weights, Ciphertext& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::rotate_bsgs_sum]";
+    apply_galois_bsgs(P, encrypted, hoisted_elements_from_steps(P, encrypted, baby_steps), hoisted_elements_from_steps(P, encrypted, giant_steps), galois_keys,
+                      weights, destination, pool);
 }
 
 // ------------------------------------------------------------------------------------------------

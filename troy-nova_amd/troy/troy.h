@@ -1599,6 +1599,51 @@ public:
         Ciphertext d; rotate_weighted_sum(encrypted, steps, galois_keys, weights, d, pool); return d;
     }
 
+    // ADDITION to the reference's interface: the other half of a baby-step/giant-step (BSGS) product (troyn_apply_galois_sum_each /
+    //   troyn_linear_transform_bsgs, include/troyn.h states the contract on integers).
+    //   apply_galois_sum_each: destination = SUM_t (key-switched automorphism X -> X^elements[t] of *encrypted[t]) -- one ciphertext PER TERM,
+    //                          summed BEFORE the division by the special prime: ONE tail.  The element 1 adds its ciphertext unrotated.
+    //   rotate_sum_each:       the same for rotation steps; a step of 0 is the identity.
+    //   rotate_bsgs_sum:       destination = SUM_g rotate( SUM_b weights[g][b] * rotate(encrypted, baby_steps[b]), giant_steps[g] ): one digit
+    //                          decomposition of `encrypted`, one division per giant step for the inner sums and ONE for the outer sum.  The
+    //                          caller supplies weights[g][b] ALREADY ROTATED BACK by giant_steps[g] (the diagonal of the matrix that multiplies
+    //                          the rotation by giant_steps[g] + baby_steps[b], rotated by -giant_steps[g]); a null weight leaves the pair out;
+    //                          every giant step needs a weight.  Weights as for rotate_weighted_sums (key level, NTT form, close scales);
+    //                          CKKS: the destination's scale is encrypted.scale() * the weight scale.
+    //   apply_galois_bsgs_sum: the same for Galois elements.
+    //   The operands of the _each forms must share their level, form and (CKKS) scale.  A missing key throws "Galois key not present." (no NAF
+    //   chain); BFV and CKKS, BGV throws std::invalid_argument.  "Double hoisting" (no division of the inner c0) is not done.
+    // Call combining does not take part: these methods always launch directly.
+    void apply_galois_sum_each(const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                               Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        apply_galois_each("[Evaluator::apply_galois_sum_each]", encrypted, galois_elements, galois_keys, destination, pool);
+    }
+    Ciphertext apply_galois_sum_each_new(const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                         MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; apply_galois_sum_each(encrypted, galois_elements, galois_keys, d, pool); return d;
+    }
+    void rotate_sum_each(const std::vector<const Ciphertext*>& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, Ciphertext& destination,
+                         MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext rotate_sum_each_new(const std::vector<const Ciphertext*>& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                                   MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; rotate_sum_each(encrypted, steps, galois_keys, d, pool); return d;
+    }
+    void apply_galois_bsgs_sum(const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
+                               const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights, Ciphertext& destination,
+                               MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        apply_galois_bsgs("[Evaluator::apply_galois_bsgs_sum]", encrypted, baby_elements, giant_elements, galois_keys, weights, destination, pool);
+    }
+    Ciphertext apply_galois_bsgs_sum_new(const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
+                                         const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; apply_galois_bsgs_sum(encrypted, baby_elements, giant_elements, galois_keys, weights, d, pool); return d;
+    }
+    void rotate_bsgs_sum(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps, const GaloisKeys& galois_keys,
+                         const std::vector<WeightRow>& weights, Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext rotate_bsgs_sum_new(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps, const GaloisKeys& galois_keys,
+                                   const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; rotate_bsgs_sum(encrypted, baby_steps, giant_steps, galois_keys, weights, d, pool); return d;
+    }
+
     // ciphertext x plaintext -- evaluator.h (multiply_plain*, transform_plain_to_ntt*); evaluator_multiply_plain.cu,
     // evaluator_transform_ntt.cu:35-70
     void transform_plain_to_ntt(const Plaintext& plain, const ParmsID& parms_id, Plaintext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -1852,6 +1897,17 @@ private:
     // the weighted sums (addition): out[s] = SUM_t weights[s][t] * sigma_{elements[t]}(encrypted); element 1 is the ciphertext itself
     void apply_galois_weighted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
                                const std::vector<std::vector<const Plaintext*>>& weights, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const;
+    // the tables the weighted, _each and BSGS methods hand to the library: elements with their key pointers, and the checked weight pointers (returns the weights' scale)
+    void hoisted_key_table(const char* P, const Ciphertext& like, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys, uint32_t L,
+                           std::vector<uint64_t>& elements, std::vector<const uint64_t*>& keys, MemoryPoolHandle pool) const;
+    double weight_table(const char* P, SchemeType scheme, size_t n, const std::vector<std::vector<const Plaintext*>>& weights, size_t terms, const char* row_name,
+                        std::vector<const uint64_t*>& wptrs) const;
+    // the sum over different ciphertexts and the baby-step/giant-step transform (additions)
+    void apply_galois_each(const char* P, const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                           Ciphertext& destination, MemoryPoolHandle pool) const;
+    void apply_galois_bsgs(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
+                           const GaloisKeys& galois_keys, const std::vector<std::vector<const Plaintext*>>& weights, Ciphertext& destination,
+                           MemoryPoolHandle pool) const;
     void switch_key_internal(const Ciphertext& encrypted, const uint64_t* target, const KSwitchKeys& kswitch_keys, size_t kswitch_keys_index,
                              SwitchKeyDestinationAssignMethod assign_method, Ciphertext& destination, MemoryPoolHandle pool) const;
     void relinearize_inplace_internal(Ciphertext& encrypted, const RelinKeys& relin_keys, size_t destination_size, MemoryPoolHandle pool) const;
