@@ -220,6 +220,38 @@ int troyn_ckks_multiply_accumulate_relinearize_rescale(const troyn_plan* plan, u
                                                        size_t batch, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Scalar-weighted sums of ciphertexts: a small dense matrix of residues times a vector of ciphertexts in ONE pass.  An ADDITION to the
+ * reference's surface (as the dot-product block above): the step between the powers and the recombination of a polynomial evaluation,
+ * SUM_t s_t * ct_t + c, which is otherwise `terms` x (troyn_multiply_scalar + troyn_add) per output.
+ *   in         host array of `terms` DEVICE pointers, in[t] -> u64[batch][pcount][in_nmod[t]][N], 16-byte aligned
+ *   in_nmod    host, in_nmod[t] >= nmod: only the first nmod limbs of every input are read (dropping limbs in RNS is ignoring them, so
+ *              inputs at a higher level than the output need no troyn_mod_switch_drop first)
+ *   scalars    host [slots][terms][nmod], canonical residues (word < q_{mod_start+l})
+ *   constants  host [slots][nmod] canonical residues, or NULL
+ *   constant_at_index0   0: the constant is added at every index of polynomial 0 (a constant in NTT form); 1: at index 0 only
+ *              (coefficient form).  Apart from this flag the entry does not look at the form: it is scheme-agnostic RNS arithmetic.
+ *   out        [slots][batch][pcount][nmod][N], 16-byte aligned
+ * Contract on integers:
+ *   out[s][b][c][l][i] = ( SUM_t scalars[s][t][l] * in[t][b][c][l][i] + (c == 0 and (i == 0 or !constant_at_index0) ? constants[s][l] : 0) )
+ *                        mod q_{mod_start+l}, in canonical form.
+ * Hence the words are bit-identical to folding troyn_multiply_scalar and troyn_add (plus the constant) term by term: the sum modulo q does
+ * not depend on where the reductions happen.  Every input is read once per tile of up to 8 slots, every output word is written once after
+ * one Barrett reduction; sums of more than 64 terms run as successive launches that carry `out` (64 products of residues below 2^61
+ * plus a canonical carry stay below 2^128), the words do not depend on the cut.
+ * TROYN_E_INVALID: terms == 0, slots == 0 or pcount == 0, a null table or entry, a misaligned pointer, in_nmod[t] < nmod, a modulus slice
+ * outside the plan, a scalar or constant word >= its modulus, `out` overlapping an input.  TROYN_E_WORKSPACE for a workspace below the
+ * queried size.  batch == 0 returns TROYN_OK, launches nothing and looks at no buffer (`out` and the workspace may be null).  The host
+ * tables are read before the call returns: the scalars and constants go through one upload into the workspace, the pointers and limb
+ * counts travel in the kernel arguments.
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_scalar_weighted_sums_workspace_bytes(const troyn_plan* plan, uint32_t nmod, size_t terms, size_t slots);
+int troyn_scalar_weighted_sums(const troyn_plan* plan, uint32_t mod_start, uint32_t nmod,
+                               const uint64_t* const* in, const uint32_t* in_nmod, size_t terms,
+                               const uint64_t* scalars, const uint64_t* constants, int constant_at_index0,
+                               size_t pcount, uint64_t* out, size_t slots, size_t batch,
+                               void* workspace, size_t workspace_bytes, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Modulus switching.
  * troyn_divide_and_round_q_last      RNSTool::divide_and_round_q_last (utils/rns_tool.cu:374-466),
  *                                    BFV mod_switch_to_next, coefficient form.

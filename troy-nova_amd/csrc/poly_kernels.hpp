@@ -151,6 +151,90 @@ __global__ __launch_bounds__(POLY_BLOCK) void dyadic_convolute_accumulate_kernel
     }
 }
 
+// Scalar-weighted sums of ciphertexts (an addition to the reference's kernels, troyn_scalar_weighted_sums): a small dense matrix of residues
+// times a vector of ciphertexts, out[s] = SUM_t scalars[s][t] * in[t] (+ constants[s]), in[t] -> [batch][pcount][in_nmod[t]][N] of which only the
+// first nmod limbs are read, out [slots][batch][pcount][nmod][N].
+// Geometry of dyadic_convolute_accumulate_kernel: a thread owns two adjacent coefficients of one (item, polynomial, limb) row.  New is the SLOT
+// TILE: the thread keeps the 128-bit accumulators of TS slots (8 * TS VGPRs), an input word loaded once is multiplied into all of them, so
+// the inputs are read ceil(slots / TS) times in total (grid = tiles x rows x chunks) and every output word is written once, after ONE
+// barrett128.  The last tile may be partial: `live` is wave-uniform, a dead slot costs neither a multiply nor a store.
+// Bound: plan moduli are < 2^61, so 64 products plus one canonical carry-in stay below 2^128 (64 (2^61 - 1)^2 + 2^61 < 2^128); an
+// accumulator takes ONE product per term, hence at most SSUM_MAX_TERMS = 64 terms per launch.  The driver cuts longer sums into launches
+// that carry `out`; the constant is added after the reduction of the last launch (add_mod), so it does not count against the bound.
+// The pointer table travels in the kernel arguments; the scalars come from a table the driver lays out as [tile][limb][term][TS], so the
+// TS residues of a (tile, limb, term) are one wave-uniform run that the compiler fetches with scalar loads into SGPRs.  The term loop is
+// wave-uniform and unrolled by UNROLL terms with all UNROLL 16-byte loads issued before the multiplies.  No LDS, no scratch.
+constexpr unsigned SSUM_MAX_TERMS = 64;
+struct ScalarSumPtrs { const u64* in[SSUM_MAX_TERMS]; unsigned in_nmod[SSUM_MAX_TERMS]; };
+
+template <int TS, int UNROLL>
+__global__ __launch_bounds__(POLY_BLOCK) void scalar_weighted_sums_kernel(unsigned chunks, const DevModulus* __restrict__ mods, unsigned mod_start, unsigned nmod,
+                                                                          unsigned n, ScalarSumPtrs ptrs, unsigned terms,
+                                                                          const u64* __restrict__ scal, unsigned scal_terms, unsigned term0,
+                                                                          const u64* __restrict__ consts, int constant_at_index0, unsigned pcount,
+                                                                          unsigned rows, unsigned slots, u64* __restrict__ out, int carry) {
+    const unsigned tile = blk_row(chunks) / rows;
+    const unsigned r = blk_row(chunks) % rows;      // (item * pcount + c) * nmod + limb
+    const unsigned limb = r % nmod;
+    const size_t pi = r / nmod;
+    const DevModulus md = mods[mod_start + limb];
+    const unsigned slot0 = tile * TS;
+    const unsigned live = slots - slot0 < (unsigned)TS ? slots - slot0 : (unsigned)TS;
+    const u64* w = scal + (((size_t)tile * nmod + limb) * scal_terms + term0) * TS;
+    u64* op = out + ((size_t)slot0 * rows + r) * n;
+    const size_t slot_stride = (size_t)rows * n;
+    const bool with_const = consts && pi % pcount == 0;
+    for (unsigned i = blk_col(chunks) * 2; i < n; i += chunks * blockDim.x * 2) {
+        u64 loa[TS], hia[TS], lob[TS], hib[TS];
+#pragma unroll
+        for (int s = 0; s < TS; ++s) {
+            loa[s] = hia[s] = lob[s] = hib[s] = 0;
+            if (carry && s < (int)live) {    // canonical carry-in: the earlier launches of a long sum
+                const u64x2 c = ld2(op + s * slot_stride + i);
+                loa[s] = c.a; lob[s] = c.b;
+            }
+        }
+        unsigned t = 0;
+        for (; t + UNROLL <= terms; t += UNROLL) {
+            u64x2 v[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) v[u] = ld2(ptrs.in[t + u] + (pi * ptrs.in_nmod[t + u] + limb) * n + i);
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+#pragma unroll
+                for (int s = 0; s < TS; ++s) {
+                    if (s < (int)live) {
+                        const u64 k = w[(size_t)(t + u) * TS + s];
+                        mac128(loa[s], hia[s], v[u].a, k); mac128(lob[s], hib[s], v[u].b, k);
+                    }
+                }
+            }
+        }
+        for (; t < terms; ++t) {
+            const u64x2 v = ld2(ptrs.in[t] + (pi * ptrs.in_nmod[t] + limb) * n + i);
+#pragma unroll
+            for (int s = 0; s < TS; ++s) {
+                if (s < (int)live) {
+                    const u64 k = w[(size_t)t * TS + s];
+                    mac128(loa[s], hia[s], v.a, k); mac128(lob[s], hib[s], v.b, k);
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < TS; ++s) {
+            if (s < (int)live) {
+                u64 r0 = barrett128(loa[s], hia[s], md.q, md.ratio_lo, md.ratio_hi), r1 = barrett128(lob[s], hib[s], md.q, md.ratio_lo, md.ratio_hi);
+                if (with_const) {
+                    const u64 c = consts[(size_t)(slot0 + s) * nmod + limb];
+                    if (!constant_at_index0) { r0 = add_mod(r0, c, md.q); r1 = add_mod(r1, c, md.q); }
+                    else if (i == 0) r0 = add_mod(r0, c, md.q);
+                }
+                st2(op + s * slot_stride + i, r0, r1);
+            }
+        }
+    }
+}
+
 // generic (any pa, pb) version with the reference's loop structure
 __global__ __launch_bounds__(POLY_BLOCK) void dyadic_convolute_generic_kernel(unsigned chunks, const DevModulus* mods, unsigned mod_start, unsigned nmod,
                                                                               unsigned n, const u64* a, unsigned pa, const u64* b, unsigned pb, u64* out) {

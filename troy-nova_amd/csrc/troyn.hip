@@ -938,6 +938,104 @@ extern "C" int troyn_dyadic_convolute_accumulate(const troyn_plan* p, uint32_t m
     return launch_convolute_accumulate(p->d_mods, p->n, mod_start, nmod, a, b, terms, (u64*)out, accumulate, batch, (hipStream_t)stream);
 }
 
+// Scalar-weighted sums (poly_kernels.hpp scalar_weighted_sums_kernel).  The slot tile of a launch: the smallest instantiated tile that holds
+// every slot, 8 beyond that.
+static inline unsigned ssum_tile(size_t slots) { return slots > 4 ? 8u : slots > 2 ? 4u : slots > 1 ? 2u : 1u; }
+// workspace: the scalars as [tile][limb][term][TS] (dead slots of the last tile zero), then the constants [slots][nmod]
+static inline size_t ssum_scalar_words(size_t nmod, size_t terms, size_t slots) {
+    const size_t ts = ssum_tile(slots);
+    return (slots + ts - 1) / ts * ts * nmod * terms;
+}
+
+extern "C" size_t troyn_scalar_weighted_sums_workspace_bytes(const troyn_plan* p, uint32_t nmod, size_t terms, size_t slots) {
+    (void)p;
+    return (ssum_scalar_words(nmod, terms, slots) + slots * (size_t)nmod) * sizeof(u64);
+}
+
+template <int TS>
+static void launch_scalar_sums_tile(unsigned blocks, hipStream_t s, unsigned ch, const DevModulus* mods, uint32_t mod_start, uint32_t nmod, unsigned n,
+                                    const ScalarSumPtrs& g, unsigned cnt, const u64* scal, unsigned scal_terms, unsigned term0, const u64* consts,
+                                    int at0, unsigned pcount, unsigned rows, unsigned slots, u64* out, int carry) {
+    if (cnt >= 4)
+        hipLaunchKernelGGL((scalar_weighted_sums_kernel<TS, 4>), dim3(blocks), dim3(POLY_BLOCK), 0, s, ch, mods, mod_start, nmod, n, g, cnt, scal, scal_terms,
+                           term0, consts, at0, pcount, rows, slots, out, carry);
+    else
+        hipLaunchKernelGGL((scalar_weighted_sums_kernel<TS, 2>), dim3(blocks), dim3(POLY_BLOCK), 0, s, ch, mods, mod_start, nmod, n, g, cnt, scal, scal_terms,
+                           term0, consts, at0, pcount, rows, slots, out, carry);
+}
+
+extern "C" int troyn_scalar_weighted_sums(const troyn_plan* p, uint32_t mod_start, uint32_t nmod, const uint64_t* const* in, const uint32_t* in_nmod,
+                                          size_t terms, const uint64_t* scalars, const uint64_t* constants, int constant_at_index0, size_t pcount,
+                                          uint64_t* out, size_t slots, size_t batch, void* workspace, size_t workspace_bytes, troyn_stream_t stream) {
+    select_device(p);
+    const std::string P = "[troyn_scalar_weighted_sums]";
+    if (!p || !in || !in_nmod || !scalars) return fail(TROYN_E_INVALID, P + " null argument");
+    if (terms == 0) return fail(TROYN_E_INVALID, P + " no terms");
+    if (slots == 0) return fail(TROYN_E_INVALID, P + " no slots");
+    if (pcount == 0) return fail(TROYN_E_INVALID, P + " no polynomials");
+    if (nmod == 0 || (size_t)mod_start + nmod > p->K) return fail(TROYN_E_INVALID, P + " modulus slice out of range");
+    if (terms > 0xffffffffull || slots > 0xffffffffull || pcount > 0xffffffffull) return fail(TROYN_E_INVALID, P + " table too large");
+    for (size_t t = 0; t < terms; t++)
+        if (in_nmod[t] < nmod) return fail(TROYN_E_INVALID, P + " an input has fewer limbs than nmod");
+    for (size_t s = 0; s < slots; s++) {
+        for (size_t l = 0; l < nmod; l++) {
+            const u64 q = p->moduli[mod_start + l];
+            for (size_t t = 0; t < terms; t++)
+                if (scalars[(s * terms + t) * nmod + l] >= q) return fail(TROYN_E_INVALID, P + " a scalar is not a canonical residue");
+            if (constants && constants[s * nmod + l] >= q) return fail(TROYN_E_INVALID, P + " a constant is not a canonical residue");
+        }
+    }
+    if (batch == 0) return TROYN_OK;      // the host tables have been checked; nothing to launch, no device buffer or pointer entry is looked at
+    if (!out || !workspace) return fail(TROYN_E_INVALID, P + " null argument");
+    if (((uintptr_t)out & 15) || ((uintptr_t)workspace & 15)) return fail(TROYN_E_INVALID, P + " misaligned destination or workspace");
+    const unsigned n = p->n;
+    const size_t rows = batch * pcount * nmod;
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + slots * rows * n * sizeof(u64);
+    for (size_t t = 0; t < terms; t++) {
+        const uintptr_t q = (uintptr_t)in[t];
+        if (!q || (q & 15)) return fail(TROYN_E_INVALID, P + " null or misaligned pointer in the table");
+        if (q < o1 && o0 < q + batch * pcount * in_nmod[t] * (size_t)n * sizeof(u64)) return fail(TROYN_E_INVALID, P + " out overlaps an input");
+    }
+    if (workspace_bytes < troyn_scalar_weighted_sums_workspace_bytes(p, nmod, terms, slots)) return fail(TROYN_E_WORKSPACE, P + " workspace too small");
+    const unsigned ts = ssum_tile(slots);
+    const size_t tiles = (slots + ts - 1) / ts;
+    const unsigned ch = chunks_pairs(n);
+    if (rows > 0xffffffffull) return fail(TROYN_E_INVALID, "[troyn] batch too large for one launch");
+    if (int rc = check_rows(tiles * rows, ch)) return rc;
+    // the host tables are read here: one upload of the re-laid scalars and the constants into the workspace
+    const size_t sw = ssum_scalar_words(nmod, terms, slots);
+    std::vector<u64> tab(sw + (constants ? slots * (size_t)nmod : 0), 0);
+    for (size_t s = 0; s < slots; s++)
+        for (size_t t = 0; t < terms; t++)
+            for (size_t l = 0; l < nmod; l++)
+                tab[(((s / ts) * nmod + l) * terms + t) * ts + s % ts] = scalars[(s * terms + t) * nmod + l];
+    if (constants) std::copy(constants, constants + slots * (size_t)nmod, tab.begin() + sw);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = upload_host_table(s, workspace, tab.data(), tab.size() * sizeof(u64))) return rc;
+    const u64* d_scal = (const u64*)workspace;
+    const u64* d_const = constants ? d_scal + sw : nullptr;
+    const unsigned blocks = (unsigned)(tiles * rows * ch);
+    for (size_t t0 = 0; t0 < terms; t0 += SSUM_MAX_TERMS) {
+        const unsigned cnt = (unsigned)std::min<size_t>(terms - t0, SSUM_MAX_TERMS);
+        ScalarSumPtrs g;
+        for (unsigned t = 0; t < SSUM_MAX_TERMS; t++) {
+            g.in[t] = reinterpret_cast<const u64*>(in[t0 + (t < cnt ? t : 0)]);
+            g.in_nmod[t] = in_nmod[t0 + (t < cnt ? t : 0)];
+        }
+        const int carry = t0 > 0 ? 1 : 0;
+        const u64* cst = t0 + cnt == terms ? d_const : nullptr;      // the constant goes in with the last launch, after its reduction
+#define TROYN_SSUM_LAUNCH(TS) launch_scalar_sums_tile<TS>(blocks, s, ch, p->d_mods, mod_start, nmod, n, g, cnt, d_scal, (unsigned)terms, (unsigned)t0, cst, \
+                                                          constant_at_index0 ? 1 : 0, (unsigned)pcount, (unsigned)rows, (unsigned)slots, (u64*)out, carry)
+        if (ts == 8) TROYN_SSUM_LAUNCH(8);
+        else if (ts == 4) TROYN_SSUM_LAUNCH(4);
+        else if (ts == 2) TROYN_SSUM_LAUNCH(2);
+        else TROYN_SSUM_LAUNCH(1);
+#undef TROYN_SSUM_LAUNCH
+        LAUNCH_CHECK();
+    }
+    return TROYN_OK;
+}
+
 extern "C" int troyn_dyadic_square(const troyn_plan* p, uint32_t mod_start, uint32_t nmod,
                                    const uint64_t* a, uint64_t* out, size_t batch, troyn_stream_t stream) {
     select_device(p);

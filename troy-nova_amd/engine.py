@@ -525,6 +525,48 @@ class Plan:
                                                                                C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
 
+    def scalar_weighted_sums(self, inputs, in_nmod, scalars, nmod, pcount, constants=None, constant_at_index0=False, mod_start=0, out=None, batch=None):
+        """out [slots][batch][pcount][nmod][N]: out[s] = SUM_t scalars[s][t] * inputs[t] (+ constants[s] on polynomial 0), one pass over the inputs
+        for every tile of slots (include/troyn.h states the contract).  inputs[t]: [batch][pcount][in_nmod[t]][N] with in_nmod[t] >= nmod, only
+        its first nmod limbs are read; scalars [slots][terms][nmod] and constants [slots][nmod] (or None) are canonical residues on the host.
+        `batch` is taken from inputs[0] unless given (batch = 0 launches nothing and looks at no buffer: entries and `out` may be None)."""
+        who = "[troyn_scalar_weighted_sums]"
+        terms = len(inputs)
+        if len(in_nmod) != terms:
+            raise capi.TroynInvalidArgument("%s one limb count per input is needed" % who)
+        sc = np.ascontiguousarray(np.array(scalars, dtype=np.uint64))
+        slots = len(scalars)
+        if terms and slots and nmod and sc.shape != (slots, terms, nmod):      # (an empty table is the library's to refuse)
+            raise capi.TroynInvalidArgument("%s scalars are not [slots][terms][nmod]" % who)
+        if sc.size == 0:
+            sc = np.zeros(1, dtype=np.uint64)
+        cs = None
+        if constants is not None:
+            cs = np.ascontiguousarray(np.array(constants, dtype=np.uint64))
+            if cs.shape != (slots, nmod):
+                raise capi.TroynInvalidArgument("%s constants are not [slots][nmod]" % who)
+        if batch is None:
+            words = pcount * int(in_nmod[0]) * self.n if terms else 0
+            if not words or inputs[0] is None or inputs[0].numel() % words:
+                raise capi.TroynInvalidArgument("%s inputs[0] is not [batch][pcount][in_nmod[0]][N]" % who)
+            batch = inputs[0].numel() // words
+        for t, x in enumerate(inputs):
+            if x is not None and batch and x.numel() != batch * pcount * int(in_nmod[t]) * self.n:
+                raise capi.TroynInvalidArgument("%s inputs[%d] is not [batch][pcount][in_nmod][N]" % (who, t))
+        parr = (C.c_void_p * max(terms, 1))(*[None if x is None else _ptr(x).value for x in inputs])
+        narr = (C.c_uint32 * max(terms, 1))(*[int(v) for v in in_nmod])
+        shape = (slots, batch, pcount, nmod, self.n)
+        if out is None and batch:
+            out = torch.empty(shape, dtype=torch.int64, device=self.device)
+        elif out is not None and out.numel() != int(np.prod(shape)):
+            raise capi.TroynInvalidArgument("%s out is not [slots][batch][pcount][nmod][N]" % who)
+        ws = self.workspace(self.lib.troyn_scalar_weighted_sums_workspace_bytes(self.h, nmod, terms, slots)) if batch else None
+        capi.check(self.lib.troyn_scalar_weighted_sums(
+            self.h, mod_start, nmod, parr, narr, terms, sc.ctypes.data_as(capi.p64), None if cs is None else cs.ctypes.data_as(capi.p64),
+            int(bool(constant_at_index0)), pcount, None if out is None else _ptr(out), slots, batch,
+            None if ws is None else C.c_void_p(ws.data_ptr()), 0 if ws is None else ws.numel(), _stream()))
+        return out
+
     # -- modulus switching -------------------------------------------------------------------------
     def divide_and_round_q_last(self, L, x, pcount, out=None):
         batch = x.numel() // (pcount * L * self.n)

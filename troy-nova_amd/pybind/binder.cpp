@@ -496,6 +496,26 @@ PYBIND11_MODULE(pytroy_raw, m) {
     ev.def("multiply_accumulate_relinearize_rescale_new", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, const RelinKeys& k, PoolArg p) {
         return s.multiply_accumulate_relinearize_rescale_new(const_ptrs(a), const_ptrs(b), k, P(p)); },
            py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), POOL);
+    // additions: real linear combinations of ciphertexts in one pass and polynomial evaluation on the fixed Paterson-Stockmeyer schedule (troy.h)
+    ev.def("linear_combinations", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<std::vector<double>>& w, const std::vector<double>& c, double scale,
+                                     const std::vector<Ciphertext*>& d, PoolArg p) {
+        std::vector<Ciphertext> out = s.linear_combinations_new(const_ptrs(a), w, c, scale, P(p));
+        if (d.size() != out.size()) throw std::invalid_argument("[Evaluator::linear_combinations] destination needs one ciphertext per result.");
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },
+           py::arg("encrypted"), py::arg("weights"), py::arg("constants"), py::arg("scale"), py::arg("destination"), POOL);
+    ev.def("linear_combinations_new", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<std::vector<double>>& w, const std::vector<double>& c, double scale,
+                                         PoolArg p) { return s.linear_combinations_new(const_ptrs(a), w, c, scale, P(p)); },
+           py::arg("encrypted"), py::arg("weights"), py::arg("constants"), py::arg("scale"), POOL);
+    ev.def("linear_combination", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<double>& w, double c, double scale, Ciphertext& d, PoolArg p) {
+        s.linear_combination(const_ptrs(a), w, c, scale, d, P(p)); },
+           py::arg("encrypted"), py::arg("weights"), py::arg("constant"), py::arg("scale"), py::arg("destination"), POOL);
+    ev.def("linear_combination_new", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<double>& w, double c, double scale, PoolArg p) {
+        return s.linear_combination_new(const_ptrs(a), w, c, scale, P(p)); },
+           py::arg("encrypted"), py::arg("weights"), py::arg("constant"), py::arg("scale"), POOL);
+    ev.def("evaluate_polynomial", [](const Evaluator& s, const Ciphertext& a, const std::vector<double>& c, const RelinKeys& k, Ciphertext& d, PoolArg p) {
+        s.evaluate_polynomial(a, c, k, d, P(p)); }, py::arg("encrypted"), py::arg("coefficients"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    ev.def("evaluate_polynomial_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<double>& c, const RelinKeys& k, PoolArg p) {
+        return s.evaluate_polynomial_new(a, c, k, P(p)); }, py::arg("encrypted"), py::arg("coefficients"), py::arg("relin_keys"), POOL);
     // additions: the BFV inner product, one scale-down for the sum (troy.h)
     ev.def("bfv_multiply_accumulate", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, Ciphertext& d, PoolArg p) {
         s.bfv_multiply_accumulate(const_ptrs(a), const_ptrs(b), d, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("destination"), POOL);

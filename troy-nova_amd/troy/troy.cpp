@@ -14,6 +14,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <functional>
 #include <istream>
 #include <ostream>
 #include <sstream>
@@ -1727,6 +1728,218 @@ void Evaluator::multiply_accumulate_relinearize_rescale(const std::vector<const 
         detail::LaunchGate gate;
         troyn_check(troyn_ckks_multiply_accumulate_relinearize_rescale(context_->plan(), L0, a.data(), b.data(), a.size(), keys0.data(), out.data().raw_pointer(),
                                                                        ws.raw_pointer(), bytes, 1, current_stream()));
+    }
+    destination = std::move(out);
+}
+
+
+// -- real linear combinations and polynomial evaluation (additions; troyn_scalar_weighted_sums, include/troyn.h) -----------------------------
+namespace {
+// round half away from zero, then the canonical residue: negative values go to q - (|v| mod q)
+uint64_t signed_residue(__int128 v, uint64_t q) {
+    const unsigned __int128 mag = v < 0 ? (unsigned __int128)(-v) : (unsigned __int128)v;
+    const uint64_t r = (uint64_t)(mag % q);
+    return (v < 0 && r) ? q - r : r;
+}
+// value = c * factor in long double (64-bit significand: nothing of the double c is lost), |value| < 2^limit_bits or std::invalid_argument
+// (in_double: the product itself is formed in double, as Evaluator::linear_combinations states; the internal leaf constants of about 2^80 keep long double)
+__int128 scaled_integer(const char* P, double c, double factor, int limit_bits, bool in_double = false) {
+    const long double v = in_double ? (long double)std::round(c * factor) : roundl((long double)c * (long double)factor);
+    if (!(fabsl(v) < ldexpl(1.0L, limit_bits))) throw std::invalid_argument(std::string(P) + " A scaled coefficient does not fit in " + std::to_string(limit_bits) + " bits.");
+    return (__int128)v;
+}
+// one troyn_scalar_weighted_sums over whole ciphertexts: ints [slots][terms] and consts [slots] (or empty) are reduced per limb here
+void scalar_sums_on(const detail::StepEnv& env, const troyn_plan* plan, const std::vector<uint64_t>& moduli, uint32_t nmod, const std::vector<const Ciphertext*>& ins,
+                    const std::vector<__int128>& ints, const std::vector<__int128>& consts, size_t slots, size_t pcount, uint64_t* out) {
+    const size_t terms = ins.size();
+    std::vector<const uint64_t*> ptrs(terms);
+    std::vector<uint32_t> in_nmod(terms);
+    for (size_t t = 0; t < terms; t++) { ptrs[t] = ins[t]->data().raw_pointer(); in_nmod[t] = static_cast<uint32_t>(ins[t]->coeff_modulus_size()); }
+    std::vector<uint64_t> sc(slots * terms * nmod), cs(consts.empty() ? 0 : slots * nmod);
+    for (size_t s = 0; s < slots; s++)
+        for (uint32_t l = 0; l < nmod; l++) {
+            for (size_t t = 0; t < terms; t++) sc[(s * terms + t) * nmod + l] = signed_residue(ints[s * terms + t], moduli[l]);
+            if (!consts.empty()) cs[s * nmod + l] = signed_residue(consts[s], moduli[l]);
+        }
+    const size_t bytes = troyn_scalar_weighted_sums_workspace_bytes(plan, nmod, terms, slots);
+    utils::DynamicArray ws((bytes + 15) / 8, true, env.pool);
+    detail::LaunchGate gate(env.gated);
+    env.check(troyn_scalar_weighted_sums(plan, 0, nmod, ptrs.data(), in_nmod.data(), terms, sc.data(), consts.empty() ? nullptr : cs.data(), 0, pcount, out, slots, 1,
+                                         ws.raw_pointer(), bytes, env.stream));
+}
+}  // namespace
+
+void Evaluator::linear_combinations(const std::vector<const Ciphertext*>& encrypted, const std::vector<std::vector<double>>& weights, const std::vector<double>& constants,
+                                    double scale, std::vector<Ciphertext>& destination, MemoryPoolHandle pool) const {
+    linear_combinations(encrypted, weights, constants, scale, destination, pool, "[Evaluator::linear_combinations]");
+}
+
+void Evaluator::linear_combinations(const std::vector<const Ciphertext*>& encrypted, const std::vector<std::vector<double>>& weights, const std::vector<double>& constants,
+                                    double scale, std::vector<Ciphertext>& destination, MemoryPoolHandle pool, const char* P) const {
+    if (context_->key_context_data().value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(std::string(P) + " CKKS only.");
+    if (encrypted.empty() || weights.empty()) throw std::invalid_argument(std::string(P) + " Empty operand list.");
+    if (!constants.empty() && constants.size() != weights.size()) throw std::invalid_argument(std::string(P) + " One constant per result is needed.");
+    if (!(scale > 0.0) || !std::isfinite(scale)) throw std::invalid_argument(std::string(P) + " Scale out of bounds");
+    const size_t terms = encrypted.size(), slots = weights.size();
+    const Ciphertext* lowest = nullptr;
+    for (const Ciphertext* c : encrypted) {
+        if (!c) throw std::invalid_argument(std::string(P) + " Null operand.");
+        check_no_seed(P, *c); check_on_device(P, context_, *c);
+        if (!c->is_ntt_form()) throw std::invalid_argument(std::string(P) + " Ciphertext must be in NTT form.");
+        get_context_data(P, c->parms_id());
+        if (c->polynomial_count() != 2 && c->polynomial_count() != 3) throw std::invalid_argument(std::string(P) + " Operands must have two or three polynomials.");
+        if (c->polynomial_count() != encrypted[0]->polynomial_count()) throw std::invalid_argument(std::string(P) + " Operands have different polynomial counts.");
+        if (!lowest || c->coeff_modulus_size() < lowest->coeff_modulus_size()) lowest = c;
+    }
+    std::vector<__int128> ints(slots * terms), consts(constants.empty() ? 0 : slots);
+    for (size_t s = 0; s < slots; s++) {
+        if (weights[s].size() != terms) throw std::invalid_argument(std::string(P) + " A weight row needs one weight per operand.");
+        for (size_t t = 0; t < terms; t++) ints[s * terms + t] = scaled_integer(P, weights[s][t], scale / encrypted[t]->scale(), 62, true);
+        if (!constants.empty()) consts[s] = scaled_integer(P, constants[s], scale, 62, true);
+    }
+    auto cd = get_context_data(P, lowest->parms_id());
+    const uint32_t nmod = static_cast<uint32_t>(lowest->coeff_modulus_size());
+    std::vector<uint64_t> moduli(nmod);
+    for (uint32_t l = 0; l < nmod; l++) moduli[l] = cd->parms().coeff_modulus()[l].value();
+    const size_t pc = lowest->polynomial_count();
+    std::vector<Ciphertext> out(slots);
+    for (size_t s = 0; s < slots; s++) {
+        out[s] = Ciphertext::like(*lowest, pc, false, pool);
+        out[s].scale() = scale; out[s].is_ntt_form() = true;
+    }
+    const detail::StepEnv env = on_current_stream(pool, true);
+    if (slots == 1) {
+        scalar_sums_on(env, context_->plan(), moduli, nmod, encrypted, ints, consts, 1, pc, out[0].data().raw_pointer());
+    } else {
+        const size_t words = out[0].data().size();
+        utils::DynamicArray block(slots * words, true, pool);
+        scalar_sums_on(env, context_->plan(), moduli, nmod, encrypted, ints, consts, slots, pc, block.raw_pointer());
+        for (size_t s = 0; s < slots; s++)
+            detail::hip_check(hipMemcpyAsync(out[s].data().raw_pointer(), block.raw_pointer() + s * words, words * 8, hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
+    }
+    destination = std::move(out);
+}
+
+void Evaluator::evaluate_polynomial(const Ciphertext& x, const std::vector<double>& coefficients, const RelinKeys& relin_keys, Ciphertext& destination,
+                                    MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::evaluate_polynomial]";
+    if (context_->key_context_data().value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(std::string(P) + " CKKS only.");
+    check_no_seed(P, x); check_on_device(P, context_, x);
+    if (!x.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Ciphertext must be in NTT form.");
+    if (x.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " The ciphertext must have two polynomials.");
+    size_t d = coefficients.size();
+    while (d > 0 && coefficients[d - 1] == 0.0) d--;
+    if (d == 0) throw std::invalid_argument(std::string(P) + " All coefficients are zero.");
+    d--;     // the degree
+    auto coef = [&](size_t m) { return m <= d ? coefficients[m] : 0.0; };
+    auto clog2 = [](size_t v) { size_t r = 0; while ((size_t(1) << r) < v) r++; return r; };
+    size_t k = 1, g = 1, rec_depth = 0, depth = 1;
+    if (d >= 2) {
+        k = 2; while (k * k < d + 1) k *= 2;
+        g = (d + k) / k;
+        rec_depth = std::max(clog2((g - 1) * k), clog2(k) + 1);
+        depth = rec_depth + 1;
+    }
+    auto cd0 = get_context_data(P, x.parms_id());
+    const size_t L0 = x.coeff_modulus_size();
+    if (L0 < depth + 1)
+        throw std::invalid_argument(std::string(P) + " Too few levels: degree " + std::to_string(d) + " needs " + std::to_string(depth + 1) + " limbs, the ciphertext has " +
+                                    std::to_string(L0) + ".");
+    std::vector<uint64_t> moduli(L0);
+    for (size_t l = 0; l < L0; l++) moduli[l] = cd0->parms().coeff_modulus()[l].value();
+    const double S = x.scale();
+    const detail::StepEnv env = on_current_stream(pool, true);
+    const troyn_plan* plan = context_->plan();
+    const size_t n = x.poly_modulus_degree();
+    auto level_down = [&](size_t steps) { auto cd = cd0; for (size_t i = 0; i < steps; i++) cd = cd->next_context_data().value(); return cd; };
+
+    // one leaf sum over `ins` at `nmod` limbs for `slots` rows of coefficients, then the batched rescale: [slots][2][nmod - 1][N]
+    auto leaves = [&](const std::vector<const Ciphertext*>& ins, size_t nmod, size_t slots, const std::vector<double>& sum_scale,
+                      const std::function<double(size_t, size_t)>& c, utils::DynamicArray& out) {
+        const size_t terms = ins.size();
+        std::vector<__int128> ints(slots * terms), consts(slots);
+        for (size_t s = 0; s < slots; s++) {
+            for (size_t t = 0; t < terms; t++) ints[s * terms + t] = scaled_integer(P, c(s, t + 1), sum_scale[s] / ins[t]->scale(), 62);
+            consts[s] = scaled_integer(P, c(s, 0), sum_scale[s], 126);
+        }
+        utils::DynamicArray sum(slots * 2 * nmod * n, true, pool);
+        scalar_sums_on(env, plan, moduli, static_cast<uint32_t>(nmod), ins, ints, consts, slots, 2, sum.raw_pointer());
+        out = utils::DynamicArray(slots * 2 * (nmod - 1) * n, true, pool);
+        detail::rescale_step(env, plan, static_cast<uint32_t>(nmod), sum.raw_pointer(), 2, out.raw_pointer(), slots);
+    };
+
+    if (d <= 1) {
+        utils::DynamicArray leaf;
+        leaves({&x}, L0, 1, {S * static_cast<double>(moduli[L0 - 1])}, [&](size_t, size_t i) { return coef(i); }, leaf);
+        Ciphertext out = Ciphertext::like(x, 2, L0 - 1, false, pool);
+        out.parms_id() = level_down(1)->parms_id(); out.scale() = S; out.is_ntt_form() = true;
+        detail::hip_check(hipMemcpyAsync(out.data().raw_pointer(), leaf.raw_pointer(), out.data().size() * 8, hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
+        destination = std::move(out);
+        return;
+    }
+
+    // the powers, memoised
+    std::map<size_t, Ciphertext> powers;
+    std::function<const Ciphertext&(size_t)> power = [&](size_t m) -> const Ciphertext& {
+        if (m == 1) return x;
+        auto it = powers.find(m);
+        if (it != powers.end()) return it->second;
+        size_t a = 1; while (a * 2 < m) a *= 2;      // the largest power of two below m (m / 2 for a power of two)
+        const Ciphertext* pa = &power(a);
+        const Ciphertext* pb = &power(m - a);
+        Ciphertext lowered;
+        if (pa->coeff_modulus_size() > pb->coeff_modulus_size()) { mod_switch_to(*pa, pb->parms_id(), lowered, pool); pa = &lowered; }
+        else if (pb->coeff_modulus_size() > pa->coeff_modulus_size()) { mod_switch_to(*pb, pa->parms_id(), lowered, pool); pb = &lowered; }
+        Ciphertext prod;
+        multiply_relinearize_rescale(*pa, *pb, relin_keys, prod, pool);
+        return powers.emplace(m, std::move(prod)).first->second;
+    };
+    std::vector<const Ciphertext*> babies;
+    for (size_t i = 1; i < k; i++) babies.push_back(&power(i));
+    const size_t Lrec = L0 - rec_depth;                         // limbs at the recombination level l*
+    auto cd_rec = level_down(rec_depth);
+    std::vector<Ciphertext> lowered_giants(g - 1);               // only the giants above l* are copied (brought down)
+    std::vector<const Ciphertext*> giants(g - 1);
+    for (size_t j = 1; j < g; j++) {
+        const Ciphertext& G = power(j * k);
+        if (G.coeff_modulus_size() > Lrec) { mod_switch_to(G, cd_rec->parms_id(), lowered_giants[j - 1], pool); giants[j - 1] = &lowered_giants[j - 1]; }
+        else giants[j - 1] = &G;
+    }
+    const double T = S * static_cast<double>(moduli[Lrec - 1]);
+    // leaves 1..g-1 at Lrec + 1 limbs: leaf_j at T / scale(x^(jk)) after the division by q_{Lrec}
+    std::vector<double> sum_scale(g - 1);
+    for (size_t j = 1; j < g; j++) sum_scale[j - 1] = T / giants[j - 1]->scale() * static_cast<double>(moduli[Lrec]);
+    utils::DynamicArray upper, leaf0;
+    leaves(babies, Lrec + 1, g - 1, sum_scale, [&](size_t s, size_t i) { return coef((s + 1) * k + i); }, upper);
+    // leaf_0 at Lrec limbs and scale T: its division lands on the result's level and scale
+    leaves(babies, Lrec, 1, {T}, [&](size_t, size_t i) { return coef(i); }, leaf0);
+    // the recombination: SUM_j leaf_j * x^(jk), one key switch and one rescale
+    // every product leaf_j * x^(jk) has the scale T: that is the scale to hold against the modulus at l*; then relinearize's key checks
+    if (!is_scale_within_bounds(T, cd_rec)) throw std::invalid_argument(std::string(P) + " Scale out of bounds");
+    if (relin_keys.parms_id() != context_->key_parms_id()) throw std::invalid_argument(std::string(P) + " Relin keys has incorrect parms id.");
+    const size_t key_index = RelinKeys::get_index(2);
+    if (key_index >= relin_keys.data().size()) throw std::out_of_range(std::string(P) + " Key switch keys index out of range.");
+    if (!context_->using_keyswitching()) throw std::invalid_argument(std::string(P) + " Keyswitching is not supported.");
+    if (relin_keys.data()[key_index].size() < Lrec) throw std::invalid_argument(std::string(P) + " Key switching key has too few components for this level.");
+    for (const auto& key : relin_keys.data()[key_index]) {
+        check_no_seed(P, key.as_ciphertext());
+        if (!key.on_device()) throw std::invalid_argument(std::string(P) + " Incompatible encryption parameters.");
+    }
+    const uint32_t L = static_cast<uint32_t>(Lrec);
+    const ParmsID next = cd_rec->next_context_data().value()->parms_id();
+    const std::vector<const uint64_t*> keys = relin_keys.get_data_ptrs(key_index);
+    std::vector<const uint64_t*> a(g - 1), b(g - 1);
+    const size_t leaf_words = 2 * Lrec * n;
+    for (size_t j = 0; j + 1 < g; j++) { a[j] = upper.raw_pointer() + j * leaf_words; b[j] = giants[j]->data().raw_pointer(); }
+    Ciphertext out = Ciphertext::like(*giants[0], 2, Lrec - 1, false, pool);
+    out.parms_id() = next; out.scale() = S; out.is_ntt_form() = true;
+    const size_t bytes = troyn_ckks_multiply_accumulate_relinearize_rescale_workspace_bytes(plan, L, a.size(), 1);
+    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
+    {
+        detail::LaunchGate gate;
+        troyn_check(troyn_ckks_multiply_accumulate_relinearize_rescale(plan, L, a.data(), b.data(), a.size(), keys.data(), out.data().raw_pointer(), ws.raw_pointer(), bytes, 1,
+                                                                       env.stream));
+        troyn_check(troyn_add(plan, 0, static_cast<uint32_t>(Lrec - 1), out.data().raw_pointer(), leaf0.raw_pointer(), out.data().raw_pointer(), 2, env.stream));
     }
     destination = std::move(out);
 }

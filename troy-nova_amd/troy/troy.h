@@ -1494,6 +1494,50 @@ public:
         Ciphertext d; multiply_accumulate_relinearize_rescale(e1, e2, relin_keys, d, pool); return d;
     }
 
+    // ADDITION to the reference's interface: real linear combinations of ciphertexts and polynomial evaluation (CKKS).
+    //   linear_combinations: destination[s] = SUM_t weights[s][t] * encrypted[t] + constants[s], ONE pass over the operands for all results
+    //   (troyn_scalar_weighted_sums, include/troyn.h).  Every operand is on the device, in NTT form, with two or three polynomials (the same
+    //   count for all); levels may differ, the results sit at the lowest level among the operands (limbs above it are ignored, no copy).  The
+    //   caller gives the scale of the results: the integer for (s, t) is weights[s][t] * (scale / encrypted[t].scale()), computed in double in
+    //   that order and rounded half away from zero, the constant's integer is constants[s] * scale; negative values go to q_l - (|v| mod q_l);
+    //   a magnitude of 2^62 or more is std::invalid_argument.  The result's scale is set to `scale` exactly.  `constants` may be empty.
+    //   evaluate_polynomial: destination = p(encrypted), p(x) = SUM_m coefficients[m] x^m (power basis), degree d = the index of the last
+    //   non-zero coefficient.  The schedule is fixed (Paterson-Stockmeyer): k = the smallest power of two with k^2 >= d + 1, g = ceil((d + 1) / k);
+    //   powers by multiply_relinearize_rescale, memoised (a power of two is the square of x^(m/2), any other m is x^a * x^(m-a) with a the
+    //   largest power of two below m, the operand at the higher level brought down first), depth(x^m) = ceil(log2 m);
+    //   p = leaf_0 + SUM_{0<j<g} leaf_j * x^(jk), leaf_j = SUM_{i<k} c_{jk+i} x^i: the leaves j >= 1 are ONE troyn_scalar_weighted_sums over the
+    //   babies x..x^(k-1) and one batched division, leaf_0 a second one; the recombination is ONE
+    //   troyn_ckks_multiply_accumulate_relinearize_rescale over the g - 1 pairs at the level l* = input level - max(ceil(log2((g-1)k)), log2 k + 1)
+    //   (the giants are brought there), leaf_0 is added after it.  Scales match exactly by construction: with T = encrypted.scale() * q_last(l*),
+    //   leaf_j is produced at T / scale(x^(jk)) and leaf_0 at T at level l*; the result's scale is set to encrypted.scale().  Total depth:
+    //   max(ceil(log2((g-1)k)), log2 k + 1) + 1 levels; d <= 1 is a single linear combination and one rescale (depth 1).  Too few levels,
+    //   an all-zero coefficient vector, another scheme, coefficient form: std::invalid_argument naming the method.
+    //   Out of scope: the Chebyshev basis, and recursive splitting for degrees beyond about 63.
+    // Call combining does not take part: these methods always launch directly.
+    void linear_combinations(const std::vector<const Ciphertext*>& encrypted, const std::vector<std::vector<double>>& weights, const std::vector<double>& constants,
+                             double scale, std::vector<Ciphertext>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::vector<Ciphertext> linear_combinations_new(const std::vector<const Ciphertext*>& encrypted, const std::vector<std::vector<double>>& weights,
+                                                    const std::vector<double>& constants, double scale, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; linear_combinations(encrypted, weights, constants, scale, d, pool); return d;
+    }
+    void linear_combination(const std::vector<const Ciphertext*>& encrypted, const std::vector<double>& weights, double constant, double scale, Ciphertext& destination,
+                            MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; linear_combinations(encrypted, {weights}, {constant}, scale, d, pool, "[Evaluator::linear_combination]"); destination = std::move(d[0]);
+    }
+    Ciphertext linear_combination_new(const std::vector<const Ciphertext*>& encrypted, const std::vector<double>& weights, double constant, double scale,
+                                      MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; linear_combination(encrypted, weights, constant, scale, d, pool); return d;
+    }
+    void evaluate_polynomial(const Ciphertext& encrypted, const std::vector<double>& coefficients, const RelinKeys& relin_keys, Ciphertext& destination,
+                             MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext evaluate_polynomial_new(const Ciphertext& encrypted, const std::vector<double>& coefficients, const RelinKeys& relin_keys,
+                                       MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; evaluate_polynomial(encrypted, coefficients, relin_keys, d, pool); return d;
+    }
+    // (the form that names the calling method in its refusals)
+    void linear_combinations(const std::vector<const Ciphertext*>& encrypted, const std::vector<std::vector<double>>& weights, const std::vector<double>& constants,
+                             double scale, std::vector<Ciphertext>& destination, MemoryPoolHandle pool, const char* method) const;
+
     // ADDITION to the reference's interface: the BFV inner product.  destination = the BEHZ multiply (evaluator.cu:29-116) with the tensor
     //   products of all pairs summed BEFORE its scale-down: one floor (and, in the relinearizing form, one key switch,
     //   evaluator_keyswitching.cu:119-144) for the whole sum (troyn_bfv_multiply_accumulate[_relinearize], include/troyn.h).  It decrypts to
