@@ -448,8 +448,8 @@ int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t L, int is_
  * troyn_apply_galois_sum_each on that result with the giant elements and keys: one decomposition of ct, `giants` divisions for the inner
  * sums, ONE division for the outer sum.  One workspace, one table upload per stage (per group of TROYN_HOIST_EACH_GROUP giant steps in
  * the second); the inner results live in the workspace and are never visible.
- * Out of scope: "double hoisting", keeping the inner c0 component on the extended basis and skipping its division.  It changes the words
- * of the inner stage and is a separate step.
+ * "double hoisting", keeping the inner c0 component on the extended basis and skipping its division, changes the words of the inner
+ * stage: it is troyn_linear_transform_bsgs_double_hoisted, the block below.
  * TROYN_E_INVALID: babies == 0, giants == 0, a giant step with no weight, a misaligned weight, and what the two entries refuse for their
  * tables and buffers (`out` may not overlap `ct`).  TROYN_E_WORKSPACE: a workspace below
  * troyn_linear_transform_bsgs_workspace_bytes(plan, L, babies, giants, batch, is_ntt_form).  batch == 0 returns TROYN_OK and launches
@@ -466,6 +466,46 @@ int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, int is_ckks,
                                 const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
                                 const uint64_t* const* weights, uint64_t* out,
                                 void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The double-hoisted BSGS linear transform: troyn_linear_transform_bsgs with the second hoisting level (Bossuat et al.).  The inner sums
+ * stay on the extended basis q_0 .. q_{L-1}, q_special; of a giant step only component 1 is divided by the special prime, because only c1
+ * is decomposed for the giant key; component 0 goes through the giant automorphism on the extended basis and into the outer sum before
+ * the ONE final division.  An ADDITION; the arguments, layouts, alignment rules and refusals are those of troyn_linear_transform_bsgs
+ * (babies, giants, both key tables, weights[g * babies + b] in key-level layout and already rotated back by the giant step; BFV in
+ * coefficient form, CKKS in NTT form).
+ * Contract, per item, on integers (tests/bsgs_double_spec.py; the notation of the three blocks above).  T_g = {b : weight (g, b) non-NULL}:
+ *   X^(g)_c[m]   the inner extended-basis value of the weighted-sums block for slot g WITH its unkeyed contributions injected, for every
+ *                m in {q_0 .. q_{L-1}, q_special}:
+ *                SUM_{b in T_g, B_b != 1} w_{g,b}[m] (*) SUM_j (e_{b,j} mod m) (*) k_{b,j}[c][m]  +  (q_special mod m) * U^(g)_c[m]   mod m
+ *                U_0 = SUM_{b in T_g} w_{g,b} (*) sigma_{B_b}(c0),   U_1 = SUM_{b in T_g, B_b = 1} w_{g,b} (*) c1;  nothing is added on
+ *                the special row (q_special mod q_special = 0)
+ *   G_g != 1:    v^(g)[l] = (X^(g)_1[q_l] - r) * q_special^-1 mod q_l, r the centred representative of the special row exactly as in
+ *                troyn_switch_key -- the ONLY inner division, on component 1 alone
+ *                d^(g)_j = limb j of v^(g) in coefficient form,  e^(g)_j = sigma_{G_g}(d^(g)_j), signed
+ *                Y_c[m] += SUM_j (e^(g)_j mod m) (*) kG_{g,j}[c][m]
+ *                Y_0[m] += sigma_{G_g}(X^(g)_0[m])  on EVERY row, the special one included; sigma acts on a residue row as the signed
+ *                permutation modulo m
+ *   G_g = 1:     Y_c[m] += X^(g)_c[m] for both components: no division, no key
+ *   out_c[l] = (Y_c[q_l] - r_c) * q_special^-1 mod q_l, r_c the centred representative of Y_c[q_special]: ONE division for the transform
+ * The words are NOT those of troyn_linear_transform_bsgs: that entry rounds both components of every inner sum; this one rounds only
+ * component 1 of the giant steps with a key.  Both decrypt to the same message under the same kind of noise bound, and this entry has
+ * one rounding per giant step fewer.  Per giant step with a key it saves the inverse transform of one special row, L forward transforms
+ * and one finish pass; per identity giant step the whole inner division.
+ * The workspace holds the inner results [giants][batch][2][L+1][N]; everything else is sized by one group of TROYN_HOIST_EACH_GROUP giant
+ * steps.  One table upload for the inner stage and one per group.
+ * Scope: BFV and CKKS.  BGV is left out (its tail divides differently).
+ * TROYN_E_INVALID / TROYN_E_WORKSPACE: as troyn_linear_transform_bsgs, against
+ * troyn_linear_transform_bsgs_double_hoisted_workspace_bytes(plan, L, babies, giants, batch, is_ntt_form).  batch == 0 returns TROYN_OK and
+ * launches nothing.  The tables are read before the call returns.
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_linear_transform_bsgs_double_hoisted_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t babies, size_t giants, size_t batch,
+                                                                  int is_ntt_form);
+int troyn_linear_transform_bsgs_double_hoisted(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
+                                               const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                                               const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                               const uint64_t* const* weights, uint64_t* out,
+                                               void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * BGV.  BGV ciphertexts live in NTT form and reuse troyn_ntt, troyn_dyadic_convolute (bgv_multiply,

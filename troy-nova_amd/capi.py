@@ -78,6 +78,9 @@ SYMBOLS = {
     "troyn_linear_transform_bsgs_workspace_bytes": (sz, [vp, u32, sz, sz, sz, C.c_int]),
     "troyn_linear_transform_bsgs": (C.c_int, [vp, u32, C.c_int, C.c_int, vp, p64, C.POINTER(vp), sz, p64, C.POINTER(vp), sz, C.POINTER(vp), vp,
                                               vp, sz, sz, vp]),
+    "troyn_linear_transform_bsgs_double_hoisted_workspace_bytes": (sz, [vp, u32, sz, sz, sz, C.c_int]),
+    "troyn_linear_transform_bsgs_double_hoisted": (C.c_int, [vp, u32, C.c_int, C.c_int, vp, p64, C.POINTER(vp), sz, p64, C.POINTER(vp), sz,
+                                                             C.POINTER(vp), vp, vp, sz, sz, vp]),
     "troyn_behz_gamma": (u64, [vp]),
     "troyn_bfv_scale_up": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, sz, C.c_int, sz, vp]),
     "troyn_bfv_decrypt_scale_and_round": (C.c_int, [vp, vp, vp, sz, vp]),

@@ -375,4 +375,116 @@ __global__ __launch_bounds__(POLY_BLOCK) void hoist_each_kernel(unsigned chunks,
     }
 }
 
+// hoist_double_kernel (troyn_linear_transform_bsgs_double_hoisted): the rows, item groups, gather and term groups of hoist_each_kernel for
+// the outer stage of the double-hoisted BSGS transform.  Term t is a giant step; x_ntt holds the inner stage's extended-basis sums
+// X^(t)[item][c][k] in NTT form (hoist_weighted_kernel's output, unkeyed contributions already injected), digits_ntt the transformed digits
+// of v^(t), the divided component 1 of X^(t):
+//     poly_prod[item][c][k][i] (+)= SUM_t ( SUM_j D[t][item][k][j][pi_t(i)] * key_{t,j}[c][k][i]  +  [c = 0] X^(t)[item][0][k][pi_t(i)] )    (g_t != 1)
+//                                         X^(t)[item][c][k][i]                                                                                (g_t  = 1)
+//   mod m_k on EVERY row k = 0 .. L, the special row included: component 0 stays on the extended basis, so nothing is scaled by q_special
+//   here and no c0 is transformed -- the gather of X_0 replaces hoist_each_kernel's injection.  An identity term reads no digits and no
+//   keys.  Per item and non-identity term a row streams 8 L N bytes of digits and 8 N bytes of X_0 next to the 16 L N bytes of keys the
+//   items share.  No LDS, no scratch.
+struct HoistDoubleArgs {
+    const DevModulus* mods;
+    unsigned K, L, log_n, batch;
+    unsigned groups;               // ceil(batch / IB)
+    unsigned terms;                // the giant steps of this launch (one group)
+    int accumulate;                // a later group: add into poly_prod
+    const u64* digits_ntt;         // D [terms][batch][L+1][L][N]; the blocks of an identity term are not read
+    const u64* v_ntt;              // NTT-form limb l of v^(t) of item b at v_ntt + ((t * batch + b) * L + l) * N (read when diag_from_v)
+    int diag_from_v;               // skip_diag: digit k of row k < L was not produced, it is v's NTT-form limb k
+    const u64* x_ntt;              // X [terms][batch][2][L+1][N]
+    const u64* const* keys;        // device table [terms][L] -> u64[2][K][N]; the entries of an identity term are not read
+    const u64* elements;           // device table [terms]
+    u64* poly_prod;                // [batch][2][L+1][N]
+};
+
+template <int IB>
+__global__ __launch_bounds__(POLY_BLOCK) void hoist_double_kernel(unsigned chunks, HoistDoubleArgs a) {
+    const unsigned L = a.L, K = a.K, n = 1u << a.log_n;
+    const unsigned row = blk_row(chunks);
+    const unsigned k = row % (L + 1);
+    const unsigned grp = row / (L + 1);
+    const unsigned key_index = (k == L) ? K - 1 : k;
+    const DevModulus md = a.mods[key_index];
+    const size_t key_poly = (size_t)K * n;
+    const size_t digit_item = (size_t)(L + 1) * L * n;
+    const size_t comp = (size_t)(L + 1) * n;
+    const bool diag = a.diag_from_v && k < L;
+    // items past the batch's end recompute the last item and store nothing
+    size_t item[IB];
+#pragma unroll
+    for (int b = 0; b < IB; ++b) {
+        const unsigned it = grp * IB + b;
+        item[b] = it < a.batch ? it : a.batch - 1;
+    }
+    for (unsigned x = blk_col(chunks) * 2; x < n; x += chunks * blockDim.x * 2) {
+        u64 r[IB][2][2];
+#pragma unroll
+        for (int b = 0; b < IB; ++b) {
+            if (a.accumulate) {
+                const u64* pp = a.poly_prod + item[b] * 2 * comp + (size_t)k * n + x;
+                const u64x2 p0 = ld2(pp), p1 = ld2(pp + comp);
+                r[b][0][0] = p0.a; r[b][0][1] = p0.b; r[b][1][0] = p1.a; r[b][1][1] = p1.b;
+            } else r[b][0][0] = r[b][0][1] = r[b][1][0] = r[b][1][1] = 0;
+        }
+        for (unsigned t = 0; t < a.terms; ++t) {
+            const unsigned g = (unsigned)a.elements[t];
+            const size_t first = (size_t)t * a.batch;      // the term's first item
+            if (g != 1) {
+                const unsigned src = hoist_ntt_source(x, g, a.log_n);
+                const unsigned pair = src & ~1u;
+                const bool swap = src & 1u;
+                u64 lo[IB][2][2], hi[IB][2][2];
+#pragma unroll
+                for (int b = 0; b < IB; ++b)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) lo[b][c][0] = lo[b][c][1] = hi[b][c][0] = hi[b][c][1] = 0;
+                for (unsigned j = 0; j < L; ++j) {
+                    const u64* kj = a.keys[(size_t)t * L + j] + (size_t)key_index * n + x;
+                    const u64x2 k0 = ld2(kj), k1 = ld2(kj + key_poly);
+#pragma unroll
+                    for (int b = 0; b < IB; ++b) {
+                        const u64* drow = (diag && j == k) ? a.v_ntt + ((first + item[b]) * L + k) * (size_t)n
+                                                           : a.digits_ntt + (first + item[b]) * digit_item + ((size_t)k * L + j) * n;
+                        const u64x2 v = ld2(drow + pair);
+                        const u64 d0 = swap ? v.b : v.a, d1 = swap ? v.a : v.b;
+                        mac128(lo[b][0][0], hi[b][0][0], d0, k0.a); mac128(lo[b][0][1], hi[b][0][1], d1, k0.b);
+                        mac128(lo[b][1][0], hi[b][1][0], d0, k1.a); mac128(lo[b][1][1], hi[b][1][1], d1, k1.b);
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < IB; ++b) {
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        r[b][c][0] = add_mod(r[b][c][0], barrett128(lo[b][c][0], hi[b][c][0], md.q, md.ratio_lo, md.ratio_hi), md.q);
+                        r[b][c][1] = add_mod(r[b][c][1], barrett128(lo[b][c][1], hi[b][c][1], md.q, md.ratio_lo, md.ratio_hi), md.q);
+                    }
+                    // sigma_g of row k of X_0, the special row included: the permutation of the NTT-form words
+                    const u64x2 v = ld2(a.x_ntt + (first + item[b]) * 2 * comp + (size_t)k * n + pair);
+                    r[b][0][0] = add_mod(r[b][0][0], swap ? v.b : v.a, md.q);
+                    r[b][0][1] = add_mod(r[b][0][1], swap ? v.a : v.b, md.q);
+                }
+            } else {
+                // the identity giant step: both components as they are, no division and no key
+#pragma unroll
+                for (int b = 0; b < IB; ++b) {
+                    const u64* xp = a.x_ntt + (first + item[b]) * 2 * comp + (size_t)k * n + x;
+                    const u64x2 v0 = ld2(xp), v1 = ld2(xp + comp);
+                    r[b][0][0] = add_mod(r[b][0][0], v0.a, md.q); r[b][0][1] = add_mod(r[b][0][1], v0.b, md.q);
+                    r[b][1][0] = add_mod(r[b][1][0], v1.a, md.q); r[b][1][1] = add_mod(r[b][1][1], v1.b, md.q);
+                }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < IB; ++b) {
+            if (grp * IB + b >= a.batch) break;
+            u64* pp = a.poly_prod + item[b] * 2 * comp + (size_t)k * n + x;
+            st2(pp, r[b][0][0], r[b][0][1]);
+            st2(pp + comp, r[b][1][0], r[b][1][1]);
+        }
+    }
+}
+
 }  // namespace troyn

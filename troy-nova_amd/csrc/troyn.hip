@@ -1217,9 +1217,9 @@ static int prepare_keys_int(const troyn_plan* p, const KeyPtrs& kp, unsigned L, 
     return TROYN_OK;
 }
 // INTT of the two special-prime rows of poly_prod [item][2][L+1][N] into dst [item][2][N]
-static NttArgs special_rows_args(const troyn_plan* p, const u64* poly_prod, u64* dst, unsigned L) {
+static NttArgs special_rows_args(const troyn_plan* p, const u64* poly_prod, u64* dst, unsigned L, unsigned comps = 2) {
     const unsigned n = p->n;
-    NttArgs a = contiguous_args(p, poly_prod + (size_t)L * n, dst, 2, 1, p->K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
+    NttArgs a = contiguous_args(p, poly_prod + (size_t)L * n, dst, comps, 1, p->K - 1, 1, TROYN_IDX_COMPONENTWISE, 0);
     a.in_pstride = (long long)(L + 1) * n; a.in_bstride = 2ll * (L + 1) * n;
     return a;
 }
@@ -1303,7 +1303,12 @@ struct KsCall {
     u64* dest; const u64* addend; size_t addend_bstride;
     u64* ws; KsLayout w; size_t batch; hipStream_t s; const BgvTail* bgv;
     const u64* digits; size_t digits_bstride;      // the target in coefficient form: the caller's rows, or target_intt after ks_digits
+    // the tail's polynomials per item: 2 = both components of poly_prod [item][2][L+1][N] into dest [item][2][L][N]; 1 = component 1 alone into
+    // dest [item][L][N] (the inner division of the double-hoisted BSGS transform; the items of poly_prod stay 2 (L+1) N apart)
+    unsigned comps = 2;
 };
+// the first polynomial of poly_prod the tail divides
+static u64* ks_tail_prod(const KsCall& c) { return c.ws + c.w.poly_prod + (c.comps == 1 ? (size_t)(c.L + 1) * c.p->n : 0); }
 
 // (1) NTT form: bring the target back to coefficient form (evaluator_keyswitching_core.cu:817-821)
 static int ks_digits(KsCall& c) {
@@ -1432,12 +1437,12 @@ static int ks_inner_product(const KsCall& c, const KeyPtrs& kp, const KsPath& pa
 // finishes with the divide-by-special-prime / assign epilogue (ski_util7_merged)
 static NttArgs ks_ntt_tail_args(const KsCall& c, const u64* src) {
     const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
-    NttArgs a = contiguous_args(p, src, c.dest, 2, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
-    a.in_bstride = 2ll * n; a.in_pstride = n; a.in_cstride = 0;
+    NttArgs a = contiguous_args(p, src, c.dest, c.comps, L, 0, L, TROYN_IDX_COMPONENTWISE, 0);
+    a.in_bstride = (long long)c.comps * n; a.in_pstride = n; a.in_cstride = 0;
     a.load_mode = NTT_LOAD_KS_ROUND; a.aux_mod = K - 1;
     a.store_mode = NTT_STORE_KS_FINISH;
     a.flags = (c.is_ckks ? 1u : 0u) | ((unsigned)c.assign_method << 1);
-    a.ext0 = c.ws + c.w.poly_prod; a.ext0_bstride = 2ll * (L + 1) * n; a.ext0_pstride = (long long)(L + 1) * n; a.ext0_cstride = n;
+    a.ext0 = ks_tail_prod(c); a.ext0_bstride = 2ll * (L + 1) * n; a.ext0_pstride = (long long)(L + 1) * n; a.ext0_cstride = n;
     a.ext1 = c.addend; a.ext1_bstride = (long long)c.addend_bstride; a.ext1_pstride = (long long)L * n; a.ext1_cstride = n;
     a.inv_table = p->d_inv_last + (size_t)K * K;
     return a;
@@ -1447,15 +1452,15 @@ static NttArgs ks_ntt_tail_args(const KsCall& c, const u64* src) {
 static int ks_tail_small(const KsCall& c) {
     const troyn_plan* p = c.p;
     const bool tail_f64 = use_f64(p, 0, c.L) && use_f64(p, p->K - 1, 1);      // else both transforms on the integer kernels (small launches are not split by class)
-    u64* special = c.ws + c.w.poly_prod + (size_t)c.L * p->n;
-    NttArgs pa = special_rows_args(p, c.ws + c.w.poly_prod, special, c.L);
+    u64* special = ks_tail_prod(c) + (size_t)c.L * p->n;
+    NttArgs pa = special_rows_args(p, ks_tail_prod(c), special, c.L, c.comps);
     pa.out_pstride = pa.in_pstride; pa.out_bstride = pa.in_bstride;
-    return small_tail(p, tail_f64, pa, c.batch * 2, ks_ntt_tail_args(c, c.ws + c.w.prod_intt), c.ws + c.w.temp_last, c.batch * 2, c.s);
+    return small_tail(p, tail_f64, pa, c.batch * c.comps, ks_ntt_tail_args(c, c.ws + c.w.prod_intt), c.ws + c.w.temp_last, c.batch * c.comps, c.s);
 }
 // (4) INTT of only the special-prime rows, the result stays in NTT form (:991-996); then (5)-(7) as one launch
 static int ks_tail_ntt_fused(const KsCall& c) {
     u64* spec = c.ws + c.w.prod_intt;
-    if (int rc = launch_ntt(c.p, special_rows_args(c.p, c.ws + c.w.poly_prod, spec, c.L), c.batch, true, c.s)) return rc;
+    if (int rc = launch_ntt(c.p, special_rows_args(c.p, ks_tail_prod(c), spec, c.L, c.comps), c.batch, true, c.s)) return rc;
     // N >= 32768 transforms in two passes: the pass in between goes to temp_last (unused on this path), never to dest
     return launch_ntt(c.p, ks_ntt_tail_args(c, spec), c.batch, false, c.s, c.ws + c.w.temp_last);
 }
@@ -1464,14 +1469,14 @@ static int ks_tail_ntt_fused(const KsCall& c) {
 static int ks_tail_coeff_fused(const KsCall& c) {
     const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
     u64* spec = c.ws + c.w.prod_intt;
-    if (int rc = launch_ntt(p, special_rows_args(p, c.ws + c.w.poly_prod, spec, L), c.batch, true, c.s)) return rc;
-    NttArgs f = contiguous_args(p, c.ws + c.w.poly_prod, c.dest, 2, L, 0, K, TROYN_IDX_COMPONENTWISE, 0);
+    if (int rc = launch_ntt(p, special_rows_args(p, ks_tail_prod(c), spec, L, c.comps), c.batch, true, c.s)) return rc;
+    NttArgs f = contiguous_args(p, ks_tail_prod(c), c.dest, c.comps, L, 0, K, TROYN_IDX_COMPONENTWISE, 0);
     f.in_pstride = (long long)(L + 1) * n; f.in_bstride = 2ll * (L + 1) * n;
     f.load_mode = NTT_LOAD_KS_ROUND; f.aux_mod = K - 1;      // constants of the rounding fix (no forward prologue runs)
     f.store_mode = NTT_STORE_KS_FINISH;
     f.flags = (c.is_ckks ? 1u : 0u) | ((unsigned)c.assign_method << 1);
-    f.in2 = spec; f.in2_bstride = 2ll * n; f.in2_pstride = n;
-    f.ext0 = c.dest; f.ext0_bstride = 2ll * L * n; f.ext0_pstride = (long long)L * n; f.ext0_cstride = n;   // unused by this epilogue
+    f.in2 = spec; f.in2_bstride = (long long)c.comps * n; f.in2_pstride = n;
+    f.ext0 = c.dest; f.ext0_bstride = (long long)c.comps * L * n; f.ext0_pstride = (long long)L * n; f.ext0_cstride = n;   // unused by this epilogue
     f.ext1 = c.addend; f.ext1_bstride = (long long)c.addend_bstride; f.ext1_pstride = (long long)L * n; f.ext1_cstride = n;
     f.inv_table = p->d_inv_last + (size_t)K * K;
     // two-pass sizes: the pass in between goes to the free part of prod_intt, never to dest (AddInplace reads the old destination)
@@ -1481,22 +1486,28 @@ static int ks_tail_coeff_fused(const KsCall& c) {
 static int ks_tail_unfused(const KsCall& c) {
     const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
     const bool ntt = c.is_ntt_form;
-    const size_t batch = c.batch, rows = batch * 2 * L;
+    const size_t batch = c.batch, rows = batch * c.comps * L;
     const unsigned ch = c.bgv ? chunks_single(n) : chunks_pairs(n);
     hipStream_t s = c.s;
     u64* prod_intt = c.ws + c.w.prod_intt;
     u64* temp_last = c.ws + c.w.temp_last;
     int rc;
     // (4) INTT: only the special-prime rows when the result stays in NTT form; all rows otherwise (:991-996)
-    if (ntt) rc = launch_ntt(p, special_rows_args(p, c.ws + c.w.poly_prod, prod_intt, L), batch, true, s);
-    else rc = launch_ntt(p, contiguous_args(p, c.ws + c.w.poly_prod, prod_intt, 2, L + 1, 0, K, TROYN_IDX_KS_SKIP_FINALS, L), batch, true, s);
+    if (ntt) rc = launch_ntt(p, special_rows_args(p, ks_tail_prod(c), prod_intt, L, c.comps), batch, true, s);
+    else {
+        NttArgs iv = contiguous_args(p, ks_tail_prod(c), prod_intt, c.comps, L + 1, 0, K, TROYN_IDX_KS_SKIP_FINALS, L);
+        iv.in_bstride = 2ll * (L + 1) * n;
+        rc = launch_ntt(p, iv, batch, true, s);
+    }
     if (rc || (rc = check_rows(rows, ch))) return rc;
     const u64* last_src = ntt ? prod_intt : prod_intt + (size_t)L * n;      // the special-prime rows in coefficient form
     const size_t last_stride = ntt ? n : (size_t)(L + 1) * n;
-    const u64* prod_for_util7 = ntt ? c.ws + c.w.poly_prod : prod_intt;
+    // (one component in NTT form: the items of poly_prod are 2 (L + 1) rows apart, the INTT'd copy is compact)
+    const u64* prod_for_util7 = ntt ? ks_tail_prod(c) : prod_intt;
+    const unsigned prod_rows = (ntt && c.comps == 1) ? 2 * (L + 1) : L + 1;
     // (5) rounding fix of the special-prime component, per data limb (:570-598).  In NTT form the result goes to
     //     the unused tail of the prod_intt region so that step (6) can transform out of place.
-    u64* util6_out = ntt ? prod_intt + batch * 2 * (size_t)n : temp_last;
+    u64* util6_out = ntt ? prod_intt + batch * 2 * (size_t)n : temp_last;      // (comps <= 2: past the special rows either way)
     if (c.bgv) {
         // kernel_ski_util5_merged_step1 (:436-476): delta_j = (k mod q_j) * q_special + c mod q_j, k = -c * q_special^-1 mod t
         hipLaunchKernelGGL(bgv_delta_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
@@ -1508,7 +1519,7 @@ static int ks_tail_unfused(const KsCall& c) {
         LAUNCH_CHECK();
     }   // coefficient form: ks_util7_kernel forms the fix itself from the special-prime row
     // (6) back to NTT form when needed (:1033-1036)
-    if (ntt && (rc = launch_ntt(p, contiguous_args(p, util6_out, temp_last, 2, L, 0, L, TROYN_IDX_COMPONENTWISE, 0), batch, false, s))) return rc;
+    if (ntt && (rc = launch_ntt(p, contiguous_args(p, util6_out, temp_last, c.comps, L, 0, L, TROYN_IDX_COMPONENTWISE, 0), batch, false, s))) return rc;
     // (7) divide by the special prime and assign (:625-658; BGV: kernel_ski_util5_merged_step2 :506-538)
     if (c.bgv) {
         hipLaunchKernelGGL(bgv_finish_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
@@ -1516,7 +1527,7 @@ static int ks_tail_unfused(const KsCall& c) {
         LAUNCH_CHECK();
     } else {
         hipLaunchKernelGGL(ks_util7_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
-                           ch, p->d_mods, L, L + 1, n, prod_for_util7, temp_last,
+                           ch, p->d_mods, L, prod_rows, n, prod_for_util7, temp_last,
                            p->d_inv_last + (size_t)K * K, c.is_ckks, c.assign_method, c.dest, c.addend, c.addend_bstride,
                            ntt ? (const u64*)nullptr : last_src, last_stride, K);
         LAUNCH_CHECK();
@@ -1748,12 +1759,13 @@ extern "C" size_t troyn_apply_galois_weighted_workspace_bytes(const troyn_plan* 
     return weighted_layout(plan, L, terms, slots, batch, is_ntt_form != 0).total * sizeof(u64);
 }
 
-extern "C" int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
-                                                const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms,
-                                                const uint64_t* const* weights, size_t slots, uint64_t* out_,
-                                                void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
-    select_device(plan);
-    const char* P = "[troyn_apply_galois_weighted_sums]";
+// the entry's work.  layout: the caller's own placement of the same regions (null: weighted_layout); finish = false stops after the
+// extended-basis sums, poly_prod [slots][batch][2][L+1][N] in NTT form, and leaves `out` unwritten (the double-hoisted BSGS transform)
+static int weighted_sums_impl(const char* P, const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
+                              const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms,
+                              const uint64_t* const* weights, size_t slots, uint64_t* out_,
+                              void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream,
+                              const WeightedLayout* layout, bool finish) {
     const troyn_plan* p = plan;
     const u64* ct = (const u64*)ct_;
     u64* out = (u64*)out_;
@@ -1773,9 +1785,10 @@ extern "C" int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t
     const unsigned K = p->K, n = p->n;
     if (batch == 0) return TROYN_OK;      // nothing to do: neither ct, out nor the workspace is looked at
     const size_t items = slots * batch, ct_words = (size_t)2 * L * n;
-    if (int rc = hoist_check_buffers(P, p, L, ct, out, workspace, batch, items)) return rc;
+    // (finish = false writes no `out`: the caller has checked its own buffers)
+    if (finish) if (int rc = hoist_check_buffers(P, p, L, ct, out, workspace, batch, items)) return rc;
     const bool ntt = is_ntt_form != 0;
-    const WeightedLayout w = weighted_layout(p, L, terms, slots, batch, ntt);
+    const WeightedLayout w = layout ? *layout : weighted_layout(p, L, terms, slots, batch, ntt);
     if (workspace_bytes < w.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
     if (batch > 0xffffffffull || terms > 0xffffffffull || slots > 0xffffffffull) return fail(TROYN_E_INVALID, std::string(P) + " batch too large for one launch");
     u64* ws = (u64*)workspace;
@@ -1823,10 +1836,20 @@ extern "C" int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t
         else hipLaunchKernelGGL((hoist_weighted_kernel<1>), grid, block, 0, s, ch, a);
         LAUNCH_CHECK();
     }
+    if (!finish) return TROYN_OK;
     // the tail of troyn_switch_key on slots * batch items, both components overwritten
     KsCall tc = dc;
     tc.batch = items;
     return ks_tail(tc, ks_path(p, L, items, tc.is_ntt_form, false));
+}
+
+extern "C" int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
+                                                const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms,
+                                                const uint64_t* const* weights, size_t slots, uint64_t* out,
+                                                void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(plan);
+    return weighted_sums_impl("[troyn_apply_galois_weighted_sums]", plan, L, is_ckks, is_ntt_form, ct, galois_elements, keys, terms, weights, slots,
+                              out, workspace, workspace_bytes, batch, stream, nullptr, true);
 }
 
 // ---- the sum of key-switched automorphisms of DIFFERENT ciphertexts (an addition; include/troyn.h, hoist_each_kernel) ----
@@ -1953,16 +1976,9 @@ extern "C" size_t troyn_linear_transform_bsgs_workspace_bytes(const troyn_plan* 
     return bsgs_layout(plan, L, babies, giants, batch, is_ntt_form != 0).total * sizeof(u64);
 }
 
-extern "C" int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
-                                           const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
-                                           const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
-                                           const uint64_t* const* weights, uint64_t* out_,
-                                           void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
-    select_device(plan);
-    const char* P = "[troyn_linear_transform_bsgs]";
-    const troyn_plan* p = plan;
-    const u64* ct = (const u64*)ct_;
-    u64* out = (u64*)out_;
+// what both BSGS entries check before they look at the batch: the two element and key tables and the weight table
+static int bsgs_check_tables(const char* P, const troyn_plan* p, unsigned L, const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                             const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants, const uint64_t* const* weights) {
     if (int rc = hoist_check_tables(P, p, L, baby_elements, baby_keys, babies, true)) return rc;
     if (int rc = hoist_check_tables(P, p, L, giant_elements, giant_keys, giants, true)) return rc;
     if (!weights) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
@@ -1975,6 +1991,20 @@ extern "C" int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, i
         }
         if (!any) return fail(TROYN_E_INVALID, std::string(P) + " a giant step has no weight");
     }
+    return TROYN_OK;
+}
+
+extern "C" int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
+                                           const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                                           const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                           const uint64_t* const* weights, uint64_t* out_,
+                                           void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(plan);
+    const char* P = "[troyn_linear_transform_bsgs]";
+    const troyn_plan* p = plan;
+    const u64* ct = (const u64*)ct_;
+    u64* out = (u64*)out_;
+    if (int rc = bsgs_check_tables(P, p, L, baby_elements, baby_keys, babies, giant_elements, giant_keys, giants, weights)) return rc;
     if (batch == 0) return TROYN_OK;      // nothing to do: neither ct, out nor the workspace is looked at
     if (int rc = hoist_check_buffers(P, p, L, ct, out, workspace, batch, batch)) return rc;
     const BsgsLayout b = bsgs_layout(p, L, babies, giants, batch, is_ntt_form != 0);
@@ -1987,6 +2017,123 @@ extern "C" int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, i
     // stage 2: out = SUM_g sigma_{G_g}(inner[g]), ONE division
     return apply_galois_sum_each(P, p, L, is_ckks, is_ntt_form, inner, giant_elements, giant_keys, giants, out,
                                  ws + b.stage, b.stage_words * sizeof(u64), batch, (hipStream_t)stream);
+}
+
+// ---- double-hoisted BSGS linear transform (an addition; include/troyn.h, hoist_double_kernel): the inner sums stay on the extended basis in
+// the workspace; per giant step with G != 1 only component 1 is divided (it is what the giant key decomposes), component 0 goes through the
+// giant automorphism on the extended basis into the outer sum; an identity giant step adds both components undivided.  ONE division of both
+// components ends the transform ----
+struct DoubleLayout { WeightedLayout inner; size_t v, y, total; };
+
+// Regions of one group of min(giants, TROYN_HOIST_EACH_GROUP) giant steps serve the inner stage (which needs `batch` items of them) and every
+// group of the outer stage; only X, the inner results [giants][batch][2][L+1][N], grows with `giants`.
+static DoubleLayout double_layout(const troyn_plan* p, unsigned L, size_t babies, size_t giants, size_t batch, bool is_ntt_form) {
+    const size_t n = p->n, group = std::min<size_t>(giants, TROYN_HOIST_EACH_GROUP), resident = group * batch;
+    DoubleLayout d;
+    KsLayout& k = d.inner.h.ks;
+    size_t off = 0;
+    k.target_intt = off; off += resident * L * n;
+    k.temp_ntt = off;    off += resident * (size_t)(L + 1) * L * n;
+    k.poly_prod = off;   off += giants * batch * 2 * (size_t)(L + 1) * n;      // X
+    k.prod_intt = off;   off += resident * 2 * (size_t)(L + 1) * n;            // the tails' own rows: a group's inner divisions, then the final one
+    k.temp_last = off;   off += resident * 2 * (size_t)L * n;
+    k.keys_f64 = k.split = k.keys_quo = off;      // the inner products of troyn_switch_key do not run here
+    d.v = off;           off += resident * L * n;                              // v^(g) of one group [group][batch][L][N]
+    d.y = off;           off += batch * 2 * (size_t)(L + 1) * n;               // Y, the outer sum
+    // the inner stage's tables (hoisted tables, weight pointers, q_special mod q_l: one upload), later one group's hoisted tables in their place
+    d.inner.h.table = off;
+    d.inner.weights = off + babies * (L + 2);
+    d.inner.special_mod = d.inner.weights + giants * babies;
+    off += std::max(babies * (L + 2) + giants * babies + L, group * (L + 2));
+    off = (off + 1) & ~(size_t)1;
+    d.inner.c0_ntt = off; off += is_ntt_form ? 0 : batch * L * n;              // coefficient form: the inner stage's forward transform of c0
+    d.total = d.inner.total = k.total = off;
+    return d;
+}
+
+extern "C" size_t troyn_linear_transform_bsgs_double_hoisted_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t babies, size_t giants,
+                                                                             size_t batch, int is_ntt_form) {
+    if (!plan) return 0;
+    return double_layout(plan, L, babies, giants, batch, is_ntt_form != 0).total * sizeof(u64);
+}
+
+extern "C" int troyn_linear_transform_bsgs_double_hoisted(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
+                                                          const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                                                          const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                                          const uint64_t* const* weights, uint64_t* out_,
+                                                          void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(plan);
+    const char* P = "[troyn_linear_transform_bsgs_double_hoisted]";
+    const troyn_plan* p = plan;
+    const u64* ct = (const u64*)ct_;
+    u64* out = (u64*)out_;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = bsgs_check_tables(P, p, L, baby_elements, baby_keys, babies, giant_elements, giant_keys, giants, weights)) return rc;
+    if (batch == 0) return TROYN_OK;      // nothing to do: neither ct, out nor the workspace is looked at
+    if (int rc = hoist_check_buffers(P, p, L, ct, out, workspace, batch, batch)) return rc;
+    const bool ntt = is_ntt_form != 0;
+    const DoubleLayout d = double_layout(p, L, babies, giants, batch, ntt);
+    if (workspace_bytes < d.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, std::string(P) + " workspace too small");
+    if (giants > 0xffffffffull || batch > 0xffffffffull || giants * batch > 0xffffffffull)
+        return fail(TROYN_E_INVALID, std::string(P) + " batch too large for one launch");
+    const unsigned K = p->K, n = p->n;
+    u64* ws = (u64*)workspace;
+    // stage 1: one decomposition of ct; X^(g) = the weighted sums over the baby steps on the extended basis, NOT divided
+    if (int rc = weighted_sums_impl(P, plan, L, is_ckks, is_ntt_form, ct_, baby_elements, baby_keys, babies, weights, giants, out_,
+                                    workspace, workspace_bytes, batch, stream, &d.inner, false)) return rc;
+    const KsLayout& k = d.inner.h.ks;
+    const size_t x_item = 2 * (size_t)(L + 1) * n, v_item = (size_t)L * n, digit_item = (size_t)(L + 1) * L * n, ct_words = (size_t)2 * L * n;
+    const unsigned ib = batch >= 4 ? 4u : batch >= 2 ? 2u : 1u;
+    const unsigned ch = chunks_pairs(n);
+    const size_t groups = (batch + ib - 1) / ib, rows = groups * (size_t)(L + 1);
+    if (int rc = check_rows(rows, ch)) return rc;
+    // stage 2, per group of giant steps: v^(g) = component 1 of X^(g) divided (G != 1 only), its digits, then the sum into Y
+    for (size_t t0 = 0; t0 < giants; t0 += TROYN_HOIST_EACH_GROUP) {
+        const size_t gt = std::min<size_t>(giants - t0, TROYN_HOIST_EACH_GROUP);
+        // the tables are read before the call returns (the upload waits on the stream for the launch that read the last ones)
+        if (int rc = hoist_upload_tables(p, L, giant_elements + t0, giant_keys + t0 * L, gt, {}, ws + d.inner.h.table, s)) return rc;
+        bool skip_diag = false;
+        for (size_t r0 = 0; r0 < gt;) {
+            if (giant_elements[t0 + r0] == 1) { r0++; continue; }
+            size_t r1 = r0 + 1;
+            while (r1 < gt && giant_elements[t0 + r1] != 1) r1++;
+            // a run of giant steps with a key: ONE polynomial per item through the tail of troyn_switch_key, then decomposed as a target
+            const size_t run = (r1 - r0) * batch;
+            KsLayout w = k;
+            w.poly_prod = k.poly_prod + (t0 + r0) * batch * x_item;
+            w.target_intt = k.target_intt + r0 * batch * v_item;
+            w.temp_ntt = k.temp_ntt + r0 * batch * digit_item;
+            u64* v = ws + d.v + r0 * batch * v_item;
+            KsCall vc{p, L, is_ckks, ntt, v, v_item, TROYN_ASSIGN_OVERWRITE, v, nullptr, 0, ws, w, run, s, nullptr, v, v_item};
+            vc.comps = 1;
+            if (int rc = ks_tail(vc, ks_path(p, L, run, ntt, false))) return rc;
+            if (int rc = hoist_decompose(vc, skip_diag)) return rc;
+            r0 = r1;
+        }
+        HoistDoubleArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.mods = p->d_mods; a.K = K; a.L = L; a.log_n = p->log_n; a.batch = (unsigned)batch; a.groups = (unsigned)groups;
+        a.terms = (unsigned)gt; a.accumulate = t0 ? 1 : 0;
+        a.digits_ntt = ws + k.temp_ntt; a.v_ntt = ws + d.v; a.diag_from_v = skip_diag ? 1 : 0;
+        a.x_ntt = ws + k.poly_prod + t0 * batch * x_item;
+        a.keys = reinterpret_cast<const u64* const*>(ws + d.inner.h.table);
+        a.elements = ws + d.inner.h.table + gt * L;
+        a.poly_prod = ws + d.y;
+        {
+            TimerScope ts(TROYN_TIMER_KS_INNER_PRODUCT, s);
+            const dim3 grid((unsigned)(rows * ch)), block(POLY_BLOCK);
+            if (ib == 4) hipLaunchKernelGGL((hoist_double_kernel<4>), grid, block, 0, s, ch, a);
+            else if (ib == 2) hipLaunchKernelGGL((hoist_double_kernel<2>), grid, block, 0, s, ch, a);
+            else hipLaunchKernelGGL((hoist_double_kernel<1>), grid, block, 0, s, ch, a);
+            LAUNCH_CHECK();
+        }
+    }
+    // the tail of troyn_switch_key on `batch` items, both components overwritten: the ONE division of the transform
+    const u64* c1 = ct + (size_t)L * n;
+    KsLayout wy = k;
+    wy.poly_prod = d.y;
+    KsCall tc{p, L, is_ckks, ntt, c1, ct_words, TROYN_ASSIGN_OVERWRITE, out, nullptr, 0, ws, wy, batch, s, nullptr, c1, ct_words};
+    return ks_tail(tc, ks_path(p, L, batch, ntt, false));
 }
 
 // ---------------------------------------------------------------------------------------

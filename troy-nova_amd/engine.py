@@ -350,7 +350,19 @@ class Plan:
         a plaintext matrix times an encrypted vector: one digit decomposition of ct, one division per giant step for the inner sums and ONE
         for the outer sum.  weights[g][b]: a tensor [K][N] in NTT form and key-level layout, ALREADY rotated back by the giant step, or None;
         every giant step needs a weight.  The element 1 is the identity in either list; its keys may be None."""
-        who = "[troyn_linear_transform_bsgs]"
+        return self._linear_transform_bsgs("troyn_linear_transform_bsgs", L, ct, baby_elements, baby_keys, giant_elements, giant_keys, weights,
+                                           is_ckks, is_ntt_form, out)
+
+    def linear_transform_bsgs_double_hoisted(self, L, ct, baby_elements, baby_keys, giant_elements, giant_keys, weights, is_ckks=True,
+                                             is_ntt_form=True, out=None):
+        """linear_transform_bsgs with the second hoisting level: the inner sums stay on the extended basis, only component 1 of a giant step
+        with a key is divided, and ONE division ends the transform.  Same arguments; the words differ from linear_transform_bsgs (one
+        rounding per giant step fewer), the decrypted message does not."""
+        return self._linear_transform_bsgs("troyn_linear_transform_bsgs_double_hoisted", L, ct, baby_elements, baby_keys, giant_elements,
+                                           giant_keys, weights, is_ckks, is_ntt_form, out)
+
+    def _linear_transform_bsgs(self, entry, L, ct, baby_elements, baby_keys, giant_elements, giant_keys, weights, is_ckks, is_ntt_form, out):
+        who = "[%s]" % entry
         babies, giants = len(baby_elements), len(giant_elements)
         bearr, bkarr = self._keyed_tables(who, L, baby_elements, baby_keys)
         gearr, gkarr = self._keyed_tables(who, L, giant_elements, giant_keys)
@@ -374,10 +386,10 @@ class Plan:
             out = torch.empty(shape, dtype=torch.int64, device=self.device)
         elif out.numel() != int(np.prod(shape)):
             raise capi.TroynInvalidArgument("%s out is not [batch][2][L][N]" % who)
-        ws = self.workspace(self.lib.troyn_linear_transform_bsgs_workspace_bytes(self.h, L, babies, giants, batch, int(is_ntt_form)))
-        capi.check(self.lib.troyn_linear_transform_bsgs(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(ct), bearr, bkarr, babies,
-                                                        gearr, gkarr, giants, warr, _ptr(out),
-                                                        C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        ws = self.workspace(getattr(self.lib, entry + "_workspace_bytes")(self.h, L, babies, giants, batch, int(is_ntt_form)))
+        capi.check(getattr(self.lib, entry)(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(ct), bearr, bkarr, babies,
+                                            gearr, gkarr, giants, warr, _ptr(out),
+                                            C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
 
     # -- RLWE / LWE packing (evaluator_lwes.cu) -----------------------------------------------------

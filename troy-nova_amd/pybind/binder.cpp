@@ -617,6 +617,20 @@ PYBIND11_MODULE(pytroy_raw, m) {
     ev.def("rotate_bsgs_sum_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& b, const std::vector<int>& g, const GaloisKeys& k,
                                      const std::vector<WeightRow>& w, PoolArg p) { return s.rotate_bsgs_sum_new(a, b, g, k, w, P(p)); },
            py::arg("encrypted"), py::arg("baby_steps"), py::arg("giant_steps"), py::arg("galois_keys"), py::arg("weights"), POOL);
+    ev.def("apply_galois_bsgs_sum_double_hoisted", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& b, const std::vector<size_t>& g,
+                                                      const GaloisKeys& k, const std::vector<WeightRow>& w, Ciphertext& d, PoolArg p) {
+        s.apply_galois_bsgs_sum_double_hoisted(a, b, g, k, w, d, P(p)); },
+           py::arg("encrypted"), py::arg("baby_elements"), py::arg("giant_elements"), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);
+    ev.def("apply_galois_bsgs_sum_double_hoisted_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<size_t>& b, const std::vector<size_t>& g,
+                                                          const GaloisKeys& k, const std::vector<WeightRow>& w, PoolArg p) {
+        return s.apply_galois_bsgs_sum_double_hoisted_new(a, b, g, k, w, P(p)); },
+           py::arg("encrypted"), py::arg("baby_elements"), py::arg("giant_elements"), py::arg("galois_keys"), py::arg("weights"), POOL);
+    ev.def("rotate_bsgs_sum_double_hoisted", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& b, const std::vector<int>& g, const GaloisKeys& k,
+                                                const std::vector<WeightRow>& w, Ciphertext& d, PoolArg p) { s.rotate_bsgs_sum_double_hoisted(a, b, g, k, w, d, P(p)); },
+           py::arg("encrypted"), py::arg("baby_steps"), py::arg("giant_steps"), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);
+    ev.def("rotate_bsgs_sum_double_hoisted_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& b, const std::vector<int>& g, const GaloisKeys& k,
+                                                    const std::vector<WeightRow>& w, PoolArg p) { return s.rotate_bsgs_sum_double_hoisted_new(a, b, g, k, w, P(p)); },
+           py::arg("encrypted"), py::arg("baby_steps"), py::arg("giant_steps"), py::arg("galois_keys"), py::arg("weights"), POOL);
     // ciphertext +/- plaintext
 #define EV_PLAIN(name)                                                                                                          \
     ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const Plaintext& w, Ciphertext& d, PoolArg p) { s.name(a, w, d, P(p)); },  \

@@ -2565,10 +2565,11 @@ void Evaluator::rotate_sum_each(const std::vector<const Ciphertext*>& encrypted,
     apply_galois_each(P, encrypted, hoisted_elements_from_steps(P, *encrypted[0], steps), galois_keys, destination, pool);
 }
 
-// -- baby-step/giant-step linear transform (addition; troy.h): troyn_linear_transform_bsgs, one decomposition, giants + 1 divisions --
+// -- baby-step/giant-step linear transform (addition; troy.h): troyn_linear_transform_bsgs, one decomposition, giants + 1 divisions;
+//    double_hoisted: troyn_linear_transform_bsgs_double_hoisted, the inner c0 is not divided --
 void Evaluator::apply_galois_bsgs(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
                                   const GaloisKeys& galois_keys, const std::vector<std::vector<const Plaintext*>>& weights, Ciphertext& destination,
-                                  MemoryPoolHandle pool) const {
+                                  MemoryPoolHandle pool, bool double_hoisted) const {
     if (baby_elements.empty() || giant_elements.empty()) throw std::invalid_argument(std::string(P) + " Empty element list.");
     if (weights.size() != giant_elements.size()) throw std::invalid_argument(std::string(P) + " One weight row per giant step is needed.");
     auto cd = get_context_data(P, encrypted.parms_id());
@@ -2591,12 +2592,14 @@ void Evaluator::apply_galois_bsgs(const char* P, const Ciphertext& encrypted, co
     d.scale() = scale;
     {
         const int is_ckks = scheme == SchemeType::CKKS, is_ntt = encrypted.is_ntt_form() ? 1 : 0;
-        const size_t bytes = troyn_linear_transform_bsgs_workspace_bytes(context_->plan(), L, babies, giants, 1, is_ntt);
+        const auto workspace_bytes = double_hoisted ? troyn_linear_transform_bsgs_double_hoisted_workspace_bytes : troyn_linear_transform_bsgs_workspace_bytes;
+        const auto transform = double_hoisted ? troyn_linear_transform_bsgs_double_hoisted : troyn_linear_transform_bsgs;
+        const size_t bytes = workspace_bytes(context_->plan(), L, babies, giants, 1, is_ntt);
         utils::DynamicArray ws((bytes + 7) / 8, true, pool);
         detail::LaunchGate gate;
-        troyn_check(troyn_linear_transform_bsgs(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), belements.data(), bkeys.data(), babies,
-                                                gelements.data(), gkeys.data(), giants, wptrs.data(), d.data().raw_pointer(), ws.raw_pointer(), bytes, 1,
-                                                current_stream()));
+        troyn_check(transform(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), belements.data(), bkeys.data(), babies,
+                              gelements.data(), gkeys.data(), giants, wptrs.data(), d.data().raw_pointer(), ws.raw_pointer(), bytes, 1,
+                              current_stream()));
     }
     destination = std::move(d);
 }
@@ -2606,6 +2609,14 @@ void Evaluator::rotate_bsgs_sum(const Ciphertext& encrypted, const std::vector<i
     const char* P = "[Evaluator::rotate_bsgs_sum]";
     apply_galois_bsgs(P, encrypted, hoisted_elements_from_steps(P, encrypted, baby_steps), hoisted_elements_from_steps(P, encrypted, giant_steps), galois_keys,
                       weights, destination, pool);
+}
+
+void Evaluator::rotate_bsgs_sum_double_hoisted(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps,
+                                               const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights, Ciphertext& destination,
+                                               MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::rotate_bsgs_sum_double_hoisted]";
+    apply_galois_bsgs(P, encrypted, hoisted_elements_from_steps(P, encrypted, baby_steps), hoisted_elements_from_steps(P, encrypted, giant_steps), galois_keys,
+                      weights, destination, pool, true);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1656,7 +1656,7 @@ public:
     //                          CKKS: the destination's scale is encrypted.scale() * the weight scale.
     //   apply_galois_bsgs_sum: the same for Galois elements.
     //   The operands of the _each forms must share their level, form and (CKKS) scale.  A missing key throws "Galois key not present." (no NAF
-    //   chain); BFV and CKKS, BGV throws std::invalid_argument.  "Double hoisting" (no division of the inner c0) is not done.
+    //   chain); BFV and CKKS, BGV throws std::invalid_argument.  "Double hoisting" (no division of the inner c0) is the _double_hoisted pair below.
     // Call combining does not take part: these methods always launch directly.
     void apply_galois_sum_each(const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
                                Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
@@ -1686,6 +1686,28 @@ public:
     Ciphertext rotate_bsgs_sum_new(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps, const GaloisKeys& galois_keys,
                                    const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
         Ciphertext d; rotate_bsgs_sum(encrypted, baby_steps, giant_steps, galois_keys, weights, d, pool); return d;
+    }
+    // ADDITION: rotate_bsgs_sum / apply_galois_bsgs_sum with the second hoisting level (troyn_linear_transform_bsgs_double_hoisted, include/troyn.h):
+    //   the inner sums stay on the extended basis, only component 1 of a giant step with a key is divided, ONE division ends the transform.  Same
+    //   arguments, checks and scale; the ciphertext WORDS differ from the single-hoisted methods (one rounding per giant step fewer), the decrypted
+    //   message does not (BFV: exactly; CKKS: within the same kind of noise bound).
+    void apply_galois_bsgs_sum_double_hoisted(const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
+                                              const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights, Ciphertext& destination,
+                                              MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        apply_galois_bsgs("[Evaluator::apply_galois_bsgs_sum_double_hoisted]", encrypted, baby_elements, giant_elements, galois_keys, weights, destination, pool, true);
+    }
+    Ciphertext apply_galois_bsgs_sum_double_hoisted_new(const Ciphertext& encrypted, const std::vector<size_t>& baby_elements,
+                                                        const std::vector<size_t>& giant_elements, const GaloisKeys& galois_keys,
+                                                        const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; apply_galois_bsgs_sum_double_hoisted(encrypted, baby_elements, giant_elements, galois_keys, weights, d, pool); return d;
+    }
+    void rotate_bsgs_sum_double_hoisted(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps,
+                                        const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights, Ciphertext& destination,
+                                        MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext rotate_bsgs_sum_double_hoisted_new(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps,
+                                                  const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights,
+                                                  MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; rotate_bsgs_sum_double_hoisted(encrypted, baby_steps, giant_steps, galois_keys, weights, d, pool); return d;
     }
 
     // ciphertext x plaintext -- evaluator.h (multiply_plain*, transform_plain_to_ntt*); evaluator_multiply_plain.cu,
@@ -1951,7 +1973,7 @@ private:
                            Ciphertext& destination, MemoryPoolHandle pool) const;
     void apply_galois_bsgs(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
                            const GaloisKeys& galois_keys, const std::vector<std::vector<const Plaintext*>>& weights, Ciphertext& destination,
-                           MemoryPoolHandle pool) const;
+                           MemoryPoolHandle pool, bool double_hoisted = false) const;
     void switch_key_internal(const Ciphertext& encrypted, const uint64_t* target, const KSwitchKeys& kswitch_keys, size_t kswitch_keys_index,
                              SwitchKeyDestinationAssignMethod assign_method, Ciphertext& destination, MemoryPoolHandle pool) const;
     void relinearize_inplace_internal(Ciphertext& encrypted, const RelinKeys& relin_keys, size_t destination_size, MemoryPoolHandle pool) const;
