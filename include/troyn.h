@@ -610,6 +610,32 @@ int troyn_ckks_decode_polynomial(const troyn_ckks* h, uint32_t L, const uint64_t
 int troyn_ckks_decode_simd(const troyn_ckks* h, uint32_t L, const uint64_t* plain, double scale, double* out, void* workspace, size_t workspace_bytes,
                            size_t batch, troyn_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * CKKS ModRaise (an addition to the reference's API): the exact centred base extension of a ciphertext from the plan's moduli
+ * 0..L_in-1 to its moduli 0..L_out-1, the first step of a bootstrap.  On the troyn_ckks handle, which owns the Garner table q_j^-1 mod q_i.
+ * Layouts of troyn_mod_switch_drop: in u64 [batch][pcount][L_in][N], out u64 [batch][pcount][L_out][N], row i under modulus i.
+ *
+ * MODRAISE CONTRACT (on integers):
+ *   1. for every coefficient position in coefficient form, x = the centred representative in (-Q/2, Q/2] of the L_in input residues,
+ *      Q = q_0 ... q_{L_in-1} -- the convention of decoding step 2: X > floor(Q/2) stands for X - Q;
+ *   2. out_j = x mod q_j in [0, q_j) for every j < L_out.
+ *   Input words are canonical (< q_i); under that precondition rows j < L_in of `out` equal the input rows word for word.
+ *   is_ntt_form = 1: the map is NTT o extend o INTT.  Rows j < L_in are copied and never transformed; only the L_in input rows take the
+ *   inverse transform and only the L_out - L_in new rows the forward one, both through the launch layer of troyn_ntt.
+ *   is_ntt_form = 0: no transform runs.
+ *   `in` and `out` must not overlap.
+ *   1 <= L_in < L_out <= n_moduli.  L_in <= 16 (as the decoder); above that TROYN_E_UNSUPPORTED.
+ *
+ * The workspace (troyn_ckks_mod_raise_workspace_bytes; device memory, 16-byte aligned) holds the coefficient forms of the input rows and of
+ * the new rows in NTT form; it is empty in coefficient form, where it may be null.
+ * TROYN_E_INVALID: a null handle or pointer, a misaligned pointer (16 bytes), limb counts outside the range above, `out` overlapping `in`.
+ * TROYN_E_WORKSPACE: a workspace below the entry's size.  batch == 0 (or pcount == 0) returns TROYN_OK and touches nothing; only the handle and the
+ * limb counts are looked at before.  Everything is enqueued on the caller's stream; no entry synchronises or touches the default stream.
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_ckks_mod_raise_workspace_bytes(const troyn_ckks* h, uint32_t L_in, uint32_t L_out, size_t pcount, size_t batch, int is_ntt_form);
+int troyn_ckks_mod_raise(const troyn_ckks* h, uint32_t L_in, uint32_t L_out, int is_ntt_form, const uint64_t* in, size_t pcount,
+                         uint64_t* out, void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+
 /* RLWE / LWE packing (evaluator_lwes.cu):
  *   troyn_negacyclic_shift     utils::negacyclic_shift_ps (utils/poly_small_mod.cu:927-968): multiply `count` RNS polynomials by
  *                              X^shift, any shift (taken modulo 2N as the reference does); out of place

@@ -115,6 +115,8 @@ SYMBOLS = {
     "troyn_ckks_encode_polynomial": (C.c_int, [vp, u32, vp, sz, C.c_double, vp, vp, vp, sz, sz, vp]),
     "troyn_ckks_decode_polynomial": (C.c_int, [vp, u32, vp, C.c_double, vp, vp, sz, sz, vp]),
     "troyn_ckks_decode_simd": (C.c_int, [vp, u32, vp, C.c_double, vp, vp, sz, sz, vp]),
+    "troyn_ckks_mod_raise_workspace_bytes": (sz, [vp, u32, u32, sz, sz, C.c_int]),
+    "troyn_ckks_mod_raise": (C.c_int, [vp, u32, u32, C.c_int, vp, sz, vp, vp, sz, sz, vp]),
     "troyn_gather_workspace_bytes": (sz, [sz]),
     "troyn_gather": (C.c_int, [vp, sz, sz, vp, vp, sz, vp]),
     "troyn_scatter": (C.c_int, [vp, vp, sz, sz, vp, sz, vp]),

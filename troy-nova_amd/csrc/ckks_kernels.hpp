@@ -19,6 +19,7 @@
 // in four interleaved 16-lane groups, ds_write_b128 at 13 cycles) has no pad that serves every round.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "dev_math.hpp"
 
 namespace troyn {
@@ -214,26 +215,37 @@ struct CkksComposeArgs {
     double* out;                          // [batch][N]
 };
 
+// f(std::integral_constant<int, I>) for I = BEGIN .. END-1: a loop whose counter is a constant of every iteration
+template <int BEGIN, int END, class F>
+__device__ __forceinline__ void ckks_static_for(F&& f) {
+    if constexpr (BEGIN < END) { f(std::integral_constant<int, BEGIN>{}); ckks_static_for<BEGIN + 1, END>(f); }
+}
+
+// Mixed-radix (Garner) digit i of a coefficient: X = d_0 + q_0 (d_1 + q_1 (d_2 + ...)), 0 <= d_i < q_i.  `residue` is the word of row i, d[0..i)
+// the digits below, m = mods[i], garner_row = garner + i * K.  Shared by the decoder's composition and the base extension of
+// raise_kernels.hpp.  i is a constant at every call (an unrolled loop's counter, or ckks_static_for's), so d stays in registers.
+template <int LM>
+__device__ __forceinline__ u64 ckks_mixed_radix_digit(int i, u64 residue, const u64 (&d)[LM], const DevModulus m, const ulonglong2* garner_row) {
+    u64 v = barrett64(residue, m.q, m.ratio_hi);
+#pragma unroll
+    for (int j = 0; j < i; j++) {
+        const ulonglong2 w = garner_row[j];
+        v = shoup_mul(sub_mod(v, barrett64(d[j], m.q, m.ratio_hi), m.q), w.x, w.y, m.q);
+    }
+    return v;
+}
+
 // LM: the primes and the words held in registers (L <= LM; every loop is unrolled, so nothing is indexed at run time)
 template <int LM>
 __global__ __launch_bounds__(256) void ckks_compose_kernel(CkksComposeArgs a) {
     const unsigned chunks = a.n / 256, item = blockIdx.x / chunks, x = (blockIdx.x % chunks) * 256 + threadIdx.x;
     const unsigned L = a.L;
-    // mixed-radix (Garner) digits: X = d_0 + q_0 (d_1 + q_1 (d_2 + ...)), 0 <= d_i < q_i
     u64 d[LM];
 #pragma unroll
     for (int i = 0; i < LM; i++) {
         d[i] = 0;
-        if ((unsigned)i < L) {
-            const DevModulus m = a.mods[i];
-            u64 v = barrett64(a.residues[((size_t)item * L + i) * a.n + x], m.q, m.ratio_hi);
-#pragma unroll
-            for (int j = 0; j < i; j++) {
-                const ulonglong2 w = a.garner[(size_t)i * a.K + j];
-                v = shoup_mul(sub_mod(v, barrett64(d[j], m.q, m.ratio_hi), m.q), w.x, w.y, m.q);
-            }
-            d[i] = v;
-        }
+        if ((unsigned)i < L)
+            d[i] = ckks_mixed_radix_digit<LM>(i, a.residues[((size_t)item * L + i) * a.n + x], d, a.mods[i], a.garner + (size_t)i * a.K);
     }
     // Horner from the top digit: X as LM words (X < Q < 2^(61 L))
     u64 X[LM];

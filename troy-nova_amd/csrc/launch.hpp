@@ -118,5 +118,9 @@ bool launch_ckks_fft(unsigned log_n, bool decode, const CkksFftArgs& a, size_t b
 void launch_ckks_encode_polynomial(const double* coeffs, unsigned count, double scale, unsigned n, const DevModulus* mods, unsigned L, u64* residues,
                                    unsigned* too_large, size_t batch, hipStream_t s);
 bool launch_ckks_compose(const CkksComposeArgs& a, size_t batch, hipStream_t s);
+// CKKS ModRaise (troyn_raise.hip, raise_kernels.hpp): the centred base extension of items = batch * pcount polynomials in coefficient form, `chunks`
+// workgroups per polynomial (L <= CKKS_MAX_L; false above)
+struct ModRaiseArgs;
+bool launch_ckks_mod_raise(const ModRaiseArgs& a, size_t items, unsigned chunks, hipStream_t s);
 
 }  // namespace troyn

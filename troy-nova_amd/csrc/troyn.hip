@@ -30,6 +30,7 @@
 #include "hoist_kernels.hpp"
 #include "ckks_kernels.hpp"
 #include "ckks_tables.hpp"
+#include "raise_kernels.hpp"
 
 using namespace troyn;
 
@@ -3751,11 +3752,16 @@ struct troyn_ckks {
     double2* d_inv_roots = nullptr;                             // [N]
     ulonglong2* d_garner = nullptr;                             // [K][K] q_j^-1 mod q_i, j < i
     u64* d_q_words = nullptr;                                   // [min(K, CKKS_MAX_L)][2][CKKS_MAX_L]: Q_L, floor(Q_L / 2)
+    // ModRaise (raise_kernels.hpp)
+    ulonglong2* d_radix = nullptr;                              // [K][CKKS_MAX_L] q_i mod q_j at [j][i]
+    u64* d_half_digits = nullptr;                               // [CKKS_MAX_L][CKKS_MAX_L]: row L-1 = mixed-radix digits of floor(Q_L / 2)
+    u64* d_q_mod = nullptr;                                     // [CKKS_MAX_L][K]: Q_L mod q_j at [L-1][j]
 };
 
 extern "C" int troyn_ckks_destroy(troyn_ckks* h) {
     if (!h) return TROYN_OK;
-    for (void* p : {(void*)h->d_slot_of, (void*)h->d_roots, (void*)h->d_inv_roots, (void*)h->d_garner, (void*)h->d_q_words})
+    for (void* p : {(void*)h->d_slot_of, (void*)h->d_roots, (void*)h->d_inv_roots, (void*)h->d_garner, (void*)h->d_q_words, (void*)h->d_radix, (void*)h->d_half_digits,
+                    (void*)h->d_q_mod})
         if (p) (void)hipFree(p);
     delete h;
     return TROYN_OK;
@@ -3789,11 +3795,25 @@ extern "C" int troyn_ckks_create(troyn_ckks** out, const troyn_plan* plan) {
         for (size_t w = 0; w < big.size(); w++) qw[w] = big[w];
         for (size_t w = 0; w < (size_t)CKKS_MAX_L; w++) qw[CKKS_MAX_L + w] = (qw[w] >> 1) | (w + 1 < (size_t)CKKS_MAX_L ? qw[w + 1] << 63 : 0);
     }
+    // ModRaise: q_i mod q_j for the Horner over the digits, and per input level L the mixed-radix digits of floor(Q_L / 2) and Q_L mod q_j
+    std::vector<ulonglong2> radix(K * CKKS_MAX_L, make_ulonglong2(0, 0));
+    for (size_t j = 0; j < K; j++) for (size_t i = 0; i < levels; i++) radix[j * CKKS_MAX_L + i] = shoup_pair(plan->moduli[i], plan->moduli[j]);
+    std::vector<u64> half_digits((size_t)CKKS_MAX_L * CKKS_MAX_L, 0), q_mod((size_t)CKKS_MAX_L * K, 0);
+    for (size_t L = 1; L <= levels; L++) {
+        const u64* qw = &words[(L - 1) * 2 * CKKS_MAX_L];
+        const std::vector<u64> big(qw, qw + CKKS_MAX_L);
+        std::vector<u64> half(qw + CKKS_MAX_L, qw + 2 * CKKS_MAX_L);
+        for (size_t i = 0; i < L; i++) half_digits[(L - 1) * CKKS_MAX_L + i] = host::big_divmod_small(half, plan->moduli[i]);
+        for (size_t j = 0; j < K; j++) q_mod[(L - 1) * K + j] = host::big_mod_small(big, plan->moduli[j]);
+    }
     if (int rc = upload_vector(&h->d_slot_of, slot_of)) return rc;
     if (int rc = upload_vector(&h->d_roots, fwd)) return rc;
     if (int rc = upload_vector(&h->d_inv_roots, inv)) return rc;
     if (int rc = upload_vector(&h->d_garner, garner)) return rc;
     if (int rc = upload_vector(&h->d_q_words, words)) return rc;
+    if (int rc = upload_vector(&h->d_radix, radix)) return rc;
+    if (int rc = upload_vector(&h->d_half_digits, half_digits)) return rc;
+    if (int rc = upload_vector(&h->d_q_mod, q_mod)) return rc;
     *out = h.release();
     return TROYN_OK;
 }
@@ -3930,6 +3950,78 @@ extern "C" int troyn_ckks_decode_polynomial(const troyn_ckks* h, uint32_t L, con
 extern "C" int troyn_ckks_decode_simd(const troyn_ckks* h, uint32_t L, const uint64_t* plain, double scale, double* out, void* workspace, size_t workspace_bytes,
                                       size_t batch, troyn_stream_t stream) {
     return ckks_decode(h, true, L, plain, scale, out, workspace, workspace_bytes, batch, stream);
+}
+
+// ---- ModRaise: the centred base extension of [batch][pcount][L_in][N] to [batch][pcount][L_out][N] (raise_kernels.hpp) ----
+namespace {
+// NTT form: the inverse transforms of the input rows, then the new rows in coefficient form; coefficient form: nothing
+struct RaiseWorkspace { size_t coeffs, fresh, total; };
+RaiseWorkspace raise_workspace(const troyn_plan* p, size_t L_in, size_t L_out, size_t pcount, size_t batch, bool ntt) {
+    RaiseWorkspace w;
+    w.coeffs = 0;
+    w.fresh = ntt ? ckks_align(batch * pcount * L_in * p->n * sizeof(u64)) : 0;
+    w.total = ntt ? w.fresh + ckks_align(batch * pcount * (L_out - L_in) * p->n * sizeof(u64)) : 0;
+    return w;
+}
+inline bool raise_levels_ok(const troyn_ckks* h, uint32_t L_in, uint32_t L_out) { return L_in >= 1 && L_in < L_out && L_out <= h->plan->K; }
+}  // namespace
+
+extern "C" size_t troyn_ckks_mod_raise_workspace_bytes(const troyn_ckks* h, uint32_t L_in, uint32_t L_out, size_t pcount, size_t batch, int is_ntt_form) {
+    if (!h || !raise_levels_ok(h, L_in, L_out)) return 0;
+    return raise_workspace(h->plan, L_in, L_out, pcount, batch, is_ntt_form != 0).total;
+}
+
+extern "C" int troyn_ckks_mod_raise(const troyn_ckks* h, uint32_t L_in, uint32_t L_out, int is_ntt_form, const uint64_t* in, size_t pcount,
+                                    uint64_t* out, void* ws, size_t ws_bytes, size_t batch, troyn_stream_t stream) {
+    const std::string P = "[troyn_ckks_mod_raise]";
+    select_device(h);
+    if (!h) return fail(TROYN_E_INVALID, P + " null handle");
+    if (!raise_levels_ok(h, L_in, L_out)) return fail(TROYN_E_INVALID, P + " limb counts out of range (1 <= L_in < L_out <= n_moduli)");
+    const size_t items = batch * pcount;
+    if (items == 0) return TROYN_OK;
+    if (!in || !out) return fail(TROYN_E_INVALID, P + " null argument");
+    if (((uintptr_t)in & 15) || ((uintptr_t)out & 15) || ((uintptr_t)ws & 15)) return fail(TROYN_E_INVALID, P + " misaligned pointer");
+    const troyn_plan* p = h->plan;
+    const size_t n = p->n;
+    {
+        const uintptr_t i0 = (uintptr_t)in, i1 = i0 + items * L_in * n * sizeof(u64), o0 = (uintptr_t)out, o1 = o0 + items * L_out * n * sizeof(u64);
+        if (i0 < o1 && o0 < i1) return fail(TROYN_E_INVALID, P + " `out` overlaps `in`");
+    }
+    const unsigned ch = chunks_pairs(p->n);
+    if (int rc = check_rows(items * L_out, ch)) return rc;
+    const bool ntt = is_ntt_form != 0;
+    const RaiseWorkspace w = raise_workspace(p, L_in, L_out, pcount, batch, ntt);
+    if (ws_bytes < w.total || (w.total && !ws)) return fail(TROYN_E_WORKSPACE, P + " workspace too small");
+    if (L_in > (uint32_t)CKKS_MAX_L) return fail(TROYN_E_UNSUPPORTED, P + " more than 16 input moduli");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned fresh_rows = L_out - L_in;
+    ModRaiseArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.mods = p->d_mods; a.garner = h->d_garner; a.radix = h->d_radix;
+    a.half_digits = h->d_half_digits + (size_t)(L_in - 1) * CKKS_MAX_L; a.q_mod = h->d_q_mod + (size_t)(L_in - 1) * p->K;
+    a.K = p->K; a.L = L_in; a.LO = L_out; a.n = p->n;
+    if (!ntt) {
+        // the kernel writes all L_out rows: the low rows as it read them
+        a.in = (const u64*)in; a.low = (u64*)out; a.low_stride = (size_t)L_out * n;
+        a.out = (u64*)out + (size_t)L_in * n; a.out_stride = (size_t)L_out * n;
+        if (!launch_ckks_mod_raise(a, items, ch, s)) return fail(TROYN_E_UNSUPPORTED, P + " more than 16 input moduli");
+        LAUNCH_CHECK();
+        return TROYN_OK;
+    }
+    // NTT o extend o INTT: the low rows are copied, the L_in input rows take the inverse transform, the new rows the forward one
+    u64* coeffs = reinterpret_cast<u64*>((char*)ws + w.coeffs);
+    u64* fresh = reinterpret_cast<u64*>((char*)ws + w.fresh);
+    hipLaunchKernelGGL(copy_limbs_kernel, dim3((unsigned)(items * L_in * ch)), dim3(POLY_BLOCK), 0, s,
+                       ch, p->n, (const u64*)in, (size_t)L_in * n, 0u, (u64*)out, (size_t)L_out * n, L_in);
+    LAUNCH_CHECK();
+    NttArgs ia = contiguous_args(p, (const u64*)in, coeffs, pcount, L_in, 0, L_in, TROYN_IDX_COMPONENTWISE, 0);
+    if (int rc = launch_ntt(p, ia, batch, true, s)) return rc;
+    a.in = coeffs; a.low = nullptr; a.out = fresh; a.out_stride = (size_t)fresh_rows * n;
+    if (!launch_ckks_mod_raise(a, items, ch, s)) return fail(TROYN_E_UNSUPPORTED, P + " more than 16 input moduli");
+    LAUNCH_CHECK();
+    NttArgs fa = contiguous_args(p, fresh, (u64*)out + (size_t)L_in * n, pcount, fresh_rows, L_in, fresh_rows, TROYN_IDX_COMPONENTWISE, 0);
+    fa.out_pstride = (long long)L_out * n; fa.out_bstride = (long long)pcount * L_out * n;
+    return launch_ntt(p, fa, batch, false, s);
 }
 
 extern "C" size_t troyn_gather_workspace_bytes(size_t count) { return (count + 1) * sizeof(u64); }

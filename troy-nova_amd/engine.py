@@ -858,6 +858,16 @@ class CkksEncoder:
         """plain [batch][L][N] NTT form -> float64 [batch][N/2][2]"""
         return self._decode(self.plan.lib.troyn_ckks_decode_simd, L, plain, scale, (self.plan.n // 2, 2))
 
+    def mod_raise(self, rows, L_in, L_out, pcount, is_ntt_form):
+        """troyn_ckks_mod_raise: rows int64 [batch][pcount][L_in][N] -> [batch][pcount][L_out][N], the residues of the centred representative of
+        every coefficient modulo the plan's first L_out moduli (rows below L_in unchanged)"""
+        n = self.plan.n
+        batch = rows.numel() // (pcount * L_in * n)
+        out = torch.empty((batch, pcount, L_out, n), dtype=torch.int64, device=self.plan.device)
+        ws, ws_bytes = self._ws(self.lib.troyn_ckks_mod_raise_workspace_bytes(self.h, L_in, L_out, pcount, batch, 1 if is_ntt_form else 0))
+        capi.check(self.lib.troyn_ckks_mod_raise(self.h, L_in, L_out, 1 if is_ntt_form else 0, _ptr(rows), pcount, _ptr(out), ws, ws_bytes, batch, _stream()))
+        return out
+
 
 class Behz:
     """troyn_behz: BEHZ constants (RNSTool, utils/rns_tool.cu:29-275) for level L and plain modulus t."""

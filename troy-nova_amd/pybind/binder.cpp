@@ -516,6 +516,15 @@ PYBIND11_MODULE(pytroy_raw, m) {
         s.evaluate_polynomial(a, c, k, d, P(p)); }, py::arg("encrypted"), py::arg("coefficients"), py::arg("relin_keys"), py::arg("destination"), POOL);
     ev.def("evaluate_polynomial_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<double>& c, const RelinKeys& k, PoolArg p) {
         return s.evaluate_polynomial_new(a, c, k, P(p)); }, py::arg("encrypted"), py::arg("coefficients"), py::arg("relin_keys"), POOL);
+    // additions: CKKS ModRaise, the centred base extension to a higher level (troy.h); parms_id = None: the first data level
+    ev.def("mod_raise", [](const Evaluator& s, const Ciphertext& a, Ciphertext& d, std::optional<ParmsID> id, PoolArg p) { s.mod_raise(a, d, id, P(p)); },
+           py::arg("encrypted"), py::arg("destination"), py::arg("parms_id") = std::nullopt, POOL);
+    ev.def("mod_raise_new", [](const Evaluator& s, const Ciphertext& a, std::optional<ParmsID> id, PoolArg p) { return s.mod_raise_new(a, id, P(p)); },
+           py::arg("encrypted"), py::arg("parms_id") = std::nullopt, POOL);
+    ev.def("mod_raise_inplace", [](const Evaluator& s, Ciphertext& a, std::optional<ParmsID> id, PoolArg p) { s.mod_raise_inplace(a, id, P(p)); },
+           py::arg("encrypted"), py::arg("parms_id") = std::nullopt, POOL);
+    ev.def("mod_raise_batched", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& d, std::optional<ParmsID> id, PoolArg p) {
+        s.mod_raise_batched(const_ptrs(a), d, id, P(p)); }, py::arg("encrypted"), py::arg("destination"), py::arg("parms_id") = std::nullopt, POOL);
     // additions: the BFV inner product, one scale-down for the sum (troy.h)
     ev.def("bfv_multiply_accumulate", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, Ciphertext& d, PoolArg p) {
         s.bfv_multiply_accumulate(const_ptrs(a), const_ptrs(b), d, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("destination"), POOL);

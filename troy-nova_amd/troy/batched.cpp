@@ -180,6 +180,17 @@ void Evaluator::rescale_to_next_batched(const CVec& encrypted, const Vec& destin
         });
 }
 
+// -- ModRaise (addition) -----------------------------------------------------------------------------------------------------------------
+void Evaluator::mod_raise_batched(const CVec& encrypted, const Vec& destination, std::optional<ParmsID> parms_id, MemoryPoolHandle pool) const {
+    run_batched("[Evaluator::mod_raise_batched]", {&encrypted}, destination, pool, always,
+        [&](size_t i, Ciphertext& out) { mod_raise(*encrypted[i], out, parms_id, pool); },
+        [&](Ciphertext& proto) { mod_raise_prepare(*encrypted[0], proto, parms_id, pool); },
+        [&](const detail::StepEnv& env, const Ciphertext& proto, const uint64_t* in, const uint64_t*, uint64_t* out, size_t count) {
+            detail::mod_raise_step(env, context_->ckks(), static_cast<uint32_t>(encrypted[0]->coeff_modulus_size()), static_cast<uint32_t>(proto.coeff_modulus_size()),
+                                   proto.is_ntt_form(), in, proto.polynomial_count(), out, count);
+        });
+}
+
 // -- NTT ---------------------------------------------------------------------------------------------------------------
 void Evaluator::transform_batched(bool inverse, const CVec& encrypted, const Vec& destination, MemoryPoolHandle pool) const {
     run_batched(inverse ? "[Evaluator::transform_from_ntt_batched]" : "[Evaluator::transform_to_ntt_batched]", {&encrypted}, destination, pool, always,

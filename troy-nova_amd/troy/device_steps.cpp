@@ -97,6 +97,13 @@ void mod_switch_drop_step(const StepEnv& env, const troyn_plan* plan, uint32_t L
     env.check(troyn_mod_switch_drop(plan, L_in, L_out, in, polys, out, count, env.stream));
 }
 
+void mod_raise_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t L_in, uint32_t L_out, bool ntt_form, const uint64_t* in, size_t polys, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_ckks_mod_raise_workspace_bytes(ckks, L_in, L_out, polys, count, ntt_form ? 1 : 0);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_ckks_mod_raise(ckks, L_in, L_out, ntt_form ? 1 : 0, in, polys, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
 void negate_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t polys) {
     env.check(troyn_negate(plan, 0, L, in, out, polys, env.stream));
 }

@@ -60,6 +60,8 @@ void rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const 
 void divide_round_q_last_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, size_t polys, uint64_t* out, size_t count);   // BFV
 void bgv_mod_t_divide_step(const StepEnv& env, const troyn_bgv* bgv, const uint64_t* in, size_t polys, uint64_t* out, size_t count);
 void mod_switch_drop_step(const StepEnv& env, const troyn_plan* plan, uint32_t L_in, uint32_t L_out, const uint64_t* in, size_t polys, uint64_t* out, size_t count);
+// the centred base extension [count][polys][L_in][N] -> [count][polys][L_out][N] (CKKS ModRaise)
+void mod_raise_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t L_in, uint32_t L_out, bool ntt_form, const uint64_t* in, size_t polys, uint64_t* out, size_t count);
 void negate_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t polys);
 void add_sub_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, bool subtract, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t polys);
 void ntt_step(const StepEnv& env, const troyn_plan* plan, bool inverse, const uint64_t* in, uint64_t* out, size_t count, size_t polys, uint32_t L);

@@ -1733,6 +1733,33 @@ void Evaluator::multiply_accumulate_relinearize_rescale(const std::vector<const 
 }
 
 
+// -- ModRaise (addition; troyn_ckks_mod_raise, include/troyn.h) ------------------------------------------------------------------------------
+// the argument checks and the result object at the target level WITHOUT the device work
+void Evaluator::mod_raise_prepare(const Ciphertext& encrypted, Ciphertext& out, const std::optional<ParmsID>& target, MemoryPoolHandle pool) const {
+    const std::string P = "[Evaluator::mod_raise]";
+    if (context_->key_context_data().value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(P + " CKKS only.");
+    check_no_seed(P.c_str(), encrypted); check_on_device(P.c_str(), context_, encrypted);
+    auto cd = get_context_data(P.c_str(), encrypted.parms_id());
+    const ParmsID to = target.has_value() ? target.value() : context_->first_parms_id();
+    auto tcd = context_->get_context_data(to);
+    if (!tcd.has_value()) throw std::invalid_argument(P + " The target parms id is not in the modulus chain.");
+    if (to == context_->key_parms_id() && context_->key_parms_id() != context_->first_parms_id()) throw std::invalid_argument(P + " The key level cannot be the target.");
+    const size_t L_in = cd->parms().coeff_modulus().size(), L_out = tcd.value()->parms().coeff_modulus().size();
+    if (L_out <= L_in) throw std::invalid_argument(P + " The target must be strictly above the ciphertext's level.");
+    if (L_in > 16) throw std::invalid_argument(P + " More than 16 input limbs.");
+    if (encrypted.coeff_modulus_size() != L_in) throw std::invalid_argument(P + " The ciphertext's limb count does not match its parms id.");
+    out = Ciphertext::like(encrypted, encrypted.polynomial_count(), L_out, false, pool);
+    out.parms_id() = to;
+}
+
+void Evaluator::mod_raise(const Ciphertext& encrypted, Ciphertext& destination, std::optional<ParmsID> parms_id, MemoryPoolHandle pool) const {
+    Ciphertext out;
+    mod_raise_prepare(encrypted, out, parms_id, pool);
+    detail::mod_raise_step(on_current_stream(pool, true), context_->ckks(), static_cast<uint32_t>(encrypted.coeff_modulus_size()), static_cast<uint32_t>(out.coeff_modulus_size()),
+                           encrypted.is_ntt_form(), encrypted.data().raw_pointer(), encrypted.polynomial_count(), out.data().raw_pointer(), 1);
+    destination = std::move(out);
+}
+
 // -- real linear combinations and polynomial evaluation (additions; troyn_scalar_weighted_sums, include/troyn.h) -----------------------------
 namespace {
 // round half away from zero, then the canonical residue: negative values go to q - (|v| mod q)

@@ -1538,6 +1538,26 @@ public:
     void linear_combinations(const std::vector<const Ciphertext*>& encrypted, const std::vector<std::vector<double>>& weights, const std::vector<double>& constants,
                              double scale, std::vector<Ciphertext>& destination, MemoryPoolHandle pool, const char* method) const;
 
+    // ADDITION to the reference's interface: CKKS ModRaise, the first step of a bootstrap (troyn_ckks_mod_raise, include/troyn.h).  A ciphertext at a
+    //   level with modulus Q_in is raised to the level `parms_id` (default: context->first_parms_id()): every coefficient's centred representative in
+    //   (-Q_in/2, Q_in/2] is re-expressed modulo the target's primes, exactly.  The result has the target's parms_id and limb count; the scale, the
+    //   NTT-form flag and the polynomial count are unchanged, and its rows under the input's primes are the input's rows.
+    //   What the caller gets: the raised ciphertext decrypts to m + Q_in * I, where ||I||_inf <= (h + 1) / 2 for a secret of Hamming weight h (this key
+    //   generator's ternary secrets have h <= N).  Removing I is the job of the steps that follow (CoeffToSlot, EvalMod, SlotToCoeff) and not part of
+    //   this call.
+    //   std::invalid_argument "[Evaluator::mod_raise] ...": a BFV / BGV context (CKKS only), a target that is not in the chain, that is not strictly
+    //   above the ciphertext's level or that is the key level, more than 16 input limbs, a seed, an operand on the host.
+    // Call combining does not take part: these methods always launch directly.
+    void mod_raise(const Ciphertext& encrypted, Ciphertext& destination, std::optional<ParmsID> parms_id = std::nullopt, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext mod_raise_new(const Ciphertext& encrypted, std::optional<ParmsID> parms_id = std::nullopt, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; mod_raise(encrypted, d, parms_id, pool); return d;
+    }
+    void mod_raise_inplace(Ciphertext& encrypted, std::optional<ParmsID> parms_id = std::nullopt, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; mod_raise(encrypted, d, parms_id, pool); encrypted = std::move(d);
+    }
+    void mod_raise_batched(const std::vector<const Ciphertext*>& encrypted, const std::vector<Ciphertext*>& destination, std::optional<ParmsID> parms_id = std::nullopt,
+                           MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+
     // ADDITION to the reference's interface: the BFV inner product.  destination = the BEHZ multiply (evaluator.cu:29-116) with the tensor
     //   products of all pairs summed BEFORE its scale-down: one floor (and, in the relinearizing form, one key switch,
     //   evaluator_keyswitching.cu:119-144) for the whole sum (troyn_bfv_multiply_accumulate[_relinearize], include/troyn.h).  It decrypts to
@@ -1939,6 +1959,7 @@ private:
     SchemeType mod_switch_scale_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
     void mod_switch_drop_prepare(const Ciphertext& encrypted, Ciphertext& out, const ParmsID& target, MemoryPoolHandle pool) const;
     SchemeType mod_switch_to_next_prepare(const Ciphertext& encrypted, Ciphertext& out, MemoryPoolHandle pool) const;
+    void mod_raise_prepare(const Ciphertext& encrypted, Ciphertext& out, const std::optional<ParmsID>& target, MemoryPoolHandle pool) const;
     void apply_galois_prepare(const Ciphertext& encrypted, size_t galois_element, const GaloisKeys& galois_keys, Ciphertext& out, std::vector<const uint64_t*>& key_ptrs,
                               MemoryPoolHandle pool) const;
     void apply_keyswitching_prepare(const Ciphertext& encrypted, const KSwitchKeys& kswitch_keys, Ciphertext& out, std::vector<const uint64_t*>& key_ptrs,
