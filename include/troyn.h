@@ -220,6 +220,38 @@ int troyn_ckks_multiply_accumulate_relinearize_rescale(const troyn_plan* plan, u
                                                        size_t batch, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Product plus affine part, relinearized and rescaled: the Chebyshev recurrence T_{a+b} = 2 T_a T_b - T_{a-b} and the double angle
+ * cos 2t = 2 cos^2 t - 1 as ONE step.  An ADDITION to the reference's surface, on the accumulate -> relinearize -> rescale driver path of
+ * troyn_ckks_multiply_accumulate_relinearize_rescale above.  For each item i < batch
+ *   P_0 = alpha_i (a0 . b0) + w_i c0 + k_i          (k_i at every index: a constant in NTT form)
+ *   P_1 = alpha_i (a0 . b1 + a1 . b0) + w_i c1
+ *   P_2 = alpha_i (a1 . b1)
+ *   out_i = divide_and_round_q_last_ntt( relinearize( P ) )
+ * all modulo q_l in canonical form, on limbs 0 .. L-1.
+ *   a, b, c    host arrays of `batch` DEVICE pointers (the form of troyn_dyadic_convolute_accumulate: the operands of a ladder live in
+ *              separate ciphertexts, there is no gather).  a[i], b[i] -> u64[2][L][N] in NTT form; c[i] -> u64[2][c_nmod[i]][N] with
+ *              c_nmod[i] >= L, of which only the first L limbs are read, or NULL: then there is no addend and w_i is ignored.
+ *              Every pointer 16-byte aligned.
+ *   alpha, weight, constant   host [batch][L], canonical residues (word < q_l); `constant` may be NULL
+ *   keys       as for troyn_switch_key
+ *   out        [batch][2][L-1][N] in NTT form, 16-byte aligned
+ * Contract on integers: P_c[l][j] = ( alpha_i[l] * conv_c(a, b)[l][j] + (c < 2 and c[i] ? w_i[l] * c_c[l][j] : 0) + (c == 0 ? k_i[l] : 0) )
+ * mod q_l with conv = troyn_dyadic_convolute's tensor product.  Hence the result is bit-identical to this sequence per item:
+ * troyn_dyadic_convolute, troyn_multiply_scalar by alpha, troyn_multiply_scalar and troyn_add of the addend, the constant,
+ * troyn_relinearize, troyn_divide_and_round_q_last_ntt -- the sum modulo q does not depend on where the reductions happen.
+ * P is formed in the workspace in ONE pass: each word of a, b and c is read once, each word of P written once.
+ * TROYN_E_INVALID: L < 2 (or no next level), a null table, a null a[i] or b[i], a misaligned pointer, c_nmod[i] < L, a scalar word >= its
+ * modulus, `out` (or the workspace) overlapping an input, `out` overlapping the workspace.  TROYN_E_WORKSPACE for a workspace below the queried size.  batch == 0 returns
+ * TROYN_OK, launches nothing and looks at no buffer.  The host tables are read before the call returns: the scalars go through one upload
+ * into the workspace, the pointers and limb counts travel in the kernel arguments (32 items per launch).
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_ckks_multiply_affine_relinearize_rescale_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t batch);
+int troyn_ckks_multiply_affine_relinearize_rescale(const troyn_plan* plan, uint32_t L, const uint64_t* const* a, const uint64_t* const* b,
+                                                   const uint64_t* const* c, const uint32_t* c_nmod, const uint64_t* alpha,
+                                                   const uint64_t* weight, const uint64_t* constant, const uint64_t* const* keys,
+                                                   uint64_t* out, void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Scalar-weighted sums of ciphertexts: a small dense matrix of residues times a vector of ciphertexts in ONE pass.  An ADDITION to the
  * reference's surface (as the dot-product block above): the step between the powers and the recombination of a polynomial evaluation,
  * SUM_t s_t * ct_t + c, which is otherwise `terms` x (troyn_multiply_scalar + troyn_add) per output.

@@ -50,6 +50,9 @@ SYMBOLS = {
     "troyn_dyadic_convolute_accumulate": (C.c_int, [vp, u32, u32, C.POINTER(vp), C.POINTER(vp), sz, vp, C.c_int, sz, vp]),
     "troyn_ckks_multiply_accumulate_relinearize_rescale_workspace_bytes": (sz, [vp, u32, sz, sz]),
     "troyn_ckks_multiply_accumulate_relinearize_rescale": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(vp), vp, vp, sz, sz, vp]),
+    "troyn_ckks_multiply_affine_relinearize_rescale_workspace_bytes": (sz, [vp, u32, sz]),
+    "troyn_ckks_multiply_affine_relinearize_rescale": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u32), p64, p64, p64,
+                                                                 C.POINTER(vp), vp, vp, sz, sz, vp]),
     "troyn_scalar_weighted_sums_workspace_bytes": (sz, [vp, u32, sz, sz]),
     "troyn_scalar_weighted_sums": (C.c_int, [vp, u32, u32, C.POINTER(vp), C.POINTER(u32), sz, p64, p64, C.c_int, sz, vp, sz, sz, vp, sz, vp]),
     "troyn_divide_and_round_q_last": (C.c_int, [vp, u32, vp, sz, vp, sz, vp]),

@@ -235,6 +235,66 @@ __global__ __launch_bounds__(POLY_BLOCK) void scalar_weighted_sums_kernel(unsign
     }
 }
 
+// Tensor product plus affine part (an addition to the reference's kernels, troyn_ckks_multiply_affine_relinearize_rescale): the Chebyshev
+// step 2 T_a T_b - T_c and the double angle 2 x^2 - 1 before their ONE relinearize and rescale.  Per item of the batch
+//   P_0 = alpha (a0 . b0) + w c0 + k,   P_1 = alpha (a0 . b1 + a1 . b0) + w c1,   P_2 = alpha (a1 . b1)
+// a[i], b[i] -> [2][nmod][N], c[i] -> [2][c_nmod[i]][N] (only the first nmod limbs are read) or null (no addend), out [items][3][nmod][N].
+// Geometry of dyadic_convolute_accumulate_kernel: a thread owns two adjacent coefficients of one (item, limb) row; every word of a, b and c is read
+// ONCE with a 16-byte load and every word of P written once.  Headroom: plan moduli are < 2^61, so a0 b1 + a1 b0 < 2^123 is reduced (barrett128)
+// BEFORE it meets alpha; then t alpha + w c + k < 2^123 + 2^61 takes the one final reduction of the word.  The sum modulo q in canonical form is
+// the value that multiply_scalar, add and the constant give step by step.
+// The item pointers travel in the kernel arguments, at most MAFF_MAX_ITEMS items per launch; the per-(item, limb) scalars come from a table
+// [item][limb][4] = (alpha, w, k, 0), one wave-uniform 32-byte run that the compiler fetches with a scalar load.  The "has an addend" branch is
+// wave-uniform and taken OUTSIDE the coefficient loop (a select per load would serialise the loads).  No LDS, no scratch.
+constexpr unsigned MAFF_MAX_ITEMS = 32;
+struct MulAffinePtrs { const u64* a[MAFF_MAX_ITEMS]; const u64* b[MAFF_MAX_ITEMS]; const u64* c[MAFF_MAX_ITEMS]; unsigned c_nmod[MAFF_MAX_ITEMS]; };
+
+__device__ __forceinline__ u64 affine_word(u64 lo, u64 hi, u64 alpha, u64 w, u64 c, u64 k, const DevModulus& md) {
+    const u64 t = barrett128(lo, hi, md.q, md.ratio_lo, md.ratio_hi);
+    u64 l, h;
+    mul128(t, alpha, l, h);
+    mac128(l, h, w, c);
+    const u128 acc = (((u128)h << 64) | l) + k;
+    return barrett128((u64)acc, (u64)(acc >> 64), md.q, md.ratio_lo, md.ratio_hi);
+}
+
+template <bool HAS_C>
+__device__ __forceinline__ void multiply_affine_row(unsigned chunks, const DevModulus& md, unsigned n, size_t pc, const u64* ap, const u64* bp,
+                                                    const u64* cp, size_t c_pc, u64 alpha, u64 w, u64 k, u64* op) {
+    for (unsigned i = blk_col(chunks) * 2; i < n; i += chunks * blockDim.x * 2) {
+        const u64x2 a0 = ld2(ap + i), a1 = ld2(ap + pc + i), b0 = ld2(bp + i), b1 = ld2(bp + pc + i);
+        u64x2 c0{0, 0}, c1{0, 0};
+        if constexpr (HAS_C) { c0 = ld2(cp + i); c1 = ld2(cp + c_pc + i); }
+        const u64 wc = HAS_C ? w : 0;
+        u64 lo, hi, r0, r1;
+        mul128(a0.a, b0.a, lo, hi); r0 = affine_word(lo, hi, alpha, wc, c0.a, k, md);
+        mul128(a0.b, b0.b, lo, hi); r1 = affine_word(lo, hi, alpha, wc, c0.b, k, md);
+        st2(op + i, r0, r1);
+        mul128(a0.a, b1.a, lo, hi); mac128(lo, hi, a1.a, b0.a); r0 = affine_word(lo, hi, alpha, wc, c1.a, 0, md);
+        mul128(a0.b, b1.b, lo, hi); mac128(lo, hi, a1.b, b0.b); r1 = affine_word(lo, hi, alpha, wc, c1.b, 0, md);
+        st2(op + pc + i, r0, r1);
+        r0 = mul_mod(mul_mod(a1.a, b1.a, md), alpha, md);      // P_2 has no affine part
+        r1 = mul_mod(mul_mod(a1.b, b1.b, md), alpha, md);
+        st2(op + 2 * pc + i, r0, r1);
+    }
+}
+
+// scal: the table of the launch's first item; out: P of the launch's first item
+__global__ __launch_bounds__(POLY_BLOCK) void multiply_affine_kernel(unsigned chunks, const DevModulus* __restrict__ mods, unsigned nmod, unsigned n,
+                                                                     MulAffinePtrs ptrs, const u64* __restrict__ scal, u64* __restrict__ out) {
+    const unsigned limb = blk_row(chunks) % nmod;
+    const unsigned item = blk_row(chunks) / nmod;      // < MAFF_MAX_ITEMS: the grid is items * nmod * chunks blocks
+    const DevModulus md = mods[limb];
+    const size_t pc = (size_t)nmod * n;
+    const size_t in_off = (size_t)limb * n;
+    const u64* s = scal + ((size_t)item * nmod + limb) * 4;
+    const u64 alpha = s[0], w = s[1], k = s[2];
+    const u64* cp = ptrs.c[item];
+    u64* op = out + (size_t)item * 3 * pc + in_off;
+    if (cp) multiply_affine_row<true>(chunks, md, n, pc, ptrs.a[item] + in_off, ptrs.b[item] + in_off, cp + in_off, (size_t)ptrs.c_nmod[item] * n, alpha, w, k, op);
+    else multiply_affine_row<false>(chunks, md, n, pc, ptrs.a[item] + in_off, ptrs.b[item] + in_off, nullptr, 0, alpha, 0, k, op);
+}
+
 // generic (any pa, pb) version with the reference's loop structure
 __global__ __launch_bounds__(POLY_BLOCK) void dyadic_convolute_generic_kernel(unsigned chunks, const DevModulus* mods, unsigned mod_start, unsigned nmod,
                                                                               unsigned n, const u64* a, unsigned pa, const u64* b, unsigned pb, u64* out) {

@@ -2569,6 +2569,87 @@ extern "C" int troyn_ckks_multiply_accumulate_relinearize_rescale(const troyn_pl
     return troyn_divide_and_round_q_last_ntt(p, L, (const uint64_t*)(ws + w.relin2), 2, out, ws + w.sub, w.sub_bytes, batch, stream);
 }
 
+// Tensor product plus affine part, then the same two drivers (an addition: the Chebyshev recurrence and the double angle as ONE step).
+//   workspace: the layout of the entry above (P is formed in prod3), then the scalar table [batch][L][4] = (alpha, w, k, 0)
+static inline size_t maff_table_offset(const MarrLayout& w) { return (w.total_bytes + 15) & ~(size_t)15; }
+
+extern "C" size_t troyn_ckks_multiply_affine_relinearize_rescale_workspace_bytes(const troyn_plan* plan, uint32_t L, size_t batch) {
+    if (!plan || plan->K < 2 || L < 2 || L > plan->K - 1) return 0;     // (the levels the entry itself refuses)
+    return maff_table_offset(marr_layout(plan, L, batch)) + batch * (size_t)L * 4 * sizeof(u64);
+}
+
+extern "C" int troyn_ckks_multiply_affine_relinearize_rescale(const troyn_plan* p, uint32_t L, const uint64_t* const* a, const uint64_t* const* b,
+                                                              const uint64_t* const* c, const uint32_t* c_nmod, const uint64_t* alpha,
+                                                              const uint64_t* weight, const uint64_t* constant, const uint64_t* const* keys,
+                                                              uint64_t* out, void* workspace, size_t workspace_bytes, size_t batch,
+                                                              troyn_stream_t stream) {
+    select_device(p);
+    const std::string P = "[troyn_ckks_multiply_affine_relinearize_rescale]";
+    if (!p) return fail(TROYN_E_INVALID, P + " null argument");
+    if (p->K < 2) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] Keyswitching is not supported.");
+    if (L < 2 || L > p->K - 1) return fail(TROYN_E_INVALID, "[Evaluator::mod_switch_scale_to_next_internal] Next context data is not set.");
+    if (batch == 0) return TROYN_OK;      // nothing to launch: no table, buffer or pointer entry is looked at
+    if (!a || !b || !c || !c_nmod || !alpha || !weight || !keys || !out || !workspace) return fail(TROYN_E_INVALID, P + " null argument");
+    if (((uintptr_t)out & 15) || ((uintptr_t)workspace & 15)) return fail(TROYN_E_INVALID, P + " misaligned destination or workspace");
+    const unsigned n = p->n;
+    const size_t pc = (size_t)L * n;
+    const MarrLayout w = marr_layout(p, L, batch);
+    const size_t tab_off = maff_table_offset(w), total = tab_off + batch * (size_t)L * 4 * sizeof(u64);
+    // neither `out` nor the workspace (where P is formed while the operands are still being read) may overlap an operand
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + batch * 2 * (pc - n) * sizeof(u64);
+    const uintptr_t w0 = (uintptr_t)workspace, w1 = w0 + total;
+    if (o0 < w1 && w0 < o1) return fail(TROYN_E_INVALID, P + " out overlaps the workspace");
+    for (size_t i = 0; i < batch; i++) {
+        if (!a[i] || !b[i]) return fail(TROYN_E_INVALID, P + " null pointer in the operand tables");
+        if (c[i] && c_nmod[i] < L) return fail(TROYN_E_INVALID, P + " an addend has fewer limbs than L");
+        const uintptr_t q[3] = {(uintptr_t)a[i], (uintptr_t)b[i], (uintptr_t)c[i]};
+        const size_t bytes[3] = {2 * pc * sizeof(u64), 2 * pc * sizeof(u64), c[i] ? 2 * (size_t)c_nmod[i] * n * sizeof(u64) : 0};
+        for (int j = 0; j < 3; j++) {
+            if (!q[j]) continue;
+            if (q[j] & 15) return fail(TROYN_E_INVALID, P + " misaligned pointer in the tables");
+            if (q[j] < o1 && o0 < q[j] + bytes[j]) return fail(TROYN_E_INVALID, P + " out overlaps an input");
+            if (q[j] < w1 && w0 < q[j] + bytes[j]) return fail(TROYN_E_INVALID, P + " the workspace overlaps an input");
+        }
+        for (size_t l = 0; l < L; l++) {
+            const u64 q_l = p->moduli[l];
+            if (alpha[i * L + l] >= q_l || (c[i] && weight[i * L + l] >= q_l) || (constant && constant[i * L + l] >= q_l))
+                return fail(TROYN_E_INVALID, P + " a scalar is not a canonical residue");
+        }
+    }
+    if (workspace_bytes < total) return fail(TROYN_E_WORKSPACE, P + " workspace too small");
+    const unsigned ch = chunks_pairs(n);
+    if (int rc = check_rows(std::min<size_t>(batch, MAFF_MAX_ITEMS) * L, ch)) return rc;
+    // the host tables are read here: one upload of (alpha, w, k, 0) per (item, limb)
+    std::vector<u64> tab(batch * (size_t)L * 4, 0);
+    for (size_t i = 0; i < batch * (size_t)L; i++) {
+        tab[4 * i] = alpha[i];
+        tab[4 * i + 1] = c[i / L] ? weight[i] : 0;
+        tab[4 * i + 2] = constant ? constant[i] : 0;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    u64* ws = (u64*)workspace;
+    const u64* d_tab = reinterpret_cast<const u64*>((const char*)workspace + tab_off);
+    int rc;
+    if ((rc = upload_host_table(s, (void*)d_tab, tab.data(), tab.size() * sizeof(u64)))) return rc;
+    for (size_t i0 = 0; i0 < batch; i0 += MAFF_MAX_ITEMS) {
+        const unsigned cnt = (unsigned)std::min<size_t>(batch - i0, MAFF_MAX_ITEMS);
+        MulAffinePtrs g;
+        for (unsigned i = 0; i < MAFF_MAX_ITEMS; i++) {
+            const size_t j = i0 + (i < cnt ? i : 0);
+            g.a[i] = reinterpret_cast<const u64*>(a[j]);
+            g.b[i] = reinterpret_cast<const u64*>(b[j]);
+            g.c[i] = reinterpret_cast<const u64*>(c[j]);
+            g.c_nmod[i] = c[j] ? c_nmod[j] : 0;
+        }
+        hipLaunchKernelGGL(multiply_affine_kernel, dim3((unsigned)((size_t)cnt * L * ch)), dim3(POLY_BLOCK), 0, s, ch, p->d_mods, (unsigned)L, n, g,
+                           d_tab + i0 * (size_t)L * 4, ws + w.prod3 + i0 * 3 * pc);
+        LAUNCH_CHECK();
+    }
+    // Evaluator::relinearize (evaluator_keyswitching.cu:119-144) -> rescale_to_next (utils/rns_tool.cu:499-694), the drivers of the entry above
+    if ((rc = troyn_relinearize(p, L, 1, 1, (const uint64_t*)(ws + w.prod3), keys, (uint64_t*)(ws + w.relin2), ws + w.sub, w.sub_bytes, batch, stream))) return rc;
+    return troyn_divide_and_round_q_last_ntt(p, L, (const uint64_t*)(ws + w.relin2), 2, out, ws + w.sub, w.sub_bytes, batch, stream);
+}
+
 extern "C" int troyn_mod_switch_drop(const troyn_plan* p, uint32_t L_in, uint32_t L_out, const uint64_t* in, size_t pcount,
                                      uint64_t* out, size_t batch, troyn_stream_t stream) {
     select_device(p);

@@ -579,6 +579,45 @@ class Plan:
             None if ws is None else C.c_void_p(ws.data_ptr()), 0 if ws is None else ws.numel(), _stream()))
         return out
 
+    def multiply_affine_relinearize_rescale(self, L, a_list, b_list, c_list, c_nmod, alpha, weight, keys, constant=None, out=None):
+        """out [batch][2][L-1][N]: out[i] = rescale_to_next(relinearize(alpha[i] * a_list[i] (x) b_list[i] + weight[i] * c_list[i] + constant[i])), the
+        Chebyshev recurrence / double angle as one step (include/troyn.h states the contract).  a_list[i], b_list[i]: [2][L][N]; c_list[i]:
+        [2][c_nmod[i]][N] with c_nmod[i] >= L, or None (no addend; c_list itself may be None); alpha, weight [batch][L] and constant [batch][L] (or None) are canonical
+        residues on the host.  An empty batch launches nothing and looks at no buffer."""
+        who = "[troyn_ckks_multiply_affine_relinearize_rescale]"
+        batch = len(a_list)
+        if c_list is None:      # no addend anywhere (the double angle): c_nmod and weight may be None as well
+            c_list, c_nmod = [None] * batch, [0] * batch
+            weight = [[0] * L] * batch if weight is None else weight
+        if len(b_list) != batch or len(c_list) != batch or len(c_nmod) != batch:
+            raise capi.TroynInvalidArgument("%s one b, c and limb count per item is needed" % who)
+        tabs = []
+        for name, t in (("alpha", alpha), ("weight", weight), ("constant", constant)):
+            if t is None and name == "constant":
+                tabs.append(None)
+                continue
+            arr = np.ascontiguousarray(np.array(t, dtype=np.uint64))
+            if batch and arr.shape != (batch, L):
+                raise capi.TroynInvalidArgument("%s %s is not [batch][L]" % (who, name))
+            tabs.append(arr if arr.size else np.zeros(1, dtype=np.uint64))
+        for name, ts, words in (("a", a_list, [2 * L * self.n] * batch), ("b", b_list, [2 * L * self.n] * batch),
+                                ("c", c_list, [2 * int(v) * self.n for v in c_nmod])):
+            for i, t in enumerate(ts):
+                if t is not None and _ptr(t) and t.numel() != words[i]:
+                    raise capi.TroynInvalidArgument("%s %s[%d] is not [2][limbs][N]" % (who, name, i))
+        arr = lambda ts: (C.c_void_p * max(len(ts), 1))(*[None if t is None else t.data_ptr() for t in ts])
+        narr = (C.c_uint32 * max(batch, 1))(*[int(v) for v in c_nmod])
+        if out is None and batch:
+            out = torch.empty((batch, 2, max(L - 1, 0), self.n), dtype=torch.int64, device=self.device)
+        elif out is not None and out.numel() != batch * 2 * (L - 1) * self.n:
+            raise capi.TroynInvalidArgument("%s out is not [batch][2][L-1][N]" % who)
+        ws = self.workspace(self.lib.troyn_ckks_multiply_affine_relinearize_rescale_workspace_bytes(self.h, L, batch)) if batch else None
+        capi.check(self.lib.troyn_ckks_multiply_affine_relinearize_rescale(
+            self.h, L, arr(a_list), arr(b_list), arr(c_list), narr, tabs[0].ctypes.data_as(capi.p64), tabs[1].ctypes.data_as(capi.p64),
+            None if tabs[2] is None else tabs[2].ctypes.data_as(capi.p64), self._key_ptrs(keys, L) if batch else None,
+            None if out is None else _ptr(out), None if ws is None else C.c_void_p(ws.data_ptr()), 0 if ws is None else ws.numel(), batch, _stream()))
+        return out
+
     # -- modulus switching -------------------------------------------------------------------------
     def divide_and_round_q_last(self, L, x, pcount, out=None):
         batch = x.numel() // (pcount * L * self.n)

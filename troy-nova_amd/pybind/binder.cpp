@@ -525,6 +525,29 @@ PYBIND11_MODULE(pytroy_raw, m) {
            py::arg("encrypted"), py::arg("parms_id") = std::nullopt, POOL);
     ev.def("mod_raise_batched", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& d, std::optional<ParmsID> id, PoolArg p) {
         s.mod_raise_batched(const_ptrs(a), d, id, P(p)); }, py::arg("encrypted"), py::arg("destination"), py::arg("parms_id") = std::nullopt, POOL);
+    // additions: the fused product-plus-affine step, Chebyshev evaluation and EvalMod (troy.h)
+    ev.def("multiply_affine_relinearize_rescale", [](const Evaluator& s, const Ciphertext& a, const Ciphertext& b, int64_t alpha, const Ciphertext* c, double gamma, double constant,
+                                                     const RelinKeys& k, Ciphertext& d, PoolArg p) { s.multiply_affine_relinearize_rescale(a, b, alpha, c, gamma, constant, k, d, P(p)); },
+           py::arg("encrypted1"), py::arg("encrypted2"), py::arg("alpha"), py::arg("addend"), py::arg("gamma"), py::arg("constant"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    ev.def("multiply_affine_relinearize_rescale_new", [](const Evaluator& s, const Ciphertext& a, const Ciphertext& b, int64_t alpha, const Ciphertext* c, double gamma, double constant,
+                                                         const RelinKeys& k, PoolArg p) { return s.multiply_affine_relinearize_rescale_new(a, b, alpha, c, gamma, constant, k, P(p)); },
+           py::arg("encrypted1"), py::arg("encrypted2"), py::arg("alpha"), py::arg("addend"), py::arg("gamma"), py::arg("constant"), py::arg("relin_keys"), POOL);
+    ev.def("multiply_affine_relinearize_rescale_batched", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, const std::vector<int64_t>& alpha,
+                                                             const std::vector<Ciphertext*>& c, const std::vector<double>& gamma, const std::vector<double>& constant,
+                                                             const RelinKeys& k, const std::vector<Ciphertext*>& d, PoolArg p) {
+        std::vector<Ciphertext> out;
+        s.multiply_affine_relinearize_rescale_batched(const_ptrs(a), const_ptrs(b), alpha, const_ptrs(c), gamma, constant, k, out, P(p));
+        if (d.size() != out.size()) throw std::invalid_argument("[Evaluator::multiply_affine_relinearize_rescale_batched] destination needs one ciphertext per item.");
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },
+           py::arg("encrypted1"), py::arg("encrypted2"), py::arg("alpha"), py::arg("addend"), py::arg("gamma"), py::arg("constant"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    ev.def("evaluate_chebyshev", [](const Evaluator& s, const Ciphertext& a, const std::vector<double>& c, double hw, const RelinKeys& k, Ciphertext& d, PoolArg p) {
+        s.evaluate_chebyshev(a, c, hw, k, d, P(p)); }, py::arg("encrypted"), py::arg("coefficients"), py::arg("half_width"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    ev.def("evaluate_chebyshev_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<double>& c, double hw, const RelinKeys& k, PoolArg p) {
+        return s.evaluate_chebyshev_new(a, c, hw, k, P(p)); }, py::arg("encrypted"), py::arg("coefficients"), py::arg("half_width"), py::arg("relin_keys"), POOL);
+    ev.def("eval_mod", [](const Evaluator& s, const Ciphertext& a, const RelinKeys& k, double hw, size_t degree, size_t r, Ciphertext& d, PoolArg p) {
+        s.eval_mod(a, k, hw, degree, r, d, P(p)); }, py::arg("encrypted"), py::arg("relin_keys"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"), py::arg("destination"), POOL);
+    ev.def("eval_mod_new", [](const Evaluator& s, const Ciphertext& a, const RelinKeys& k, double hw, size_t degree, size_t r, PoolArg p) {
+        return s.eval_mod_new(a, k, hw, degree, r, P(p)); }, py::arg("encrypted"), py::arg("relin_keys"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"), POOL);
     // additions: the BFV inner product, one scale-down for the sum (troy.h)
     ev.def("bfv_multiply_accumulate", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, Ciphertext& d, PoolArg p) {
         s.bfv_multiply_accumulate(const_ptrs(a), const_ptrs(b), d, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("destination"), POOL);

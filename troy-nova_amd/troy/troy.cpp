@@ -1847,6 +1847,26 @@ void Evaluator::linear_combinations(const std::vector<const Ciphertext*>& encryp
     destination = std::move(out);
 }
 
+namespace {
+// the fixed schedule for degree d >= 2: k the smallest power of two with k^2 >= d + 1, g = ceil((d + 1) / k), recombination depth
+void ps_schedule(size_t d, size_t& k, size_t& g, size_t& rec_depth) {
+    auto clog2 = [](size_t v) { size_t r = 0; while ((size_t(1) << r) < v) r++; return r; };
+    k = 1; g = 1; rec_depth = 0;
+    if (d >= 2) {
+        k = 2; while (k * k < d + 1) k *= 2;
+        g = (d + k) / k;
+        rec_depth = std::max(clog2((g - 1) * k), clog2(k) + 1);
+    }
+}
+// the degree: the index of the last non-zero coefficient
+size_t ps_degree(const char* P, const std::vector<double>& coefficients) {
+    size_t d = coefficients.size();
+    while (d > 0 && coefficients[d - 1] == 0.0) d--;
+    if (d == 0) throw std::invalid_argument(std::string(P) + " All coefficients are zero.");
+    return d - 1;
+}
+}  // namespace
+
 void Evaluator::evaluate_polynomial(const Ciphertext& x, const std::vector<double>& coefficients, const RelinKeys& relin_keys, Ciphertext& destination,
                                     MemoryPoolHandle pool) const {
     const char* P = "[Evaluator::evaluate_polynomial]";
@@ -1854,19 +1874,34 @@ void Evaluator::evaluate_polynomial(const Ciphertext& x, const std::vector<doubl
     check_no_seed(P, x); check_on_device(P, context_, x);
     if (!x.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Ciphertext must be in NTT form.");
     if (x.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " The ciphertext must have two polynomials.");
-    size_t d = coefficients.size();
-    while (d > 0 && coefficients[d - 1] == 0.0) d--;
-    if (d == 0) throw std::invalid_argument(std::string(P) + " All coefficients are zero.");
-    d--;     // the degree
+    const size_t d = ps_degree(P, coefficients);
     auto coef = [&](size_t m) { return m <= d ? coefficients[m] : 0.0; };
-    auto clog2 = [](size_t v) { size_t r = 0; while ((size_t(1) << r) < v) r++; return r; };
-    size_t k = 1, g = 1, rec_depth = 0, depth = 1;
-    if (d >= 2) {
-        k = 2; while (k * k < d + 1) k *= 2;
-        g = (d + k) / k;
-        rec_depth = std::max(clog2((g - 1) * k), clog2(k) + 1);
-        depth = rec_depth + 1;
-    }
+    size_t k, g, rec_depth;
+    ps_schedule(d, k, g, rec_depth);
+    // the powers, memoised
+    std::map<size_t, Ciphertext> powers;
+    std::function<const Ciphertext&(size_t)> power = [&](size_t m) -> const Ciphertext& {
+        if (m == 1) return x;
+        auto it = powers.find(m);
+        if (it != powers.end()) return it->second;
+        size_t a = 1; while (a * 2 < m) a *= 2;      // the largest power of two below m (m / 2 for a power of two)
+        const Ciphertext* pa = &power(a);
+        const Ciphertext* pb = &power(m - a);
+        Ciphertext lowered;
+        if (pa->coeff_modulus_size() > pb->coeff_modulus_size()) { mod_switch_to(*pa, pb->parms_id(), lowered, pool); pa = &lowered; }
+        else if (pb->coeff_modulus_size() > pa->coeff_modulus_size()) { mod_switch_to(*pb, pa->parms_id(), lowered, pool); pb = &lowered; }
+        Ciphertext prod;
+        multiply_relinearize_rescale(*pa, *pb, relin_keys, prod, pool);
+        return powers.emplace(m, std::move(prod)).first->second;
+    };
+    paterson_stockmeyer(P, x, d, 0, power, [&](size_t j, size_t i) { return coef(j * k + i); }, relin_keys, destination, pool);
+}
+
+void Evaluator::paterson_stockmeyer(const char* P, const Ciphertext& x, size_t d, size_t extra_levels, const std::function<const Ciphertext&(size_t)>& power,
+                                    const std::function<double(size_t, size_t)>& u, const RelinKeys& relin_keys, Ciphertext& destination, MemoryPoolHandle pool) const {
+    size_t k, g, rec_depth;
+    ps_schedule(d, k, g, rec_depth);
+    const size_t depth = rec_depth + 1 + extra_levels;
     auto cd0 = get_context_data(P, x.parms_id());
     const size_t L0 = x.coeff_modulus_size();
     if (L0 < depth + 1)
@@ -1897,7 +1932,7 @@ void Evaluator::evaluate_polynomial(const Ciphertext& x, const std::vector<doubl
 
     if (d <= 1) {
         utils::DynamicArray leaf;
-        leaves({&x}, L0, 1, {S * static_cast<double>(moduli[L0 - 1])}, [&](size_t, size_t i) { return coef(i); }, leaf);
+        leaves({&x}, L0, 1, {S * static_cast<double>(moduli[L0 - 1])}, [&](size_t, size_t i) { return u(0, i); }, leaf);
         Ciphertext out = Ciphertext::like(x, 2, L0 - 1, false, pool);
         out.parms_id() = level_down(1)->parms_id(); out.scale() = S; out.is_ntt_form() = true;
         detail::hip_check(hipMemcpyAsync(out.data().raw_pointer(), leaf.raw_pointer(), out.data().size() * 8, hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
@@ -1905,22 +1940,6 @@ void Evaluator::evaluate_polynomial(const Ciphertext& x, const std::vector<doubl
         return;
     }
 
-    // the powers, memoised
-    std::map<size_t, Ciphertext> powers;
-    std::function<const Ciphertext&(size_t)> power = [&](size_t m) -> const Ciphertext& {
-        if (m == 1) return x;
-        auto it = powers.find(m);
-        if (it != powers.end()) return it->second;
-        size_t a = 1; while (a * 2 < m) a *= 2;      // the largest power of two below m (m / 2 for a power of two)
-        const Ciphertext* pa = &power(a);
-        const Ciphertext* pb = &power(m - a);
-        Ciphertext lowered;
-        if (pa->coeff_modulus_size() > pb->coeff_modulus_size()) { mod_switch_to(*pa, pb->parms_id(), lowered, pool); pa = &lowered; }
-        else if (pb->coeff_modulus_size() > pa->coeff_modulus_size()) { mod_switch_to(*pb, pa->parms_id(), lowered, pool); pb = &lowered; }
-        Ciphertext prod;
-        multiply_relinearize_rescale(*pa, *pb, relin_keys, prod, pool);
-        return powers.emplace(m, std::move(prod)).first->second;
-    };
     std::vector<const Ciphertext*> babies;
     for (size_t i = 1; i < k; i++) babies.push_back(&power(i));
     const size_t Lrec = L0 - rec_depth;                         // limbs at the recombination level l*
@@ -1937,9 +1956,9 @@ void Evaluator::evaluate_polynomial(const Ciphertext& x, const std::vector<doubl
     std::vector<double> sum_scale(g - 1);
     for (size_t j = 1; j < g; j++) sum_scale[j - 1] = T / giants[j - 1]->scale() * static_cast<double>(moduli[Lrec]);
     utils::DynamicArray upper, leaf0;
-    leaves(babies, Lrec + 1, g - 1, sum_scale, [&](size_t s, size_t i) { return coef((s + 1) * k + i); }, upper);
+    leaves(babies, Lrec + 1, g - 1, sum_scale, [&](size_t s, size_t i) { return u(s + 1, i); }, upper);
     // leaf_0 at Lrec limbs and scale T: its division lands on the result's level and scale
-    leaves(babies, Lrec, 1, {T}, [&](size_t, size_t i) { return coef(i); }, leaf0);
+    leaves(babies, Lrec, 1, {T}, [&](size_t, size_t i) { return u(0, i); }, leaf0);
     // the recombination: SUM_j leaf_j * x^(jk), one key switch and one rescale
     // every product leaf_j * x^(jk) has the scale T: that is the scale to hold against the modulus at l*; then relinearize's key checks
     if (!is_scale_within_bounds(T, cd_rec)) throw std::invalid_argument(std::string(P) + " Scale out of bounds");
@@ -1969,6 +1988,170 @@ void Evaluator::evaluate_polynomial(const Ciphertext& x, const std::vector<doubl
         troyn_check(troyn_add(plan, 0, static_cast<uint32_t>(Lrec - 1), out.data().raw_pointer(), leaf0.raw_pointer(), out.data().raw_pointer(), 2, env.stream));
     }
     destination = std::move(out);
+}
+
+
+// -- the Chebyshev basis and EvalMod (additions; troyn_ckks_multiply_affine_relinearize_rescale, include/troyn.h) ----------------------------
+void Evaluator::multiply_affine_relinearize_rescale_batched(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const std::vector<int64_t>& alpha,
+                                                            const std::vector<const Ciphertext*>& addend, const std::vector<double>& gamma, const std::vector<double>& constant,
+                                                            const RelinKeys& relin_keys, std::vector<Ciphertext>& destination, MemoryPoolHandle pool, const char* P) const {
+    const size_t batch = e1.size();
+    if (batch == 0) throw std::invalid_argument(std::string(P) + " Empty operand list.");
+    if (e2.size() != batch || alpha.size() != batch || addend.size() != batch || gamma.size() != batch || constant.size() != batch)
+        throw std::invalid_argument(std::string(P) + " Every list needs one entry per item.");
+    if (context_->key_context_data().value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(std::string(P) + " CKKS only.");
+    uint32_t L = 0; ParmsID next; std::vector<const uint64_t*> keys;
+    std::vector<double> out_scale(batch);
+    std::vector<__int128> weight(batch, 0), konst(batch, 0);
+    std::vector<const uint64_t*> a(batch), b(batch), c(batch, nullptr);
+    std::vector<uint32_t> c_nmod(batch, 0);
+    for (size_t i = 0; i < batch; i++) {
+        if (!e1[i] || !e2[i]) throw std::invalid_argument(std::string(P) + " Null operand.");
+        uint32_t Li = 0; ParmsID ni; std::vector<const uint64_t*> ki;
+        bool fused = false;
+        try { fused = multiply_relinearize_rescale_prepare(*e1[i], *e2[i], relin_keys, Li, ni, out_scale[i], ki); }      // multiply's, relinearize's and rescale's refusals
+        catch (const std::out_of_range& e) { throw std::out_of_range(std::string(P) + " " + e.what()); }
+        catch (const std::invalid_argument& e) { throw std::invalid_argument(std::string(P) + " " + e.what()); }
+        if (!fused) throw std::invalid_argument(std::string(P) + " Operands must be two-polynomial ciphertexts.");
+        if (i == 0) { L = Li; next = ni; keys = std::move(ki); }
+        else if (e1[i]->parms_id() != e1[0]->parms_id()) throw std::invalid_argument(std::string(P) + " Items have different parms_id.");
+        if (alpha[i] == 0) throw std::invalid_argument(std::string(P) + " alpha must not be zero.");
+        const double S = e1[i]->scale() * e2[i]->scale();
+        if (addend[i]) {
+            const Ciphertext& ad = *addend[i];
+            check_no_seed(P, ad); check_on_device(P, context_, ad);
+            if (!ad.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Ciphertext must be in NTT form.");
+            get_context_data(P, ad.parms_id());
+            if (ad.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " The addend must have two polynomials.");
+            if (ad.coeff_modulus_size() < L) throw std::invalid_argument(std::string(P) + " The addend sits at a lower level than the operands.");
+            if (!std::isfinite(gamma[i])) throw std::invalid_argument(std::string(P) + " gamma is not finite.");
+            weight[i] = scaled_integer(P, gamma[i], S / ad.scale(), 62, true);
+            c[i] = ad.data().raw_pointer(); c_nmod[i] = static_cast<uint32_t>(ad.coeff_modulus_size());
+        }
+        if (!std::isfinite(constant[i])) throw std::invalid_argument(std::string(P) + " The constant is not finite.");
+        konst[i] = scaled_integer(P, constant[i], S, 126);
+        a[i] = e1[i]->data().raw_pointer(); b[i] = e2[i]->data().raw_pointer();
+    }
+    auto cd = get_context_data(P, e1[0]->parms_id());
+    std::vector<uint64_t> al(batch * L), w(batch * L), k(batch * L);
+    for (size_t i = 0; i < batch; i++)
+        for (uint32_t l = 0; l < L; l++) {
+            const uint64_t q = cd->parms().coeff_modulus()[l].value();
+            al[i * L + l] = signed_residue(alpha[i], q); w[i * L + l] = signed_residue(weight[i], q); k[i * L + l] = signed_residue(konst[i], q);
+        }
+    const size_t n = e1[0]->poly_modulus_degree(), words = 2 * (size_t)(L - 1) * n;
+    utils::DynamicArray block(batch * words, true, pool);
+    const size_t bytes = troyn_ckks_multiply_affine_relinearize_rescale_workspace_bytes(context_->plan(), L, batch);
+    utils::DynamicArray ws((bytes + 15) / 8, true, pool);
+    std::vector<Ciphertext> out(batch);
+    const detail::StepEnv env = on_current_stream(pool, true);
+    {
+        detail::LaunchGate gate(env.gated);
+        env.check(troyn_ckks_multiply_affine_relinearize_rescale(context_->plan(), L, a.data(), b.data(), c.data(), c_nmod.data(), al.data(), w.data(), k.data(), keys.data(),
+                                                                 block.raw_pointer(), ws.raw_pointer(), bytes, batch, env.stream));
+    }
+    for (size_t i = 0; i < batch; i++) {
+        out[i] = Ciphertext::like(*e1[i], 2, L - 1, false, pool);
+        out[i].parms_id() = next; out[i].scale() = out_scale[i]; out[i].is_ntt_form() = true;
+        detail::hip_check(hipMemcpyAsync(out[i].data().raw_pointer(), block.raw_pointer() + i * words, words * 8, hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
+    }
+    destination = std::move(out);
+}
+
+void Evaluator::evaluate_chebyshev(const Ciphertext& x, const std::vector<double>& coefficients, double half_width, const RelinKeys& relin_keys, Ciphertext& destination,
+                                   MemoryPoolHandle pool, const char* P, size_t levels_after) const {
+    if (context_->key_context_data().value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(std::string(P) + " CKKS only.");
+    check_no_seed(P, x); check_on_device(P, context_, x);
+    if (!x.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Ciphertext must be in NTT form.");
+    if (x.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " The ciphertext must have two polynomials.");
+    if (!(half_width > 0.0) || !std::isfinite(half_width)) throw std::invalid_argument(std::string(P) + " The half width must be positive and finite.");
+    const size_t d = ps_degree(P, coefficients);
+    if (d > 127) throw std::invalid_argument(std::string(P) + " Degrees above 127 are not supported.");
+    size_t k, g, rec_depth;
+    ps_schedule(d, k, g, rec_depth);
+    // the leaf coefficients: T_i T_jk = (T_(jk+i) + T_(jk-i)) / 2, from the top block down
+    std::vector<double> r(std::max<size_t>(g * k, 2), 0.0), u(std::max<size_t>(g * k, 2), 0.0);
+    for (size_t m = 0; m <= d; m++) r[m] = coefficients[m];
+    for (size_t j = g - 1; j >= 1; j--) {
+        u[j * k] = r[j * k];
+        for (size_t i = 1; i < k; i++) { u[j * k + i] = 2.0 * r[j * k + i]; r[j * k - i] -= r[j * k + i]; }
+    }
+    for (size_t i = 0; i < std::max<size_t>(k, 2); i++) u[i] = r[i];
+    // y = x / K: the same payload at K times the scale
+    Ciphertext y = x.clone(pool);
+    y.scale() = x.scale() * half_width;
+    // the ladder, built at the first request (after the level check): one batched step per depth
+    std::map<size_t, Ciphertext> T;
+    bool built = false;
+    auto split = [](size_t m, size_t& a, size_t& b, size_t& c) { a = 1; while (a * 2 < m) a *= 2; b = m - a; c = 2 * a - m; };
+    auto build = [&]() {
+        std::set<size_t> want;
+        std::vector<size_t> todo;
+        for (size_t i = 2; i < k; i++) todo.push_back(i);
+        for (size_t j = 1; j < g; j++) todo.push_back(j * k);
+        while (!todo.empty()) {
+            const size_t m = todo.back(); todo.pop_back();
+            if (m <= 1 || !want.insert(m).second) continue;
+            size_t a, b, c; split(m, a, b, c);
+            todo.push_back(a); todo.push_back(b); todo.push_back(c);
+        }
+        auto clog2 = [](size_t v) { size_t q = 0; while ((size_t(1) << q) < v) q++; return q; };
+        auto at = [&](size_t m) -> const Ciphertext& { return m == 1 ? y : T.at(m); };
+        for (size_t dep = 1; dep <= 7; dep++) {
+            std::vector<size_t> ms;
+            for (size_t m : want) if (clog2(m) == dep) ms.push_back(m);
+            if (ms.empty()) continue;
+            const size_t cnt = ms.size();
+            std::vector<Ciphertext> lowered(cnt), out;
+            std::vector<const Ciphertext*> e1(cnt), e2(cnt), ad(cnt, nullptr);
+            std::vector<int64_t> alpha(cnt, 2);
+            std::vector<double> gamma(cnt, -1.0), konst(cnt, 0.0);
+            for (size_t t = 0; t < cnt; t++) {
+                size_t a, b, c; split(ms[t], a, b, c);
+                e1[t] = &at(a); e2[t] = &at(b);
+                if (e2[t]->coeff_modulus_size() > e1[t]->coeff_modulus_size()) { mod_switch_to(*e2[t], e1[t]->parms_id(), lowered[t], pool); e2[t] = &lowered[t]; }
+                if (c == 0) konst[t] = -1.0; else ad[t] = &at(c);
+            }
+            multiply_affine_relinearize_rescale_batched(e1, e2, alpha, ad, gamma, konst, relin_keys, out, pool, P);
+            for (size_t t = 0; t < cnt; t++) T.emplace(ms[t], std::move(out[t]));
+        }
+        built = true;
+    };
+    std::function<const Ciphertext&(size_t)> basis = [&](size_t m) -> const Ciphertext& {
+        if (m == 1) return y;
+        // deferred on purpose: paterson_stockmeyer asks for a basis element only after its level check, so a ciphertext with too few levels is
+        // refused with that message before any step of the ladder runs (and fails on its own last level)
+        if (!built) build();
+        return T.at(m);
+    };
+    paterson_stockmeyer(P, y, d, levels_after, basis, [&](size_t j, size_t i) { return u[j * k + i]; }, relin_keys, destination, pool);
+}
+
+void Evaluator::eval_mod(const Ciphertext& encrypted, const RelinKeys& relin_keys, double half_width, size_t degree, size_t double_angles, Ciphertext& destination,
+                         MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::eval_mod]";
+    if (degree < 1 || degree > 127) throw std::invalid_argument(std::string(P) + " The degree must be in 1 .. 127.");
+    if (double_angles > 16) throw std::invalid_argument(std::string(P) + " More than 16 double-angle steps.");
+    if (!(half_width > 0.0) || !std::isfinite(half_width)) throw std::invalid_argument(std::string(P) + " The half width must be positive and finite.");
+    // the Chebyshev interpolant of f(y) = cos(2 pi (K y - 1/4) / 2^r) on [-1, 1] from the degree + 1 Chebyshev nodes
+    const size_t nodes = degree + 1;
+    const double pi = 3.14159265358979323846, div = std::ldexp(1.0, static_cast<int>(double_angles));
+    std::vector<double> f(nodes), coeffs(nodes, 0.0);
+    for (size_t t = 0; t < nodes; t++) f[t] = std::cos(2.0 * pi * (half_width * std::cos(pi * (t + 0.5) / nodes) - 0.25) / div);
+    for (size_t j = 0; j < nodes; j++) {
+        double s = 0.0;
+        for (size_t t = 0; t < nodes; t++) s += f[t] * std::cos(pi * j * (t + 0.5) / nodes);
+        coeffs[j] = s * (j == 0 ? 1.0 : 2.0) / nodes;
+    }
+    Ciphertext ct;
+    evaluate_chebyshev(encrypted, coeffs, half_width, relin_keys, ct, pool, P, double_angles);
+    for (size_t s = 0; s < double_angles; s++) {
+        std::vector<Ciphertext> next;
+        multiply_affine_relinearize_rescale_batched({&ct}, {&ct}, {2}, {nullptr}, {0.0}, {-1.0}, relin_keys, next, pool, P);
+        ct = std::move(next[0]);
+    }
+    ct.scale() *= 2.0 * pi;      // the slots read sin(2 pi x) / (2 pi)
+    destination = std::move(ct);
 }
 
 

@@ -28,6 +28,8 @@
 #include <cstring>
 #include <iosfwd>
 #include <ostream>
+#include <functional>
+#include <set>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1558,6 +1560,64 @@ public:
     void mod_raise_batched(const std::vector<const Ciphertext*>& encrypted, const std::vector<Ciphertext*>& destination, std::optional<ParmsID> parms_id = std::nullopt,
                            MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
 
+    // ADDITION to the reference's interface: the Chebyshev basis on a fused product-plus-affine step, and EvalMod (CKKS).  (The block above keeps
+    //   the power basis; what it calls out of scope is built here.)
+    //   multiply_affine_relinearize_rescale: destination = rescale_to_next(relinearize(alpha * e1 * e2 + gamma * addend + constant)) as ONE library
+    //   call (troyn_ckks_multiply_affine_relinearize_rescale, include/troyn.h): the affine part joins the three-polynomial product before the
+    //   one key switch and the one division.  alpha is a non-zero signed integer.  With S = e1.scale() * e2.scale(), the addend's integer weight
+    //   is gamma * (S / addend.scale()), computed in double in that order and rounded half away from zero; a magnitude of 2^62 or more is
+    //   std::invalid_argument (linear_combinations' rule).  The constant's integer is constant * S, formed in 128 bits before the per-limb
+    //   reduction (as the leaf constants of evaluate_polynomial).  The result's scale is S / q_last, set exactly.  The addend (two polynomials,
+    //   NTT form) may sit at a higher level than e1 and e2: its limbs above theirs are ignored; it may be null, then gamma is ignored.  Every
+    //   refusal of multiply, relinearize and rescale_to_next applies, its message prefixed with this method's name.  The _batched form takes
+    //   one entry per item in every list (addend entries may be null); all items share one parms_id and go into ONE call.
+    //   evaluate_chebyshev: destination = p(encrypted), p(x) = SUM_m coefficients[m] T_m(x / K) for slots in [-K, K], K = half_width > 0.
+    //   The change of variable costs no level: the working ciphertext is `encrypted` with its scale multiplied by K (choose the scale so
+    //   that scale * K is close to the primes).  The schedule is evaluate_polynomial's: the same k and g, leaves by
+    //   troyn_scalar_weighted_sums, ONE troyn_ckks_multiply_accumulate_relinearize_rescale over the g - 1 pairs; the basis T_1 .. T_(k-1),
+    //   T_k, T_2k, .. replaces the powers.  The leaf coefficients u_(j,i) come from T_i T_jk = (T_(jk+i) + T_(jk-i)) / 2, solved from the top
+    //   block down on the host.  Every T_m with m > 1 is one step of the method above: a power of two is 2 T_(m/2)^2 - 1, any other m is
+    //   2 T_a T_(m-a) - T_(2a-m) with a the largest power of two below m; all T_m of one depth go into one batched call;
+    //   depth(T_m) = ceil(log2 m); total depth as stated for evaluate_polynomial.  Degrees up to 127.  The result's scale is the working
+    //   scale, encrypted.scale() * K.  Refusals as evaluate_polynomial, and degree > 127, and a half_width that is not positive and finite.
+    //   eval_mod: for slots x = m + I with integer |I| <= K - 1 and small |m|, the result's slots are sin(2 pi x) / (2 pi), about m.  The
+    //   Chebyshev interpolant of cos(2 pi (K y - 1/4) / 2^r) on y in [-1, 1] of the given degree is built on the host in double from the
+    //   Chebyshev nodes and evaluated by evaluate_chebyshev; r = double_angles steps cos 2t = 2 cos^2 t - 1 follow through the method above
+    //   (e1 = e2, alpha = 2, no addend, constant -1); the factor 1 / (2 pi) goes into the result's scale and costs no level.
+    //   Depth: depth(evaluate_chebyshev) + r.
+    // Call combining does not take part: these methods always launch directly.
+    void multiply_affine_relinearize_rescale(const Ciphertext& e1, const Ciphertext& e2, int64_t alpha, const Ciphertext* addend, double gamma, double constant,
+                                             const RelinKeys& relin_keys, Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d;
+        multiply_affine_relinearize_rescale_batched({&e1}, {&e2}, {alpha}, {addend}, {gamma}, {constant}, relin_keys, d, pool, "[Evaluator::multiply_affine_relinearize_rescale]");
+        destination = std::move(d[0]);
+    }
+    Ciphertext multiply_affine_relinearize_rescale_new(const Ciphertext& e1, const Ciphertext& e2, int64_t alpha, const Ciphertext* addend, double gamma, double constant,
+                                                       const RelinKeys& relin_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; multiply_affine_relinearize_rescale(e1, e2, alpha, addend, gamma, constant, relin_keys, d, pool); return d;
+    }
+    void multiply_affine_relinearize_rescale_batched(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const std::vector<int64_t>& alpha,
+                                                     const std::vector<const Ciphertext*>& addend, const std::vector<double>& gamma, const std::vector<double>& constant,
+                                                     const RelinKeys& relin_keys, std::vector<Ciphertext>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool(),
+                                                     const char* method = "[Evaluator::multiply_affine_relinearize_rescale_batched]") const;
+    void evaluate_chebyshev(const Ciphertext& encrypted, const std::vector<double>& coefficients, double half_width, const RelinKeys& relin_keys, Ciphertext& destination,
+                            MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        evaluate_chebyshev(encrypted, coefficients, half_width, relin_keys, destination, pool, "[Evaluator::evaluate_chebyshev]");
+    }
+    Ciphertext evaluate_chebyshev_new(const Ciphertext& encrypted, const std::vector<double>& coefficients, double half_width, const RelinKeys& relin_keys,
+                                      MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; evaluate_chebyshev(encrypted, coefficients, half_width, relin_keys, d, pool); return d;
+    }
+    void eval_mod(const Ciphertext& encrypted, const RelinKeys& relin_keys, double half_width, size_t degree, size_t double_angles, Ciphertext& destination,
+                  MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext eval_mod_new(const Ciphertext& encrypted, const RelinKeys& relin_keys, double half_width, size_t degree, size_t double_angles,
+                            MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; eval_mod(encrypted, relin_keys, half_width, degree, double_angles, d, pool); return d;
+    }
+    // (the form that names the calling method in its refusals; `levels_after`: levels the caller still needs below the result)
+    void evaluate_chebyshev(const Ciphertext& encrypted, const std::vector<double>& coefficients, double half_width, const RelinKeys& relin_keys, Ciphertext& destination,
+                            MemoryPoolHandle pool, const char* method, size_t levels_after = 0) const;
+
     // ADDITION to the reference's interface: the BFV inner product.  destination = the BEHZ multiply (evaluator.cu:29-116) with the tensor
     //   products of all pairs summed BEFORE its scale-down: one floor (and, in the relinearizing form, one key switch,
     //   evaluator_keyswitching.cu:119-144) for the whole sum (troyn_bfv_multiply_accumulate[_relinearize], include/troyn.h).  It decrypts to
@@ -2005,6 +2065,10 @@ private:
     // argument checks + result metadata of multiply -> relinearize -> rescale_to_next; false: the operands do not take the fused entry
     bool multiply_relinearize_rescale_prepare(const Ciphertext& e1, const Ciphertext& e2, const RelinKeys& relin_keys, uint32_t& L, ParmsID& next_parms_id, double& scale,
                                               std::vector<const uint64_t*>& key_ptrs) const;
+    // the basis-independent part of the fixed Paterson-Stockmeyer schedule (evaluate_polynomial, evaluate_chebyshev): the level check, the leaves
+    // SUM_i u(j, i) basis(i) and the recombination SUM_j leaf_j basis(jk); basis(m) for m >= 1 is asked for only after the level check
+    void paterson_stockmeyer(const char* P, const Ciphertext& x, size_t d, size_t extra_levels, const std::function<const Ciphertext&(size_t)>& basis,
+                             const std::function<double(size_t, size_t)>& u, const RelinKeys& relin_keys, Ciphertext& destination, MemoryPoolHandle pool) const;
     // multiply_prepare's checks for one two-polynomial CKKS / BGV pair of a sum, without the result object; the product's scale and correction factor
     void multiply_accumulate_pair_checks(const Ciphertext& e1, const Ciphertext& e2, SchemeType scheme, double& scale, uint64_t& correction_factor) const;
     void bfv_multiply_accumulate_prepare(const char* P, const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2,
