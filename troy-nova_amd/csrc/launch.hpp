@@ -74,6 +74,10 @@ void launch_mrr_quartet(unsigned log_n, size_t batch, const NttArgs& sp, const N
 void launch_mrr_quartet_load(unsigned log_n, size_t groups, const NttArgs& iv, const NttArgs& fw, hipStream_t s, bool f64);
 // the same tail on whole-limb tiles for the batches that fill the chip (troyn_mrr_tail.hip; log_n = 14, all-FP64 chains): one launch for steps (3)-(5)
 void launch_mrr_tail(unsigned log_n, size_t batch, const NttArgs& sp, const NttArgs& la, const NttArgs& ta, hipStream_t s);
+// step (1) of the same chain for the same class on half-limb tiles, two workgroups per CU (troyn_mulpair_half.hip; log_n = 14, all-FP64 chains);
+// false: no kernel for this size
+struct MulpairHalfArgs;
+bool launch_mulpair_half(unsigned log_n, size_t batch, const MulpairHalfArgs& a, hipStream_t s);
 // first-generation fused key-switch inner product (ks_mac_kernel)
 inline bool launch_ks_mac(unsigned log_n, bool f64, const NttArgs& a, const KeyPtrs& kp, size_t blocks, const LaunchCtx& lc) {
     return in_ntt_unit(log_n, f64, [&](auto u) { return decltype(u)::ks_mac(log_n, a, kp, blocks, lc); });

@@ -26,6 +26,7 @@
 #include "ntt_kernels.hpp"
 #include "ksmac_kernels.hpp"
 #include "ksmaci_kernels.hpp"
+#include "mulpair_half_kernels.hpp"
 #include "poly_kernels.hpp"
 #include "hoist_kernels.hpp"
 #include "ckks_kernels.hpp"
@@ -248,10 +249,11 @@ struct TroynOptions {
     bool ntt_overlap_off = false;    // TROYN_NTT_OVERLAP=0: the per-class launches of a chain with wide moduli run one after the other on the caller's stream
     bool ntt_small_two_pass_off = false;   // TROYN_NTT_SMALL_TWO_PASS=0
     int tensor_wgs = 8;              // TROYN_TENSOR_WGS=8|3|2
+    bool mulpair_half_off = false;   // TROYN_MULPAIR_HALF=0: step (1) of the fused chain keeps the whole-limb kernel at N = 16384 (mulpair_half_kernels.hpp)
 };
 static const char* const TROYN_OPTION_NAMES[] = {"TROYN_NTT_ARITH", "TROYN_NTT_SPLIT", "TROYN_BFV_TENSOR", "TROYN_KS_ORDER", "TROYN_KS_SPLIT", "TROYN_KS_TAIL", "TROYN_KS_MAC",
     "TROYN_KS_DIAG", "TROYN_KS_ROWS", "TROYN_KS_MAC_SHOUP", "TROYN_MRR_MIXED", "TROYN_MRR_SMALL", "TROYN_MRR", "TROYN_MRR_CHUNK", "TROYN_MRR_STREAMS", "TROYN_BEHZ", "TROYN_BEHZ_BASE", "TROYN_BEHZ_LIFT",
-    "TROYN_PLAIN_MAC", "TROYN_NTT_HALF", "TROYN_NTT_SMALL_TWO_PASS", "TROYN_TENSOR_WGS", "TROYN_NTT_OVERLAP"};
+    "TROYN_PLAIN_MAC", "TROYN_NTT_HALF", "TROYN_NTT_SMALL_TWO_PASS", "TROYN_TENSOR_WGS", "TROYN_NTT_OVERLAP", "TROYN_MULPAIR_HALF"};
 // value == nullptr or "": the option's default.  Returns 1 = applied, 0 = unknown name, -1 = a value this option does not have (nothing is changed:
 // a misspelt value must not silently select a variant -- TROYN_TENSOR_WGS=foo used to parse as 0 and pick the two-workgroup kernel).
 static int option_apply(TroynOptions& o, const char* name, const char* value) {
@@ -296,6 +298,7 @@ static int option_apply(TroynOptions& o, const char* name, const char* value) {
     else if (n == "TROYN_NTT_HALF") t.ntt_half = num(0, 0xffff, d.ntt_half);
     else if (n == "TROYN_NTT_SMALL_TWO_PASS") t.ntt_small_two_pass_off = num(0, 1, 1) == 0;
     else if (n == "TROYN_NTT_OVERLAP") t.ntt_overlap_off = num(0, 1, 1) == 0;
+    else if (n == "TROYN_MULPAIR_HALF") t.mulpair_half_off = num(0, 1, 1) == 0;
     else if (n == "TROYN_TENSOR_WGS") { t.tensor_wgs = num(2, 8, d.tensor_wgs); if (t.tensor_wgs != 8 && t.tensor_wgs != 3 && t.tensor_wgs != 2) bad = true; }
     else return 0;
     if (bad) return -1;
@@ -330,6 +333,9 @@ struct troyn_plan {
     // ksmaci_kernel (same sizes, any modulus): the same two copies as (operand, quotient) pairs
     ulonglong2* d_fwd_r1i = nullptr;      // [K][N/1024][32]
     ulonglong2* d_fwd_r2i = nullptr;      // [K][N], lane-interleaved (ksm_perm)
+    // mulpair_half_kernel (N = 16384, moduli < 2^50): the inverse twiddles in the order ITS register rounds read them
+    double* d_inv_r1 = nullptr;           // [K][N/1024][32]
+    double* d_inv_r2 = nullptr;           // [K][N], lane-interleaved (ksm_perm)
 };
 
 // One host thread may drive several devices (the reference calls utils::set_device before every launch, fgk/ntt_grouped.cu:286):
@@ -441,6 +447,27 @@ static void round_vectors(const troyn_plan* p, Conv conv, std::vector<T>& r1, st
     }
 }
 
+// The same two copies of the INVERSE twiddles for mulpair_half_kernel, whose rounds walk ksmac2's backwards: round A keeps tile bits [0, 5) in
+// registers (r2: per thread T = index >> 5), round B bits [5, 10) (r1: per value th of the index bits above bit 9).  Slot (1 << lvl) + g holds the
+// twiddle of butterfly group g of register bit 4 - lvl: Gentleman-Sande layer of index bit `bit` = forward-numbered layer l = log_n - 1 - bit,
+// table entry n - (2 << l) + 1 + (index >> (bit + 1))  (ntt_pass_body).
+template <typename T, typename Conv>
+static void inverse_round_vectors(const troyn_plan* p, Conv conv, std::vector<T>& r1, std::vector<T>& r2) {
+    const size_t K = p->K, n = p->n, r1n = (n >> 10) * 32;
+    r1.assign(K * r1n, conv(0, host::Shoup{0, 0}));
+    r2.assign(K * n, conv(0, host::Shoup{0, 0}));
+    for (size_t i = 0; i < K; i++) {
+        const auto& iv = p->tables[i].inv;
+        for (unsigned s = 1; s < 32; s++) {
+            unsigned lvl = 0;
+            while ((2u << lvl) <= s) lvl++;
+            const unsigned g = s - (1u << lvl);
+            for (size_t th = 0; th < (n >> 10); th++) r1[i * r1n + th * 32 + s] = conv(i, iv[n - ((n >> 9) << lvl) + 1 + (th << lvl) + g]);
+            for (size_t T_ = 0; T_ < (n >> 5); T_++) r2[i * n + ksm_perm((unsigned)(T_ * 32 + s))] = conv(i, iv[n - ((n >> 4) << lvl) + 1 + (T_ << lvl) + g]);
+        }
+    }
+}
+
 static int plan_upload(troyn_plan* p) {
     const size_t K = p->K, n = p->n;
     std::vector<DevModulus> mods(K);
@@ -485,6 +512,11 @@ static int plan_upload(troyn_plan* p) {
         round_vectors(p, pair, r1i, r2i);
         if ((rc = upload_vector(&p->d_fwd_r1i, r1i)) || (rc = upload_vector(&p->d_fwd_r2i, r2i))) return rc;
     }
+    if (p->log_n == 14) {
+        std::vector<double> r1, r2;
+        inverse_round_vectors(p, f64, r1, r2);
+        if ((rc = upload_vector(&p->d_inv_r1, r1)) || (rc = upload_vector(&p->d_inv_r2, r2))) return rc;
+    }
     return TROYN_OK;
 }
 
@@ -500,6 +532,8 @@ static void plan_free(troyn_plan* p) {
     if (p->d_fwd_r2) (void)hipFree(p->d_fwd_r2);
     if (p->d_fwd_r1i) (void)hipFree(p->d_fwd_r1i);
     if (p->d_fwd_r2i) (void)hipFree(p->d_fwd_r2i);
+    if (p->d_inv_r1) (void)hipFree(p->d_inv_r1);
+    if (p->d_inv_r2) (void)hipFree(p->d_inv_r2);
     delete p;
 }
 
@@ -2301,9 +2335,26 @@ struct MrrCall {
     }
 };
 
+// the launches mrr_tail_kernel serves: N = 16384, an all-FP64 chain, a batch beyond the small-batch forms (mrr_chain's choice of the tail)
+static bool mrr_whole_limb_class(const MrrCall& c) {
+    const troyn_plan* p = c.p;
+    return c.all_f64 && p->log_n == 14 && !p->opt.mrr_small_off && !small_tail_wanted(p, c.batch * 2 * (size_t)(c.L - 1));
+}
+
 // (1) digits = INTT(c2), c2 = a1 (.) b1 formed in the loader (kernel_dyadic_convolute's third output + transform_from_ntt, :817-821)
 static int mrr_digits(const MrrCall& c) {
     const troyn_plan* p = c.p; const unsigned L = c.L, n = p->n;
+    if (mrr_whole_limb_class(c) && !p->opt.mulpair_half_off && p->d_inv_r2) {
+        // the class of the merged whole-limb tail: half-limb tiles, two workgroups per CU (troyn_mulpair_half.hip; TROYN_MULPAIR_HALF=0: the kernel below)
+        MulpairHalfArgs x;
+        x.a1 = c.a + c.ct_p(); x.b1 = c.b + c.ct_p(); x.in_bstride = c.ct_b();
+        x.out = c.ws + c.w.digits; x.out_bstride = (long long)L * n;
+        x.mods = p->d_mods; x.tw = p->d_inv_f64; x.tw_r1 = p->d_inv_r1; x.tw_r2 = p->d_inv_r2;
+        x.L = L; x.store_f64 = 1u;          // all-FP64: the digits go to ksmac2 as doubles
+        if (!launch_mulpair_half(p->log_n, c.batch, x, c.s)) return fail(TROYN_E_INVALID, "[troyn_ckks_multiply_relinearize_rescale] batch too large for one launch");
+        LAUNCH_CHECK();
+        return TROYN_OK;
+    }
     return c.for_runs(L, 1, [&](unsigned j0, unsigned j1, hipStream_t rs) {
         NttArgs x = contiguous_args(p, c.a + (size_t)j0 * n, c.ws + c.w.digits + (size_t)j0 * n, 1, j1 - j0, j0, j1 - j0, TROYN_IDX_COMPONENTWISE, 0);
         x.in_bstride = c.ct_b(); x.in_pstride = c.ct_p();                  // (the loader reads mul_a / mul_b; `in` only anchors the shapes)
@@ -2421,7 +2472,7 @@ static int mrr_chain(const troyn_plan* p, uint32_t L, const KsRows& rows, const 
     if ((rc = mrr_digits(c))) return rc;
     if ((rc = mrr_inner_product(c, rows, kf, ki, raw))) return rc;
     if (c.all_f64 && (small_tail_wanted(p, batch * 2 * (size_t)(L - 1)) || (p->log_n == 15 && !p->opt.mrr_small_off))) return mrr_tail_merged(c, true);
-    if (c.all_f64 && p->log_n == 14 && !p->opt.mrr_small_off) return mrr_tail_merged(c, false);
+    if (mrr_whole_limb_class(c)) return mrr_tail_merged(c, false);
     // (3) s = INTT of the special-prime rows (:991-996, only the two rows the NTT-form tail needs)
     {
         NttArgs x = special_rows_args(p, c.poly_prod(), ws + w.spec_intt, L);
