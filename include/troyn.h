@@ -571,6 +571,39 @@ int troyn_bgv_relinearize(const troyn_bgv* key_level, uint32_t L, const uint64_t
                           size_t workspace_bytes, size_t batch, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fused BGV chain: Evaluator::multiply (bgv_multiply, evaluator.cu:150-173) -> Evaluator::relinearize -> Evaluator::mod_switch_to_next
+ * of `batch` ciphertext pairs in one call.  An ADDITION to the reference's surface (as the fused CKKS chain above).
+ *   key_level  troyn_bgv_create(plan, n_moduli, t), as for troyn_bgv_switch_key
+ *   level      troyn_bgv_create(plan, L, t) on the same plan with the same t; L is taken from it, 2 <= L <= n_moduli - 1
+ *   a, b       [batch][2][L][N] NTT form, canonical residues;  keys: L device pointers to u64[2][K][N], as for troyn_bgv_relinearize
+ *   out        [batch][2][L-1][N] NTT form
+ * Contract: the output words equal, word for word, those of these three calls in order:
+ *   1. troyn_dyadic_convolute(a, b) on limbs 0 .. L-1
+ *   2. troyn_bgv_relinearize(key_level, L, ...)
+ *   3. troyn_bgv_mod_t_and_divide_q_last_ntt(level, pcount = 2)
+ * As with the stand-alone modulus switch the correction-factor bookkeeping stays with the caller, who multiplies the product's factor
+ * by troyn_bgv_inv_q_last_mod_t(level).
+ * Derivation (exact integer arithmetic modulo each q_j; qk the special prime, ql = q_{L-1} the dropped one, c = a (x) b):
+ *   P        the key-switch inner product of c_2;   s = INTT of P's special row
+ *   dk_j(s)  = [-s qk^-1 mod t]_{q_j} qk + [s]_{q_j}
+ *   Q_j      = P_j qk^-1 + c_j
+ *   l        = INTT(Q_{L-1}) - dk_{L-1}(s) qk^-1 mod q_{L-1}, canonical
+ *   dl_j(l)  = [-l ql^-1 mod t]_{q_j} ql + [l]_{q_j}
+ *   out_j    = (Q_j - NTT_j(dk_j(s) qk^-1 + dl_j(l))) ql^-1 mod q_j,  j < L-1
+ * By linearity of the transforms both corrections are added in coefficient form: one forward transform of 2 (L-1) rows per item where
+ * the three calls take 2 L and then 2 (L-1); the relinearized ciphertext and c_0, c_1 never reach memory (bgv_chain_kernels.hpp).
+ * TROYN_E_INVALID: a null handle or pointer, a misaligned pointer (16 bytes), handles on different plans or with different t, key_level
+ * not at the key level, L outside [2, n_moduli - 1], a null key entry, `out` overlapping a or b.  TROYN_E_MODULUS: either handle lacks
+ * its inverse mod t ("[RNSTool::RNSTool] Unable to invert q[last] mod t.").  TROYN_E_WORKSPACE: a workspace below the query.
+ * batch == 0 returns TROYN_OK, launches nothing and looks at none of a, b, out and the workspace (all may be null).  Everything is
+ * enqueued on the caller's stream; the entry does not synchronise and does not touch the default stream.
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_bgv_multiply_relinearize_mod_switch_workspace_bytes(const troyn_bgv* key_level, uint32_t L, size_t batch);
+int troyn_bgv_multiply_relinearize_mod_switch(const troyn_bgv* key_level, const troyn_bgv* level, const uint64_t* a, const uint64_t* b,
+                                              const uint64_t* const* keys, uint64_t* out, void* workspace, size_t workspace_bytes,
+                                              size_t batch, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Ring-2^k polynomial encoder (src/app/bfv_ring2k.{h,cu}: PolynomialEncoderRNSHelper<T>, T = uint32_t / uint64_t / uint128_t):
  * plaintext modulus t = 2^k outside the context's own plain modulus.  One handle per level (first L primes), k and element width.
  *   troyn_ring2k_scale_up     scale_up (:299-360): src elements [count] -> out u64[L][N] = round(Q/t * m), zero beyond `count`

@@ -21,6 +21,7 @@
 #include "launch.hpp"
 #include "crypto_kernels.hpp"
 #include "bgv_kernels.hpp"
+#include "bgv_chain_kernels.hpp"
 #include "ring2k_kernels.hpp"
 #include "host_math.hpp"
 #include "ntt_kernels.hpp"
@@ -2858,6 +2859,102 @@ extern "C" int troyn_bgv_relinearize(const troyn_bgv* key_level, uint32_t L, con
     const size_t pc = (size_t)L * plan->n;
     return switch_key_impl(plan, L, 0, 1, (const u64*)ct3 + 2 * pc, 3 * pc, keys, TROYN_ASSIGN_OVERWRITE, (u64*)out2, (const u64*)ct3, 3 * pc, workspace, workspace_bytes,
                            batch, (hipStream_t)stream, &tail);
+}
+
+// ---- fused BGV chain (an addition to the reference's surface; include/troyn.h, bgv_chain_kernels.hpp) ----
+// multiply -> relinearize -> mod_switch_to_next with ONE forward transform per output limb: the key switch's and the modulus switch's mod-t
+// corrections are added in coefficient form.  The digit decomposition and the inner product are the key switch's own steps on c_2.
+struct BgvChainLayout {
+    KsLayout ks;
+    size_t c2, spec, q_last, q_last_intt, delta, delta_ntt, total;      // element offsets
+};
+static BgvChainLayout bgv_chain_layout(const troyn_plan* p, unsigned L, size_t batch) {
+    const size_t n = p->n;
+    BgvChainLayout w;
+    w.ks = ks_layout(p, L, batch);
+    size_t off = w.ks.total;
+    w.c2 = off;          off += batch * L * n;                       // a1 . b1, the key switch's target
+    w.spec = off;        off += batch * 2 * n;                       // s: INTT of the special rows
+    w.q_last = off;      off += batch * 2 * n;                       // Q_{L-1}
+    w.q_last_intt = off; off += batch * 2 * n;
+    w.delta = off;       off += batch * 2 * (size_t)(L - 1) * n;     // d_j in coefficient form
+    w.delta_ntt = off;   off += batch * 2 * (size_t)(L - 1) * n;
+    w.total = off;
+    return w;
+}
+
+static bool bgv_chain_level_ok(const troyn_bgv* key_level, uint32_t L) {
+    return key_level && key_level->plan && key_level->plan->K >= 3 && L >= 2 && L <= key_level->plan->K - 1;
+}
+
+extern "C" size_t troyn_bgv_multiply_relinearize_mod_switch_workspace_bytes(const troyn_bgv* key_level, uint32_t L, size_t batch) {
+    if (!bgv_chain_level_ok(key_level, L)) return 0;
+    return bgv_chain_layout(key_level->plan, L, batch).total * sizeof(u64);
+}
+
+extern "C" int troyn_bgv_multiply_relinearize_mod_switch(const troyn_bgv* key_level, const troyn_bgv* level, const uint64_t* a_, const uint64_t* b_,
+                                                         const uint64_t* const* keys, uint64_t* out_, void* workspace, size_t workspace_bytes,
+                                                         size_t batch, troyn_stream_t stream) {
+    select_device(key_level);
+    const std::string P = "[troyn_bgv_multiply_relinearize_mod_switch]";
+    if (!key_level || !level || !keys) return fail(TROYN_E_INVALID, P + " null argument");
+    const troyn_plan* p = key_level->plan;
+    if (level->plan != p || level->t != key_level->t) return fail(TROYN_E_INVALID, P + " the two handles differ in plan or plain modulus");
+    const unsigned K = p->K, n = p->n, L = level->L;
+    if (K < 2) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] Keyswitching is not supported.");
+    if (key_level->L != K) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] BGV key switching needs the key level's constants");
+    if (L > K - 1) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] Invalid target size.");
+    if (L < 2) return fail(TROYN_E_INVALID, "[Evaluator::mod_switch_scale_to_next_internal] Next context data is not set.");
+    if (!key_level->can_divide || !level->can_divide) return fail(TROYN_E_MODULUS, "[RNSTool::RNSTool] Unable to invert q[last] mod t.");
+    KeyPtrs kp;
+    std::memset(&kp, 0, sizeof(kp));
+    for (unsigned j = 0; j < L; j++) {
+        if (!keys[j]) return fail(TROYN_E_INVALID, "[Evaluator::switch_key_inplace_internal] null key pointer");
+        kp.p[j] = (const u64*)keys[j];
+    }
+    if (batch == 0) return TROYN_OK;
+    if (!a_ || !b_ || !out_ || !workspace) return fail(TROYN_E_INVALID, P + " null argument");
+    if (((uintptr_t)a_ | (uintptr_t)b_ | (uintptr_t)out_ | (uintptr_t)workspace) & 15) return fail(TROYN_E_INVALID, P + " misaligned pointer");
+    const BgvChainLayout w = bgv_chain_layout(p, L, batch);
+    if (workspace_bytes < w.total * sizeof(u64)) return fail(TROYN_E_WORKSPACE, P + " workspace too small");
+    {   // `out` is written while a and b are still being read (the finish kernel forms c_0 and c_1 from them)
+        const uintptr_t o0 = (uintptr_t)out_, o1 = o0 + batch * 2 * (size_t)(L - 1) * n * sizeof(u64);
+        const size_t in_bytes = batch * 2 * (size_t)L * n * sizeof(u64);
+        for (uintptr_t q : {(uintptr_t)a_, (uintptr_t)b_})
+            if (q < o1 && o0 < q + in_bytes) return fail(TROYN_E_INVALID, P + " out overlaps an input");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const u64* a = (const u64*)a_; const u64* b = (const u64*)b_;
+    u64* ws = (u64*)workspace;
+    const unsigned ch = chunks_pairs(n);
+    int rc;
+    if ((rc = check_rows(batch * 2 * (size_t)L, ch))) return rc;
+    // c_2 = a1 . b1; then steps (1)-(3) of the key switch on it, on the path every BGV key switch takes
+    hipLaunchKernelGGL(bgv_chain_c2_kernel, dim3((unsigned)(batch * L * ch)), dim3(POLY_BLOCK), 0, s, ch, p->d_mods, L, n, a, b, ws + w.c2);
+    LAUNCH_CHECK();
+    KsCall c{p, L, 0, true, ws + w.c2, (size_t)L * n, TROYN_ASSIGN_OVERWRITE, nullptr, nullptr, 0, ws, w.ks, batch, s, nullptr, ws + w.c2, (size_t)L * n};
+    const KsPath path = ks_path(p, L, batch, true, true);
+    if ((rc = ks_digits(c))) return rc;
+    if ((rc = ks_inner_product(c, kp, path))) return rc;
+    const u64* prod = ws + w.ks.poly_prod;
+    const ulonglong2* inv_k = p->d_inv_last + (size_t)K * K;
+    // s and INTT(Q_{L-1}): two rows per item each
+    if ((rc = launch_ntt(p, special_rows_args(p, prod, ws + w.spec, L), batch, true, s))) return rc;
+    hipLaunchKernelGGL(bgv_chain_last_row_kernel, dim3((unsigned)(batch * 2 * ch)), dim3(POLY_BLOCK), 0, s, ch, p->d_mods, L, n, prod, a, b, inv_k, ws + w.q_last);
+    LAUNCH_CHECK();
+    if ((rc = launch_ntt(p, contiguous_args(p, ws + w.q_last, ws + w.q_last_intt, 2, 1, L - 1, 1, TROYN_IDX_COMPONENTWISE, 0), batch, true, s))) return rc;
+    BgvChainDeltaArgs g;
+    g.mods = p->d_mods; g.inv_k = inv_k; g.t = key_level->t_mod;
+    g.inv_k_mod_t = key_level->inv_q_last_mod_t; g.inv_l_mod_t = level->inv_q_last_mod_t;
+    g.qk = p->moduli[K - 1]; g.ql = p->moduli[L - 1]; g.L = L; g.n = n;
+    hipLaunchKernelGGL(bgv_chain_delta_kernel, dim3((unsigned)(batch * 2 * ch)), dim3(POLY_BLOCK), 0, s, ch, g, ws + w.spec, ws + w.q_last_intt, ws + w.delta);
+    LAUNCH_CHECK();
+    // the ONE forward transform: 2 (L-1) rows per item
+    if ((rc = launch_ntt(p, contiguous_args(p, ws + w.delta, ws + w.delta_ntt, 2, L - 1, 0, L - 1, TROYN_IDX_COMPONENTWISE, 0), batch, false, s))) return rc;
+    hipLaunchKernelGGL(bgv_chain_finish_kernel, dim3((unsigned)(batch * (L - 1) * ch)), dim3(POLY_BLOCK), 0, s, ch, p->d_mods, L, n, prod, a, b, ws + w.delta_ntt,
+                       inv_k, p->d_inv_last + (size_t)L * K, (u64*)out_);
+    LAUNCH_CHECK();
+    return TROYN_OK;
 }
 
 // ---------------------------------------------------------------------------------------

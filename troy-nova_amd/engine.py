@@ -718,11 +718,12 @@ class Bgv:
     def inv_q_last_mod_t(self):
         return int(self.plan.lib.troyn_bgv_inv_q_last_mod_t(self.h))
 
-    def mod_t_and_divide_q_last_ntt(self, x, pcount):
+    def mod_t_and_divide_q_last_ntt(self, x, pcount, out=None):
         """x [batch][pcount][L][N] NTT form -> [batch][pcount][L-1][N]"""
         n, L = self.plan.n, self.L
         batch = x.numel() // (pcount * L * n)
-        out = torch.empty((batch, pcount, L - 1, n), dtype=torch.int64, device=x.device)
+        if out is None:
+            out = torch.empty((batch, pcount, L - 1, n), dtype=torch.int64, device=x.device)
         ws = self.plan.workspace(self.plan.lib.troyn_bgv_mod_switch_workspace_bytes(self.h, pcount, batch))
         capi.check(self.plan.lib.troyn_bgv_mod_t_and_divide_q_last_ntt(self.h, _ptr(x), pcount, _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
@@ -750,12 +751,26 @@ class Bgv:
         capi.check(plan.lib.troyn_bgv_switch_key(self.h, L, _ptr(target), plan._key_ptrs(keys, L), assign, _ptr(dest), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return dest
 
-    def relinearize(self, L, ct3, keys):
+    def relinearize(self, L, ct3, keys, out=None):
         plan = self.plan
         batch = ct3.numel() // (3 * L * plan.n)
-        out = torch.empty((batch, 2, L, plan.n), dtype=torch.int64, device=ct3.device)
+        if out is None:
+            out = torch.empty((batch, 2, L, plan.n), dtype=torch.int64, device=ct3.device)
         ws = plan.workspace(plan.lib.troyn_relinearize_workspace_bytes(plan.h, L, batch))
         capi.check(plan.lib.troyn_bgv_relinearize(self.h, L, _ptr(ct3), plan._key_ptrs(keys, L), _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        return out
+
+    def multiply_relinearize_mod_switch(self, level_handle, a, b, keys, out=None):
+        """self must be the key level (L = plan.K), level_handle the Bgv of the operands' level L; a, b [batch][2][L][N] NTT form ->
+        [batch][2][L-1][N], word for word dyadic_convolute + relinearize + level_handle.mod_t_and_divide_q_last_ntt.  The caller multiplies
+        the product's correction factor by level_handle.inv_q_last_mod_t."""
+        plan, L = self.plan, level_handle.L
+        batch = a.numel() // (2 * L * plan.n)
+        if out is None:
+            out = torch.empty((batch, 2, L - 1, plan.n), dtype=torch.int64, device=a.device)
+        ws = plan.workspace(plan.lib.troyn_bgv_multiply_relinearize_mod_switch_workspace_bytes(self.h, L, batch))
+        capi.check(plan.lib.troyn_bgv_multiply_relinearize_mod_switch(self.h, level_handle.h, _ptr(a), _ptr(b), plan._key_ptrs(keys, L), _ptr(out),
+                                                                      C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
 
 

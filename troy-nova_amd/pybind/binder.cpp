@@ -484,6 +484,15 @@ PYBIND11_MODULE(pytroy_raw, m) {
                                                       const std::vector<Ciphertext*>& d, PoolArg p) {
         s.multiply_relinearize_rescale_batched(const_ptrs(a), const_ptrs(b), k, d, P(p)); },
            py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    // addition, BGV: multiply -> relinearize -> mod_switch_to_next behind one call (troy.h)
+    ev.def("multiply_relinearize_mod_switch", [](const Evaluator& s, const Ciphertext& a, const Ciphertext& b, const RelinKeys& k, Ciphertext& d, PoolArg p) {
+        s.multiply_relinearize_mod_switch(a, b, k, d, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    ev.def("multiply_relinearize_mod_switch_new", [](const Evaluator& s, const Ciphertext& a, const Ciphertext& b, const RelinKeys& k, PoolArg p) {
+        return s.multiply_relinearize_mod_switch_new(a, b, k, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), POOL);
+    ev.def("multiply_relinearize_mod_switch_batched", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, const RelinKeys& k,
+                                                         const std::vector<Ciphertext*>& d, PoolArg p) {
+        s.multiply_relinearize_mod_switch_batched(const_ptrs(a), const_ptrs(b), k, d, P(p)); },
+           py::arg("encrypted1"), py::arg("encrypted2"), py::arg("relin_keys"), py::arg("destination"), POOL);
     // additions: dot products of ciphertexts with lazy relinearization (troy.h)
     ev.def("multiply_accumulate", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, Ciphertext& d, PoolArg p) {
         s.multiply_accumulate(const_ptrs(a), const_ptrs(b), d, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("destination"), POOL);

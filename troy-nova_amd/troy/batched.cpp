@@ -41,13 +41,13 @@ void same_size(const char* prompt, size_t a, size_t b) {
 // the operation's own `batchable` runs as ONE device step: `prepare` shapes the result of item 0 (checks + metadata, no device work), the
 // operands are staged as [count][words] (used in place when they are adjacent windows already), `step` gets the staged operands and a
 // block of count results, and the destinations become windows of that block.  Any other batch goes through `each` object by object
-// (into a temporary, so that in-place calls work).
+// (into a temporary, so that in-place calls work).  `threshold`: the reference's BATCH_OP_THRESHOLD; an addition that promises one call for any count passes 1.
 template <typename Batchable, typename Each, typename Prepare, typename Step>
 void run_batched(const char* prompt, std::initializer_list<const CVec*> operands, const Vec& destination, MemoryPoolHandle pool, Batchable batchable, Each each,
-                 Prepare prepare, Step step) {
+                 Prepare prepare, Step step, size_t threshold = Evaluator::BATCH_OP_THRESHOLD) {
     const size_t count = destination.size();
     for (const CVec* v : operands) same_size(prompt, v->size(), count);
-    bool batched = count >= Evaluator::BATCH_OP_THRESHOLD;
+    bool batched = count >= threshold;
     for (const CVec* v : operands) batched = batched && uniform(*v);
     if (!batched || !batchable()) {
         for (size_t i = 0; i < count; i++) { Ciphertext out; each(i, out); *destination[i] = std::move(out); }
@@ -135,6 +135,18 @@ void Evaluator::multiply_relinearize_rescale_batched(const CVec& e1, const CVec&
         [&](const detail::StepEnv& env, const Ciphertext&, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count) {
             detail::multiply_relinearize_rescale_step(env, context_->plan(), L, a, b, keys.data(), out, count);
         });
+}
+
+// -- multiply -> relinearize -> mod_switch_to_next, BGV, one call for the whole batch (addition) -----------------------------------------
+void Evaluator::multiply_relinearize_mod_switch_batched(const CVec& e1, const CVec& e2, const RelinKeys& relin_keys, const Vec& destination, MemoryPoolHandle pool) const {
+    std::vector<const uint64_t*> keys;
+    run_batched("[Evaluator::multiply_relinearize_mod_switch_batched]", {&e1, &e2}, destination, pool, always,
+        [&](size_t i, Ciphertext& out) { multiply_relinearize_mod_switch(*e1[i], *e2[i], relin_keys, out, pool); },
+        [&](Ciphertext& proto) { multiply_relinearize_mod_switch_prepare(*e1[0], *e2[0], relin_keys, proto, keys, pool); },   // item 0 stands for every item of a uniform batch
+        [&](const detail::StepEnv& env, const Ciphertext&, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count) {
+            const size_t L = e1[0]->coeff_modulus_size();
+            detail::bgv_multiply_relinearize_mod_switch_step(env, key_level_bgv(SchemeType::BGV), context_->bgv(L), static_cast<uint32_t>(L), a, b, keys.data(), out, count);
+        }, 1);
 }
 
 // -- relinearize -------------------------------------------------------------------------------------------------------

@@ -152,5 +152,12 @@ void multiply_relinearize_rescale_step(const StepEnv& env, const troyn_plan* pla
     env.check(troyn_ckks_multiply_relinearize_rescale(plan, L, a, b, keys, out, ws.raw_pointer(), bytes, count, env.stream));
 }
 
+void bgv_multiply_relinearize_mod_switch_step(const StepEnv& env, const troyn_bgv* key_level, const troyn_bgv* level, uint32_t L, const uint64_t* a, const uint64_t* b,
+                                              const uint64_t* const* keys, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_bgv_multiply_relinearize_mod_switch_workspace_bytes(key_level, L, count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    env.check(troyn_bgv_multiply_relinearize_mod_switch(key_level, level, a, b, keys, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
 }  // namespace detail
 }  // namespace troy

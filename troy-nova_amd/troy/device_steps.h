@@ -74,6 +74,9 @@ void apply_keyswitching_step(const StepEnv& env, const troyn_plan* plan, const t
 void negacyclic_shift_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t shift, size_t polys);
 void multiply_relinearize_rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* a, const uint64_t* b, const uint64_t* const* keys,
                                        uint64_t* out, size_t count);
+// BGV: multiply -> relinearize -> mod_switch_to_next of `count` pairs at level L; key_level / level as troyn_bgv_multiply_relinearize_mod_switch
+void bgv_multiply_relinearize_mod_switch_step(const StepEnv& env, const troyn_bgv* key_level, const troyn_bgv* level, uint32_t L, const uint64_t* a, const uint64_t* b,
+                                              const uint64_t* const* keys, uint64_t* out, size_t count);
 
 #pragma GCC visibility pop
 }  // namespace detail

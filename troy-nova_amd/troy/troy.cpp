@@ -1651,6 +1651,43 @@ void Evaluator::multiply_relinearize_rescale(const Ciphertext& e1, const Ciphert
 }
 
 
+// -- multiply -> relinearize -> mod_switch_to_next as one call, BGV (addition; evaluator.cu:150-173, evaluator_keyswitching.cu:119-144, ---------
+// -- evaluator_modswitch.cu:14-74, :275-300) -------------------------------------------------------------------------------------------
+void Evaluator::multiply_relinearize_mod_switch_prepare(const Ciphertext& e1, const Ciphertext& e2, const RelinKeys& relin_keys, Ciphertext& out,
+                                                        std::vector<const uint64_t*>& key_ptrs, MemoryPoolHandle pool) const {
+    const std::string M = "[Evaluator::multiply_relinearize_mod_switch] ";
+    if (context_->key_context_data().value()->parms().scheme() != SchemeType::BGV)
+        throw std::invalid_argument(M + "BGV contexts only (CKKS: multiply_relinearize_rescale).");
+    if (e1.polynomial_count() != 2 || e2.polynomial_count() != 2) throw std::invalid_argument(M + "Operands must have two polynomials.");
+    try {
+        // the three methods' own prepares, chained on result objects that are never computed: their checks, in their order, and their metadata
+        Ciphertext prod, relin;
+        multiply_prepare(e1, e2, prod, pool);
+        relinearize_prepare(prod, relin_keys, relin, key_ptrs, pool);
+        relin.correction_factor() = prod.correction_factor();
+        mod_switch_to_next_prepare(relin, out, pool);
+        // evaluator_modswitch.cu:62-72: the plaintext is multiplied by q_last^-1 mod t
+        const uint64_t t = context_->get_context_data(out.parms_id()).value()->parms().plain_modulus().value();
+        out.correction_factor() = static_cast<uint64_t>((static_cast<unsigned __int128>(prod.correction_factor()) *
+                                                         troyn_bgv_inv_q_last_mod_t(context_->bgv(e1.coeff_modulus_size()))) % t);
+    } catch (const std::out_of_range& e) {
+        throw std::out_of_range(M + e.what());
+    } catch (const std::invalid_argument& e) {
+        throw std::invalid_argument(M + e.what());
+    }
+}
+
+void Evaluator::multiply_relinearize_mod_switch(const Ciphertext& e1, const Ciphertext& e2, const RelinKeys& relin_keys, Ciphertext& destination, MemoryPoolHandle pool) const {
+    Ciphertext out;
+    std::vector<const uint64_t*> keys;
+    multiply_relinearize_mod_switch_prepare(e1, e2, relin_keys, out, keys, pool);
+    detail::bgv_multiply_relinearize_mod_switch_step(on_current_stream(pool), key_level_bgv(SchemeType::BGV), context_->bgv(e1.coeff_modulus_size()),
+                                                     static_cast<uint32_t>(e1.coeff_modulus_size()), e1.data().raw_pointer(), e2.data().raw_pointer(), keys.data(),
+                                                     out.data().raw_pointer(), 1);
+    destination = std::move(out);
+}
+
+
 // -- dot products with lazy relinearization (additions; the sum of evaluator.cu:118-173's products, then evaluator_keyswitching.cu:119-144 and -----
 // -- evaluator_modswitch.cu:445-461 once) ---------------------------------------------------------------------------------------------------
 void Evaluator::multiply_accumulate_pair_checks(const Ciphertext& e1, const Ciphertext& e2, SchemeType scheme, double& scale, uint64_t& correction_factor) const {

@@ -1473,6 +1473,23 @@ public:
     void multiply_relinearize_rescale_batched(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const RelinKeys& relin_keys,
                                               const std::vector<Ciphertext*>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
 
+    // ADDITION to the reference's interface, BGV contexts only: destination = mod_switch_to_next(relinearize(multiply(e1, e2), relin_keys)) as ONE
+    // library call (troyn_bgv_multiply_relinearize_mod_switch: the key switch's and the modulus switch's mod-t corrections share one forward
+    // transform per output limb; the three-polynomial product and the relinearized ciphertext never reach HBM).  The result -- payload, parms_id
+    // (the next level's), NTT-form flag and correction factor -- is bit-identical to composing evaluator.h's three methods (evaluator.cu:150-173,
+    // evaluator_keyswitching.cu:119-144, evaluator_modswitch.cu:14-74, :275-300).  Every refusal of those three applies, with the reference's
+    // message behind the prefix "[Evaluator::multiply_relinearize_mod_switch]"; a ciphertext at the last level gets mod_switch_to_next's "End of
+    // modulus switching chain reached."  CKKS and BFV contexts and operands that are not two-polynomial ciphertexts get std::invalid_argument
+    // (CKKS users have multiply_relinearize_rescale).  The _batched form puts all items of a uniform batch, of any size, into ONE library call;
+    // call combining does not take part.
+    void multiply_relinearize_mod_switch(const Ciphertext& e1, const Ciphertext& e2, const RelinKeys& relin_keys, Ciphertext& destination,
+                                         MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext multiply_relinearize_mod_switch_new(const Ciphertext& e1, const Ciphertext& e2, const RelinKeys& relin_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; multiply_relinearize_mod_switch(e1, e2, relin_keys, d, pool); return d;
+    }
+    void multiply_relinearize_mod_switch_batched(const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2, const RelinKeys& relin_keys,
+                                                 const std::vector<Ciphertext*>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+
     // ADDITION to the reference's interface: dot products of ciphertexts with lazy relinearization.
     //   multiply_accumulate: destination = SUM_t multiply(e1[t], e2[t]), the three-polynomial sum, formed by ONE launch over all terms
     //   (troyn_dyadic_convolute_accumulate: one pointer per term, no gather).  CKKS and BGV, two-polynomial NTT-form operands.  Payload, parms_id,
@@ -2065,6 +2082,9 @@ private:
     // argument checks + result metadata of multiply -> relinearize -> rescale_to_next; false: the operands do not take the fused entry
     bool multiply_relinearize_rescale_prepare(const Ciphertext& e1, const Ciphertext& e2, const RelinKeys& relin_keys, uint32_t& L, ParmsID& next_parms_id, double& scale,
                                               std::vector<const uint64_t*>& key_ptrs) const;
+    // argument checks of multiply -> relinearize -> mod_switch_to_next (BGV) and the result object one level down, metadata set, WITHOUT the device work
+    void multiply_relinearize_mod_switch_prepare(const Ciphertext& e1, const Ciphertext& e2, const RelinKeys& relin_keys, Ciphertext& out,
+                                                 std::vector<const uint64_t*>& key_ptrs, MemoryPoolHandle pool) const;
     // the basis-independent part of the fixed Paterson-Stockmeyer schedule (evaluate_polynomial, evaluate_chebyshev): the level check, the leaves
     // SUM_i u(j, i) basis(i) and the recombination SUM_j leaf_j basis(jk); basis(m) for m >= 1 is asked for only after the level check
     void paterson_stockmeyer(const char* P, const Ciphertext& x, size_t d, size_t extra_levels, const std::function<const Ciphertext&(size_t)>& basis,
