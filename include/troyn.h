@@ -382,6 +382,7 @@ int troyn_apply_galois_plain(const troyn_plan* plan, uint64_t modulus, uint64_t 
  * are key switches with digits bounded by q_j in magnitude, so both decrypt to the same message under the same noise bound; the
  * contract is the integer specification above, not the reference's words.
  * Scope: BFV and CKKS.  BGV is left out (its tail divides differently, troyn_bgv_switch_key).
+ * BGV has entries of its own with the same arguments: troyn_bgv_apply_galois_many / _sum in the hoisted BGV block below.
  * TROYN_E_INVALID: terms == 0, a null table or entry, a misaligned pointer, an element that is even, 1 or >= 2N, L outside [1, K-1],
  * `out` overlapping `ct`.  TROYN_E_WORKSPACE: a workspace below troyn_apply_galois_hoisted_workspace_bytes(plan, L, terms, batch, sum)
  * (sum = 0 for _many, 1 for _sum).  batch == 0 returns TROYN_OK, launches nothing and looks at neither `ct`, `out` nor the workspace.  The
@@ -423,6 +424,7 @@ int troyn_apply_galois_sum(const troyn_plan* plan, uint32_t L, int is_ckks, int 
  * those of troyn_apply_galois + troyn_switch_key + a plaintext multiplication: the digits of a negated coefficient differ by multiples
  * of q_j, and the reference would round once per term; both decrypt to the same message under the same kind of noise bound.
  * Scope: BFV and CKKS.  BGV is left out (its tail divides differently).
+ * BGV has an entry of its own with the same arguments: troyn_bgv_apply_galois_weighted_sums in the hoisted BGV block below.
  * TROYN_E_INVALID: terms == 0, slots == 0, a slot with no weight, a null table, a null or misaligned key entry of a term with g != 1, a
  * misaligned pointer (ct, out, workspace, a weight), an element that is even or >= 2N, L outside [1, K-1], `out` overlapping `ct`.
  * TROYN_E_WORKSPACE: a workspace below troyn_apply_galois_weighted_workspace_bytes(plan, L, terms, slots, batch, is_ntt_form).
@@ -462,6 +464,8 @@ int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t L, int is_
  * modulo each key modulus.  Modular addition is associative: the words do not depend on the grouping, and the workspace does not grow
  * with `terms` beyond one group.
  * Scope: BFV and CKKS.  BGV is left out (its tail divides differently).
+ * BGV has entries of its own with the same arguments: troyn_bgv_apply_galois_sum_each and troyn_bgv_linear_transform_bsgs, in the
+ * hoisted BGV block below.
  * TROYN_E_INVALID: terms == 0, a null table, a null or misaligned key entry of a term with g != 1, a misaligned pointer (cts, out,
  * workspace), an element that is even or >= 2N, L outside [1, K-1], `out` overlapping `cts`.  TROYN_E_WORKSPACE: a workspace below
  * troyn_apply_galois_sum_each_workspace_bytes(plan, L, terms, batch, is_ntt_form).  batch == 0 returns TROYN_OK, launches nothing and
@@ -527,6 +531,7 @@ int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, int is_ckks,
  * The workspace holds the inner results [giants][batch][2][L+1][N]; everything else is sized by one group of TROYN_HOIST_EACH_GROUP giant
  * steps.  One table upload for the inner stage and one per group.
  * Scope: BFV and CKKS.  BGV is left out (its tail divides differently).
+ * The hoisted BGV block below has no double-hoisted entry: the inner division on one component needs a BGV tail of its own.
  * TROYN_E_INVALID / TROYN_E_WORKSPACE: as troyn_linear_transform_bsgs, against
  * troyn_linear_transform_bsgs_double_hoisted_workspace_bytes(plan, L, babies, giants, batch, is_ntt_form).  batch == 0 returns TROYN_OK and
  * launches nothing.  The tables are read before the call returns.
@@ -569,6 +574,63 @@ int troyn_bgv_switch_key(const troyn_bgv* key_level, uint32_t L, const uint64_t*
                          uint64_t* destination, void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
 int troyn_bgv_relinearize(const troyn_bgv* key_level, uint32_t L, const uint64_t* ct3, const uint64_t* const* keys, uint64_t* out2, void* workspace,
                           size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Hoisted BGV rotations: the hoisted family above (many Galois keys on one decomposition, plaintext-weighted sums, the sum over different
+ * ciphertexts, the baby-step/giant-step linear transform) with the BGV division as its tail.  All five entries are ADDITIONS to the
+ * reference's surface.  Each takes the arguments of its namesake -- troyn_apply_galois_many, troyn_apply_galois_sum,
+ * troyn_apply_galois_weighted_sums, troyn_apply_galois_sum_each, troyn_linear_transform_bsgs -- with `key_level` in place of
+ * `plan, is_ckks, is_ntt_form`:
+ *   key_level  troyn_bgv_create(plan, n_moduli, t), as for troyn_bgv_switch_key: created with L = the plan's modulus count (its last prime
+ *              is the special prime) and with its inverse of the special prime mod t present.  The errors are troyn_bgv_switch_key's.
+ * Operands are in NTT form.  The layouts (ct, cts, galois_elements, keys, out), the alignment rules, the identity element where the
+ * namesake allows it, and the weights -- u64[K][N] NTT-form rows in KEY-LEVEL layout, NULL = absent -- are those of the namesakes.
+ * Contract, per item (and slot), on integers (tests/bgv_hoist_spec.py; the notation of the hoisted blocks above):
+ *   X_c[m]       unchanged: the extended-basis value of the namesake, for every key modulus m in {q_0 .. q_{L-1}, q_special}, with the same
+ *                signed hoisted digits e_{t,j} = sigma_{g_t}(d_j) and the same injection of the unkeyed terms
+ *   s_c          the special row X_c[q_special] in coefficient form, canonical (an integer in [0, q_special))
+ *   dk_l(s)      = [-s * q_special^-1 mod t]_{q_l} * q_special + [s]_{q_l}  mod q_l
+ *   result_c[l]  exactly as in troyn_bgv_switch_key: result_c[l] = (X_c[q_l] - dk_l(s_c)) * q_special^-1 mod q_l (ski_util5: X_c - dk(s_c)
+ *                is divisible by q_special and congruent to X_c mod t)
+ *   out          from result_c and the unkeyed terms exactly as the namesake states
+ * The unkeyed contributions y may be added after the division or injected before it as (q_special mod q_l) * y on the rows q_l and
+ * nothing on the special row; the WORDS are the same either way, by the argument of the weighted block: dk_l depends on the special row
+ * alone, and ((X + q_special * y) - dk_l) * q_special^-1 = (X - dk_l) * q_special^-1 + y mod q_l.  troyn_bgv_apply_galois_many / _sum add
+ * the permuted c0 after the division, the other entries inject before it.
+ * The words are those of NEITHER troyn_apply_galois + troyn_bgv_switch_key NOR the reference, for the reason the hoisted blocks give: where
+ * the automorphism negates a coefficient x of d_j the hoisted digit under key modulus m is (-x) mod m, not (q_j - x) mod m, and a sum
+ * is divided once, not once per term.  Both are BGV key switches with digits bounded by q_j in magnitude: both decrypt to the same
+ * plaintext mod t, exactly, while the noise stays within the bound.  The plaintext's correction factor is unchanged, as for
+ * troyn_bgv_switch_key; its bookkeeping stays with the caller.
+ * The words of troyn_bgv_linear_transform_bsgs equal troyn_bgv_apply_galois_weighted_sums (slots = giants) followed by
+ * troyn_bgv_apply_galois_sum_each on that result with the giant elements and keys.
+ * Workspace: the namesakes' queries with is_ntt_form = 1 -- troyn_apply_galois_hoisted_workspace_bytes (sum = 0 for _many, 1 for _sum),
+ * troyn_apply_galois_weighted_workspace_bytes, troyn_apply_galois_sum_each_workspace_bytes, troyn_linear_transform_bsgs_workspace_bytes --
+ * on the handle's plan, as troyn_bgv_switch_key uses troyn_switch_key_workspace_bytes.
+ * Refusals: a null handle, a handle not at the key level (TROYN_E_INVALID) or without its inverse mod t (TROYN_E_MODULUS,
+ * "[RNSTool::RNSTool] Unable to invert q[last] mod t."), checked first; then TROYN_E_INVALID / TROYN_E_WORKSPACE exactly as the namesake.
+ * batch == 0 returns TROYN_OK, launches nothing and looks at neither the ciphertexts, `out` nor the workspace.  The tables are read before
+ * the call returns.  troyn_linear_transform_bsgs_double_hoisted has no BGV form.
+ * The division runs as two element-wise kernels around the transforms (bgv_hoist_kernels.hpp): the special row is read once per item and
+ * component and the mod-t multiplier formed once per coefficient; the rows of every slot and item share one launch.
+ * ------------------------------------------------------------------------------------- */
+int troyn_bgv_apply_galois_many(const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* galois_elements,
+                                const uint64_t* const* keys, size_t terms, uint64_t* out, void* workspace, size_t workspace_bytes,
+                                size_t batch, troyn_stream_t stream);
+int troyn_bgv_apply_galois_sum(const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* galois_elements,
+                               const uint64_t* const* keys, size_t terms, uint64_t* out, void* workspace, size_t workspace_bytes,
+                               size_t batch, troyn_stream_t stream);
+int troyn_bgv_apply_galois_weighted_sums(const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* galois_elements,
+                                         const uint64_t* const* keys, size_t terms, const uint64_t* const* weights, size_t slots,
+                                         uint64_t* out, void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
+int troyn_bgv_apply_galois_sum_each(const troyn_bgv* key_level, uint32_t L, const uint64_t* cts, const uint64_t* galois_elements,
+                                    const uint64_t* const* keys, size_t terms, uint64_t* out, void* workspace, size_t workspace_bytes,
+                                    size_t batch, troyn_stream_t stream);
+int troyn_bgv_linear_transform_bsgs(const troyn_bgv* key_level, uint32_t L, const uint64_t* ct,
+                                    const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                                    const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                    const uint64_t* const* weights, uint64_t* out,
+                                    void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Fused BGV chain: Evaluator::multiply (bgv_multiply, evaluator.cu:150-173) -> Evaluator::relinearize -> Evaluator::mod_switch_to_next

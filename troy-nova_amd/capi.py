@@ -102,6 +102,12 @@ SYMBOLS = {
     "troyn_bgv_multiply_scalar_mod_t": (C.c_int, [vp, vp, u64, vp, sz, vp]),
     "troyn_bgv_switch_key": (C.c_int, [vp, u32, vp, vp, C.c_int, vp, vp, sz, sz, vp]),
     "troyn_bgv_relinearize": (C.c_int, [vp, u32, vp, vp, vp, vp, sz, sz, vp]),
+    "troyn_bgv_apply_galois_many": (C.c_int, [vp, u32, vp, p64, C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
+    "troyn_bgv_apply_galois_sum": (C.c_int, [vp, u32, vp, p64, C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
+    "troyn_bgv_apply_galois_weighted_sums": (C.c_int, [vp, u32, vp, p64, C.POINTER(vp), sz, C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
+    "troyn_bgv_apply_galois_sum_each": (C.c_int, [vp, u32, vp, p64, C.POINTER(vp), sz, vp, vp, sz, sz, vp]),
+    "troyn_bgv_linear_transform_bsgs": (C.c_int, [vp, u32, vp, p64, C.POINTER(vp), sz, p64, C.POINTER(vp), sz, C.POINTER(vp), vp,
+                                                  vp, sz, sz, vp]),
     "troyn_bgv_multiply_relinearize_mod_switch_workspace_bytes": (sz, [vp, u32, sz]),
     "troyn_bgv_multiply_relinearize_mod_switch": (C.c_int, [vp, vp, vp, vp, C.POINTER(vp), vp, vp, sz, sz, vp]),
     "troyn_ring2k_create": (C.c_int, [C.POINTER(vp), vp, u32, u32, u32]),

@@ -22,6 +22,7 @@
 #include "crypto_kernels.hpp"
 #include "bgv_kernels.hpp"
 #include "bgv_chain_kernels.hpp"
+#include "bgv_hoist_kernels.hpp"
 #include "ring2k_kernels.hpp"
 #include "host_math.hpp"
 #include "ntt_kernels.hpp"
@@ -1518,6 +1519,11 @@ static int ks_tail_coeff_fused(const KsCall& c) {
     // two-pass sizes: the pass in between goes to the free part of prod_intt, never to dest (AddInplace reads the old destination)
     return launch_ntt(p, f, c.batch, true, c.s, spec + c.batch * 2 * (size_t)n);
 }
+// The NTT-form tails that correct before they divide (ks_tail_unfused, bgv_hoist_tail) make ONE use of the key-switch regions, comps <= 2: the special
+// rows in coefficient form lead prod_intt ([batch][2][N]), the per-limb corrections follow them ([batch][2][L][N]: the region holds 2 (L + 1) rows per
+// item), and temp_last ([batch][2][L][N]) takes their forward transform.  Every layout that feeds a tail (ks_workspace, hoist_layout, the sum_each and
+// BSGS layouts) sizes the two regions as batch * 2 * (L + 1) * n and batch * 2 * L * n words; both tails take the corrections' place from here.
+static inline u64* ks_ntt_correction_rows(const KsCall& c) { return c.ws + c.w.prod_intt + c.batch * 2 * (size_t)c.p->n; }
 // steps (4)-(7) as separate launches: tiny rings, BGV, TROYN_KS_TAIL=split
 static int ks_tail_unfused(const KsCall& c) {
     const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
@@ -1543,7 +1549,7 @@ static int ks_tail_unfused(const KsCall& c) {
     const unsigned prod_rows = (ntt && c.comps == 1) ? 2 * (L + 1) : L + 1;
     // (5) rounding fix of the special-prime component, per data limb (:570-598).  In NTT form the result goes to
     //     the unused tail of the prod_intt region so that step (6) can transform out of place.
-    u64* util6_out = ntt ? prod_intt + batch * 2 * (size_t)n : temp_last;      // (comps <= 2: past the special rows either way)
+    u64* util6_out = ntt ? ks_ntt_correction_rows(c) : temp_last;      // (comps <= 2: past the special rows either way)
     if (c.bgv) {
         // kernel_ski_util5_merged_step1 (:436-476): delta_j = (k mod q_j) * q_special + c mod q_j, k = -c * q_special^-1 mod t
         hipLaunchKernelGGL(bgv_delta_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, s,
@@ -1575,6 +1581,41 @@ static int ks_tail(const KsCall& c, const KsPath& path) {
     if (path.tail == KS_TAIL_SMALL) return ks_tail_small(c);
     if (path.tail == KS_TAIL_NTT_FUSED) return ks_tail_ntt_fused(c);
     return path.tail == KS_TAIL_COEFF_FUSED ? ks_tail_coeff_fused(c) : ks_tail_unfused(c);
+}
+
+// The division of the hoisted BGV entries (bgv_hoist_kernels.hpp), NTT form, both components of `batch` items: the steps of ks_tail_unfused
+// in its regions, with the special row read once per (item, component) and two coefficients per thread in both element-wise passes.
+static int bgv_hoist_tail(const KsCall& c) {
+    const troyn_plan* p = c.p; const unsigned L = c.L, K = p->K, n = p->n;
+    const size_t batch = c.batch;
+    hipStream_t s = c.s;
+    u64* spec = c.ws + c.w.prod_intt;
+    u64* delta = ks_ntt_correction_rows(c);            // the rest of the prod_intt region: [batch][2][L][N], where ks_tail_unfused puts its own
+    u64* delta_ntt = c.ws + c.w.temp_last;
+    const unsigned ch = chunks_pairs(n);
+    if (int rc = check_rows(batch * 2 * L, ch)) return rc;
+    // (4) the special rows in coefficient form
+    if (int rc = launch_ntt(p, special_rows_args(p, ks_tail_prod(c), spec, L, 2), batch, true, s)) return rc;
+    // (5) dk_j(s) for every data limb, the mod-t multiplier formed once per coefficient
+    hipLaunchKernelGGL(bgv_hoist_delta_kernel, dim3((unsigned)(batch * 2 * ch)), dim3(POLY_BLOCK), 0, s,
+                       ch, p->d_mods, L, n, c.bgv->t, c.bgv->inv_special_mod_t, p->moduli[K - 1], spec, delta);
+    LAUNCH_CHECK();
+    // (6) back to NTT form
+    if (int rc = launch_ntt(p, contiguous_args(p, delta, delta_ntt, 2, L, 0, L, TROYN_IDX_COMPONENTWISE, 0), batch, false, s)) return rc;
+    // (7) (X - NTT(delta)) / q_special into the destination
+    const dim3 grid((unsigned)(batch * 2 * L * ch)), block(POLY_BLOCK);
+    const ulonglong2* inv_k = p->d_inv_last + (size_t)K * K;
+    if (c.assign_method == TROYN_ASSIGN_OVERWRITE_EXCEPT_FIRST)
+        hipLaunchKernelGGL((bgv_hoist_finish_kernel<true>), grid, block, 0, s, ch, p->d_mods, L, n, ks_tail_prod(c), delta_ntt, inv_k, c.dest);
+    else
+        hipLaunchKernelGGL((bgv_hoist_finish_kernel<false>), grid, block, 0, s, ch, p->d_mods, L, n, ks_tail_prod(c), delta_ntt, inv_k, c.dest);
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+// the tail of a hoisted entry on `c.batch` items: troyn_switch_key's, or the BGV division when the call carries its constants
+static int hoist_tail(const KsCall& c) {
+    if (c.bgv) return bgv_hoist_tail(c);
+    return ks_tail(c, ks_path(c.p, c.L, c.batch, c.is_ntt_form, false));
 }
 
 static int switch_key_impl(const troyn_plan* p, unsigned L, int is_ckks, int is_ntt_form,
@@ -1704,7 +1745,7 @@ static int hoist_decompose(KsCall& dc, bool& skip_diag) {
 
 static int apply_galois_hoisted(const char* P, const troyn_plan* p, unsigned L, int is_ckks, int is_ntt_form, const u64* ct,
                                 const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, u64* out,
-                                void* workspace, size_t workspace_bytes, size_t batch, hipStream_t s, bool sum) {
+                                void* workspace, size_t workspace_bytes, size_t batch, hipStream_t s, bool sum, const BgvTail* bgv = nullptr) {
     if (int rc = hoist_check_tables(P, p, L, galois_elements, keys, terms, false)) return rc;
     const unsigned K = p->K, n = p->n;
     if (batch == 0) return TROYN_OK;      // nothing to do: neither ct, out nor the workspace is looked at
@@ -1717,7 +1758,7 @@ static int apply_galois_hoisted(const char* P, const troyn_plan* p, unsigned L, 
     if (int rc = hoist_upload_tables(p, L, galois_elements, keys, terms, {}, ws + h.table, s)) return rc;
     const u64* c1 = ct + (size_t)L * n;
     KsCall dc{p, L, is_ckks, is_ntt_form != 0, c1, ct_words, TROYN_ASSIGN_OVERWRITE_EXCEPT_FIRST, out, nullptr, 0,
-              ws, h.ks, batch, s, nullptr, c1, ct_words};
+              ws, h.ks, batch, s, bgv, c1, ct_words};
     bool skip_diag = false;
     if (int rc = hoist_decompose(dc, skip_diag)) return rc;
     HoistArgs a;
@@ -1754,7 +1795,7 @@ static int apply_galois_hoisted(const char* P, const troyn_plan* p, unsigned L, 
     // (5) the tail of troyn_switch_key on slots * batch items: dest[.][0] += result_0, dest[.][1] = result_1
     KsCall tc = dc;
     tc.batch = items;
-    return ks_tail(tc, ks_path(p, L, items, tc.is_ntt_form, false));
+    return hoist_tail(tc);
 }
 
 extern "C" int troyn_apply_galois_many(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
@@ -1801,7 +1842,7 @@ static int weighted_sums_impl(const char* P, const troyn_plan* plan, uint32_t L,
                               const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms,
                               const uint64_t* const* weights, size_t slots, uint64_t* out_,
                               void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream,
-                              const WeightedLayout* layout, bool finish) {
+                              const WeightedLayout* layout, bool finish, const BgvTail* bgv = nullptr) {
     const troyn_plan* p = plan;
     const u64* ct = (const u64*)ct_;
     u64* out = (u64*)out_;
@@ -1835,7 +1876,7 @@ static int weighted_sums_impl(const char* P, const troyn_plan* plan, uint32_t L,
     if (int rc = hoist_upload_tables(p, L, galois_elements, keys, terms, extra, ws + w.h.table, s)) return rc;
     const u64* c1 = ct + (size_t)L * n;
     KsCall dc{p, L, is_ckks, ntt, c1, ct_words, TROYN_ASSIGN_OVERWRITE, out, nullptr, 0,
-              ws, w.h.ks, batch, s, nullptr, c1, ct_words};
+              ws, w.h.ks, batch, s, bgv, c1, ct_words};
     bool skip_diag = false;
     if (int rc = hoist_decompose(dc, skip_diag)) return rc;
     HoistWeightedArgs a;
@@ -1876,7 +1917,7 @@ static int weighted_sums_impl(const char* P, const troyn_plan* plan, uint32_t L,
     // the tail of troyn_switch_key on slots * batch items, both components overwritten
     KsCall tc = dc;
     tc.batch = items;
-    return ks_tail(tc, ks_path(p, L, items, tc.is_ntt_form, false));
+    return hoist_tail(tc);
 }
 
 extern "C" int troyn_apply_galois_weighted_sums(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct,
@@ -1919,7 +1960,7 @@ extern "C" size_t troyn_apply_galois_sum_each_workspace_bytes(const troyn_plan* 
 // the entry's work once the element and key tables have passed hoist_check_tables
 static int apply_galois_sum_each(const char* P, const troyn_plan* p, unsigned L, int is_ckks, int is_ntt_form, const u64* cts,
                                  const uint64_t* galois_elements, const uint64_t* const* keys, size_t terms, u64* out,
-                                 void* workspace, size_t workspace_bytes, size_t batch, hipStream_t s) {
+                                 void* workspace, size_t workspace_bytes, size_t batch, hipStream_t s, const BgvTail* bgv = nullptr) {
     const unsigned K = p->K, n = p->n;
     if (batch == 0) return TROYN_OK;      // nothing to do: neither cts, out nor the workspace is looked at
     const size_t ct_words = (size_t)2 * L * n;
@@ -1979,8 +2020,8 @@ static int apply_galois_sum_each(const char* P, const troyn_plan* p, unsigned L,
     // the tail of troyn_switch_key on `batch` items, both components overwritten
     const u64* c1 = cts + (size_t)L * n;
     KsCall tc{p, L, is_ckks, ntt, c1, ct_words, TROYN_ASSIGN_OVERWRITE, out, nullptr, 0,
-              ws, e.ks, batch, s, nullptr, c1, ct_words};
-    return ks_tail(tc, ks_path(p, L, batch, ntt, false));
+              ws, e.ks, batch, s, bgv, c1, ct_words};
+    return hoist_tail(tc);
 }
 
 extern "C" int troyn_apply_galois_sum_each(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* cts,
@@ -2030,13 +2071,12 @@ static int bsgs_check_tables(const char* P, const troyn_plan* p, unsigned L, con
     return TROYN_OK;
 }
 
-extern "C" int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
-                                           const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
-                                           const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
-                                           const uint64_t* const* weights, uint64_t* out_,
-                                           void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
-    select_device(plan);
-    const char* P = "[troyn_linear_transform_bsgs]";
+// the driver of both BSGS entries; P names the entry, PW its inner stage
+static int linear_transform_bsgs_impl(const char* P, const char* PW, const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
+                                      const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                                      const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                      const uint64_t* const* weights, uint64_t* out_,
+                                      void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream, const BgvTail* bgv) {
     const troyn_plan* p = plan;
     const u64* ct = (const u64*)ct_;
     u64* out = (u64*)out_;
@@ -2048,11 +2088,22 @@ extern "C" int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, i
     u64* ws = (u64*)workspace;
     u64* inner = ws + b.inner;
     // stage 1: one decomposition of ct, `giants` divisions -- inner[g] = SUM_b w_{g,b} (.) sigma_{B_b}(ct)
-    if (int rc = troyn_apply_galois_weighted_sums(plan, L, is_ckks, is_ntt_form, ct_, baby_elements, baby_keys, babies, weights, giants,
-                                                  (uint64_t*)inner, ws + b.stage, b.stage_words * sizeof(u64), batch, stream)) return rc;
+    if (int rc = weighted_sums_impl(PW, plan, L, is_ckks, is_ntt_form, ct_, baby_elements, baby_keys, babies, weights, giants,
+                                    (uint64_t*)inner, ws + b.stage, b.stage_words * sizeof(u64), batch, stream, nullptr, true, bgv)) return rc;
     // stage 2: out = SUM_g sigma_{G_g}(inner[g]), ONE division
     return apply_galois_sum_each(P, p, L, is_ckks, is_ntt_form, inner, giant_elements, giant_keys, giants, out,
-                                 ws + b.stage, b.stage_words * sizeof(u64), batch, (hipStream_t)stream);
+                                 ws + b.stage, b.stage_words * sizeof(u64), batch, (hipStream_t)stream, bgv);
+}
+
+extern "C" int troyn_linear_transform_bsgs(const troyn_plan* plan, uint32_t L, int is_ckks, int is_ntt_form, const uint64_t* ct_,
+                                           const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                                           const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                           const uint64_t* const* weights, uint64_t* out_,
+                                           void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(plan);
+    return linear_transform_bsgs_impl("[troyn_linear_transform_bsgs]", "[troyn_apply_galois_weighted_sums]", plan, L, is_ckks, is_ntt_form, ct_,
+                                      baby_elements, baby_keys, babies, giant_elements, giant_keys, giants, weights, out_,
+                                      workspace, workspace_bytes, batch, stream, nullptr);
 }
 
 // ---- double-hoisted BSGS linear transform (an addition; include/troyn.h, hoist_double_kernel): the inner sums stay on the extended basis in
@@ -2859,6 +2910,59 @@ extern "C" int troyn_bgv_relinearize(const troyn_bgv* key_level, uint32_t L, con
     const size_t pc = (size_t)L * plan->n;
     return switch_key_impl(plan, L, 0, 1, (const u64*)ct3 + 2 * pc, 3 * pc, keys, TROYN_ASSIGN_OVERWRITE, (u64*)out2, (const u64*)ct3, 3 * pc, workspace, workspace_bytes,
                            batch, (hipStream_t)stream, &tail);
+}
+
+// ---- hoisted BGV rotations (additions; include/troyn.h, bgv_hoist_kernels.hpp): the hoisted entries' host paths in NTT form with the BGV
+// division as their tail.  The handle is checked before anything else, as in troyn_bgv_switch_key ----
+extern "C" int troyn_bgv_apply_galois_many(const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* galois_elements,
+                                           const uint64_t* const* keys, size_t terms, uint64_t* out, void* workspace, size_t workspace_bytes,
+                                           size_t batch, troyn_stream_t stream) {
+    select_device(key_level);
+    BgvTail tail;
+    if (int rc = bgv_tail_from(key_level, tail)) return rc;
+    return apply_galois_hoisted("[troyn_bgv_apply_galois_many]", key_level->plan, L, 0, 1, (const u64*)ct, galois_elements, keys, terms,
+                                (u64*)out, workspace, workspace_bytes, batch, (hipStream_t)stream, false, &tail);
+}
+extern "C" int troyn_bgv_apply_galois_sum(const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* galois_elements,
+                                          const uint64_t* const* keys, size_t terms, uint64_t* out, void* workspace, size_t workspace_bytes,
+                                          size_t batch, troyn_stream_t stream) {
+    select_device(key_level);
+    BgvTail tail;
+    if (int rc = bgv_tail_from(key_level, tail)) return rc;
+    return apply_galois_hoisted("[troyn_bgv_apply_galois_sum]", key_level->plan, L, 0, 1, (const u64*)ct, galois_elements, keys, terms,
+                                (u64*)out, workspace, workspace_bytes, batch, (hipStream_t)stream, true, &tail);
+}
+extern "C" int troyn_bgv_apply_galois_weighted_sums(const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* galois_elements,
+                                                    const uint64_t* const* keys, size_t terms, const uint64_t* const* weights, size_t slots,
+                                                    uint64_t* out, void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(key_level);
+    BgvTail tail;
+    if (int rc = bgv_tail_from(key_level, tail)) return rc;
+    return weighted_sums_impl("[troyn_bgv_apply_galois_weighted_sums]", key_level->plan, L, 0, 1, ct, galois_elements, keys, terms, weights, slots,
+                              out, workspace, workspace_bytes, batch, stream, nullptr, true, &tail);
+}
+extern "C" int troyn_bgv_apply_galois_sum_each(const troyn_bgv* key_level, uint32_t L, const uint64_t* cts, const uint64_t* galois_elements,
+                                               const uint64_t* const* keys, size_t terms, uint64_t* out, void* workspace, size_t workspace_bytes,
+                                               size_t batch, troyn_stream_t stream) {
+    select_device(key_level);
+    BgvTail tail;
+    if (int rc = bgv_tail_from(key_level, tail)) return rc;
+    const char* P = "[troyn_bgv_apply_galois_sum_each]";
+    if (int rc = hoist_check_tables(P, key_level->plan, L, galois_elements, keys, terms, true)) return rc;
+    return apply_galois_sum_each(P, key_level->plan, L, 0, 1, (const u64*)cts, galois_elements, keys, terms, (u64*)out,
+                                 workspace, workspace_bytes, batch, (hipStream_t)stream, &tail);
+}
+extern "C" int troyn_bgv_linear_transform_bsgs(const troyn_bgv* key_level, uint32_t L, const uint64_t* ct,
+                                               const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies,
+                                               const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                               const uint64_t* const* weights, uint64_t* out,
+                                               void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
+    select_device(key_level);
+    BgvTail tail;
+    if (int rc = bgv_tail_from(key_level, tail)) return rc;
+    return linear_transform_bsgs_impl("[troyn_bgv_linear_transform_bsgs]", "[troyn_bgv_apply_galois_weighted_sums]", key_level->plan, L, 0, 1, ct,
+                                      baby_elements, baby_keys, babies, giant_elements, giant_keys, giants, weights, out,
+                                      workspace, workspace_bytes, batch, stream, &tail);
 }
 
 // ---- fused BGV chain (an addition to the reference's surface; include/troyn.h, bgv_chain_kernels.hpp) ----

@@ -227,8 +227,14 @@ class Plan:
         return out
 
     # -- hoisted rotations (additions: one digit decomposition for many Galois keys) ----------------
-    def _apply_galois_hoisted(self, summed, L, ct, elements, keys_per_element, is_ckks, is_ntt_form, out):
-        who = "[troyn_apply_galois_sum]" if summed else "[troyn_apply_galois_many]"
+    def _hoist_entry(self, name, L, is_ckks, is_ntt_form, bgv):
+        """(who, function, leading arguments) of a hoisted entry: the plan's own, or its troyn_bgv_* form on a key-level Bgv handle"""
+        if bgv is None:
+            return "[troyn_%s]" % name, getattr(self.lib, "troyn_" + name), (self.h, L, int(is_ckks), int(is_ntt_form))
+        return "[troyn_bgv_%s]" % name, getattr(self.lib, "troyn_bgv_" + name), (bgv.h, L)
+
+    def _apply_galois_hoisted(self, summed, L, ct, elements, keys_per_element, is_ckks, is_ntt_form, out, bgv=None):
+        who, fn, head = self._hoist_entry("apply_galois_sum" if summed else "apply_galois_many", L, is_ckks, is_ntt_form, bgv)
         terms = len(elements)
         if len(keys_per_element) != terms:
             raise capi.TroynInvalidArgument("%s one key per Galois element is needed" % who)
@@ -249,9 +255,7 @@ class Plan:
         elif out.numel() != int(np.prod(shape)):
             raise capi.TroynInvalidArgument("%s out is not %s" % (who, "[batch][2][L][N]" if summed else "[terms][batch][2][L][N]"))
         ws = self.workspace(self.lib.troyn_apply_galois_hoisted_workspace_bytes(self.h, L, terms, batch, int(summed)))
-        fn = self.lib.troyn_apply_galois_sum if summed else self.lib.troyn_apply_galois_many
-        capi.check(fn(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(ct), earr, karr, terms, _ptr(out),
-                      C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        capi.check(fn(*head, _ptr(ct), earr, karr, terms, _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
 
     def apply_galois_many(self, L, ct, elements, keys_per_element, is_ckks=True, is_ntt_form=True, out=None):
@@ -269,7 +273,10 @@ class Plan:
         one digit decomposition and ONE division by the special prime per slot (the diagonal method; include/troyn.h states the contract).
         weights[s][t]: a tensor [K][N] in NTT form and key-level layout (special prime last), or None = the term is absent from slot s.
         The element 1 is the unrotated ciphertext; its entry of keys_per_element may be None."""
-        who = "[troyn_apply_galois_weighted_sums]"
+        return self._apply_galois_weighted_sums(L, ct, elements, keys_per_element, weights, is_ckks, is_ntt_form, out)
+
+    def _apply_galois_weighted_sums(self, L, ct, elements, keys_per_element, weights, is_ckks, is_ntt_form, out, bgv=None):
+        who, fn, head = self._hoist_entry("apply_galois_weighted_sums", L, is_ckks, is_ntt_form, bgv)
         terms, slots = len(elements), len(weights)
         if len(keys_per_element) != terms:
             raise capi.TroynInvalidArgument("%s one key per Galois element is needed" % who)
@@ -301,8 +308,7 @@ class Plan:
         elif out.numel() != int(np.prod(shape)):
             raise capi.TroynInvalidArgument("%s out is not [slots][batch][2][L][N]" % who)
         ws = self.workspace(self.lib.troyn_apply_galois_weighted_workspace_bytes(self.h, L, terms, slots, batch, int(is_ntt_form)))
-        capi.check(self.lib.troyn_apply_galois_weighted_sums(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(ct), earr, karr, terms, warr, slots,
-                                                             _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        capi.check(fn(*head, _ptr(ct), earr, karr, terms, warr, slots, _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
 
     # -- sums over different ciphertexts and the baby-step/giant-step transform (additions) ---------
@@ -325,7 +331,10 @@ class Plan:
         """cts [terms][batch][2][L][N] -> [batch][2][L][N]: the SUM over t of the key-switched automorphism X -> X^elements[t] of cts[t], one
         ciphertext PER TERM, summed before ONE division by the special prime (include/troyn.h states the contract).  The element 1 adds the
         term unrotated; its entry of keys_per_element may be None."""
-        who = "[troyn_apply_galois_sum_each]"
+        return self._apply_galois_sum_each(L, cts, elements, keys_per_element, is_ckks, is_ntt_form, out)
+
+    def _apply_galois_sum_each(self, L, cts, elements, keys_per_element, is_ckks, is_ntt_form, out, bgv=None):
+        who, fn, head = self._hoist_entry("apply_galois_sum_each", L, is_ckks, is_ntt_form, bgv)
         terms = len(elements)
         earr, karr = self._keyed_tables(who, L, elements, keys_per_element)
         words = 2 * L * self.n
@@ -340,8 +349,7 @@ class Plan:
         elif out.numel() != int(np.prod(shape)):
             raise capi.TroynInvalidArgument("%s out is not [batch][2][L][N]" % who)
         ws = self.workspace(self.lib.troyn_apply_galois_sum_each_workspace_bytes(self.h, L, terms, batch, int(is_ntt_form)))
-        capi.check(self.lib.troyn_apply_galois_sum_each(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(cts), earr, karr, terms, _ptr(out),
-                                                        C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        capi.check(fn(*head, _ptr(cts), earr, karr, terms, _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
 
     def linear_transform_bsgs(self, L, ct, baby_elements, baby_keys, giant_elements, giant_keys, weights, is_ckks=True, is_ntt_form=True,
@@ -361,8 +369,9 @@ class Plan:
         return self._linear_transform_bsgs("troyn_linear_transform_bsgs_double_hoisted", L, ct, baby_elements, baby_keys, giant_elements,
                                            giant_keys, weights, is_ckks, is_ntt_form, out)
 
-    def _linear_transform_bsgs(self, entry, L, ct, baby_elements, baby_keys, giant_elements, giant_keys, weights, is_ckks, is_ntt_form, out):
-        who = "[%s]" % entry
+    def _linear_transform_bsgs(self, entry, L, ct, baby_elements, baby_keys, giant_elements, giant_keys, weights, is_ckks, is_ntt_form, out,
+                               bgv=None):
+        who, fn, head = self._hoist_entry(entry[len("troyn_"):], L, is_ckks, is_ntt_form, bgv)
         babies, giants = len(baby_elements), len(giant_elements)
         bearr, bkarr = self._keyed_tables(who, L, baby_elements, baby_keys)
         gearr, gkarr = self._keyed_tables(who, L, giant_elements, giant_keys)
@@ -387,9 +396,8 @@ class Plan:
         elif out.numel() != int(np.prod(shape)):
             raise capi.TroynInvalidArgument("%s out is not [batch][2][L][N]" % who)
         ws = self.workspace(getattr(self.lib, entry + "_workspace_bytes")(self.h, L, babies, giants, batch, int(is_ntt_form)))
-        capi.check(getattr(self.lib, entry)(self.h, L, int(is_ckks), int(is_ntt_form), _ptr(ct), bearr, bkarr, babies,
-                                            gearr, gkarr, giants, warr, _ptr(out),
-                                            C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
+        capi.check(fn(*head, _ptr(ct), bearr, bkarr, babies, gearr, gkarr, giants, warr, _ptr(out),
+                      C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
 
     # -- RLWE / LWE packing (evaluator_lwes.cu) -----------------------------------------------------
@@ -759,6 +767,31 @@ class Bgv:
         ws = plan.workspace(plan.lib.troyn_relinearize_workspace_bytes(plan.h, L, batch))
         capi.check(plan.lib.troyn_bgv_relinearize(self.h, L, _ptr(ct3), plan._key_ptrs(keys, L), _ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(), batch, _stream()))
         return out
+
+    # -- hoisted rotations (additions: the Plan methods of the same names on NTT-form operands, with the BGV division as their tail;
+    #    self must be the key level; the workspaces are the plan's queries with is_ntt_form = 1) --
+    def apply_galois_many(self, L, ct, elements, keys_per_element, out=None):
+        """ct [batch][2][L][N] -> [terms][batch][2][L][N], ONE digit decomposition of ct (include/troyn.h states the contract)"""
+        return self.plan._apply_galois_hoisted(False, L, ct, elements, keys_per_element, False, True, out, bgv=self)
+
+    def apply_galois_sum(self, L, ct, elements, keys_per_element, out=None):
+        """ct [batch][2][L][N] -> [batch][2][L][N]: the sum over the elements, one decomposition and ONE division by the special prime"""
+        return self.plan._apply_galois_hoisted(True, L, ct, elements, keys_per_element, False, True, out, bgv=self)
+
+    def apply_galois_weighted_sums(self, L, ct, elements, keys_per_element, weights, out=None):
+        """ct [batch][2][L][N] -> [slots][batch][2][L][N]: out[s] = SUM_t weights[s][t] (.) sigma_elements[t](ct), one division per slot;
+        weights[s][t]: [K][N] NTT form, key-level layout, or None"""
+        return self.plan._apply_galois_weighted_sums(L, ct, elements, keys_per_element, weights, False, True, out, bgv=self)
+
+    def apply_galois_sum_each(self, L, cts, elements, keys_per_element, out=None):
+        """cts [terms][batch][2][L][N] -> [batch][2][L][N]: SUM_t sigma_elements[t](cts[t]) with ONE division by the special prime"""
+        return self.plan._apply_galois_sum_each(L, cts, elements, keys_per_element, False, True, out, bgv=self)
+
+    def linear_transform_bsgs(self, L, ct, baby_elements, baby_keys, giant_elements, giant_keys, weights, out=None):
+        """ct [batch][2][L][N] -> [batch][2][L][N]: SUM_g sigma_G[g]( SUM_b weights[g][b] (.) sigma_B[b](ct) ); word for word
+        apply_galois_weighted_sums followed by apply_galois_sum_each"""
+        return self.plan._linear_transform_bsgs("troyn_linear_transform_bsgs", L, ct, baby_elements, baby_keys, giant_elements, giant_keys,
+                                                weights, False, True, out, bgv=self)
 
     def multiply_relinearize_mod_switch(self, level_handle, a, b, keys, out=None):
         """self must be the key level (L = plan.K), level_handle the Bgv of the operands' level L; a, b [batch][2][L][N] NTT form ->

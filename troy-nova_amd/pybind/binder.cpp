@@ -672,6 +672,58 @@ PYBIND11_MODULE(pytroy_raw, m) {
     ev.def("rotate_bsgs_sum_double_hoisted_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& b, const std::vector<int>& g, const GaloisKeys& k,
                                                     const std::vector<WeightRow>& w, PoolArg p) { return s.rotate_bsgs_sum_double_hoisted_new(a, b, g, k, w, P(p)); },
            py::arg("encrypted"), py::arg("baby_steps"), py::arg("giant_steps"), py::arg("galois_keys"), py::arg("weights"), POOL);
+    // additions: the hoisted family on BGV contexts (troy.h): bgv_NAME takes NAME's arguments.  SEL is the element / step list's type and keyword
+#define EV_BGV_MANY(name, SEL, sel, what)                                                                                                          \
+    ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& g, const GaloisKeys& k, const std::vector<Ciphertext*>& d, PoolArg p) {  \
+        std::vector<Ciphertext> out = s.name##_new(a, g, k, P(p));                                                                                 \
+        if (d.size() != out.size()) throw std::invalid_argument("[Evaluator::" #name "] destination needs one ciphertext per " what ".");          \
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },                                                                      \
+           py::arg("encrypted"), py::arg(sel), py::arg("galois_keys"), py::arg("destination"), POOL);                                              \
+    ev.def(#name "_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& g, const GaloisKeys& k, PoolArg p) {                  \
+        return s.name##_new(a, g, k, P(p)); }, py::arg("encrypted"), py::arg(sel), py::arg("galois_keys"), POOL);
+#define EV_BGV_SUM(name, CT, SEL, sel)                                                                                                             \
+    ev.def(#name, [](const Evaluator& s, const CT& a, const std::vector<SEL>& g, const GaloisKeys& k, Ciphertext& d, PoolArg p) {                  \
+        s.name(a, g, k, d, P(p)); }, py::arg("encrypted"), py::arg(sel), py::arg("galois_keys"), py::arg("destination"), POOL);                    \
+    ev.def(#name "_new", [](const Evaluator& s, const CT& a, const std::vector<SEL>& g, const GaloisKeys& k, PoolArg p) {                          \
+        return s.name##_new(a, g, k, P(p)); }, py::arg("encrypted"), py::arg(sel), py::arg("galois_keys"), POOL);
+#define EV_BGV_WEIGHTED_SUMS(name, SEL, sel)                                                                                                       \
+    ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& g, const GaloisKeys& k, const std::vector<WeightRow>& w,     \
+                     const std::vector<Ciphertext*>& d, PoolArg p) {                                                                               \
+        std::vector<Ciphertext> out = s.name##_new(a, g, k, w, P(p));                                                                              \
+        if (d.size() != out.size()) throw std::invalid_argument("[Evaluator::" #name "] destination needs one ciphertext per slot.");              \
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },                                                                      \
+           py::arg("encrypted"), py::arg(sel), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);                          \
+    ev.def(#name "_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& g, const GaloisKeys& k, const std::vector<WeightRow>& w, PoolArg p) {  \
+        return s.name##_new(a, g, k, w, P(p)); }, py::arg("encrypted"), py::arg(sel), py::arg("galois_keys"), py::arg("weights"), POOL);
+#define EV_BGV_WEIGHTED_SUM(name, SEL, sel)                                                                                                        \
+    ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& g, const GaloisKeys& k, const WeightRow& w, Ciphertext& d, PoolArg p) {  \
+        s.name(a, g, k, w, d, P(p)); }, py::arg("encrypted"), py::arg(sel), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);  \
+    ev.def(#name "_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& g, const GaloisKeys& k, const WeightRow& w, PoolArg p) {  \
+        return s.name##_new(a, g, k, w, P(p)); }, py::arg("encrypted"), py::arg(sel), py::arg("galois_keys"), py::arg("weights"), POOL);
+#define EV_BGV_BSGS(name, SEL, baby, giant)                                                                                                        \
+    ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& b, const std::vector<SEL>& g, const GaloisKeys& k,           \
+                     const std::vector<WeightRow>& w, Ciphertext& d, PoolArg p) { s.name(a, b, g, k, w, d, P(p)); },                               \
+           py::arg("encrypted"), py::arg(baby), py::arg(giant), py::arg("galois_keys"), py::arg("weights"), py::arg("destination"), POOL);         \
+    ev.def(#name "_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& b, const std::vector<SEL>& g, const GaloisKeys& k,    \
+                            const std::vector<WeightRow>& w, PoolArg p) { return s.name##_new(a, b, g, k, w, P(p)); },                             \
+           py::arg("encrypted"), py::arg(baby), py::arg(giant), py::arg("galois_keys"), py::arg("weights"), POOL);
+    EV_BGV_MANY(bgv_apply_galois_many, size_t, "galois_elements", "element")
+    EV_BGV_MANY(bgv_rotate_many, int, "steps", "step")
+    EV_BGV_SUM(bgv_apply_galois_sum, Ciphertext, size_t, "galois_elements")
+    EV_BGV_SUM(bgv_rotate_sum, Ciphertext, int, "steps")
+    EV_BGV_WEIGHTED_SUMS(bgv_apply_galois_weighted_sums, size_t, "galois_elements")
+    EV_BGV_WEIGHTED_SUMS(bgv_rotate_weighted_sums, int, "steps")
+    EV_BGV_WEIGHTED_SUM(bgv_apply_galois_weighted_sum, size_t, "galois_elements")
+    EV_BGV_WEIGHTED_SUM(bgv_rotate_weighted_sum, int, "steps")
+    EV_BGV_SUM(bgv_apply_galois_sum_each, CtRow, size_t, "galois_elements")
+    EV_BGV_SUM(bgv_rotate_sum_each, CtRow, int, "steps")
+    EV_BGV_BSGS(bgv_apply_galois_bsgs_sum, size_t, "baby_elements", "giant_elements")
+    EV_BGV_BSGS(bgv_rotate_bsgs_sum, int, "baby_steps", "giant_steps")
+#undef EV_BGV_MANY
+#undef EV_BGV_SUM
+#undef EV_BGV_WEIGHTED_SUMS
+#undef EV_BGV_WEIGHTED_SUM
+#undef EV_BGV_BSGS
     // ciphertext +/- plaintext
 #define EV_PLAIN(name)                                                                                                          \
     ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const Plaintext& w, Ciphertext& d, PoolArg p) { s.name(a, w, d, P(p)); },  \

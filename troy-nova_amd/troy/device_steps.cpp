@@ -159,5 +159,47 @@ void bgv_multiply_relinearize_mod_switch_step(const StepEnv& env, const troyn_bg
     env.check(troyn_bgv_multiply_relinearize_mod_switch(key_level, level, a, b, keys, out, ws.raw_pointer(), bytes, count, env.stream));
 }
 
+void bgv_apply_galois_many_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
+                                const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_apply_galois_hoisted_workspace_bytes(plan, L, terms, count, 0);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_bgv_apply_galois_many(key_level, L, ct, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void bgv_apply_galois_sum_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
+                               const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_apply_galois_hoisted_workspace_bytes(plan, L, terms, count, 1);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_bgv_apply_galois_sum(key_level, L, ct, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void bgv_apply_galois_weighted_sums_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
+                                         const uint64_t* const* keys, size_t terms, const uint64_t* const* weights, size_t slots, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_apply_galois_weighted_workspace_bytes(plan, L, terms, slots, count, 1);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_bgv_apply_galois_weighted_sums(key_level, L, ct, elements, keys, terms, weights, slots, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void bgv_apply_galois_sum_each_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* cts, const uint64_t* elements,
+                                    const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_apply_galois_sum_each_workspace_bytes(plan, L, terms, count, 1);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_bgv_apply_galois_sum_each(key_level, L, cts, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void bgv_linear_transform_bsgs_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* baby_elements,
+                                    const uint64_t* const* baby_keys, size_t babies, const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                    const uint64_t* const* weights, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_linear_transform_bsgs_workspace_bytes(plan, L, babies, giants, count, 1);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_bgv_linear_transform_bsgs(key_level, L, ct, baby_elements, baby_keys, babies, giant_elements, giant_keys, giants, weights, out, ws.raw_pointer(),
+                                              bytes, count, env.stream));
+}
+
 }  // namespace detail
 }  // namespace troy

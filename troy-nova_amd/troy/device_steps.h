@@ -78,6 +78,22 @@ void multiply_relinearize_rescale_step(const StepEnv& env, const troyn_plan* pla
 void bgv_multiply_relinearize_mod_switch_step(const StepEnv& env, const troyn_bgv* key_level, const troyn_bgv* level, uint32_t L, const uint64_t* a, const uint64_t* b,
                                               const uint64_t* const* keys, uint64_t* out, size_t count);
 
+// BGV hoisted family (troyn_bgv_apply_galois_* / troyn_bgv_linear_transform_bsgs): operands in NTT form at level L, `key_level` the key level's handle;
+// the workspaces are those of the BFV / CKKS namesakes with is_ntt_form = 1.  ct is [count][2][L][N]; keys [terms][L] (null rows for the element 1 where
+// the entry takes it); weights [slots][terms] / [giants][babies] key-level NTT rows or null
+void bgv_apply_galois_many_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
+                                const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count);     // out [count][terms][2][L][N]
+void bgv_apply_galois_sum_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
+                               const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count);      // out [count][2][L][N]
+void bgv_apply_galois_weighted_sums_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
+                                         const uint64_t* const* keys, size_t terms, const uint64_t* const* weights, size_t slots, uint64_t* out, size_t count);
+// cts [count][terms][2][L][N], one ciphertext per term
+void bgv_apply_galois_sum_each_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* cts, const uint64_t* elements,
+                                    const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count);
+void bgv_linear_transform_bsgs_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* baby_elements,
+                                    const uint64_t* const* baby_keys, size_t babies, const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
+                                    const uint64_t* const* weights, uint64_t* out, size_t count);
+
 #pragma GCC visibility pop
 }  // namespace detail
 }  // namespace troy

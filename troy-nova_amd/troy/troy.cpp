@@ -2589,14 +2589,28 @@ void Evaluator::rotate_columns(const Ciphertext& encrypted, const GaloisKeys& ga
     apply_galois(encrypted, utils::galois_element_from_step(cd->parms().poly_modulus_degree(), 0), galois_keys, destination, pool);
 }
 
+// the scheme gate of the hoisted family: the unprefixed methods are BFV / CKKS only, the bgv_ methods (troyn_bgv_apply_galois_*, the mod-t tail) BGV only
+static void hoisted_scheme_check(const char* P, SchemeType scheme, bool bgv) {
+    if (!bgv && scheme == SchemeType::BGV) throw std::invalid_argument(std::string(P) + " BGV is not supported: its key switch divides by the special prime differently.");
+    if (bgv && scheme != SchemeType::BGV) {
+        std::string name(P);                                          // "[Evaluator::bgv_NAME]" -> NAME, the BFV / CKKS method
+        name = name.substr(16, name.size() - 17);
+        throw std::invalid_argument(std::string(P) + " BGV contexts only; BFV and CKKS: Evaluator::" + name + ".");
+    }
+}
+static void bgv_ntt_form_check(const char* P, bool bgv, const Ciphertext& c) {
+    if (bgv && !c.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Ciphertext is not in NTT form.");
+}
+
 // -- hoisted rotations (addition; troy.h): one digit decomposition of `encrypted` for every Galois key, troyn_apply_galois_many / _sum --
 void Evaluator::apply_galois_hoisted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, bool allow_identity,
-                                     const GaloisKeys& galois_keys, bool sum, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const {
+                                     const GaloisKeys& galois_keys, bool sum, std::vector<Ciphertext>& out, MemoryPoolHandle pool, bool bgv) const {
     if (galois_elements.empty()) throw std::invalid_argument(std::string(P) + " Empty element list.");
     auto cd = get_context_data(P, encrypted.parms_id());
     const SchemeType scheme = cd->parms().scheme();
-    if (scheme == SchemeType::BGV) throw std::invalid_argument(std::string(P) + " BGV is not supported: its key switch divides by the special prime differently.");
+    hoisted_scheme_check(P, scheme, bgv);
     if (encrypted.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " Ciphertext size must be 2.");
+    bgv_ntt_form_check(P, bgv, encrypted);
     const size_t n = cd->parms().poly_modulus_degree();
     const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
     const size_t words = 2 * static_cast<size_t>(L) * n;
@@ -2619,7 +2633,11 @@ void Evaluator::apply_galois_hoisted(const char* P, const Ciphertext& encrypted,
     check_on_device(P, context_, encrypted);
     const size_t terms = elements.size();
     utils::DynamicArray flat(sum || terms == 0 ? 2 : terms * words, true, pool);     // many form: [terms][2][L][N], copied out per term
-    if (terms) {
+    if (terms && bgv) {
+        (sum ? detail::bgv_apply_galois_sum_step : detail::bgv_apply_galois_many_step)(
+            on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, encrypted.data().raw_pointer(), elements.data(), keys.data(), terms,
+            sum ? shells[0].data().raw_pointer() : flat.raw_pointer(), 1);
+    } else if (terms) {
         const size_t bytes = troyn_apply_galois_hoisted_workspace_bytes(context_->plan(), L, terms, 1, sum ? 1 : 0);
         utils::DynamicArray ws((bytes + 7) / 8, true, pool);
         detail::LaunchGate gate;
@@ -2716,13 +2734,14 @@ double Evaluator::weight_table(const char* P, SchemeType scheme, size_t n, const
 
 // -- plaintext-weighted hoisted rotations (addition; troy.h): troyn_apply_galois_weighted_sums, one launch chain for every slot --
 void Evaluator::apply_galois_weighted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
-                                      const std::vector<std::vector<const Plaintext*>>& weights, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const {
+                                      const std::vector<std::vector<const Plaintext*>>& weights, std::vector<Ciphertext>& out, MemoryPoolHandle pool, bool bgv) const {
     if (galois_elements.empty()) throw std::invalid_argument(std::string(P) + " Empty element list.");
     if (weights.empty()) throw std::invalid_argument(std::string(P) + " Empty slot list.");
     auto cd = get_context_data(P, encrypted.parms_id());
     const SchemeType scheme = cd->parms().scheme();
-    if (scheme == SchemeType::BGV) throw std::invalid_argument(std::string(P) + " BGV is not supported: its key switch divides by the special prime differently.");
+    hoisted_scheme_check(P, scheme, bgv);
     if (encrypted.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " Ciphertext size must be 2.");
+    bgv_ntt_form_check(P, bgv, encrypted);
     check_no_seed(P, encrypted);
     check_on_device(P, context_, encrypted);
     const size_t n = cd->parms().poly_modulus_degree();
@@ -2735,7 +2754,10 @@ void Evaluator::apply_galois_weighted(const char* P, const Ciphertext& encrypted
     const double scale = scheme == SchemeType::CKKS ? encrypted.scale() * weight_scale : encrypted.scale();
     if (scheme == SchemeType::CKKS && !is_scale_within_bounds(scale, cd)) throw std::invalid_argument(std::string(P) + " Scale out of bounds.");
     utils::DynamicArray flat(slots * words, true, pool);     // [slots][2][L][N], copied out per slot
-    {
+    if (bgv) {
+        detail::bgv_apply_galois_weighted_sums_step(on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, encrypted.data().raw_pointer(), elements.data(),
+                                                    keys.data(), terms, wptrs.data(), slots, flat.raw_pointer(), 1);
+    } else {
         const int is_ckks = scheme == SchemeType::CKKS, is_ntt = encrypted.is_ntt_form() ? 1 : 0;
         const size_t bytes = troyn_apply_galois_weighted_workspace_bytes(context_->plan(), L, terms, slots, 1, is_ntt);
         utils::DynamicArray ws((bytes + 7) / 8, true, pool);
@@ -2768,14 +2790,15 @@ void Evaluator::rotate_weighted_sum(const Ciphertext& encrypted, const std::vect
 
 // -- the sum of key-switched automorphisms of different ciphertexts (addition; troy.h): troyn_apply_galois_sum_each, ONE division --
 void Evaluator::apply_galois_each(const char* P, const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements,
-                                  const GaloisKeys& galois_keys, Ciphertext& destination, MemoryPoolHandle pool) const {
+                                  const GaloisKeys& galois_keys, Ciphertext& destination, MemoryPoolHandle pool, bool bgv) const {
     if (galois_elements.empty()) throw std::invalid_argument(std::string(P) + " Empty element list.");
     if (encrypted.size() != galois_elements.size()) throw std::invalid_argument(std::string(P) + " One ciphertext per element is needed.");
     for (const Ciphertext* c : encrypted) if (!c) throw std::invalid_argument(std::string(P) + " Null ciphertext.");
     const Ciphertext& first = *encrypted[0];
     auto cd = get_context_data(P, first.parms_id());
     const SchemeType scheme = cd->parms().scheme();
-    if (scheme == SchemeType::BGV) throw std::invalid_argument(std::string(P) + " BGV is not supported: its key switch divides by the special prime differently.");
+    hoisted_scheme_check(P, scheme, bgv);
+    bgv_ntt_form_check(P, bgv, first);
     for (const Ciphertext* c : encrypted) {
         if (c->polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " Ciphertext size must be 2.");
         check_no_seed(P, *c);
@@ -2783,6 +2806,7 @@ void Evaluator::apply_galois_each(const char* P, const std::vector<const Ciphert
         if (c->parms_id() != first.parms_id()) throw std::invalid_argument(std::string(P) + " Operands are at different levels.");
         if (c->is_ntt_form() != first.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Operands are in different forms.");
         if (scheme == SchemeType::CKKS && !are_close_double(c->scale(), first.scale())) throw std::invalid_argument(std::string(P) + " Operands have different scales.");
+        if (bgv && c->correction_factor() != first.correction_factor()) throw std::invalid_argument(std::string(P) + " Operands have different correction factors.");
     }
     const size_t n = cd->parms().poly_modulus_degree();
     const uint32_t L = static_cast<uint32_t>(cd->parms().coeff_modulus().size());
@@ -2794,7 +2818,10 @@ void Evaluator::apply_galois_each(const char* P, const std::vector<const Ciphert
     for (size_t t = 0; t < terms; t++)
         hip_check(hipMemcpyAsync(flat.raw_pointer() + t * words, encrypted[t]->data().raw_pointer(), words * 8, hipMemcpyDeviceToDevice, current_stream()), "copy_device_to_device");
     Ciphertext d = Ciphertext::like(first, false, pool);
-    {
+    if (bgv) {
+        detail::bgv_apply_galois_sum_each_step(on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, flat.raw_pointer(), elements.data(), keys.data(), terms,
+                                               d.data().raw_pointer(), 1);
+    } else {
         const int is_ckks = scheme == SchemeType::CKKS, is_ntt = first.is_ntt_form() ? 1 : 0;
         const size_t bytes = troyn_apply_galois_sum_each_workspace_bytes(context_->plan(), L, terms, 1, is_ntt);
         utils::DynamicArray ws((bytes + 7) / 8, true, pool);
@@ -2816,13 +2843,14 @@ void Evaluator::rotate_sum_each(const std::vector<const Ciphertext*>& encrypted,
 //    double_hoisted: troyn_linear_transform_bsgs_double_hoisted, the inner c0 is not divided --
 void Evaluator::apply_galois_bsgs(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
                                   const GaloisKeys& galois_keys, const std::vector<std::vector<const Plaintext*>>& weights, Ciphertext& destination,
-                                  MemoryPoolHandle pool, bool double_hoisted) const {
+                                  MemoryPoolHandle pool, bool double_hoisted, bool bgv) const {
     if (baby_elements.empty() || giant_elements.empty()) throw std::invalid_argument(std::string(P) + " Empty element list.");
     if (weights.size() != giant_elements.size()) throw std::invalid_argument(std::string(P) + " One weight row per giant step is needed.");
     auto cd = get_context_data(P, encrypted.parms_id());
     const SchemeType scheme = cd->parms().scheme();
-    if (scheme == SchemeType::BGV) throw std::invalid_argument(std::string(P) + " BGV is not supported: its key switch divides by the special prime differently.");
+    hoisted_scheme_check(P, scheme, bgv);
     if (encrypted.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " Ciphertext size must be 2.");
+    bgv_ntt_form_check(P, bgv, encrypted);
     check_no_seed(P, encrypted);
     check_on_device(P, context_, encrypted);
     const size_t n = cd->parms().poly_modulus_degree();
@@ -2837,7 +2865,10 @@ void Evaluator::apply_galois_bsgs(const char* P, const Ciphertext& encrypted, co
     if (scheme == SchemeType::CKKS && !is_scale_within_bounds(scale, cd)) throw std::invalid_argument(std::string(P) + " Scale out of bounds.");
     Ciphertext d = Ciphertext::like(encrypted, false, pool);
     d.scale() = scale;
-    {
+    if (bgv) {
+        detail::bgv_linear_transform_bsgs_step(on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, encrypted.data().raw_pointer(), belements.data(),
+                                               bkeys.data(), babies, gelements.data(), gkeys.data(), giants, wptrs.data(), d.data().raw_pointer(), 1);
+    } else {
         const int is_ckks = scheme == SchemeType::CKKS, is_ntt = encrypted.is_ntt_form() ? 1 : 0;
         const auto workspace_bytes = double_hoisted ? troyn_linear_transform_bsgs_double_hoisted_workspace_bytes : troyn_linear_transform_bsgs_workspace_bytes;
         const auto transform = double_hoisted ? troyn_linear_transform_bsgs_double_hoisted : troyn_linear_transform_bsgs;
@@ -2864,6 +2895,83 @@ void Evaluator::rotate_bsgs_sum_double_hoisted(const Ciphertext& encrypted, cons
     const char* P = "[Evaluator::rotate_bsgs_sum_double_hoisted]";
     apply_galois_bsgs(P, encrypted, hoisted_elements_from_steps(P, encrypted, baby_steps), hoisted_elements_from_steps(P, encrypted, giant_steps), galois_keys,
                       weights, destination, pool, true);
+}
+
+// -- the hoisted family on BGV contexts (additions; troy.h): the same helpers with the troyn_bgv_* entries behind their device steps --
+void Evaluator::bgv_apply_galois_many(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                      std::vector<Ciphertext>& destination, MemoryPoolHandle pool) const {
+    apply_galois_hoisted("[Evaluator::bgv_apply_galois_many]", encrypted, galois_elements, false, galois_keys, false, destination, pool, true);
+}
+
+void Evaluator::bgv_apply_galois_sum(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys, Ciphertext& destination,
+                                     MemoryPoolHandle pool) const {
+    std::vector<Ciphertext> d;
+    apply_galois_hoisted("[Evaluator::bgv_apply_galois_sum]", encrypted, galois_elements, false, galois_keys, true, d, pool, true);
+    destination = std::move(d[0]);
+}
+
+void Evaluator::bgv_rotate_many(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, std::vector<Ciphertext>& destination,
+                                MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::bgv_rotate_many]";
+    apply_galois_hoisted(P, encrypted, hoisted_elements_from_steps(P, encrypted, steps), true, galois_keys, false, destination, pool, true);
+}
+
+void Evaluator::bgv_rotate_sum(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, Ciphertext& destination,
+                               MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::bgv_rotate_sum]";
+    std::vector<Ciphertext> d;
+    apply_galois_hoisted(P, encrypted, hoisted_elements_from_steps(P, encrypted, steps), true, galois_keys, true, d, pool, true);
+    destination = std::move(d[0]);
+}
+
+void Evaluator::bgv_apply_galois_weighted_sums(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                               const std::vector<WeightRow>& weights, std::vector<Ciphertext>& destination, MemoryPoolHandle pool) const {
+    apply_galois_weighted("[Evaluator::bgv_apply_galois_weighted_sums]", encrypted, galois_elements, galois_keys, weights, destination, pool, true);
+}
+
+void Evaluator::bgv_apply_galois_weighted_sum(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                              const WeightRow& weights, Ciphertext& destination, MemoryPoolHandle pool) const {
+    std::vector<Ciphertext> d;
+    apply_galois_weighted("[Evaluator::bgv_apply_galois_weighted_sum]", encrypted, galois_elements, galois_keys, {weights}, d, pool, true);
+    destination = std::move(d[0]);
+}
+
+void Evaluator::bgv_rotate_weighted_sums(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights,
+                                         std::vector<Ciphertext>& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::bgv_rotate_weighted_sums]";
+    apply_galois_weighted(P, encrypted, hoisted_elements_from_steps(P, encrypted, steps), galois_keys, weights, destination, pool, true);
+}
+
+void Evaluator::bgv_rotate_weighted_sum(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const WeightRow& weights,
+                                        Ciphertext& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::bgv_rotate_weighted_sum]";
+    std::vector<Ciphertext> d;
+    apply_galois_weighted(P, encrypted, hoisted_elements_from_steps(P, encrypted, steps), galois_keys, {weights}, d, pool, true);
+    destination = std::move(d[0]);
+}
+
+void Evaluator::bgv_apply_galois_sum_each(const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                          Ciphertext& destination, MemoryPoolHandle pool) const {
+    apply_galois_each("[Evaluator::bgv_apply_galois_sum_each]", encrypted, galois_elements, galois_keys, destination, pool, true);
+}
+
+void Evaluator::bgv_rotate_sum_each(const std::vector<const Ciphertext*>& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                                    Ciphertext& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::bgv_rotate_sum_each]";
+    if (encrypted.empty() || !encrypted[0]) throw std::invalid_argument(std::string(P) + " Empty ciphertext list.");
+    apply_galois_each(P, encrypted, hoisted_elements_from_steps(P, *encrypted[0], steps), galois_keys, destination, pool, true);
+}
+
+void Evaluator::bgv_apply_galois_bsgs_sum(const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
+                                          const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights, Ciphertext& destination, MemoryPoolHandle pool) const {
+    apply_galois_bsgs("[Evaluator::bgv_apply_galois_bsgs_sum]", encrypted, baby_elements, giant_elements, galois_keys, weights, destination, pool, false, true);
+}
+
+void Evaluator::bgv_rotate_bsgs_sum(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps, const GaloisKeys& galois_keys,
+                                    const std::vector<WeightRow>& weights, Ciphertext& destination, MemoryPoolHandle pool) const {
+    const char* P = "[Evaluator::bgv_rotate_bsgs_sum]";
+    apply_galois_bsgs(P, encrypted, hoisted_elements_from_steps(P, encrypted, baby_steps), hoisted_elements_from_steps(P, encrypted, giant_steps), galois_keys,
+                      weights, destination, pool, false, true);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1807,6 +1807,89 @@ public:
         Ciphertext d; rotate_bsgs_sum_double_hoisted(encrypted, baby_steps, giant_steps, galois_keys, weights, d, pool); return d;
     }
 
+    // ADDITION to the reference's interface: the hoisted family above on BGV contexts (troyn_bgv_apply_galois_many / _sum / _weighted_sums / _sum_each and
+    //   troyn_bgv_linear_transform_bsgs, include/troyn.h: the same inner products, the tail of BGV's key switch -- the mod-t correction of the special
+    //   row, then the division by the special prime).  bgv_NAME is NAME for a BGV context: the same arguments, the same checks and refusals (missing
+    //   key, empty list, the identity where NAME refuses it), the same sums before ONE division; every result decrypts to exactly what rotate_rows /
+    //   apply_galois, multiply_plain and add decrypt to.  BGV contexts only (BFV and CKKS: NAME; std::invalid_argument names it); operands in NTT
+    //   form, as BGV ciphertexts are; the result carries the input's correction factor (the tail is that of apply_galois, which keeps it), and
+    //   bgv_*_sum_each refuses inputs whose correction factors differ.  Weights as for rotate_weighted_sums: key level, NTT form
+    //   (transform_plain_to_ntt_new(encode_simd_new(x), key_parms_id), the preparation the BFV methods take).  There is no double-hoisted BGV form.
+    // Call combining does not take part: these methods always launch directly.
+    void bgv_apply_galois_many(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys, std::vector<Ciphertext>& destination,
+                               MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::vector<Ciphertext> bgv_apply_galois_many_new(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                                      MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; bgv_apply_galois_many(encrypted, galois_elements, galois_keys, d, pool); return d;
+    }
+    void bgv_apply_galois_sum(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys, Ciphertext& destination,
+                              MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bgv_apply_galois_sum_new(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                        MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bgv_apply_galois_sum(encrypted, galois_elements, galois_keys, d, pool); return d;
+    }
+    void bgv_rotate_many(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, std::vector<Ciphertext>& destination,
+                         MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::vector<Ciphertext> bgv_rotate_many_new(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                                                MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; bgv_rotate_many(encrypted, steps, galois_keys, d, pool); return d;
+    }
+    void bgv_rotate_sum(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, Ciphertext& destination,
+                        MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bgv_rotate_sum_new(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                                  MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bgv_rotate_sum(encrypted, steps, galois_keys, d, pool); return d;
+    }
+    void bgv_apply_galois_weighted_sums(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                        const std::vector<WeightRow>& weights, std::vector<Ciphertext>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::vector<Ciphertext> bgv_apply_galois_weighted_sums_new(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                                               const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; bgv_apply_galois_weighted_sums(encrypted, galois_elements, galois_keys, weights, d, pool); return d;
+    }
+    void bgv_apply_galois_weighted_sum(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                       const WeightRow& weights, Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bgv_apply_galois_weighted_sum_new(const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                                 const WeightRow& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bgv_apply_galois_weighted_sum(encrypted, galois_elements, galois_keys, weights, d, pool); return d;
+    }
+    void bgv_rotate_weighted_sums(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights,
+                                  std::vector<Ciphertext>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::vector<Ciphertext> bgv_rotate_weighted_sums_new(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                                                         const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; bgv_rotate_weighted_sums(encrypted, steps, galois_keys, weights, d, pool); return d;
+    }
+    void bgv_rotate_weighted_sum(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const WeightRow& weights,
+                                 Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bgv_rotate_weighted_sum_new(const Ciphertext& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, const WeightRow& weights,
+                                           MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bgv_rotate_weighted_sum(encrypted, steps, galois_keys, weights, d, pool); return d;
+    }
+    void bgv_apply_galois_sum_each(const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                   Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bgv_apply_galois_sum_each_new(const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
+                                             MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bgv_apply_galois_sum_each(encrypted, galois_elements, galois_keys, d, pool); return d;
+    }
+    void bgv_rotate_sum_each(const std::vector<const Ciphertext*>& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys, Ciphertext& destination,
+                             MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bgv_rotate_sum_each_new(const std::vector<const Ciphertext*>& encrypted, const std::vector<int>& steps, const GaloisKeys& galois_keys,
+                                       MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bgv_rotate_sum_each(encrypted, steps, galois_keys, d, pool); return d;
+    }
+    void bgv_apply_galois_bsgs_sum(const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
+                                   const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights, Ciphertext& destination,
+                                   MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bgv_apply_galois_bsgs_sum_new(const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
+                                             const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bgv_apply_galois_bsgs_sum(encrypted, baby_elements, giant_elements, galois_keys, weights, d, pool); return d;
+    }
+    void bgv_rotate_bsgs_sum(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps, const GaloisKeys& galois_keys,
+                             const std::vector<WeightRow>& weights, Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bgv_rotate_bsgs_sum_new(const Ciphertext& encrypted, const std::vector<int>& baby_steps, const std::vector<int>& giant_steps, const GaloisKeys& galois_keys,
+                                       const std::vector<WeightRow>& weights, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bgv_rotate_bsgs_sum(encrypted, baby_steps, giant_steps, galois_keys, weights, d, pool); return d;
+    }
+
     // ciphertext x plaintext -- evaluator.h (multiply_plain*, transform_plain_to_ntt*); evaluator_multiply_plain.cu,
     // evaluator_transform_ntt.cu:35-70
     void transform_plain_to_ntt(const Plaintext& plain, const ParmsID& parms_id, Plaintext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -2056,11 +2139,11 @@ private:
     const troyn_bgv* key_level_bgv(SchemeType scheme) const;
     // the hoisted rotations (addition): out = one ciphertext per element, or their sum in out[0]; element 1 (allow_identity: a step of 0) is the ciphertext itself
     void apply_galois_hoisted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, bool allow_identity, const GaloisKeys& galois_keys,
-                              bool sum, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const;
+                              bool sum, std::vector<Ciphertext>& out, MemoryPoolHandle pool, bool bgv = false) const;   // bgv: the bgv_ methods (BGV contexts only)
     std::vector<size_t> hoisted_elements_from_steps(const char* P, const Ciphertext& encrypted, const std::vector<int>& steps) const;
     // the weighted sums (addition): out[s] = SUM_t weights[s][t] * sigma_{elements[t]}(encrypted); element 1 is the ciphertext itself
     void apply_galois_weighted(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
-                               const std::vector<std::vector<const Plaintext*>>& weights, std::vector<Ciphertext>& out, MemoryPoolHandle pool) const;
+                               const std::vector<std::vector<const Plaintext*>>& weights, std::vector<Ciphertext>& out, MemoryPoolHandle pool, bool bgv = false) const;
     // the tables the weighted, _each and BSGS methods hand to the library: elements with their key pointers, and the checked weight pointers (returns the weights' scale)
     void hoisted_key_table(const char* P, const Ciphertext& like, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys, uint32_t L,
                            std::vector<uint64_t>& elements, std::vector<const uint64_t*>& keys, MemoryPoolHandle pool) const;
@@ -2068,10 +2151,10 @@ private:
                         std::vector<const uint64_t*>& wptrs) const;
     // the sum over different ciphertexts and the baby-step/giant-step transform (additions)
     void apply_galois_each(const char* P, const std::vector<const Ciphertext*>& encrypted, const std::vector<size_t>& galois_elements, const GaloisKeys& galois_keys,
-                           Ciphertext& destination, MemoryPoolHandle pool) const;
+                           Ciphertext& destination, MemoryPoolHandle pool, bool bgv = false) const;
     void apply_galois_bsgs(const char* P, const Ciphertext& encrypted, const std::vector<size_t>& baby_elements, const std::vector<size_t>& giant_elements,
                            const GaloisKeys& galois_keys, const std::vector<std::vector<const Plaintext*>>& weights, Ciphertext& destination,
-                           MemoryPoolHandle pool, bool double_hoisted = false) const;
+                           MemoryPoolHandle pool, bool double_hoisted = false, bool bgv = false) const;
     void switch_key_internal(const Ciphertext& encrypted, const uint64_t* target, const KSwitchKeys& kswitch_keys, size_t kswitch_keys_index,
                              SwitchKeyDestinationAssignMethod assign_method, Ciphertext& destination, MemoryPoolHandle pool) const;
     void relinearize_inplace_internal(Ciphertext& encrypted, const RelinKeys& relin_keys, size_t destination_size, MemoryPoolHandle pool) const;
