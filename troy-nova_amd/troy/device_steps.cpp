@@ -1,4 +1,4 @@
-// The Evaluator's device steps (device_steps.h): workspace from the pool, then the C-ABI entry.  No argument checks, no Ciphertext.
+// The mirror's device steps (device_steps.h): workspace from the pool, then the C-ABI entry.  No argument checks, no Ciphertext.
 #include "device_steps.h"
 
 #include <hip/hip_runtime.h>
@@ -159,46 +159,139 @@ void bgv_multiply_relinearize_mod_switch_step(const StepEnv& env, const troyn_bg
     env.check(troyn_bgv_multiply_relinearize_mod_switch(key_level, level, a, b, keys, out, ws.raw_pointer(), bytes, count, env.stream));
 }
 
-void bgv_apply_galois_many_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
-                                const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count) {
+void apply_galois_many_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                            const uint64_t* elements, const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count) {
     const size_t bytes = troyn_apply_galois_hoisted_workspace_bytes(plan, L, terms, count, 0);
     utils::DynamicArray ws = workspace(env, bytes);
     LaunchGate gate(env.gated);
-    env.check(troyn_bgv_apply_galois_many(key_level, L, ct, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+    if (bgv) env.check(troyn_bgv_apply_galois_many(bgv, L, ct, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+    else env.check(troyn_apply_galois_many(plan, L, ckks, ntt_form, ct, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
 }
 
-void bgv_apply_galois_sum_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
-                               const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count) {
+void apply_galois_sum_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                           const uint64_t* elements, const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count) {
     const size_t bytes = troyn_apply_galois_hoisted_workspace_bytes(plan, L, terms, count, 1);
     utils::DynamicArray ws = workspace(env, bytes);
     LaunchGate gate(env.gated);
-    env.check(troyn_bgv_apply_galois_sum(key_level, L, ct, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+    if (bgv) env.check(troyn_bgv_apply_galois_sum(bgv, L, ct, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+    else env.check(troyn_apply_galois_sum(plan, L, ckks, ntt_form, ct, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
 }
 
-void bgv_apply_galois_weighted_sums_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
-                                         const uint64_t* const* keys, size_t terms, const uint64_t* const* weights, size_t slots, uint64_t* out, size_t count) {
-    const size_t bytes = troyn_apply_galois_weighted_workspace_bytes(plan, L, terms, slots, count, 1);
+void apply_galois_weighted_sums_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                                     const uint64_t* elements, const uint64_t* const* keys, size_t terms, const uint64_t* const* weights, size_t slots, uint64_t* out,
+                                     size_t count) {
+    const size_t bytes = troyn_apply_galois_weighted_workspace_bytes(plan, L, terms, slots, count, ntt_form ? 1 : 0);
     utils::DynamicArray ws = workspace(env, bytes);
     LaunchGate gate(env.gated);
-    env.check(troyn_bgv_apply_galois_weighted_sums(key_level, L, ct, elements, keys, terms, weights, slots, out, ws.raw_pointer(), bytes, count, env.stream));
+    if (bgv) env.check(troyn_bgv_apply_galois_weighted_sums(bgv, L, ct, elements, keys, terms, weights, slots, out, ws.raw_pointer(), bytes, count, env.stream));
+    else env.check(troyn_apply_galois_weighted_sums(plan, L, ckks, ntt_form, ct, elements, keys, terms, weights, slots, out, ws.raw_pointer(), bytes, count, env.stream));
 }
 
-void bgv_apply_galois_sum_each_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* cts, const uint64_t* elements,
-                                    const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count) {
-    const size_t bytes = troyn_apply_galois_sum_each_workspace_bytes(plan, L, terms, count, 1);
+void apply_galois_sum_each_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* cts,
+                                const uint64_t* elements, const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_apply_galois_sum_each_workspace_bytes(plan, L, terms, count, ntt_form ? 1 : 0);
     utils::DynamicArray ws = workspace(env, bytes);
     LaunchGate gate(env.gated);
-    env.check(troyn_bgv_apply_galois_sum_each(key_level, L, cts, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+    if (bgv) env.check(troyn_bgv_apply_galois_sum_each(bgv, L, cts, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+    else env.check(troyn_apply_galois_sum_each(plan, L, ckks, ntt_form, cts, elements, keys, terms, out, ws.raw_pointer(), bytes, count, env.stream));
 }
 
-void bgv_linear_transform_bsgs_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* baby_elements,
-                                    const uint64_t* const* baby_keys, size_t babies, const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
-                                    const uint64_t* const* weights, uint64_t* out, size_t count) {
-    const size_t bytes = troyn_linear_transform_bsgs_workspace_bytes(plan, L, babies, giants, count, 1);
+void linear_transform_bsgs_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                                const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies, const uint64_t* giant_elements,
+                                const uint64_t* const* giant_keys, size_t giants, const uint64_t* const* weights, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_linear_transform_bsgs_workspace_bytes(plan, L, babies, giants, count, ntt_form ? 1 : 0);
     utils::DynamicArray ws = workspace(env, bytes);
     LaunchGate gate(env.gated);
-    env.check(troyn_bgv_linear_transform_bsgs(key_level, L, ct, baby_elements, baby_keys, babies, giant_elements, giant_keys, giants, weights, out, ws.raw_pointer(),
-                                              bytes, count, env.stream));
+    if (bgv)
+        env.check(troyn_bgv_linear_transform_bsgs(bgv, L, ct, baby_elements, baby_keys, babies, giant_elements, giant_keys, giants, weights, out, ws.raw_pointer(), bytes,
+                                                  count, env.stream));
+    else
+        env.check(troyn_linear_transform_bsgs(plan, L, ckks, ntt_form, ct, baby_elements, baby_keys, babies, giant_elements, giant_keys, giants, weights, out,
+                                              ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void linear_transform_bsgs_double_hoisted_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                                               const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies, const uint64_t* giant_elements,
+                                               const uint64_t* const* giant_keys, size_t giants, const uint64_t* const* weights, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_linear_transform_bsgs_double_hoisted_workspace_bytes(plan, L, babies, giants, count, ntt_form ? 1 : 0);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_linear_transform_bsgs_double_hoisted(plan, L, ckks, ntt_form, ct, baby_elements, baby_keys, babies, giant_elements, giant_keys, giants, weights, out,
+                                                         ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void multiply_accumulate_relinearize_rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* const* a, const uint64_t* const* b, size_t terms,
+                                                  const uint64_t* const* keys, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_ckks_multiply_accumulate_relinearize_rescale_workspace_bytes(plan, L, terms, count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_ckks_multiply_accumulate_relinearize_rescale(plan, L, a, b, terms, keys, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void multiply_affine_relinearize_rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* const* a, const uint64_t* const* b,
+                                              const uint64_t* const* c, const uint32_t* c_nmod, const uint64_t* alpha, const uint64_t* weight, const uint64_t* constant,
+                                              const uint64_t* const* keys, uint64_t* out, size_t count) {
+    const size_t bytes = troyn_ckks_multiply_affine_relinearize_rescale_workspace_bytes(plan, L, count);
+    // (one spare word, as before the step: the entry rounds the offset of its 16-byte-aligned table inside its own byte count and needs none)
+    utils::DynamicArray ws((bytes + 15) / 8, true, env.pool);
+    LaunchGate gate(env.gated);
+    env.check(troyn_ckks_multiply_affine_relinearize_rescale(plan, L, a, b, c, c_nmod, alpha, weight, constant, keys, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void bfv_multiply_accumulate_step(const StepEnv& env, const troyn_behz* behz, const uint64_t* const* a, const uint64_t* const* b, size_t terms, const uint64_t* const* keys,
+                                  uint64_t* out, size_t count) {
+    const size_t bytes = keys ? troyn_bfv_multiply_accumulate_relinearize_workspace_bytes(behz, terms, count) : troyn_bfv_multiply_accumulate_workspace_bytes(behz, terms, count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    if (keys) env.check(troyn_bfv_multiply_accumulate_relinearize(behz, a, b, terms, keys, out, ws.raw_pointer(), bytes, count, env.stream));
+    else env.check(troyn_bfv_multiply_accumulate(behz, a, b, terms, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void scalar_weighted_sums_step(const StepEnv& env, const troyn_plan* plan, uint32_t nmod, const uint64_t* const* ins, const uint32_t* in_nmod, size_t terms,
+                               const uint64_t* scalars, const uint64_t* constants, size_t pcount, uint64_t* out, size_t slots) {
+    const size_t bytes = troyn_scalar_weighted_sums_workspace_bytes(plan, nmod, terms, slots);
+    // (one spare word, as before the step: the entry's byte count is a whole number of words and it aligns nothing inside the workspace)
+    utils::DynamicArray ws((bytes + 15) / 8, true, env.pool);
+    LaunchGate gate(env.gated);
+    env.check(troyn_scalar_weighted_sums(plan, 0, nmod, ins, in_nmod, terms, scalars, constants, 0, pcount, out, slots, 1, ws.raw_pointer(), bytes, env.stream));
+}
+
+void multiply_plain_accumulate_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, size_t polys, const uint64_t* const* cts, const uint64_t* const* pts,
+                                    uint64_t* const* dsts, size_t count, bool set_zero) {
+    const size_t bytes = troyn_multiply_plain_accumulate_workspace_bytes(count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_multiply_plain_accumulate(plan, 0, L, polys, cts, pts, dsts, count, set_zero ? 1 : 0, ws.raw_pointer(), bytes, env.stream));
+}
+
+void ckks_encode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const double* values, size_t row, double scale, uint64_t* out, uint32_t* flags,
+                      size_t count) {
+    const size_t bytes = troyn_ckks_encode_workspace_bytes(ckks, count);
+    utils::DynamicArray ws((bytes + 7) / 8 + 2, true, env.pool);     // (two spare words, as before the step)
+    LaunchGate gate(env.gated);
+    env.check((simd ? troyn_ckks_encode_simd : troyn_ckks_encode_polynomial)(ckks, L, values, row, scale, out, flags, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void ckks_decode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const uint64_t* in, double scale, double* out, size_t count) {
+    const size_t bytes = troyn_ckks_workspace_bytes(ckks, L, count);
+    utils::DynamicArray ws((bytes + 7) / 8 + 2, true, env.pool);     // (two spare words, as before the step)
+    LaunchGate gate(env.gated);
+    env.check((simd ? troyn_ckks_decode_simd : troyn_ckks_decode_polynomial)(ckks, L, in, scale, out, ws.raw_pointer(), bytes, count, env.stream));
+}
+
+void extract_lwe_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* const* srcs, const size_t* terms, uint64_t* c0, uint64_t* c1, size_t count) {
+    const size_t bytes = troyn_extract_lwe_workspace_bytes(count);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_extract_lwe(plan, L, srcs, terms, c0, c1, count, ws.raw_pointer(), bytes, env.stream));
+}
+
+void pack_prepare_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, size_t polys, const uint64_t* const* srcs, size_t slots, uint64_t mul, size_t shift,
+                       uint64_t* out) {
+    const size_t bytes = troyn_pack_prepare_workspace_bytes(slots);
+    utils::DynamicArray ws = workspace(env, bytes);
+    LaunchGate gate(env.gated);
+    env.check(troyn_pack_prepare(plan, L, polys, srcs, slots, mul, shift, out, ws.raw_pointer(), bytes, env.stream));
 }
 
 }  // namespace detail

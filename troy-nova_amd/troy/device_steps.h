@@ -1,10 +1,14 @@
-// The device steps of the Evaluator: ONE function per operation sizes the workspace, takes it from the pool and calls the C-ABI
+// The device steps of the mirror: ONE function per C-ABI operation sizes the workspace, takes it from the pool and calls the C-ABI
 // (include/troyn.h).  The per-object methods (troy.cpp, lwe.cpp) call a step with count = 1 on the calling thread's stream, the
 // *_batched forms (batched.cpp) with the batch's count, the call-combining rendezvous (combine.cpp) on the shared stream.  A step
 // checks no Ciphertext and touches none: the callers' *_prepare functions have done the checks and shaped the result.
 //
-// Rule: each C-ABI entry named below is called from exactly one function of the mirror -- its step.  A change to an entry's
-// workspace contract is a change to one function.
+// Rule: every C-ABI entry that takes a workspace is called from exactly one function of the mirror -- its step in device_steps.cpp --
+// and no other file asks for a workspace size.  A change to an entry's workspace contract is a change to one function
+// (tests/test_device_steps_rule.py reads the sources and holds the mirror to this).  The entries without a workspace that the Evaluator's
+// operations use have their steps here too.  The one exception class: entries WITHOUT a workspace may be called directly where no
+// Evaluator operation stands behind them -- the plaintext paths of plain_ops.cpp, ring2k.cpp and matmul.cpp, and what the encryptor,
+// decryptor, encoders, key generator and packing tree do with troyn_ntt, troyn_add, troyn_negate and troyn_apply_galois.
 //
 // Operands are [count][...] contiguous words on the device; `out` may alias an input only where the entry allows it.
 #pragma once
@@ -78,21 +82,56 @@ void multiply_relinearize_rescale_step(const StepEnv& env, const troyn_plan* pla
 void bgv_multiply_relinearize_mod_switch_step(const StepEnv& env, const troyn_bgv* key_level, const troyn_bgv* level, uint32_t L, const uint64_t* a, const uint64_t* b,
                                               const uint64_t* const* keys, uint64_t* out, size_t count);
 
-// BGV hoisted family (troyn_bgv_apply_galois_* / troyn_bgv_linear_transform_bsgs): operands in NTT form at level L, `key_level` the key level's handle;
-// the workspaces are those of the BFV / CKKS namesakes with is_ntt_form = 1.  ct is [count][2][L][N]; keys [terms][L] (null rows for the element 1 where
-// the entry takes it); weights [slots][terms] / [giants][babies] key-level NTT rows or null
-void bgv_apply_galois_many_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
-                                const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count);     // out [count][terms][2][L][N]
-void bgv_apply_galois_sum_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
-                               const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count);      // out [count][2][L][N]
-void bgv_apply_galois_weighted_sums_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* elements,
-                                         const uint64_t* const* keys, size_t terms, const uint64_t* const* weights, size_t slots, uint64_t* out, size_t count);
+// Hoisted family (troyn_apply_galois_* / troyn_linear_transform_bsgs and their troyn_bgv_* forms): `bgv` (the key level's handle) selects the BGV entry,
+// whose operands are in NTT form (ntt_form = true); the workspaces are the plan's for all three schemes.  ct is [count][2][L][N]; keys [terms][L] (null rows
+// for the element 1 where the entry takes it); weights [slots][terms] / [giants][babies] key-level NTT rows or null
+void apply_galois_many_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                            const uint64_t* elements, const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count);     // out [count][terms][2][L][N]
+void apply_galois_sum_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                           const uint64_t* elements, const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count);      // out [count][2][L][N]
+void apply_galois_weighted_sums_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                                     const uint64_t* elements, const uint64_t* const* keys, size_t terms, const uint64_t* const* weights, size_t slots, uint64_t* out,
+                                     size_t count);
 // cts [count][terms][2][L][N], one ciphertext per term
-void bgv_apply_galois_sum_each_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* cts, const uint64_t* elements,
-                                    const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count);
-void bgv_linear_transform_bsgs_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* key_level, uint32_t L, const uint64_t* ct, const uint64_t* baby_elements,
-                                    const uint64_t* const* baby_keys, size_t babies, const uint64_t* giant_elements, const uint64_t* const* giant_keys, size_t giants,
-                                    const uint64_t* const* weights, uint64_t* out, size_t count);
+void apply_galois_sum_each_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* cts,
+                                const uint64_t* elements, const uint64_t* const* keys, size_t terms, uint64_t* out, size_t count);
+void linear_transform_bsgs_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                                const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies, const uint64_t* giant_elements,
+                                const uint64_t* const* giant_keys, size_t giants, const uint64_t* const* weights, uint64_t* out, size_t count);
+// the same transform without the inner c0 divisions; BFV / CKKS only (the library has no BGV form)
+void linear_transform_bsgs_double_hoisted_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, bool ckks, bool ntt_form, const uint64_t* ct,
+                                               const uint64_t* baby_elements, const uint64_t* const* baby_keys, size_t babies, const uint64_t* giant_elements,
+                                               const uint64_t* const* giant_keys, size_t giants, const uint64_t* const* weights, uint64_t* out, size_t count);
+
+// Inner products: `a`, `b` are HOST tables of `terms` device pointers, each to [count] operands; out [count][...]
+// CKKS: SUM_t a_t * b_t -> relinearize -> rescale, out [count][2][L - 1][N]
+void multiply_accumulate_relinearize_rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* const* a, const uint64_t* const* b, size_t terms,
+                                                  const uint64_t* const* keys, uint64_t* out, size_t count);
+// CKKS: alpha * a * b + weight * c + constant -> relinearize -> rescale per item: a, b, c host tables of `count` device pointers (c: null for no addend),
+// the per-limb residue tables [count][L] prepared by the caller, out [count][2][L - 1][N]
+void multiply_affine_relinearize_rescale_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* const* a, const uint64_t* const* b,
+                                              const uint64_t* const* c, const uint32_t* c_nmod, const uint64_t* alpha, const uint64_t* weight, const uint64_t* constant,
+                                              const uint64_t* const* keys, uint64_t* out, size_t count);
+// BFV: the sum of BEHZ tensor products scaled down once, out [count][3][L][N]; with `keys` relinearized as well, out [count][2][L][N]
+void bfv_multiply_accumulate_step(const StepEnv& env, const troyn_behz* behz, const uint64_t* const* a, const uint64_t* const* b, size_t terms, const uint64_t* const* keys,
+                                  uint64_t* out, size_t count);
+// out[s] = SUM_t scalars[s][t] * in_t (+ constants[s]) on `pcount` polynomials: the host tables [slots][terms][nmod] / [slots][nmod] (or null) are residues already
+void scalar_weighted_sums_step(const StepEnv& env, const troyn_plan* plan, uint32_t nmod, const uint64_t* const* ins, const uint32_t* in_nmod, size_t terms,
+                               const uint64_t* scalars, const uint64_t* constants, size_t pcount, uint64_t* out, size_t slots);
+// dsts[i] (+)= cts[i] * pts[i] over host pointer tables of `count` items, NTT form
+void multiply_plain_accumulate_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, size_t polys, const uint64_t* const* cts, const uint64_t* const* pts,
+                                    uint64_t* const* dsts, size_t count, bool set_zero);
+
+// The CKKS encoder on the device (troyn_ckks_encode_* / troyn_ckks_decode_*): `simd` selects the slot form, else the coefficient form.
+// values [count][row] doubles (row complex values / doubles per item), out [count][L][N] NTT form, flags [count] (non-zero: too large)
+void ckks_encode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const double* values, size_t row, double scale, uint64_t* out, uint32_t* flags,
+                      size_t count);
+void ckks_decode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const uint64_t* in, double scale, double* out, size_t count);
+
+// LWE (lwe.cpp): coefficient `terms[i]` of srcs[i] as an LWE ciphertext, c0 [count][L] and c1 [count][L][N]; the leaves of the packing tree
+void extract_lwe_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* const* srcs, const size_t* terms, uint64_t* c0, uint64_t* c1, size_t count);
+void pack_prepare_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, size_t polys, const uint64_t* const* srcs, size_t slots, uint64_t mul, size_t shift,
+                       uint64_t* out);
 
 #pragma GCC visibility pop
 }  // namespace detail

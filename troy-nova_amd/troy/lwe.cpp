@@ -199,9 +199,7 @@ LWECiphertext Evaluator::extract_lwe_new(const Ciphertext& encrypted, size_t ter
     ret.c0_dyn() = utils::DynamicArray(L, true, pool);
     ret.c1_dyn() = utils::DynamicArray(static_cast<size_t>(L) * n, true, pool);
     const uint64_t* src = encrypted.data().raw_pointer();
-    const size_t bytes = troyn_extract_lwe_workspace_bytes(1);
-    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-    troyn_check_public(troyn_extract_lwe(context_->plan(), L, &src, &term, ret.c0_dyn().raw_pointer(), ret.c1_dyn().raw_pointer(), 1, ws.raw_pointer(), bytes, stream()));
+    detail::extract_lwe_step(detail::on_current_stream(pool), context_->plan(), L, &src, &term, ret.c0_dyn().raw_pointer(), ret.c1_dyn().raw_pointer(), 1);
     troyn_sync_current_stream();
     ret.parms_id() = encrypted.parms_id();
     ret.scale() = encrypted.scale();
@@ -438,11 +436,8 @@ void Evaluator::pack_rlwe_ciphertexts_batched(const std::vector<std::vector<cons
         flat += cipher_groups[j].size();
     }
     auto current = std::make_shared<utils::DynamicArray>(slots * words, true, pool);
-    {
-        const size_t bytes = troyn_pack_prepare_workspace_bytes(slots);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-        troyn_check_public(troyn_pack_prepare(plan, L, 2, src.data(), slots, n / input_interval, shift, current->raw_pointer(), ws.raw_pointer(), bytes, s));
-    }
+    const detail::StepEnv env{pool, s, troyn_check_public};
+    detail::pack_prepare_step(env, plan, L, 2, src.data(), slots, n / input_interval, shift, current->raw_pointer());
     size_t count = slots;
     for (size_t layer = 0; layer < layers; layer++) {
         const size_t pairs = count / 2;
@@ -452,7 +447,6 @@ void Evaluator::pack_rlwe_ciphertexts_batched(const std::vector<std::vector<cons
         troyn_check_public(troyn_pack_layer(plan, L, g, input_interval >> (layer + 1), current->raw_pointer(), next->raw_pointer(), target.raw_pointer(), pairs, s));
         const std::vector<const uint64_t*> keys = automorphism_keys.get_data_ptrs(GaloisKeys::get_index(g));
         if (keys.size() < L) throw std::invalid_argument("[Evaluator::switch_key_inplace_internal] Key switching key has too few components for this level.");
-        const detail::StepEnv env{pool, s, troyn_check_public};
         if (scheme == SchemeType::BGV) {
             // BGV key switching is defined on NTT-form operands (its tail removes the special prime AND keeps the result a multiple of t:
             // ski_util5, evaluator_keyswitching_core.cu:998-1030), so the reference transforms the odd member around apply_galois

@@ -1759,13 +1759,8 @@ void Evaluator::multiply_accumulate_relinearize_rescale(const std::vector<const 
     out.parms_id() = next0;
     out.scale() = scale0;
     out.is_ntt_form() = true;
-    const size_t bytes = troyn_ckks_multiply_accumulate_relinearize_rescale_workspace_bytes(context_->plan(), L0, a.size(), 1);
-    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-    {
-        detail::LaunchGate gate;
-        troyn_check(troyn_ckks_multiply_accumulate_relinearize_rescale(context_->plan(), L0, a.data(), b.data(), a.size(), keys0.data(), out.data().raw_pointer(),
-                                                                       ws.raw_pointer(), bytes, 1, current_stream()));
-    }
+    detail::multiply_accumulate_relinearize_rescale_step(on_current_stream(pool, true), context_->plan(), L0, a.data(), b.data(), a.size(), keys0.data(),
+                                                         out.data().raw_pointer(), 1);
     destination = std::move(out);
 }
 
@@ -1812,7 +1807,7 @@ __int128 scaled_integer(const char* P, double c, double factor, int limit_bits, 
     if (!(fabsl(v) < ldexpl(1.0L, limit_bits))) throw std::invalid_argument(std::string(P) + " A scaled coefficient does not fit in " + std::to_string(limit_bits) + " bits.");
     return (__int128)v;
 }
-// one troyn_scalar_weighted_sums over whole ciphertexts: ints [slots][terms] and consts [slots] (or empty) are reduced per limb here
+// one scalar_weighted_sums_step over whole ciphertexts: ints [slots][terms] and consts [slots] (or empty) are reduced per limb here
 void scalar_sums_on(const detail::StepEnv& env, const troyn_plan* plan, const std::vector<uint64_t>& moduli, uint32_t nmod, const std::vector<const Ciphertext*>& ins,
                     const std::vector<__int128>& ints, const std::vector<__int128>& consts, size_t slots, size_t pcount, uint64_t* out) {
     const size_t terms = ins.size();
@@ -1825,11 +1820,7 @@ void scalar_sums_on(const detail::StepEnv& env, const troyn_plan* plan, const st
             for (size_t t = 0; t < terms; t++) sc[(s * terms + t) * nmod + l] = signed_residue(ints[s * terms + t], moduli[l]);
             if (!consts.empty()) cs[s * nmod + l] = signed_residue(consts[s], moduli[l]);
         }
-    const size_t bytes = troyn_scalar_weighted_sums_workspace_bytes(plan, nmod, terms, slots);
-    utils::DynamicArray ws((bytes + 15) / 8, true, env.pool);
-    detail::LaunchGate gate(env.gated);
-    env.check(troyn_scalar_weighted_sums(plan, 0, nmod, ptrs.data(), in_nmod.data(), terms, sc.data(), consts.empty() ? nullptr : cs.data(), 0, pcount, out, slots, 1,
-                                         ws.raw_pointer(), bytes, env.stream));
+    detail::scalar_weighted_sums_step(env, plan, nmod, ptrs.data(), in_nmod.data(), terms, sc.data(), consts.empty() ? nullptr : cs.data(), pcount, out, slots);
 }
 }  // namespace
 
@@ -2016,14 +2007,10 @@ void Evaluator::paterson_stockmeyer(const char* P, const Ciphertext& x, size_t d
     for (size_t j = 0; j + 1 < g; j++) { a[j] = upper.raw_pointer() + j * leaf_words; b[j] = giants[j]->data().raw_pointer(); }
     Ciphertext out = Ciphertext::like(*giants[0], 2, Lrec - 1, false, pool);
     out.parms_id() = next; out.scale() = S; out.is_ntt_form() = true;
-    const size_t bytes = troyn_ckks_multiply_accumulate_relinearize_rescale_workspace_bytes(plan, L, a.size(), 1);
-    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-    {
-        detail::LaunchGate gate;
-        troyn_check(troyn_ckks_multiply_accumulate_relinearize_rescale(plan, L, a.data(), b.data(), a.size(), keys.data(), out.data().raw_pointer(), ws.raw_pointer(), bytes, 1,
-                                                                       env.stream));
-        troyn_check(troyn_add(plan, 0, static_cast<uint32_t>(Lrec - 1), out.data().raw_pointer(), leaf0.raw_pointer(), out.data().raw_pointer(), 2, env.stream));
-    }
+    detail::multiply_accumulate_relinearize_rescale_step(env, plan, L, a.data(), b.data(), a.size(), keys.data(), out.data().raw_pointer(), 1);
+    // leaf_0 is added outside the stream gate, which the step holds around the chain only: the gate is a throughput device for the threads that share a stream
+    // (LaunchGate, above), not an ordering one -- the add follows the chain in stream order
+    detail::add_sub_step(env, plan, static_cast<uint32_t>(Lrec - 1), false, out.data().raw_pointer(), leaf0.raw_pointer(), out.data().raw_pointer(), 2);
     destination = std::move(out);
 }
 
@@ -2078,15 +2065,10 @@ void Evaluator::multiply_affine_relinearize_rescale_batched(const std::vector<co
         }
     const size_t n = e1[0]->poly_modulus_degree(), words = 2 * (size_t)(L - 1) * n;
     utils::DynamicArray block(batch * words, true, pool);
-    const size_t bytes = troyn_ckks_multiply_affine_relinearize_rescale_workspace_bytes(context_->plan(), L, batch);
-    utils::DynamicArray ws((bytes + 15) / 8, true, pool);
     std::vector<Ciphertext> out(batch);
     const detail::StepEnv env = on_current_stream(pool, true);
-    {
-        detail::LaunchGate gate(env.gated);
-        env.check(troyn_ckks_multiply_affine_relinearize_rescale(context_->plan(), L, a.data(), b.data(), c.data(), c_nmod.data(), al.data(), w.data(), k.data(), keys.data(),
-                                                                 block.raw_pointer(), ws.raw_pointer(), bytes, batch, env.stream));
-    }
+    detail::multiply_affine_relinearize_rescale_step(env, context_->plan(), L, a.data(), b.data(), c.data(), c_nmod.data(), al.data(), w.data(), k.data(), keys.data(),
+                                                     block.raw_pointer(), batch);
     for (size_t i = 0; i < batch; i++) {
         out[i] = Ciphertext::like(*e1[i], 2, L - 1, false, pool);
         out[i].parms_id() = next; out[i].scale() = out_scale[i]; out[i].is_ntt_form() = true;
@@ -2220,13 +2202,8 @@ void Evaluator::bfv_multiply_accumulate(const std::vector<const Ciphertext*>& e1
     std::vector<const uint64_t*> a, b;
     bfv_multiply_accumulate_prepare("[Evaluator::bfv_multiply_accumulate]", e1, e2, a, b);
     Ciphertext out = Ciphertext::like(*e1[0], 3, false, pool);
-    const troyn_behz* bz = context_->behz(out.coeff_modulus_size());
-    const size_t bytes = troyn_bfv_multiply_accumulate_workspace_bytes(bz, a.size(), 1);
-    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-    {
-        detail::LaunchGate gate;
-        troyn_check(troyn_bfv_multiply_accumulate(bz, a.data(), b.data(), a.size(), out.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
-    }
+    detail::bfv_multiply_accumulate_step(on_current_stream(pool, true), context_->behz(out.coeff_modulus_size()), a.data(), b.data(), a.size(), nullptr,
+                                         out.data().raw_pointer(), 1);
     destination = std::move(out);
 }
 
@@ -2237,13 +2214,8 @@ void Evaluator::bfv_multiply_accumulate_relinearize(const std::vector<const Ciph
     // relinearize's checks on the shape of the sum (it is never written: the library keeps the three polynomials in its workspace)
     Ciphertext sum = Ciphertext::like(*e1[0], 3, false, pool), out;
     relinearize_prepare(sum, relin_keys, out, keys, pool);
-    const troyn_behz* bz = context_->behz(out.coeff_modulus_size());
-    const size_t bytes = troyn_bfv_multiply_accumulate_relinearize_workspace_bytes(bz, a.size(), 1);
-    utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-    {
-        detail::LaunchGate gate;
-        troyn_check(troyn_bfv_multiply_accumulate_relinearize(bz, a.data(), b.data(), a.size(), keys.data(), out.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
-    }
+    detail::bfv_multiply_accumulate_step(on_current_stream(pool, true), context_->behz(out.coeff_modulus_size()), a.data(), b.data(), a.size(), keys.data(),
+                                         out.data().raw_pointer(), 1);
     destination = std::move(out);
 }
 
@@ -2424,16 +2396,13 @@ void Evaluator::multiply_plain_ntt_accumulate(const std::vector<const Ciphertext
     for (size_t i = 0; i < encrypted.size(); i++) {
         cts[i] = encrypted[i]->data().raw_pointer(); pts[i] = plain[i]->poly(); dsts[i] = destination[i]->data().raw_pointer();
     }
-    const size_t wsb = troyn_multiply_plain_accumulate_workspace_bytes(cts.size());
-    utils::DynamicArray ws((wsb + 7) / 8, true, pool);
-    troyn_check(troyn_multiply_plain_accumulate(context_->plan(), 0, L, pc, cts.data(), pts.data(), dsts.data(), cts.size(), set_zero ? 1 : 0,
-                                                ws.raw_pointer(), wsb, current_stream()));
+    detail::multiply_plain_accumulate_step(on_current_stream(pool), context_->plan(), L, pc, cts.data(), pts.data(), dsts.data(), cts.size(), set_zero);
     if (cd->parms().scheme() == SchemeType::CKKS)
         for (size_t i = 0; i < encrypted.size(); i++) {
             destination[i]->scale() = encrypted[i]->scale() * plain[i]->scale();
             if (!is_scale_within_bounds(destination[i]->scale(), cd)) throw std::invalid_argument("[Evaluator::multiply_plain_ntt_batched] Scale out of bounds.");   // evaluator_multiply_plain.cu:250,:301
         }
-    // asynchronous like the reference's method: the pointer table went through the library's pinned ring, `ws` returns to the pool in stream order
+    // asynchronous like the reference's method: the pointer table went through the library's pinned ring, the step's workspace returned to the pool in stream order
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2633,22 +2602,10 @@ void Evaluator::apply_galois_hoisted(const char* P, const Ciphertext& encrypted,
     check_on_device(P, context_, encrypted);
     const size_t terms = elements.size();
     utils::DynamicArray flat(sum || terms == 0 ? 2 : terms * words, true, pool);     // many form: [terms][2][L][N], copied out per term
-    if (terms && bgv) {
-        (sum ? detail::bgv_apply_galois_sum_step : detail::bgv_apply_galois_many_step)(
-            on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, encrypted.data().raw_pointer(), elements.data(), keys.data(), terms,
-            sum ? shells[0].data().raw_pointer() : flat.raw_pointer(), 1);
-    } else if (terms) {
-        const size_t bytes = troyn_apply_galois_hoisted_workspace_bytes(context_->plan(), L, terms, 1, sum ? 1 : 0);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-        detail::LaunchGate gate;
-        const int is_ckks = scheme == SchemeType::CKKS, is_ntt = encrypted.is_ntt_form() ? 1 : 0;
-        if (sum)
-            troyn_check(troyn_apply_galois_sum(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), elements.data(), keys.data(), terms,
-                                               shells[0].data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
-        else
-            troyn_check(troyn_apply_galois_many(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), elements.data(), keys.data(), terms,
-                                                flat.raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
-    }
+    if (terms)      // (key_level_bgv: the BGV handle exactly for the bgv_ methods, which hoisted_scheme_check has tied to BGV contexts)
+        (sum ? detail::apply_galois_sum_step : detail::apply_galois_many_step)(
+            on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, scheme == SchemeType::CKKS, encrypted.is_ntt_form(), encrypted.data().raw_pointer(),
+            elements.data(), keys.data(), terms, sum ? shells[0].data().raw_pointer() : flat.raw_pointer(), 1);
     out.clear();
     if (sum) {
         // the identity terms: the ciphertext itself, added once per occurrence
@@ -2754,17 +2711,8 @@ void Evaluator::apply_galois_weighted(const char* P, const Ciphertext& encrypted
     const double scale = scheme == SchemeType::CKKS ? encrypted.scale() * weight_scale : encrypted.scale();
     if (scheme == SchemeType::CKKS && !is_scale_within_bounds(scale, cd)) throw std::invalid_argument(std::string(P) + " Scale out of bounds.");
     utils::DynamicArray flat(slots * words, true, pool);     // [slots][2][L][N], copied out per slot
-    if (bgv) {
-        detail::bgv_apply_galois_weighted_sums_step(on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, encrypted.data().raw_pointer(), elements.data(),
-                                                    keys.data(), terms, wptrs.data(), slots, flat.raw_pointer(), 1);
-    } else {
-        const int is_ckks = scheme == SchemeType::CKKS, is_ntt = encrypted.is_ntt_form() ? 1 : 0;
-        const size_t bytes = troyn_apply_galois_weighted_workspace_bytes(context_->plan(), L, terms, slots, 1, is_ntt);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-        detail::LaunchGate gate;
-        troyn_check(troyn_apply_galois_weighted_sums(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), elements.data(), keys.data(), terms,
-                                                     wptrs.data(), slots, flat.raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
-    }
+    detail::apply_galois_weighted_sums_step(on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, scheme == SchemeType::CKKS, encrypted.is_ntt_form(),
+                                            encrypted.data().raw_pointer(), elements.data(), keys.data(), terms, wptrs.data(), slots, flat.raw_pointer(), 1);
     out.clear();
     for (size_t sl = 0; sl < slots; sl++) {
         Ciphertext d = Ciphertext::like(encrypted, false, pool);
@@ -2818,17 +2766,8 @@ void Evaluator::apply_galois_each(const char* P, const std::vector<const Ciphert
     for (size_t t = 0; t < terms; t++)
         hip_check(hipMemcpyAsync(flat.raw_pointer() + t * words, encrypted[t]->data().raw_pointer(), words * 8, hipMemcpyDeviceToDevice, current_stream()), "copy_device_to_device");
     Ciphertext d = Ciphertext::like(first, false, pool);
-    if (bgv) {
-        detail::bgv_apply_galois_sum_each_step(on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, flat.raw_pointer(), elements.data(), keys.data(), terms,
-                                               d.data().raw_pointer(), 1);
-    } else {
-        const int is_ckks = scheme == SchemeType::CKKS, is_ntt = first.is_ntt_form() ? 1 : 0;
-        const size_t bytes = troyn_apply_galois_sum_each_workspace_bytes(context_->plan(), L, terms, 1, is_ntt);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-        detail::LaunchGate gate;
-        troyn_check(troyn_apply_galois_sum_each(context_->plan(), L, is_ckks, is_ntt, flat.raw_pointer(), elements.data(), keys.data(), terms,
-                                                d.data().raw_pointer(), ws.raw_pointer(), bytes, 1, current_stream()));
-    }
+    detail::apply_galois_sum_each_step(on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, scheme == SchemeType::CKKS, first.is_ntt_form(),
+                                       flat.raw_pointer(), elements.data(), keys.data(), terms, d.data().raw_pointer(), 1);
     destination = std::move(d);
 }
 
@@ -2865,20 +2804,15 @@ void Evaluator::apply_galois_bsgs(const char* P, const Ciphertext& encrypted, co
     if (scheme == SchemeType::CKKS && !is_scale_within_bounds(scale, cd)) throw std::invalid_argument(std::string(P) + " Scale out of bounds.");
     Ciphertext d = Ciphertext::like(encrypted, false, pool);
     d.scale() = scale;
-    if (bgv) {
-        detail::bgv_linear_transform_bsgs_step(on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, encrypted.data().raw_pointer(), belements.data(),
-                                               bkeys.data(), babies, gelements.data(), gkeys.data(), giants, wptrs.data(), d.data().raw_pointer(), 1);
-    } else {
-        const int is_ckks = scheme == SchemeType::CKKS, is_ntt = encrypted.is_ntt_form() ? 1 : 0;
-        const auto workspace_bytes = double_hoisted ? troyn_linear_transform_bsgs_double_hoisted_workspace_bytes : troyn_linear_transform_bsgs_workspace_bytes;
-        const auto transform = double_hoisted ? troyn_linear_transform_bsgs_double_hoisted : troyn_linear_transform_bsgs;
-        const size_t bytes = workspace_bytes(context_->plan(), L, babies, giants, 1, is_ntt);
-        utils::DynamicArray ws((bytes + 7) / 8, true, pool);
-        detail::LaunchGate gate;
-        troyn_check(transform(context_->plan(), L, is_ckks, is_ntt, encrypted.data().raw_pointer(), belements.data(), bkeys.data(), babies,
-                              gelements.data(), gkeys.data(), giants, wptrs.data(), d.data().raw_pointer(), ws.raw_pointer(), bytes, 1,
-                              current_stream()));
-    }
+    const bool ckks = scheme == SchemeType::CKKS;
+    if (double_hoisted && !bgv)      // (the bgv_ methods never ask for it: the library has no double-hoisted BGV form)
+        detail::linear_transform_bsgs_double_hoisted_step(on_current_stream(pool, true), context_->plan(), L, ckks, encrypted.is_ntt_form(), encrypted.data().raw_pointer(),
+                                                          belements.data(), bkeys.data(), babies, gelements.data(), gkeys.data(), giants, wptrs.data(),
+                                                          d.data().raw_pointer(), 1);
+    else
+        detail::linear_transform_bsgs_step(on_current_stream(pool, true), context_->plan(), key_level_bgv(scheme), L, ckks, encrypted.is_ntt_form(),
+                                           encrypted.data().raw_pointer(), belements.data(), bkeys.data(), babies, gelements.data(), gkeys.data(), giants, wptrs.data(),
+                                           d.data().raw_pointer(), 1);
     destination = std::move(d);
 }
 
@@ -4612,17 +4546,11 @@ std::vector<Plaintext> CKKSEncoder::encode_batched(bool simd, const std::vector<
     for (size_t i = 0; i < batch; i++)
         if (items[i].device && items[i].doubles)
             hip_check(hipMemcpyAsync(d_values + i * doubles, items[i].ptr, items[i].doubles * sizeof(double), hipMemcpyDeviceToDevice, s), "copy_device_to_device");
-    const troyn_ckks* h = context_->ckks();
-    const size_t ws_bytes = troyn_ckks_encode_workspace_bytes(h, batch);
-    utils::DynamicArray ws((ws_bytes + 7) / 8 + 2, true, pool);
     auto shared = std::make_shared<utils::DynamicArray>(batch * L * n, true, pool);
-    const int rc = simd ? troyn_ckks_encode_simd(h, static_cast<uint32_t>(L), d_values, doubles / per, scale, shared->raw_pointer(), d_flags, ws.raw_pointer(), ws_bytes, batch, s)
-                        : troyn_ckks_encode_polynomial(h, static_cast<uint32_t>(L), d_values, doubles, scale, shared->raw_pointer(), d_flags, ws.raw_pointer(), ws_bytes, batch, s);
-    if (rc != TROYN_OK) {
-        (void)stream_wait();             // copies into `staged` may be queued: it returns to the pool only after them
-        troyn_check(rc);
-    }
-    // the flags: the only wait of the call (the staged values and the workspace return to the pool after it)
+    // a refusal is thrown only after a stream wait: copies into `staged` may be queued, and it returns to the pool only after them
+    const detail::StepEnv env{pool, s, [](int rc) { if (rc != TROYN_OK) { (void)stream_wait(); troyn_check(rc); } }};
+    detail::ckks_encode_step(env, context_->ckks(), simd, static_cast<uint32_t>(L), d_values, doubles / per, scale, shared->raw_pointer(), d_flags, batch);
+    // the flags: the only wait of the call (the staged values return to the pool after it; the step's workspace has, in stream order)
     uint32_t* h_flags = reinterpret_cast<uint32_t*>(img.p + value_words * sizeof(double));
     hip_check(hipMemcpyAsync(h_flags, d_flags, batch * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy_device_to_host");
     hip_check(stream_wait(), "copy_device_to_host");
@@ -4686,12 +4614,9 @@ std::vector<double> CKKSEncoder::decode_batched(bool simd, const std::vector<con
             hip_check(hipMemcpyAsync(gathered.raw_pointer() + i * words, plains[i]->poly().raw_pointer(), words * sizeof(uint64_t),
                                      plains[i]->on_device() ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s), "copy");
     const uint64_t* src = contiguous ? plains[0]->poly().raw_pointer() : gathered.raw_pointer();
-    const troyn_ckks* h = context_->ckks();
-    const size_t ws_bytes = troyn_ckks_workspace_bytes(h, static_cast<uint32_t>(L), batch);
-    utils::DynamicArray ws((ws_bytes + 7) / 8 + 2, true, pool), out(batch * n, true, pool);
+    utils::DynamicArray out(batch * n, true, pool);
     double* d_out = reinterpret_cast<double*>(out.raw_pointer());
-    troyn_check(simd ? troyn_ckks_decode_simd(h, static_cast<uint32_t>(L), src, plains[0]->scale(), d_out, ws.raw_pointer(), ws_bytes, batch, s)
-                     : troyn_ckks_decode_polynomial(h, static_cast<uint32_t>(L), src, plains[0]->scale(), d_out, ws.raw_pointer(), ws_bytes, batch, s));
+    detail::ckks_decode_step(on_current_stream(pool), context_->ckks(), simd, static_cast<uint32_t>(L), src, plains[0]->scale(), d_out, batch);
     PinnedImage& img = pinned_image();
     const double* host = reinterpret_cast<const double*>(img.reserve(batch * n * sizeof(double)));
     hip_check(hipMemcpyAsync(const_cast<double*>(host), d_out, batch * n * sizeof(double), hipMemcpyDeviceToHost, s), "copy_device_to_host");
