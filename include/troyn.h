@@ -738,6 +738,31 @@ int troyn_ckks_decode_simd(const troyn_ckks* h, uint32_t L, const uint64_t* plai
                            size_t batch, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Matrix diagonals encoded into BSGS weights (an addition to the reference's API): `items` plaintexts, each one diagonal of a complex
+ * n x n matrix rotated back by a shift, selected and rotated while the encoder's first FFT pass loads its points -- the pre-rotated
+ * diagonals never exist in memory.
+ *
+ * CONTRACT: the words of `out` ([items][L][N], NTT form) are those troyn_ckks_encode_simd writes for batch = items, count = N/2 and the
+ * values array below; that entry is the specification.  Item t carries the two words (a_t, s_t) = pairs[t][0..1]; for 0 <= i < N/2
+ *   src_is_matrix = 0   src = diags, double [nd][n][2]:               values[t][i] = diags[a_t][(i - s_t) mod n]
+ *   src_is_matrix = 1   src = matrix, double [n][n][2], row-major:    values[t][i] = matrix[j][(j + a_t) mod n], j = (i - s_t) mod n
+ * (diagonal a of M is diag_a[j] = M[j][(j + a) mod n]).  n is a power of two, 1 <= n <= N/2; n < N/2 is the sparsely packed case: the
+ * diagonal repeats N/(2n) times across the slots.  nd is not read in matrix mode.
+ * A word of `pairs` out of range is the caller's error and never reads outside `src`: s_t is masked (s_t mod n); a_t is clamped to nd - 1 in
+ * diagonals mode and masked (a_t mod n) in matrix mode.
+ * src, pairs (u32 [items][2]), out, too_large (u32 [items] or null, as above): device memory.  The workspace is
+ * troyn_ckks_encode_diagonals_workspace_bytes(h, items) bytes (the encoder's: nothing below N = 16384, where it may be null).
+ * TROYN_E_INVALID: a null handle or pointer, a misaligned pointer (16 bytes for src, out and the workspace; 4 for pairs and too_large), n not a
+ * power of two or above N/2, nd == 0 in diagonals mode, L outside [1, n_moduli], a scale the encoder refuses.  TROYN_E_WORKSPACE: a short
+ * workspace.  items == 0 returns TROYN_OK and touches nothing; only the handle and L are looked at before.  Everything is enqueued on the
+ * caller's stream; the entry does not synchronise or touch the default stream.
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_ckks_encode_diagonals_workspace_bytes(const troyn_ckks* h, size_t items);
+int troyn_ckks_encode_diagonals(const troyn_ckks* h, uint32_t L, const double* src, int src_is_matrix, uint32_t n, uint32_t nd,
+                                const uint32_t* pairs, double scale, uint64_t* out, uint32_t* too_large,
+                                void* workspace, size_t workspace_bytes, size_t items, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * CKKS ModRaise (an addition to the reference's API): the exact centred base extension of a ciphertext from the plan's moduli
  * 0..L_in-1 to its moduli 0..L_out-1, the first step of a bootstrap.  On the troyn_ckks handle, which owns the Garner table q_j^-1 mod q_i.
  * Layouts of troyn_mod_switch_drop: in u64 [batch][pcount][L_in][N], out u64 [batch][pcount][L_out][N], row i under modulus i.

@@ -39,7 +39,16 @@ struct CkksFftArgs {
     unsigned L;
     double fix;                           // scale / N
     unsigned* too_large;                  // [batch] or null
+    // encode, first pass, SRC != CKKS_SRC_VALUES (appended: the fields above keep their kernarg offsets)
+    const double2* table;                 // diagonals [nd][n] / row-major matrix [n][n]
+    const uint2* pairs;                   // [batch]: (a_t, s_t) = (diagonal, shift)
+    unsigned n_mask, n_log, a_max;        // n - 1, log2 n, nd - 1 (diagonals: a_t is clamped) / n - 1 (matrix: a_t is masked)
 };
+
+// where the first pass of an encoding reads slot i of item t from
+constexpr int CKKS_SRC_VALUES = 0;        // values[t][i], zero beyond count
+constexpr int CKKS_SRC_DIAGONALS = 1;     // table[a_t][(i - s_t) mod n]
+constexpr int CKKS_SRC_MATRIX = 2;        // table[j][(j + a_t) mod n], j = (i - s_t) mod n
 
 // ---- rounded coefficient -> residues (set_plaintext, troy/troy.cpp) ---------------------------------------------------------------
 struct CkksInt128 { u64 lo, hi; bool neg, too_large; };
@@ -68,8 +77,9 @@ constexpr unsigned ckks_lds_slots(int tb) { return (1u << tb) + (1u << (tb - 3))
 
 // DEC = false: Gentleman-Sande layers with inv_root_powers, gap 1 upwards (encode).  DEC = true: Cooley-Tukey layers with root_powers, gap
 // N/2 downwards (decode).  STRIDED: the pass over the layers of gap >= 2^TB (two-pass sizes only).
-template <int LOGN, int TB, bool DEC, bool STRIDED>
+template <int LOGN, int TB, bool DEC, bool STRIDED, int SRC = CKKS_SRC_VALUES>
 __global__ __launch_bounds__(1 << (TB - 3)) void ckks_fft_kernel(CkksFftArgs a) {
+    static_assert(SRC == CKKS_SRC_VALUES || (!DEC && !STRIDED), "a diagonal source feeds the first pass of an encoding");
     static_assert(TB >= 6 && TB <= 13 && TB <= LOGN && 2 * TB >= LOGN, "tile geometry");
     static_assert(!STRIDED || TB < LOGN, "the strided pass exists at the two-pass sizes only");
     constexpr int LO = STRIDED ? 2 * TB - LOGN : 0;              // the tile's layers are its local bits LO .. TB-1
@@ -97,6 +107,13 @@ __global__ __launch_bounds__(1 << (TB - 3)) void ckks_fft_kernel(CkksFftArgs a) 
     // ---- load ----
     {
         const int s = round_bit(0);
+        // a diagonal source: the item's (diagonal, shift), uniform over the workgroup; out-of-range words cannot leave the table
+        unsigned src_a = 0, src_s = 0;
+        if constexpr (SRC != CKKS_SRC_VALUES) {
+            const uint2 pr = a.pairs[item];
+            src_s = pr.y & a.n_mask;
+            src_a = SRC == CKKS_SRC_DIAGONALS ? (pr.x < a.a_max ? pr.x : a.a_max) : (pr.x & a.n_mask);
+        }
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const unsigned g = global_of(local_of(s, k));
@@ -109,7 +126,13 @@ __global__ __launch_bounds__(1 << (TB - 3)) void ckks_fft_kernel(CkksFftArgs a) 
                 // set_conjugate_values: slot i at index_map[i], its conjugate at index_map[i + N/2]; zero beyond count
                 const unsigned i = a.slot_of[g], slot = i & (N / 2 - 1);
                 re[k] = 0.0; im[k] = 0.0;
-                if (slot < a.count) {
+                if constexpr (SRC != CKKS_SRC_VALUES) {
+                    // the pre-rotated diagonal, selected while loading: every slot is present (count = N/2), a short diagonal repeats
+                    const unsigned j = (slot - src_s) & a.n_mask;
+                    const size_t at = SRC == CKKS_SRC_DIAGONALS ? ((size_t)src_a << a.n_log) + j : ((size_t)j << a.n_log) + ((j + src_a) & a.n_mask);
+                    const double2 v = a.table[at];
+                    re[k] = v.x; im[k] = (i >= N / 2) ? -v.y : v.y;
+                } else if (slot < a.count) {
                     const double2 v = a.values[(size_t)item * a.count + slot];
                     re[k] = v.x; im[k] = (i >= N / 2) ? -v.y : v.y;
                 }

@@ -119,6 +119,7 @@ struct CkksFftArgs;
 struct CkksComposeArgs;
 bool ckks_fft_two_pass(unsigned log_n);
 bool launch_ckks_fft(unsigned log_n, bool decode, const CkksFftArgs& a, size_t batch, hipStream_t s);
+bool launch_ckks_fft_diagonals(unsigned log_n, bool matrix, const CkksFftArgs& a, size_t batch, hipStream_t s);
 void launch_ckks_encode_polynomial(const double* coeffs, unsigned count, double scale, unsigned n, const DevModulus* mods, unsigned L, u64* residues,
                                    unsigned* too_large, size_t batch, hipStream_t s);
 bool launch_ckks_compose(const CkksComposeArgs& a, size_t batch, hipStream_t s);

@@ -4199,9 +4199,12 @@ static int ckks_check(const char* P, const troyn_ckks* h, uint32_t L, const void
     return TROYN_OK;
 }
 
+// the source of troyn_ckks_encode_diagonals: `src` of ckks_encode is then the table, read through (diagonal, shift) pairs
+struct CkksDiagonalSource { bool matrix; uint32_t n, nd; const uint32_t* pairs; };
+
 static int ckks_encode(const troyn_ckks* h, bool simd, uint32_t L, const double* src, size_t count, double scale, uint64_t* out, uint32_t* too_large,
-                       void* ws, size_t ws_bytes, size_t batch, troyn_stream_t stream) {
-    const char* P = simd ? "[CKKSEncoder::encode_internal_complex_array]" : "[CKKSEncoder::encode_internal_double_polynomial]";
+                       void* ws, size_t ws_bytes, size_t batch, troyn_stream_t stream, const CkksDiagonalSource* ds = nullptr) {
+    const char* P = ds ? "[troyn_ckks_encode_diagonals]" : simd ? "[CKKSEncoder::encode_internal_complex_array]" : "[CKKSEncoder::encode_internal_double_polynomial]";
     select_device(h);
     // count == 0 reads nothing: a null source is then allowed
     alignas(16) static const double none[2] = {0, 0};
@@ -4210,6 +4213,12 @@ static int ckks_encode(const troyn_ckks* h, bool simd, uint32_t L, const double*
     if (rc == 1) return TROYN_OK;
     const troyn_plan* p = h->plan;
     if (count > (simd ? p->n / 2 : p->n)) return fail(TROYN_E_INVALID, std::string(P) + " Too many input values.");
+    if (ds) {
+        if (!ds->pairs) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+        if ((uintptr_t)ds->pairs & 3) return fail(TROYN_E_INVALID, std::string(P) + " misaligned pointer");
+        if (ds->n == 0 || (ds->n & (ds->n - 1)) || ds->n > p->n / 2) return fail(TROYN_E_INVALID, std::string(P) + " n must be a power of two of at most N/2");
+        if (!ds->matrix && ds->nd == 0) return fail(TROYN_E_INVALID, std::string(P) + " no diagonals");
+    }
     size_t total_bits = 0;
     for (uint32_t i = 0; i < L; i++) total_bits += 64 - (size_t)__builtin_clzll(p->moduli[i]);
     if (!(scale > 0) || std::log2(scale) + 1.0 >= static_cast<double>(total_bits)) return fail(TROYN_E_INVALID, std::string(P) + " scale out of bounds.");
@@ -4225,7 +4234,13 @@ static int ckks_encode(const troyn_ckks* h, bool simd, uint32_t L, const double*
         a.residues = (u64*)out; a.mods = p->d_mods; a.L = L;
         a.fix = scale / static_cast<double>(p->n);
         a.too_large = too_large;
-        if (!launch_ckks_fft(p->log_n, false, a, batch, s)) return fail(TROYN_E_UNSUPPORTED, std::string(P) + " no FFT kernel for this size");
+        if (ds) {
+            a.values = nullptr;
+            a.table = reinterpret_cast<const double2*>(src); a.pairs = reinterpret_cast<const uint2*>(ds->pairs);
+            a.n_mask = ds->n - 1; a.n_log = (unsigned)__builtin_ctz(ds->n); a.a_max = ds->matrix ? ds->n - 1 : ds->nd - 1;
+        }
+        if (!(ds ? launch_ckks_fft_diagonals(p->log_n, ds->matrix, a, batch, s) : launch_ckks_fft(p->log_n, false, a, batch, s)))
+            return fail(TROYN_E_UNSUPPORTED, std::string(P) + " no FFT kernel for this size");
     } else {
         launch_ckks_encode_polynomial(src, (unsigned)count, scale, p->n, p->d_mods, L, (u64*)out, too_large, batch, s);
     }
@@ -4241,6 +4256,16 @@ extern "C" int troyn_ckks_encode_simd(const troyn_ckks* h, uint32_t L, const dou
 extern "C" int troyn_ckks_encode_polynomial(const troyn_ckks* h, uint32_t L, const double* coeffs, size_t count, double scale, uint64_t* out, uint32_t* too_large,
                                             void* workspace, size_t workspace_bytes, size_t batch, troyn_stream_t stream) {
     return ckks_encode(h, false, L, coeffs, count, scale, out, too_large, workspace, workspace_bytes, batch, stream);
+}
+
+extern "C" size_t troyn_ckks_encode_diagonals_workspace_bytes(const troyn_ckks* h, size_t items) {
+    return troyn_ckks_encode_workspace_bytes(h, items);
+}
+extern "C" int troyn_ckks_encode_diagonals(const troyn_ckks* h, uint32_t L, const double* src, int src_is_matrix, uint32_t n, uint32_t nd,
+                                           const uint32_t* pairs, double scale, uint64_t* out, uint32_t* too_large,
+                                           void* workspace, size_t workspace_bytes, size_t items, troyn_stream_t stream) {
+    const CkksDiagonalSource ds = {src_is_matrix != 0, n, nd, pairs};
+    return ckks_encode(h, true, L, src, h ? h->plan->n / 2 : 0, scale, out, too_large, workspace, workspace_bytes, items, stream, &ds);
 }
 
 static int ckks_decode(const troyn_ckks* h, bool simd, uint32_t L, const uint64_t* plain, double scale, double* out, void* ws, size_t ws_bytes, size_t batch,

@@ -8,18 +8,18 @@ bool ckks_fft_two_pass(unsigned log_n) {
     return log_n >= (unsigned)NTT_LOG_N_MIN && log_n <= (unsigned)NTT_LOG_N_MAX && ntt_size((int)log_n).fft.tb < (int)log_n;
 }
 
-template <int LOGN, bool DEC>
+template <int LOGN, bool DEC, int SRC = CKKS_SRC_VALUES>
 static void ckks_fft_passes(const CkksFftArgs& a, size_t batch, hipStream_t s) {
     constexpr int TB = ntt_size(LOGN).fft.tb;
     static_assert(ntt_size(LOGN).fft.eb == 3, "ckks_fft_kernel holds 8 points per thread");
     const dim3 grid((unsigned)(batch << (LOGN - TB))), block(1u << (TB - 3));
     if constexpr (TB == LOGN) {
-        hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, DEC, false>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, DEC, false, SRC>), grid, block, 0, s, a);
     } else if constexpr (DEC) {          // gap N/2 downwards: the strided layers first
         hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, true, true>), grid, block, 0, s, a);
         hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, true, false>), grid, block, 0, s, a);
     } else {                             // gap 1 upwards: the contiguous tiles first
-        hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, false, false>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, false, false, SRC>), grid, block, 0, s, a);
         hipLaunchKernelGGL((ckks_fft_kernel<LOGN, TB, false, true>), grid, block, 0, s, a);
     }
 }
@@ -29,6 +29,17 @@ bool launch_ckks_fft(unsigned log_n, bool decode, const CkksFftArgs& a, size_t b
         constexpr int LOGN = decltype(size)::value;
         if (decode) ckks_fft_passes<LOGN, true>(a, batch, s);
         else ckks_fft_passes<LOGN, false>(a, batch, s);
+        return true;
+    });
+}
+
+// the encoder with the load of its first pass reading pre-rotated matrix diagonals (a.table, a.pairs); the second pass at the two-pass sizes is
+// the values source's
+bool launch_ckks_fft_diagonals(unsigned log_n, bool matrix, const CkksFftArgs& a, size_t batch, hipStream_t s) {
+    return for_ntt_size<0>(log_n, [&](auto size) {
+        constexpr int LOGN = decltype(size)::value;
+        if (matrix) ckks_fft_passes<LOGN, false, CKKS_SRC_MATRIX>(a, batch, s);
+        else ckks_fft_passes<LOGN, false, CKKS_SRC_DIAGONALS>(a, batch, s);
         return true;
     });
 }

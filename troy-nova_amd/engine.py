@@ -925,6 +925,22 @@ class CkksEncoder:
         batch, count = values.shape[0], values.shape[1]
         return self._encode(self.plan.lib.troyn_ckks_encode_simd, L, values, batch, count, scale, flags)
 
+    def encode_diagonals(self, L, src, pairs, scale, n, matrix=False, flags=False):
+        """troyn_ckks_encode_diagonals: src float64 [nd][n][2] (diagonals) or [n][n][2] (row-major matrix, matrix=True), pairs int32 [items][2] =
+        (diagonal, shift) -> [items][L][N]: item t encodes the diagonal rotated back by its shift, repeated across the N/2 slots"""
+        if pairs.dtype != torch.int32 or not pairs.is_contiguous() or not pairs.is_cuda or pairs.dim() != 2 or pairs.shape[1] != 2:
+            raise capi.TroynInvalidArgument("[troyn] pairs must be a contiguous int32 CUDA tensor [items][2]")
+        n = int(n)
+        if src.dim() != 3 or src.shape[1] != n or src.shape[2] != 2 or (matrix and src.shape[0] != n):
+            raise capi.TroynInvalidArgument("[troyn] src must be [nd][n][2] (diagonals) or [n][n][2] (matrix)")
+        items, nd = pairs.shape[0], src.shape[0]
+        out = torch.empty((items, L, self.plan.n), dtype=torch.int64, device=self.plan.device)
+        too_large = torch.empty(max(items, 1), dtype=torch.int32, device=self.plan.device) if flags else None
+        ws, ws_bytes = self._ws(self.lib.troyn_ckks_encode_diagonals_workspace_bytes(self.h, items))
+        capi.check(self.lib.troyn_ckks_encode_diagonals(self.h, L, self._f64(src), 1 if matrix else 0, n, nd, C.c_void_p(pairs.data_ptr()), float(scale), _ptr(out),
+                                                        C.c_void_p(too_large.data_ptr()) if flags else None, ws, ws_bytes, items, _stream()))
+        return (out, too_large[:items]) if flags else out
+
     def encode_polynomial(self, L, coeffs, scale, flags=False):
         """coeffs [batch][count] -> [batch][L][N]"""
         batch, count = coeffs.shape[0], coeffs.shape[1]

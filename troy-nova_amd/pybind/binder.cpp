@@ -13,6 +13,7 @@
 #include <sstream>
 
 #include "../troy/conv2d.h"
+#include "../troy/linear_transform.h"
 #include "../troy/matmul.h"
 #include "../troy/ring2k.h"
 #include "../troy/troy.h"
@@ -672,6 +673,44 @@ PYBIND11_MODULE(pytroy_raw, m) {
     ev.def("rotate_bsgs_sum_double_hoisted_new", [](const Evaluator& s, const Ciphertext& a, const std::vector<int>& b, const std::vector<int>& g, const GaloisKeys& k,
                                                     const std::vector<WeightRow>& w, PoolArg p) { return s.rotate_bsgs_sum_double_hoisted_new(a, b, g, k, w, P(p)); },
            py::arg("encrypted"), py::arg("baby_steps"), py::arg("giant_steps"), py::arg("galois_keys"), py::arg("weights"), POOL);
+    // addition: LinearTransform (linear_transform.h), a complex matrix as BSGS weights encoded on the device, and its evaluation
+    {
+        using CArr = py::array_t<std::complex<double>, py::array::c_style | py::array::forcecast>;
+        py::class_<LinearTransform>(m, "LinearTransform")
+            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, size_t n, const ParmsID& id, double scale, const py::dict& diagonals, size_t baby_count, PoolArg p) {
+                     LinearTransform::Diagonals d;
+                     for (const auto& kv : diagonals) {
+                         const CArr v = py::cast<CArr>(kv.second);
+                         d[py::cast<size_t>(kv.first)] = std::vector<std::complex<double>>(v.data(), v.data() + v.size());
+                     }
+                     return std::make_unique<LinearTransform>(c, e, n, id, scale, d, baby_count, P(p)); }),
+                 py::arg("context"), py::arg("encoder"), py::arg("n"), py::arg("parms_id"), py::arg("scale"), py::arg("diagonals"), py::arg("baby_count") = 0, POOL)
+            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, size_t n, const ParmsID& id, double scale, const CArr& matrix, size_t baby_count, PoolArg p) {
+                     return std::make_unique<LinearTransform>(c, e, n, id, scale, std::vector<std::complex<double>>(matrix.data(), matrix.data() + matrix.size()), baby_count, P(p)); }),
+                 py::arg("context"), py::arg("encoder"), py::arg("n"), py::arg("parms_id"), py::arg("scale"), py::arg("matrix"), py::arg("baby_count") = 0, POOL)
+            .def("n", &LinearTransform::n).def("baby_count", &LinearTransform::baby_count).def("scale", &LinearTransform::scale)
+            .def("parms_id", [](const LinearTransform& s) { return s.parms_id(); })
+            .def("baby_steps", [](const LinearTransform& s) { return s.baby_steps(); })
+            .def("giant_steps", [](const LinearTransform& s) { return s.giant_steps(); })
+            .def("rotation_steps", [](const LinearTransform& s) { return s.rotation_steps(); })
+            // copies of the weight windows (they share the transform's buffer); None where giant + baby is not a present diagonal
+            .def("weights", [](const LinearTransform& s) {
+                py::list rows;
+                for (const auto& row : s.weights()) {
+                    py::list r;
+                    for (const Plaintext* w : row) { if (w) r.append(py::cast(Plaintext(*w))); else r.append(py::none()); }
+                    rows.append(r);
+                }
+                return rows; });
+    }
+    ev.def("linear_transform", [](const Evaluator& s, const Ciphertext& a, const LinearTransform& lt, const GaloisKeys& k, Ciphertext& d, PoolArg p) {
+        s.linear_transform(a, lt, k, d, P(p)); }, py::arg("encrypted"), py::arg("lt"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("linear_transform_new", [](const Evaluator& s, const Ciphertext& a, const LinearTransform& lt, const GaloisKeys& k, PoolArg p) {
+        return s.linear_transform_new(a, lt, k, P(p)); }, py::arg("encrypted"), py::arg("lt"), py::arg("galois_keys"), POOL);
+    ev.def("linear_transform_single_hoisted", [](const Evaluator& s, const Ciphertext& a, const LinearTransform& lt, const GaloisKeys& k, Ciphertext& d, PoolArg p) {
+        s.linear_transform_single_hoisted(a, lt, k, d, P(p)); }, py::arg("encrypted"), py::arg("lt"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("linear_transform_single_hoisted_new", [](const Evaluator& s, const Ciphertext& a, const LinearTransform& lt, const GaloisKeys& k, PoolArg p) {
+        return s.linear_transform_single_hoisted_new(a, lt, k, P(p)); }, py::arg("encrypted"), py::arg("lt"), py::arg("galois_keys"), POOL);
     // additions: the hoisted family on BGV contexts (troy.h): bgv_NAME takes NAME's arguments.  SEL is the element / step list's type and keyword
 #define EV_BGV_MANY(name, SEL, sel, what)                                                                                                          \
     ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& g, const GaloisKeys& k, const std::vector<Ciphertext*>& d, PoolArg p) {  \

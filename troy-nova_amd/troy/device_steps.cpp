@@ -272,6 +272,14 @@ void ckks_encode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uin
     env.check((simd ? troyn_ckks_encode_simd : troyn_ckks_encode_polynomial)(ckks, L, values, row, scale, out, flags, ws.raw_pointer(), bytes, count, env.stream));
 }
 
+void ckks_encode_diagonals_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t L, const double* src, bool matrix, uint32_t n, uint32_t nd, const uint32_t* pairs,
+                                double scale, uint64_t* out, uint32_t* flags, size_t count) {
+    const size_t bytes = troyn_ckks_encode_diagonals_workspace_bytes(ckks, count);
+    utils::DynamicArray ws = workspace(env, bytes + 16);
+    LaunchGate gate(env.gated);
+    env.check(troyn_ckks_encode_diagonals(ckks, L, src, matrix ? 1 : 0, n, nd, pairs, scale, out, flags, ws.raw_pointer(), bytes, count, env.stream));
+}
+
 void ckks_decode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const uint64_t* in, double scale, double* out, size_t count) {
     const size_t bytes = troyn_ckks_workspace_bytes(ckks, L, count);
     utils::DynamicArray ws((bytes + 7) / 8 + 2, true, env.pool);     // (two spare words, as before the step)

@@ -126,6 +126,10 @@ void multiply_plain_accumulate_step(const StepEnv& env, const troyn_plan* plan, 
 // values [count][row] doubles (row complex values / doubles per item), out [count][L][N] NTT form, flags [count] (non-zero: too large)
 void ckks_encode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const double* values, size_t row, double scale, uint64_t* out, uint32_t* flags,
                       size_t count);
+// matrix diagonals into BSGS weights (troyn_ckks_encode_diagonals): src [nd][n][2] diagonals or [n][n][2] row-major matrix, pairs [count][2] =
+// (diagonal, shift); out and flags as above.  All device memory.
+void ckks_encode_diagonals_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t L, const double* src, bool matrix, uint32_t n, uint32_t nd, const uint32_t* pairs,
+                                double scale, uint64_t* out, uint32_t* flags, size_t count);
 void ckks_decode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const uint64_t* in, double scale, double* out, size_t count);
 
 // LWE (lwe.cpp): coefficient `terms[i]` of srcs[i] as an LWE ciphertext, c0 [count][L] and c1 [count][L][N]; the leaves of the packing tree

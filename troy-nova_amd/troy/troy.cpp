@@ -4571,6 +4571,59 @@ std::vector<Plaintext> CKKSEncoder::encode_batched(bool simd, const std::vector<
     return out;
 }
 
+std::vector<Plaintext> CKKSEncoder::encode_diagonals_new(const std::complex<double>* source, bool matrix, size_t dim, size_t nd,
+                                                         const std::vector<std::pair<uint32_t, uint32_t>>& pairs, std::optional<ParmsID> parms_id, double scale,
+                                                         MemoryPoolHandle pool) const {
+    const char* P = "[CKKSEncoder::encode_diagonals]";
+    if (!context_->on_device()) throw std::invalid_argument(std::string(P) + " HeContext is not on device (call to_device_inplace).");
+    const ParmsID pid = parms_id.value_or(context_->first_parms_id());
+    auto cdo = context_->get_context_data(pid);
+    if (!cdo.has_value()) throw std::invalid_argument(std::string(P) + " parms_id not valid for context.");
+    const size_t n = slots_ * 2, L = cdo.value()->parms().coeff_modulus().size(), batch = pairs.size();
+    if (dim == 0 || (dim & (dim - 1)) || dim > slots_) throw std::invalid_argument(std::string(P) + " the matrix size must be a power of two of at most slot_count.");
+    const size_t rows = matrix ? dim : nd;
+    if (!source || rows == 0) throw std::invalid_argument(std::string(P) + " no diagonals.");
+    for (const auto& pr : pairs)
+        if (pr.first >= rows || pr.second >= dim) throw std::invalid_argument(std::string(P) + " diagonal or shift out of range.");
+    size_t total_bits = 0;
+    for (const Modulus& mdl : cdo.value()->parms().coeff_modulus()) total_bits += mdl.bit_count();
+    if (scale <= 0 || std::log2(scale) + 1.0 >= static_cast<double>(total_bits)) throw std::invalid_argument(std::string(P) + " scale out of bounds.");
+    if (batch == 0) return {};
+    hipStream_t s = current_stream();
+    // the source [rows][dim] complex, then the pairs, then the too-large flags: uploaded once, read by every item
+    const size_t source_words = rows * dim * 2, pair_words = batch, flag_words = (batch + 1) / 2;
+    utils::DynamicArray staged(source_words + pair_words + flag_words + 2, true, pool);
+    double* d_source = reinterpret_cast<double*>(staged.raw_pointer());
+    uint32_t* d_pairs = reinterpret_cast<uint32_t*>(staged.raw_pointer() + source_words);
+    uint32_t* d_flags = reinterpret_cast<uint32_t*>(staged.raw_pointer() + source_words + pair_words);
+    std::vector<uint32_t> h_pairs(2 * batch), h_flags(batch);
+    for (size_t i = 0; i < batch; i++) { h_pairs[2 * i] = pairs[i].first; h_pairs[2 * i + 1] = pairs[i].second; }
+    hip_check(hipMemcpyAsync(d_source, source, source_words * sizeof(double), hipMemcpyHostToDevice, s), "copy_host_to_device");
+    hip_check(hipMemcpyAsync(d_pairs, h_pairs.data(), 2 * batch * sizeof(uint32_t), hipMemcpyHostToDevice, s), "copy_host_to_device");
+    auto shared = std::make_shared<utils::DynamicArray>(batch * L * n, true, pool);
+    // a refusal is thrown only after a stream wait: the uploads into `staged` are queued, and it returns to the pool only after them
+    const detail::StepEnv env{pool, s, [](int rc) { if (rc != TROYN_OK) { (void)stream_wait(); troyn_check(rc); } }};
+    detail::ckks_encode_diagonals_step(env, context_->ckks(), static_cast<uint32_t>(L), d_source, matrix, static_cast<uint32_t>(dim), static_cast<uint32_t>(rows), d_pairs, scale,
+                                       shared->raw_pointer(), d_flags, batch);
+    // the flags: the only wait of the call (it also covers the uploads from the caller's and this call's host memory)
+    hip_check(hipMemcpyAsync(h_flags.data(), d_flags, batch * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy_device_to_host");
+    hip_check(stream_wait(), "copy_device_to_host");
+    for (size_t i = 0; i < batch; i++)
+        if (h_flags[i]) throw std::invalid_argument(std::string(P) + " encoded values are too large.");
+    std::vector<Plaintext> out(batch);
+    for (size_t i = 0; i < batch; i++) {
+        Plaintext& p = out[i];
+        p.data() = utils::DynamicArray::device_view(shared->raw_pointer() + i * L * n, L * n, shared);
+        p.parms_id() = pid;
+        p.coeff_count() = n;
+        p.coeff_modulus_size() = L;
+        p.poly_modulus_degree() = n;
+        p.scale() = scale;
+        p.is_ntt_form() = true;
+    }
+    return out;
+}
+
 std::vector<Plaintext> CKKSEncoder::encode_complex64_simd_slice_new_batched(const utils::ConstSliceVec<std::complex<double>>& values, std::optional<ParmsID> parms_id, double scale,
                                                                             MemoryPoolHandle pool) const {
     std::vector<BatchItem> items;

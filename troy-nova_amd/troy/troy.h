@@ -1283,6 +1283,12 @@ public:
                                            const std::vector<Plaintext*>& destinations, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
         assign_batched("[CKKSEncoder::encode_float64_polynomial_batched]", encode_float64_polynomial_new_batched(values, parms_id, scale, pool), destinations);
     }
+    // ADDITION to the reference's interface (troyn_ckks_encode_diagonals, include/troyn.h): plaintext t is diagonal pairs[t].first of a complex n x n
+    // matrix rotated back by pairs[t].second, repeated across the slots, selected and rotated on the device while the encoder loads it.  `source` (host)
+    // is [nd][n] diagonals, or the row-major matrix [n][n] with matrix = true; it is uploaded once.  The words are those of
+    // encode_complex64_simd_new_batched on the rotated diagonals.
+    std::vector<Plaintext> encode_diagonals_new(const std::complex<double>* source, bool matrix, size_t n, size_t nd, const std::vector<std::pair<uint32_t, uint32_t>>& pairs,
+                                                std::optional<ParmsID> parms_id, double scale, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     // the plaintexts of one call share their parms_id and scale: one C-ABI call, one download
     std::vector<std::vector<std::complex<double>>> decode_complex64_simd_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     std::vector<std::vector<double>> decode_float64_polynomial_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -1420,6 +1426,8 @@ bool on_combining_stream();                // combining is on and this thread's 
 // ----------------------------------------------------------------------------------------------
 // Evaluator  (src/evaluator.h)
 // ----------------------------------------------------------------------------------------------
+class LinearTransform;     // linear_transform.h
+
 class Evaluator {
 public:
     enum class SwitchKeyDestinationAssignMethod { AddInplace = 0, Overwrite = 1, OverwriteExceptFirst = 2 };
@@ -1746,10 +1754,10 @@ public:
     //                          summed BEFORE the division by the special prime: ONE tail.  The element 1 adds its ciphertext unrotated.
     //   rotate_sum_each:       the same for rotation steps; a step of 0 is the identity.
     //   rotate_bsgs_sum:       destination = SUM_g rotate( SUM_b weights[g][b] * rotate(encrypted, baby_steps[b]), giant_steps[g] ): one digit
-    //                          decomposition of `encrypted`, one division per giant step for the inner sums and ONE for the outer sum.  The
-    //                          caller supplies weights[g][b] ALREADY ROTATED BACK by giant_steps[g] (the diagonal of the matrix that multiplies
-    //                          the rotation by giant_steps[g] + baby_steps[b], rotated by -giant_steps[g]); a null weight leaves the pair out;
-    //                          every giant step needs a weight.  Weights as for rotate_weighted_sums (key level, NTT form, close scales);
+    //                          decomposition of `encrypted`, one division per giant step for the inner sums and ONE for the outer sum.  
+    //                          weights[g][b] is the diagonal of the matrix that multiplies the rotation by giant_steps[g] + baby_steps[b], rotated
+    //                          by -giant_steps[g]: troy::LinearTransform (linear_transform.h) builds the steps and the weights from a matrix or its
+    //                          diagonals, and linear_transform below evaluates it.  A null weight leaves the pair out; every giant step needs a weight.  Weights as for rotate_weighted_sums (key level, NTT form, close scales);
     //                          CKKS: the destination's scale is encrypted.scale() * the weight scale.
     //   apply_galois_bsgs_sum: the same for Galois elements.
     //   The operands of the _each forms must share their level, form and (CKKS) scale.  A missing key throws "Galois key not present." (no NAF
@@ -1805,6 +1813,22 @@ public:
                                                   const GaloisKeys& galois_keys, const std::vector<WeightRow>& weights,
                                                   MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
         Ciphertext d; rotate_bsgs_sum_double_hoisted(encrypted, baby_steps, giant_steps, galois_keys, weights, d, pool); return d;
+    }
+    // ADDITION to the reference's interface: a LinearTransform (linear_transform.h: the diagonals of a complex matrix encoded on the device into BSGS
+    //   weights) applied to a CKKS ciphertext.  linear_transform is rotate_bsgs_sum_double_hoisted on the transform's steps and weights,
+    //   linear_transform_single_hoisted is rotate_bsgs_sum; scale and level of the result are theirs, nothing is rescaled.  Keys: lt.rotation_steps().
+    //   std::invalid_argument "[Evaluator::linear_transform] ..." for a non-CKKS context, an operand at another level than the transform's, or a
+    //   transform size that does not divide the slot count.
+    void linear_transform(const Ciphertext& encrypted, const LinearTransform& lt, const GaloisKeys& galois_keys, Ciphertext& destination,
+                          MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext linear_transform_new(const Ciphertext& encrypted, const LinearTransform& lt, const GaloisKeys& galois_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; linear_transform(encrypted, lt, galois_keys, d, pool); return d;
+    }
+    void linear_transform_single_hoisted(const Ciphertext& encrypted, const LinearTransform& lt, const GaloisKeys& galois_keys, Ciphertext& destination,
+                                         MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext linear_transform_single_hoisted_new(const Ciphertext& encrypted, const LinearTransform& lt, const GaloisKeys& galois_keys,
+                                                   MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; linear_transform_single_hoisted(encrypted, lt, galois_keys, d, pool); return d;
     }
 
     // ADDITION to the reference's interface: the hoisted family above on BGV contexts (troyn_bgv_apply_galois_many / _sum / _weighted_sums / _sum_each and
