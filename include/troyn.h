@@ -763,6 +763,34 @@ int troyn_ckks_encode_diagonals(const troyn_ckks* h, uint32_t L, const double* s
                                 void* workspace, size_t workspace_bytes, size_t items, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Factors of the special DFT (an addition to the reference's API): the matrices of CoeffToSlot / SlotToCoeff for the reference's slot order,
+ * Galois generator 3, written to device memory by their present diagonals in the layout troyn_ckks_encode_diagonals reads in diagonals mode.
+ *
+ * N is the ring degree, n = N/2, m = log2 n, zeta = exp(2 pi i / 2N).  With t the N real coefficients, w_k = t_k + i t_{k+n} and z_j the
+ * slots, zh_j = z_j (j even) / conj(z_j) (j odd) is an ordinary special FFT on the rotation group (-3)^j (3 = -1 mod 4: odd slots see conj(w)):
+ *   zh = L_{m-1} ... L_0 BR w,   BR the bit reversal on m bits; layer b has lh = 2^b, len = 2 lh and tw_b(j) = zeta^(((-3)^j mod 4 len) 2N / 4 len);
+ *   rows (i + j, i + j + lh), j < lh, of L_b are [[1, tw], [1, -tw]] and of L_b^-1 they are 1/2 [[1, 1], [1/tw, -1/tw]].
+ * The entry writes the product of the layers [first, first + count): forward L_{first+count-1} ... L_first, inverse (inverse != 0)
+ * L_first^-1 ... L_{first+count-1}^-1.  out is double [nd][n][2], out[a][i] = M[i][(i + d_a) mod n], d_a ascending mod n: the multiples of
+ * 2^first up to +-(2^count - 1) of them, nd = 2^(count+1) - 1, or 2^count when first + count == m (+k and -(2^count - k) then coincide).
+ * troyn_ckks_dft_factor_diagonals_count gives nd (0 for a null handle, count == 0 or layers outside [0, m]).
+ * col_mask / row_mask: 0 none, 1 keep even columns / rows, 2 keep odd ones; conjugate != 0 conjugates every entry; `constant` (real) is
+ * multiplied in.  Absent and masked entries are +0.
+ *
+ * CONTRACT: the words of `out` equal those of tests/dft_factors_spec.py (table) on the handle's own tables (troyn_ckks_get_tables): an entry
+ * is ONE product of butterfly coefficients in the order of application -- acc = (constant, 0); per layer a coefficient 1 is skipped, another
+ * one is a complex multiply (re = ar cr - ai ci, im = ar ci + ai cr, every operation rounded on its own, no FMA), the 1/2 of an inverse layer
+ * its own multiply after it -- and every twiddle is read from root_powers (zeta^k = root_powers[bitrev(k mod N)], negated for k >= N).
+ *
+ * No workspace.  out: device memory, 16-byte aligned.  The kernel is enqueued on the caller's stream; the entry does not synchronise or touch
+ * the default stream.  count == 0 returns TROYN_OK and touches nothing; only the handle is looked at before.  TROYN_E_INVALID: a null handle or
+ * pointer, a misaligned pointer, layers outside [0, log2 n] (first + count > m), an unknown mask, a constant that is not finite.
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_ckks_dft_factor_diagonals_count(const troyn_ckks* h, uint32_t first, uint32_t count);
+int troyn_ckks_dft_factor_diagonals(const troyn_ckks* h, uint32_t first, uint32_t count, int inverse, int col_mask, int row_mask, int conjugate,
+                                    double constant, double* out, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * CKKS ModRaise (an addition to the reference's API): the exact centred base extension of a ciphertext from the plan's moduli
  * 0..L_in-1 to its moduli 0..L_out-1, the first step of a bootstrap.  On the troyn_ckks handle, which owns the Garner table q_j^-1 mod q_i.
  * Layouts of troyn_mod_switch_drop: in u64 [batch][pcount][L_in][N], out u64 [batch][pcount][L_out][N], row i under modulus i.

@@ -323,4 +323,60 @@ __global__ __launch_bounds__(256) void ckks_compose_kernel(CkksComposeArgs a) {
     a.out[(size_t)item * a.n + x] = (greater ? -mag : mag) / a.scale;
 }
 
+// ---- factors of the special DFT (CoeffToSlot / SlotToCoeff; include/troyn.h, "Factors of the special DFT") --------------------------------
+// The product of the radix-2 layers [first, first + count) of the special FFT on the rotation group (-3)^j, forward or inverse, written by its
+// present diagonals in the layout the diagonal encoder reads: out[a][i] = M[i][(i + d_a) mod n].  One thread per (diagonal, slot); an entry
+// is one product of butterfly coefficients in the order of application (tests/dft_factors_spec.py states the association), each multiply its
+// own rounding: this unit is compiled with -ffp-contract=off.  Twiddles come from the handle's root_powers, the exponent (-3)^j from a
+// running product over the bits of j (mod 2^32, which every 4 len divides).  No LDS; stores are double2, coalesced along the slot.
+struct CkksDftFactorArgs {
+    const double2* roots;                 // [N] root_powers
+    double2* out;                         // [nd][n]
+    double constant;
+    unsigned log_n;                       // log2 N
+    unsigned first, count;                // layers [first, first + count), count >= 1
+    unsigned nd, wrap;                    // diagonals; wrap: first + count == log2 n (d_a = a 2^first for every a)
+    unsigned inverse, conjugate, col_mask, row_mask;     // masks: 0 none, 1 even, 2 odd
+};
+
+// (-3)^(j mod 2^b) mod 2^32 by squaring over the b <= 14 low bits of j
+__device__ __forceinline__ unsigned ckks_rotation_power(unsigned j, unsigned b) {
+    unsigned p = 1, sq = 0u - 3u;
+    for (unsigned t = 0; t < b; t++) { if ((j >> t) & 1) p *= sq; sq *= sq; }
+    return p;
+}
+
+static __global__ __launch_bounds__(256) void ckks_dft_factor_kernel(CkksDftFactorArgs a) {
+    const unsigned n = 1u << (a.log_n - 1);
+    const unsigned row = blockIdx.x * 256u + threadIdx.x, da = blockIdx.y;
+    if (row >= n) return;
+    const unsigned reach = 1u << a.count;
+    const unsigned d = (a.wrap || da < reach) ? da << a.first : n - ((a.nd - da) << a.first);
+    const unsigned col = (row + d) & (n - 1);
+    bool present = ((row ^ col) & ~((reach - 1) << a.first)) == 0;
+    if (a.row_mask) present = present && (row & 1) == (a.row_mask == 2u);
+    if (a.col_mask) present = present && (col & 1) == (a.col_mask == 2u);
+    double ar = 0.0, ai = 0.0;
+    if (present) {
+        ar = a.constant;
+        // forward: the layers upwards, the twiddle index from the row; inverse: downwards, from the column
+        const unsigned j = a.inverse ? col : row;
+        for (unsigned step = 0; step < a.count; step++) {
+            const unsigned b = a.inverse ? a.first + a.count - 1 - step : a.first + step;
+            const unsigned rb = (row >> b) & 1, cb = (col >> b) & 1;
+            if (a.inverse ? rb : cb) {
+                const unsigned k = (ckks_rotation_power(j, b) & ((8u << b) - 1)) << (a.log_n - b - 2);   // ((-3)^j mod 4 len) (2N / 4 len) in [0, 2N)
+                const double2 r = a.roots[__brev(k & ((1u << a.log_n) - 1)) >> (32 - a.log_n)];
+                double tr = r.x, ti = a.inverse ? -r.y : r.y;
+                if ((k >> a.log_n) ^ (a.inverse ? cb : rb)) { tr = -tr; ti = -ti; }
+                const double nr = ar * tr - ai * ti, ni = ar * ti + ai * tr;
+                ar = nr; ai = ni;
+            }
+            if (a.inverse) { ar = ar * 0.5; ai = ai * 0.5; }
+        }
+        if (a.conjugate) ai = -ai;
+    }
+    a.out[(size_t)da * n + row] = make_double2(ar, ai);
+}
+
 }  // namespace troyn

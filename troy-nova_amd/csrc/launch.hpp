@@ -117,12 +117,14 @@ void launch_behz2_floor(unsigned L, bool smallq, unsigned grid, hipStream_t s, u
 // size's form, ntt_sizes.hpp column fft), the coefficient-wise encoding, and the CRT composition of a decoded plaintext (L <= CKKS_MAX_L)
 struct CkksFftArgs;
 struct CkksComposeArgs;
+struct CkksDftFactorArgs;
 bool ckks_fft_two_pass(unsigned log_n);
 bool launch_ckks_fft(unsigned log_n, bool decode, const CkksFftArgs& a, size_t batch, hipStream_t s);
 bool launch_ckks_fft_diagonals(unsigned log_n, bool matrix, const CkksFftArgs& a, size_t batch, hipStream_t s);
 void launch_ckks_encode_polynomial(const double* coeffs, unsigned count, double scale, unsigned n, const DevModulus* mods, unsigned L, u64* residues,
                                    unsigned* too_large, size_t batch, hipStream_t s);
 bool launch_ckks_compose(const CkksComposeArgs& a, size_t batch, hipStream_t s);
+void launch_ckks_dft_factor(const CkksDftFactorArgs& a, hipStream_t s);
 // CKKS ModRaise (troyn_raise.hip, raise_kernels.hpp): the centred base extension of items = batch * pcount polynomials in coefficient form, `chunks`
 // workgroups per polynomial (L <= CKKS_MAX_L; false above)
 struct ModRaiseArgs;

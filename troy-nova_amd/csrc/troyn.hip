@@ -4268,6 +4268,39 @@ extern "C" int troyn_ckks_encode_diagonals(const troyn_ckks* h, uint32_t L, cons
     return ckks_encode(h, true, L, src, h ? h->plan->n / 2 : 0, scale, out, too_large, workspace, workspace_bytes, items, stream, &ds);
 }
 
+// the number of present diagonals of the product of the layers [first, first + count) of the special DFT on n = N/2 slots; 0: nothing to write
+static uint32_t ckks_dft_factor_count(const troyn_ckks* h, uint32_t first, uint32_t count) {
+    if (!h || count == 0) return 0;
+    const uint32_t m = h->plan->log_n - 1;
+    if (first > m || count > m - first) return 0;
+    return first + count == m ? 1u << count : (2u << count) - 1;
+}
+
+extern "C" size_t troyn_ckks_dft_factor_diagonals_count(const troyn_ckks* h, uint32_t first, uint32_t count) {
+    return ckks_dft_factor_count(h, first, count);
+}
+extern "C" int troyn_ckks_dft_factor_diagonals(const troyn_ckks* h, uint32_t first, uint32_t count, int inverse, int col_mask, int row_mask, int conjugate,
+                                               double constant, double* out, troyn_stream_t stream) {
+    const char* P = "[troyn_ckks_dft_factor_diagonals]";
+    if (!h) return fail(TROYN_E_INVALID, std::string(P) + " null handle");
+    if (count == 0) return TROYN_OK;
+    select_device(h);
+    const uint32_t m = h->plan->log_n - 1;
+    if (first > m || count > m - first) return fail(TROYN_E_INVALID, std::string(P) + " layers outside [0, log2 n]");
+    if (col_mask < 0 || col_mask > 2 || row_mask < 0 || row_mask > 2) return fail(TROYN_E_INVALID, std::string(P) + " unknown mask");
+    if (!std::isfinite(constant)) return fail(TROYN_E_INVALID, std::string(P) + " the constant is not finite");
+    if (!out) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if ((uintptr_t)out & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned pointer");
+    CkksDftFactorArgs a{};
+    a.roots = h->d_roots; a.out = reinterpret_cast<double2*>(out); a.constant = constant;
+    a.log_n = h->plan->log_n; a.first = first; a.count = count;
+    a.nd = ckks_dft_factor_count(h, first, count); a.wrap = first + count == m;
+    a.inverse = inverse != 0; a.conjugate = conjugate != 0; a.col_mask = (unsigned)col_mask; a.row_mask = (unsigned)row_mask;
+    launch_ckks_dft_factor(a, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+
 static int ckks_decode(const troyn_ckks* h, bool simd, uint32_t L, const uint64_t* plain, double scale, double* out, void* ws, size_t ws_bytes, size_t batch,
                        troyn_stream_t stream) {
     const char* P = "[CKKSEncoder::decode_internal]";

@@ -59,4 +59,10 @@ bool launch_ckks_compose(const CkksComposeArgs& a, size_t batch, hipStream_t s) 
     return true;
 }
 
+// one thread per (diagonal, slot): 256 slots per workgroup along x, the diagonal along y
+void launch_ckks_dft_factor(const CkksDftFactorArgs& a, hipStream_t s) {
+    const unsigned n = 1u << (a.log_n - 1);
+    hipLaunchKernelGGL(ckks_dft_factor_kernel, dim3((n + 255) / 256, a.nd), dim3(256), 0, s, a);
+}
+
 }  // namespace troyn

@@ -941,6 +941,15 @@ class CkksEncoder:
                                                         C.c_void_p(too_large.data_ptr()) if flags else None, ws, ws_bytes, items, _stream()))
         return (out, too_large[:items]) if flags else out
 
+    def dft_factor_diagonals(self, first, count, inverse=False, col_mask=0, row_mask=0, conjugate=False, constant=1.0):
+        """troyn_ckks_dft_factor_diagonals: the product of the layers [first, first + count) of the special DFT (CoeffToSlot / SlotToCoeff) by its
+        present diagonals -> float64 [nd][N/2][2], the source of encode_diagonals; masks: 0 none, 1 even, 2 odd"""
+        nd = int(self.lib.troyn_ckks_dft_factor_diagonals_count(self.h, first, count))
+        out = torch.empty((nd, self.plan.n // 2, 2), dtype=torch.float64, device=self.plan.device)
+        capi.check(self.lib.troyn_ckks_dft_factor_diagonals(self.h, first, count, 1 if inverse else 0, int(col_mask), int(row_mask), 1 if conjugate else 0,
+                                                            float(constant), C.c_void_p(out.data_ptr()), _stream()))
+        return out
+
     def encode_polynomial(self, L, coeffs, scale, flags=False):
         """coeffs [batch][count] -> [batch][L][N]"""
         batch, count = coeffs.shape[0], coeffs.shape[1]

@@ -16,6 +16,7 @@
 #include "../troy/linear_transform.h"
 #include "../troy/matmul.h"
 #include "../troy/ring2k.h"
+#include "../troy/slot_transform.h"
 #include "../troy/troy.h"
 
 namespace py = pybind11;
@@ -711,6 +712,37 @@ PYBIND11_MODULE(pytroy_raw, m) {
         s.linear_transform_single_hoisted(a, lt, k, d, P(p)); }, py::arg("encrypted"), py::arg("lt"), py::arg("galois_keys"), py::arg("destination"), POOL);
     ev.def("linear_transform_single_hoisted_new", [](const Evaluator& s, const Ciphertext& a, const LinearTransform& lt, const GaloisKeys& k, PoolArg p) {
         return s.linear_transform_single_hoisted_new(a, lt, k, P(p)); }, py::arg("encrypted"), py::arg("lt"), py::arg("galois_keys"), POOL);
+    // addition: CoeffToSlotPlan / SlotToCoeffPlan (slot_transform.h), the factored special DFT of a bootstrap, and their evaluation
+    {
+        py::class_<SlotTransformPlan>(m, "SlotTransformPlan")
+            .def("n", &SlotTransformPlan::n).def("scale", &SlotTransformPlan::scale).def("constant", &SlotTransformPlan::constant)
+            .def("groups", &SlotTransformPlan::groups).def("levels", &SlotTransformPlan::levels).def("rotations", &SlotTransformPlan::rotations)
+            .def("boundary_group", &SlotTransformPlan::boundary_group).def("first_layer", &SlotTransformPlan::first_layer, py::arg("group"))
+            .def("needs_conjugate", &SlotTransformPlan::needs_conjugate)
+            .def("parms_id", [](const SlotTransformPlan& s) { return s.parms_id(); })
+            .def("group_parms_id", [](const SlotTransformPlan& s, size_t g) { return s.group_parms_id(g); }, py::arg("group"))
+            .def("layers_per_group", [](const SlotTransformPlan& s) { return s.layers_per_group(); })
+            .def("rotation_steps", [](const SlotTransformPlan& s) { return s.rotation_steps(); })
+            .def("transform", [](const SlotTransformPlan& s, size_t g) -> const LinearTransform& { return s.transform(g); }, py::arg("group"), py::return_value_policy::reference_internal)
+            .def("twin", [](const SlotTransformPlan& s) -> const LinearTransform& { return s.twin(); }, py::return_value_policy::reference_internal);
+        py::class_<CoeffToSlotPlan, SlotTransformPlan>(m, "CoeffToSlotPlan")
+            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p) {
+                     return std::make_unique<CoeffToSlotPlan>(c, e, id, scale, layers, constant, P(p)); }),
+                 py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL);
+        py::class_<SlotToCoeffPlan, SlotTransformPlan>(m, "SlotToCoeffPlan")
+            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p) {
+                     return std::make_unique<SlotToCoeffPlan>(c, e, id, scale, layers, constant, P(p)); }),
+                 py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL);
+        m.def("default_layers_per_group", &default_layers_per_group, py::arg("layers"), py::arg("at_most") = 4);
+    }
+    ev.def("coeff_to_slot", [](const Evaluator& s, const Ciphertext& a, const CoeffToSlotPlan& plan, const GaloisKeys& k, Ciphertext& d, PoolArg p) {
+        s.coeff_to_slot(a, plan, k, d, P(p)); }, py::arg("encrypted"), py::arg("plan"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("coeff_to_slot_new", [](const Evaluator& s, const Ciphertext& a, const CoeffToSlotPlan& plan, const GaloisKeys& k, PoolArg p) {
+        return s.coeff_to_slot_new(a, plan, k, P(p)); }, py::arg("encrypted"), py::arg("plan"), py::arg("galois_keys"), POOL);
+    ev.def("slot_to_coeff", [](const Evaluator& s, const Ciphertext& a, const SlotToCoeffPlan& plan, const GaloisKeys& k, Ciphertext& d, PoolArg p) {
+        s.slot_to_coeff(a, plan, k, d, P(p)); }, py::arg("encrypted"), py::arg("plan"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("slot_to_coeff_new", [](const Evaluator& s, const Ciphertext& a, const SlotToCoeffPlan& plan, const GaloisKeys& k, PoolArg p) {
+        return s.slot_to_coeff_new(a, plan, k, P(p)); }, py::arg("encrypted"), py::arg("plan"), py::arg("galois_keys"), POOL);
     // additions: the hoisted family on BGV contexts (troy.h): bgv_NAME takes NAME's arguments.  SEL is the element / step list's type and keyword
 #define EV_BGV_MANY(name, SEL, sel, what)                                                                                                          \
     ev.def(#name, [](const Evaluator& s, const Ciphertext& a, const std::vector<SEL>& g, const GaloisKeys& k, const std::vector<Ciphertext*>& d, PoolArg p) {  \

@@ -130,6 +130,10 @@ void ckks_encode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uin
 // (diagonal, shift); out and flags as above.  All device memory.
 void ckks_encode_diagonals_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t L, const double* src, bool matrix, uint32_t n, uint32_t nd, const uint32_t* pairs,
                                 double scale, uint64_t* out, uint32_t* flags, size_t count);
+// the product of the layers [first, first + count) of the special DFT by its present diagonals (troyn_ckks_dft_factor_diagonals): out [nd][N/2][2], device
+// memory, the `src` of ckks_encode_diagonals_step in diagonals mode; masks: 0 none, 1 even, 2 odd.  No workspace.
+void ckks_dft_factor_diagonals_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t first, uint32_t count, bool inverse, int col_mask, int row_mask, bool conjugate,
+                                    double constant, double* out);
 void ckks_decode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const uint64_t* in, double scale, double* out, size_t count);
 
 // LWE (lwe.cpp): coefficient `terms[i]` of srcs[i] as an LWE ciphertext, c0 [count][L] and c1 [count][L][N]; the leaves of the packing tree

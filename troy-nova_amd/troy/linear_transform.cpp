@@ -35,8 +35,15 @@ LinearTransform::LinearTransform(HeContextPointer context, const CKKSEncoder& en
     build(context, encoder, present, matrix.data(), true, pool);
 }
 
+LinearTransform::LinearTransform(HeContextPointer context, const CKKSEncoder& encoder, size_t n, const ParmsID& parms_id, double scale, const std::vector<size_t>& present,
+                                 DeviceTable table, size_t baby_count, MemoryPoolHandle pool)
+    : n_(n), n1_(baby_count), parms_id_(parms_id), scale_(scale) {
+    if (present.empty() || !table.diagonals) throw std::invalid_argument(std::string(LT) + " no diagonals.");
+    build(context, encoder, present, nullptr, false, pool, table.diagonals);
+}
+
 void LinearTransform::build(HeContextPointer context, const CKKSEncoder& encoder, const std::vector<size_t>& present, const std::complex<double>* source, bool matrix,
-                            MemoryPoolHandle pool) {
+                            MemoryPoolHandle pool, const double* device_source) {
     if (!context || !context->get_context_data(parms_id_).has_value()) throw std::invalid_argument(std::string(LT) + " parms_id not valid for context.");
     if (context->get_context_data(parms_id_).value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(std::string(LT) + " a CKKS context is needed.");
     const size_t slots = encoder.slot_count();
@@ -62,7 +69,8 @@ void LinearTransform::build(HeContextPointer context, const CKKSEncoder& encoder
             pairs.emplace_back(static_cast<uint32_t>(matrix ? k : static_cast<size_t>(at - present.begin())), static_cast<uint32_t>(giant_steps_[g]));
             where.emplace_back(g, b);
         }
-    weights_ = encoder.encode_diagonals_new(source, matrix, n_, present.size(), pairs, context->key_parms_id(), scale_, pool);
+    weights_ = device_source ? encoder.encode_device_diagonals_new(device_source, n_, present.size(), pairs, context->key_parms_id(), scale_, pool)
+                             : encoder.encode_diagonals_new(source, matrix, n_, present.size(), pairs, context->key_parms_id(), scale_, pool);
     rows_.assign(giant_steps_.size(), WeightRow(baby_steps_.size(), nullptr));
     for (size_t i = 0; i < where.size(); i++) rows_[where[i].first][where[i].second] = &weights_[i];
 }

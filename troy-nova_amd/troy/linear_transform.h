@@ -48,8 +48,14 @@ public:
     const std::vector<int>& rotation_steps() const { return rotation_steps_; }
 
 private:
+    friend class SlotTransformPlan;     // slot_transform.h
+    // the diagonals `present` (ascending) as a table [present.size()][n] of double pairs that is already in device memory (CKKSEncoder::dft_factor_diagonals):
+    // the split and the weights of the constructors above, nothing but the (diagonal, shift) pairs uploaded
+    struct DeviceTable { const double* diagonals; };
+    LinearTransform(HeContextPointer context, const CKKSEncoder& encoder, size_t n, const ParmsID& parms_id, double scale, const std::vector<size_t>& present,
+                    DeviceTable table, size_t baby_count, MemoryPoolHandle pool);
     void build(HeContextPointer context, const CKKSEncoder& encoder, const std::vector<size_t>& present, const std::complex<double>* source, bool matrix,
-               MemoryPoolHandle pool);
+               MemoryPoolHandle pool, const double* device_source = nullptr);
     size_t n_, n1_;
     ParmsID parms_id_;
     double scale_;

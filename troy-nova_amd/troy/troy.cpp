@@ -4574,6 +4574,17 @@ std::vector<Plaintext> CKKSEncoder::encode_batched(bool simd, const std::vector<
 std::vector<Plaintext> CKKSEncoder::encode_diagonals_new(const std::complex<double>* source, bool matrix, size_t dim, size_t nd,
                                                          const std::vector<std::pair<uint32_t, uint32_t>>& pairs, std::optional<ParmsID> parms_id, double scale,
                                                          MemoryPoolHandle pool) const {
+    return encode_diagonals_from(reinterpret_cast<const double*>(source), false, matrix, dim, nd, pairs, parms_id, scale, pool);
+}
+
+std::vector<Plaintext> CKKSEncoder::encode_device_diagonals_new(const double* diagonals, size_t dim, size_t nd, const std::vector<std::pair<uint32_t, uint32_t>>& pairs,
+                                                                std::optional<ParmsID> parms_id, double scale, MemoryPoolHandle pool) const {
+    return encode_diagonals_from(diagonals, true, false, dim, nd, pairs, parms_id, scale, pool);
+}
+
+std::vector<Plaintext> CKKSEncoder::encode_diagonals_from(const double* source, bool source_on_device, bool matrix, size_t dim, size_t nd,
+                                                          const std::vector<std::pair<uint32_t, uint32_t>>& pairs, std::optional<ParmsID> parms_id, double scale,
+                                                          MemoryPoolHandle pool) const {
     const char* P = "[CKKSEncoder::encode_diagonals]";
     if (!context_->on_device()) throw std::invalid_argument(std::string(P) + " HeContext is not on device (call to_device_inplace).");
     const ParmsID pid = parms_id.value_or(context_->first_parms_id());
@@ -4590,15 +4601,15 @@ std::vector<Plaintext> CKKSEncoder::encode_diagonals_new(const std::complex<doub
     if (scale <= 0 || std::log2(scale) + 1.0 >= static_cast<double>(total_bits)) throw std::invalid_argument(std::string(P) + " scale out of bounds.");
     if (batch == 0) return {};
     hipStream_t s = current_stream();
-    // the source [rows][dim] complex, then the pairs, then the too-large flags: uploaded once, read by every item
-    const size_t source_words = rows * dim * 2, pair_words = batch, flag_words = (batch + 1) / 2;
+    // the source [rows][dim] complex (a host source only), then the pairs, then the too-large flags: uploaded once, read by every item
+    const size_t source_words = source_on_device ? 0 : rows * dim * 2, pair_words = batch, flag_words = (batch + 1) / 2;
     utils::DynamicArray staged(source_words + pair_words + flag_words + 2, true, pool);
-    double* d_source = reinterpret_cast<double*>(staged.raw_pointer());
+    const double* d_source = source_on_device ? source : reinterpret_cast<const double*>(staged.raw_pointer());
     uint32_t* d_pairs = reinterpret_cast<uint32_t*>(staged.raw_pointer() + source_words);
     uint32_t* d_flags = reinterpret_cast<uint32_t*>(staged.raw_pointer() + source_words + pair_words);
     std::vector<uint32_t> h_pairs(2 * batch), h_flags(batch);
     for (size_t i = 0; i < batch; i++) { h_pairs[2 * i] = pairs[i].first; h_pairs[2 * i + 1] = pairs[i].second; }
-    hip_check(hipMemcpyAsync(d_source, source, source_words * sizeof(double), hipMemcpyHostToDevice, s), "copy_host_to_device");
+    if (!source_on_device) hip_check(hipMemcpyAsync(staged.raw_pointer(), source, source_words * sizeof(double), hipMemcpyHostToDevice, s), "copy_host_to_device");
     hip_check(hipMemcpyAsync(d_pairs, h_pairs.data(), 2 * batch * sizeof(uint32_t), hipMemcpyHostToDevice, s), "copy_host_to_device");
     auto shared = std::make_shared<utils::DynamicArray>(batch * L * n, true, pool);
     // a refusal is thrown only after a stream wait: the uploads into `staged` are queued, and it returns to the pool only after them
@@ -4622,6 +4633,18 @@ std::vector<Plaintext> CKKSEncoder::encode_diagonals_new(const std::complex<doub
         p.is_ntt_form() = true;
     }
     return out;
+}
+
+utils::DynamicArray CKKSEncoder::dft_factor_diagonals(size_t first, size_t count, bool inverse, int col_mask, int row_mask, bool conjugate, double constant, size_t& nd,
+                                                      MemoryPoolHandle pool) const {
+    const char* P = "[CKKSEncoder::dft_factor_diagonals]";
+    if (!context_->on_device()) throw std::invalid_argument(std::string(P) + " HeContext is not on device (call to_device_inplace).");
+    nd = troyn_ckks_dft_factor_diagonals_count(context_->ckks(), static_cast<uint32_t>(first), static_cast<uint32_t>(count));
+    if (count == 0 || nd == 0) throw std::invalid_argument(std::string(P) + " the layers must be a non-empty range inside [0, log2 slot_count].");
+    utils::DynamicArray table(nd * slots_ * 2, true, pool);
+    detail::ckks_dft_factor_diagonals_step(on_current_stream(pool), context_->ckks(), static_cast<uint32_t>(first), static_cast<uint32_t>(count), inverse, col_mask, row_mask, conjugate, constant,
+                                           reinterpret_cast<double*>(table.raw_pointer()));
+    return table;
 }
 
 std::vector<Plaintext> CKKSEncoder::encode_complex64_simd_slice_new_batched(const utils::ConstSliceVec<std::complex<double>>& values, std::optional<ParmsID> parms_id, double scale,

@@ -1289,6 +1289,14 @@ public:
     // encode_complex64_simd_new_batched on the rotated diagonals.
     std::vector<Plaintext> encode_diagonals_new(const std::complex<double>* source, bool matrix, size_t n, size_t nd, const std::vector<std::pair<uint32_t, uint32_t>>& pairs,
                                                 std::optional<ParmsID> parms_id, double scale, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    // the same from a table of diagonals [nd][n] that is already in device memory (double pairs re, im; 16-byte aligned): nothing but the pairs is uploaded
+    std::vector<Plaintext> encode_device_diagonals_new(const double* diagonals, size_t n, size_t nd, const std::vector<std::pair<uint32_t, uint32_t>>& pairs,
+                                                       std::optional<ParmsID> parms_id, double scale, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    // ADDITION (troyn_ckks_dft_factor_diagonals, include/troyn.h): the product of the layers [first, first + count) of the special DFT behind CoeffToSlot /
+    // SlotToCoeff, written on the device by its present diagonals [nd][slot_count] (double pairs), the source of encode_device_diagonals_new.  Masks: 0 none,
+    // 1 even, 2 odd columns / rows kept.  nd receives the number of diagonals.  slot_transform.h builds the plans from it.
+    utils::DynamicArray dft_factor_diagonals(size_t first, size_t count, bool inverse, int col_mask, int row_mask, bool conjugate, double constant, size_t& nd,
+                                             MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     // the plaintexts of one call share their parms_id and scale: one C-ABI call, one download
     std::vector<std::vector<std::complex<double>>> decode_complex64_simd_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     std::vector<std::vector<double>> decode_float64_polynomial_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -1300,6 +1308,9 @@ private:
     // items: (pointer, doubles, on_device) of every item; words_per_value = 2 (complex) or 1
     struct BatchItem { const double* ptr; size_t doubles; bool device; };
     std::vector<Plaintext> encode_batched(bool simd, const std::vector<BatchItem>& items, std::optional<ParmsID> parms_id, double scale, MemoryPoolHandle pool) const;
+    // encode_diagonals_new / encode_device_diagonals_new: the source in host memory (uploaded) or already in device memory
+    std::vector<Plaintext> encode_diagonals_from(const double* source, bool source_on_device, bool matrix, size_t n, size_t nd,
+                                                 const std::vector<std::pair<uint32_t, uint32_t>>& pairs, std::optional<ParmsID> parms_id, double scale, MemoryPoolHandle pool) const;
     std::vector<double> decode_batched(bool simd, const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool) const;   // [batch][N] doubles either way
     void set_plaintext(const std::vector<double>& coeffs, const ParmsID& parms_id, double scale, Plaintext& destination, MemoryPoolHandle pool) const;
     std::vector<double> plaintext_coefficients(const Plaintext& plain, MemoryPoolHandle pool) const;   // centred, as doubles (not yet / scale)
@@ -1427,6 +1438,9 @@ bool on_combining_stream();                // combining is on and this thread's 
 // Evaluator  (src/evaluator.h)
 // ----------------------------------------------------------------------------------------------
 class LinearTransform;     // linear_transform.h
+class SlotTransformPlan;   // slot_transform.h
+class CoeffToSlotPlan;
+class SlotToCoeffPlan;
 
 class Evaluator {
 public:
@@ -1829,6 +1843,25 @@ public:
     Ciphertext linear_transform_single_hoisted_new(const Ciphertext& encrypted, const LinearTransform& lt, const GaloisKeys& galois_keys,
                                                    MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
         Ciphertext d; linear_transform_single_hoisted(encrypted, lt, galois_keys, d, pool); return d;
+    }
+
+    // ADDITION to the reference's interface: CoeffToSlot / SlotToCoeff of a bootstrap on fully packed CKKS slots (slot_transform.h: the factored special DFT
+    //   for the generator-3 slot order, its factors written and encoded on the device).  Group by group in the plan's order: linear_transform
+    //   (double-hoisted), then rescale_to_next; the boundary group -- the first of CoeffToSlot, the last of SlotToCoeff -- is the sum of one transform of the
+    //   operand and the complex_conjugate of a second one, at the same level.  One level per group.  coeff_to_slot leaves constant * BR(t_k + i t_{k+n}) in the slots
+    //   (t the coefficients of the plaintext over its scale, BR the bit reversal on log2 n bits), the order slot_to_coeff consumes; slot_to_coeff returns the
+    //   ciphertext whose slots are constant * decode of those coefficients.  Keys: plan.rotation_steps() and the conjugation key (step 0 of create_galois_keys_from_steps).
+    //   std::invalid_argument "[Evaluator::coeff_to_slot] ..." / "[Evaluator::slot_to_coeff] ..." for a non-CKKS context, an operand at another level than the
+    //   plan's, or a plan whose n is not the operand's slot count ("Sparse packing is not supported").
+    void coeff_to_slot(const Ciphertext& encrypted, const CoeffToSlotPlan& plan, const GaloisKeys& galois_keys, Ciphertext& destination,
+                       MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext coeff_to_slot_new(const Ciphertext& encrypted, const CoeffToSlotPlan& plan, const GaloisKeys& galois_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; coeff_to_slot(encrypted, plan, galois_keys, d, pool); return d;
+    }
+    void slot_to_coeff(const Ciphertext& encrypted, const SlotToCoeffPlan& plan, const GaloisKeys& galois_keys, Ciphertext& destination,
+                       MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext slot_to_coeff_new(const Ciphertext& encrypted, const SlotToCoeffPlan& plan, const GaloisKeys& galois_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; slot_to_coeff(encrypted, plan, galois_keys, d, pool); return d;
     }
 
     // ADDITION to the reference's interface: the hoisted family above on BGV contexts (troyn_bgv_apply_galois_many / _sum / _weighted_sums / _sum_each and
