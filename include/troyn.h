@@ -791,6 +791,38 @@ int troyn_ckks_dft_factor_diagonals(const troyn_ckks* h, uint32_t first, uint32_
                                     double constant, double* out, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Real and imaginary parts of CKKS slots (an addition to the reference's API): the two streaming steps between CoeffToSlot, EvalMod and
+ * SlotToCoeff of a bootstrap, on the multiplication by i that costs no key switch, no level and no scale.
+ *
+ * The slot order is Galois generator 3: slot j evaluates a plaintext at zeta^(3^j), zeta = exp(2 pi i / 2N), and
+ * (zeta^(3^j))^(N/2) = i^(3^j) = i (-1)^j.  Multiplying a ciphertext by the monomial X^(N/2) therefore multiplies slot j by i (-1)^j, whatever
+ * the slots hold.  With w a ciphertext and wc its complex conjugate (troyn_apply_galois with the element 2N - 1, then a key switch):
+ *   s = w + wc                 slots 2 Re w
+ *   d = (wc - w) X^(N/2)       slots (-1)^j 2 Im w           (wc - w = -2i Im w, times i (-1)^j)
+ *   out = s' + d' X^(N/2)      slots Re' + i Im' when s' holds Re' and d' holds (-1)^j Im'        ((-1)^j squared)
+ * The sign pattern (-1)^j passes through any ODD slot-wise function (EvalMod's sine) and cancels in the join.
+ *
+ * In NTT form the product with X^(N/2) is a dyadic product with mu, the forward transform of the monomial: mu = iota_l on the lower half
+ * of a row (indices below N/2) and q_l - iota_l on the upper half, iota_l = psi_l^(N/2) the square root of -1 modulo q_l that
+ * troyn_plan_get_root_powers holds at index 1 (tests/bootstrap_spec.py derives the halves from the tables and checks them against the transform).
+ *   troyn_ckks_complex_split   s = a + b,  d = mu . (b - a)      (a = w, b = wc)
+ *   troyn_ckks_complex_join    out = a + mu . b
+ * modulo q_l, canonical words in and out.  a, b, s, d, out: [batch][2][L][N] on the plan's first L moduli, NTT form, device memory, 16-byte
+ * aligned.  An output may be one of the inputs (same pointer); s and d must differ.
+ *
+ * CONTRACT: the words equal those of troyn_add, troyn_sub and troyn_dyadic_product with the transformed monomial (troyn_ntt_forward of
+ * X^(N/2)), word for word: every result is the canonical residue of the same integer.  split reads four rows and writes four rows per limb,
+ * once each, in ONE launch (composed: three launches and about twice the traffic); join reads two rows and writes one.
+ *
+ * No workspace.  The kernel is enqueued on the caller's stream; the entries do not synchronise or touch the default stream.  batch == 0
+ * returns TROYN_OK and touches nothing; only the plan and L are looked at before.  TROYN_E_INVALID: a null plan or pointer, a misaligned
+ * pointer, L == 0, L above the plan's moduli, s == d, a batch too large for one launch.
+ * ------------------------------------------------------------------------------------- */
+int troyn_ckks_complex_split(const troyn_plan* plan, uint32_t L, const uint64_t* a, const uint64_t* b, uint64_t* s, uint64_t* d, size_t batch,
+                             troyn_stream_t stream);
+int troyn_ckks_complex_join(const troyn_plan* plan, uint32_t L, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t batch, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * CKKS ModRaise (an addition to the reference's API): the exact centred base extension of a ciphertext from the plan's moduli
  * 0..L_in-1 to its moduli 0..L_out-1, the first step of a bootstrap.  On the troyn_ckks handle, which owns the Garner table q_j^-1 mod q_i.
  * Layouts of troyn_mod_switch_drop: in u64 [batch][pcount][L_in][N], out u64 [batch][pcount][L_out][N], row i under modulus i.

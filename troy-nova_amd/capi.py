@@ -53,6 +53,8 @@ SYMBOLS = {
     "troyn_ckks_multiply_affine_relinearize_rescale_workspace_bytes": (sz, [vp, u32, sz]),
     "troyn_ckks_multiply_affine_relinearize_rescale": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u32), p64, p64, p64,
                                                                  C.POINTER(vp), vp, vp, sz, sz, vp]),
+    "troyn_ckks_complex_split": (C.c_int, [vp, u32, vp, vp, vp, vp, sz, vp]),
+    "troyn_ckks_complex_join": (C.c_int, [vp, u32, vp, vp, vp, sz, vp]),
     "troyn_scalar_weighted_sums_workspace_bytes": (sz, [vp, u32, sz, sz]),
     "troyn_scalar_weighted_sums": (C.c_int, [vp, u32, u32, C.POINTER(vp), C.POINTER(u32), sz, p64, p64, C.c_int, sz, vp, sz, sz, vp, sz, vp]),
     "troyn_divide_and_round_q_last": (C.c_int, [vp, u32, vp, sz, vp, sz, vp]),

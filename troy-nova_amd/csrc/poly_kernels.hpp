@@ -295,6 +295,50 @@ __global__ __launch_bounds__(POLY_BLOCK) void multiply_affine_kernel(unsigned ch
     else multiply_affine_row<false>(chunks, md, n, pc, ptrs.a[item] + in_off, ptrs.b[item] + in_off, nullptr, 0, alpha, 0, k, op);
 }
 
+// Real and imaginary parts of CKKS slots (additions to the reference's kernels, troyn_ckks_complex_split / troyn_ckks_complex_join): the level-free
+// multiplication by i.  mu is the forward transform of the monomial X^(N/2): iota = psi^(N/2), the square root of -1 that the forward twiddle table holds
+// at index 1 (bit_reverse(N/2)), on the lower half of a row and q - iota on the upper half -- the first butterfly layer sends the one non-zero
+// coefficient N/2 to (+iota, -iota) at distance N/2 and every later layer copies it within its half.
+//   split:  s = a + b,  d = mu . (b - a)        join:  out = a + mu . b        all modulo q_l, canonical words in and out
+// a, b, s, d, out -> [rows][N], rows = items * 2 * nmod, the limb of a row is row % nmod.  Geometry of multiply_affine_kernel: a thread owns two adjacent
+// coefficients of one row, 16-byte loads and stores, every input word read once and every output word written once, no LDS.  (iota, its Shoup quotient)
+// is one wave-uniform 16-byte load per workgroup.  The half of the row picks the ORDER of the difference (split) or the sign of b (join) with a
+// select, so q - iota is never formed: iota (b - a) below N/2, iota (a - b) above.  x + q - y lies in [1, 2q) and Shoup's product takes any 64-bit
+// word, so a word of d costs one product and one conditional subtraction; a word of out one product and the add_mod.
+__device__ __forceinline__ u64 split_word(u64 a, u64 b, bool upper, const ulonglong2& iota, u64 q) {
+    return shoup_mul((upper ? a : b) + q - (upper ? b : a), iota.x, iota.y, q);
+}
+__device__ __forceinline__ u64 join_word(u64 a, u64 b, bool upper, const ulonglong2& iota, u64 q) {
+    return add_mod(a, shoup_mul(upper ? q - b : b, iota.x, iota.y, q), q);
+}
+
+__global__ __launch_bounds__(POLY_BLOCK) void ckks_complex_split_kernel(unsigned chunks, const DevModulus* __restrict__ mods, const ulonglong2* __restrict__ fwd,
+                                                                        unsigned nmod, unsigned n, const u64* a, const u64* b, u64* s, u64* d) {
+    const unsigned limb = blk_row(chunks) % nmod;
+    const u64 q = mods[limb].q;
+    const ulonglong2 iota = fwd[(size_t)limb * n + 1];
+    const size_t base = (size_t)blk_row(chunks) * n;
+    const unsigned half = n / 2;
+    for (unsigned i = blk_col(chunks) * 2; i < n; i += chunks * blockDim.x * 2) {
+        const u64x2 va = ld2(a + base + i), vb = ld2(b + base + i);
+        st2(s + base + i, add_mod(va.a, vb.a, q), add_mod(va.b, vb.b, q));
+        st2(d + base + i, split_word(va.a, vb.a, i >= half, iota, q), split_word(va.b, vb.b, i + 1 >= half, iota, q));
+    }
+}
+
+__global__ __launch_bounds__(POLY_BLOCK) void ckks_complex_join_kernel(unsigned chunks, const DevModulus* __restrict__ mods, const ulonglong2* __restrict__ fwd,
+                                                                       unsigned nmod, unsigned n, const u64* a, const u64* b, u64* out) {
+    const unsigned limb = blk_row(chunks) % nmod;
+    const u64 q = mods[limb].q;
+    const ulonglong2 iota = fwd[(size_t)limb * n + 1];
+    const size_t base = (size_t)blk_row(chunks) * n;
+    const unsigned half = n / 2;
+    for (unsigned i = blk_col(chunks) * 2; i < n; i += chunks * blockDim.x * 2) {
+        const u64x2 va = ld2(a + base + i), vb = ld2(b + base + i);
+        st2(out + base + i, join_word(va.a, vb.a, i >= half, iota, q), join_word(va.b, vb.b, i + 1 >= half, iota, q));
+    }
+}
+
 // generic (any pa, pb) version with the reference's loop structure
 __global__ __launch_bounds__(POLY_BLOCK) void dyadic_convolute_generic_kernel(unsigned chunks, const DevModulus* mods, unsigned mod_start, unsigned nmod,
                                                                               unsigned n, const u64* a, unsigned pa, const u64* b, unsigned pb, u64* out) {

@@ -2753,6 +2753,44 @@ extern "C" int troyn_ckks_multiply_affine_relinearize_rescale(const troyn_plan* 
     return troyn_divide_and_round_q_last_ntt(p, L, (const uint64_t*)(ws + w.relin2), 2, out, ws + w.sub, w.sub_bytes, batch, stream);
 }
 
+// Real and imaginary parts of CKKS slots (include/troyn.h): the rows of `batch` two-polynomial items on the plan's first L moduli
+static int complex_rows(const troyn_plan* p, const std::string& P, uint32_t L, std::initializer_list<const void*> ptrs, size_t batch, size_t& rows, unsigned& ch) {
+    if (!p) return fail(TROYN_E_INVALID, P + " null argument");
+    if (L == 0 || L > p->K) return fail(TROYN_E_INVALID, P + " L outside [1, the plan's moduli]");
+    rows = batch * 2 * (size_t)L;
+    if (batch == 0) return TROYN_OK;      // nothing to launch: no pointer is looked at
+    for (const void* q : ptrs) {
+        if (!q) return fail(TROYN_E_INVALID, P + " null argument");
+        if ((uintptr_t)q & 15) return fail(TROYN_E_INVALID, P + " misaligned pointer");
+    }
+    ch = chunks_pairs(p->n);
+    return check_rows(rows, ch);
+}
+
+extern "C" int troyn_ckks_complex_split(const troyn_plan* p, uint32_t L, const uint64_t* a, const uint64_t* b, uint64_t* s, uint64_t* d, size_t batch,
+                                        troyn_stream_t stream) {
+    select_device(p);
+    size_t rows = 0; unsigned ch = 1;
+    if (int rc = complex_rows(p, "[troyn_ckks_complex_split]", L, {a, b, s, d}, batch, rows, ch)) return rc;
+    if (rows == 0) return TROYN_OK;
+    if (s == d) return fail(TROYN_E_INVALID, "[troyn_ckks_complex_split] s and d are the same buffer");
+    hipLaunchKernelGGL(ckks_complex_split_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, (hipStream_t)stream, ch, p->d_mods, p->d_fwd, (unsigned)L, p->n,
+                       (const u64*)a, (const u64*)b, (u64*)s, (u64*)d);
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+
+extern "C" int troyn_ckks_complex_join(const troyn_plan* p, uint32_t L, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t batch, troyn_stream_t stream) {
+    select_device(p);
+    size_t rows = 0; unsigned ch = 1;
+    if (int rc = complex_rows(p, "[troyn_ckks_complex_join]", L, {a, b, out}, batch, rows, ch)) return rc;
+    if (rows == 0) return TROYN_OK;
+    hipLaunchKernelGGL(ckks_complex_join_kernel, dim3((unsigned)(rows * ch)), dim3(POLY_BLOCK), 0, (hipStream_t)stream, ch, p->d_mods, p->d_fwd, (unsigned)L, p->n,
+                       (const u64*)a, (const u64*)b, (u64*)out);
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+
 extern "C" int troyn_mod_switch_drop(const troyn_plan* p, uint32_t L_in, uint32_t L_out, const uint64_t* in, size_t pcount,
                                      uint64_t* out, size_t batch, troyn_stream_t stream) {
     select_device(p);

@@ -626,6 +626,22 @@ class Plan:
             None if out is None else _ptr(out), None if ws is None else C.c_void_p(ws.data_ptr()), 0 if ws is None else ws.numel(), batch, _stream()))
         return out
 
+    def ckks_complex_split(self, L, a, b, s=None, d=None):
+        """troyn_ckks_complex_split: a, b [batch][2][L][N] in NTT form (a ciphertext and its complex conjugate) -> (s, d) = (a + b, mu . (b - a)), mu the
+        forward transform of X^(N/2): slots 2 Re and (-1)^j 2 Im, no level spent (include/troyn.h states the contract)"""
+        batch = a.numel() // (2 * L * self.n) if L else 0
+        s = torch.empty_like(a) if s is None else s
+        d = torch.empty_like(a) if d is None else d
+        capi.check(self.lib.troyn_ckks_complex_split(self.h, L, _ptr(a), _ptr(b), _ptr(s), _ptr(d), batch, _stream()))
+        return s, d
+
+    def ckks_complex_join(self, L, a, b, out=None):
+        """troyn_ckks_complex_join: out = a + mu . b on [batch][2][L][N] in NTT form: slots Re + i Im from slots Re and (-1)^j Im"""
+        batch = a.numel() // (2 * L * self.n) if L else 0
+        out = torch.empty_like(a) if out is None else out
+        capi.check(self.lib.troyn_ckks_complex_join(self.h, L, _ptr(a), _ptr(b), _ptr(out), batch, _stream()))
+        return out
+
     # -- modulus switching -------------------------------------------------------------------------
     def divide_and_round_q_last(self, L, x, pcount, out=None):
         batch = x.numel() // (pcount * L * self.n)

@@ -17,6 +17,7 @@
 #include "../troy/matmul.h"
 #include "../troy/ring2k.h"
 #include "../troy/slot_transform.h"
+#include "../troy/bootstrap.h"
 #include "../troy/troy.h"
 
 namespace py = pybind11;
@@ -559,6 +560,51 @@ PYBIND11_MODULE(pytroy_raw, m) {
         s.eval_mod(a, k, hw, degree, r, d, P(p)); }, py::arg("encrypted"), py::arg("relin_keys"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"), py::arg("destination"), POOL);
     ev.def("eval_mod_new", [](const Evaluator& s, const Ciphertext& a, const RelinKeys& k, double hw, size_t degree, size_t r, PoolArg p) {
         return s.eval_mod_new(a, k, hw, degree, r, P(p)); }, py::arg("encrypted"), py::arg("relin_keys"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"), POOL);
+    // additions: the same on several ciphertexts at one level and scale, every device call made once for all of them (troy.h)
+    ev.def("evaluate_chebyshev_batched", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<double>& c, double hw, const RelinKeys& k,
+                                            const std::vector<Ciphertext*>& d, PoolArg p) {
+        if (d.size() != a.size()) throw std::invalid_argument("[Evaluator::evaluate_chebyshev_batched] destination needs one ciphertext per operand.");
+        std::vector<Ciphertext> out;
+        s.evaluate_chebyshev_batched(const_ptrs(a), c, hw, k, out, P(p));
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },
+           py::arg("encrypted"), py::arg("coefficients"), py::arg("half_width"), py::arg("relin_keys"), py::arg("destination"), POOL);
+    ev.def("evaluate_chebyshev_new_batched", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<double>& c, double hw, const RelinKeys& k, PoolArg p) {
+        return s.evaluate_chebyshev_new_batched(const_ptrs(a), c, hw, k, P(p)); }, py::arg("encrypted"), py::arg("coefficients"), py::arg("half_width"), py::arg("relin_keys"), POOL);
+    ev.def("eval_mod_batched", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const RelinKeys& k, double hw, size_t degree, size_t r, const std::vector<Ciphertext*>& d, PoolArg p) {
+        if (d.size() != a.size()) throw std::invalid_argument("[Evaluator::eval_mod_batched] destination needs one ciphertext per operand.");
+        std::vector<Ciphertext> out;
+        s.eval_mod_batched(const_ptrs(a), k, hw, degree, r, out, P(p));
+        for (size_t i = 0; i < out.size(); i++) *d[i] = std::move(out[i]); },
+           py::arg("encrypted"), py::arg("relin_keys"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"), py::arg("destination"), POOL);
+    ev.def("eval_mod_new_batched", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const RelinKeys& k, double hw, size_t degree, size_t r, PoolArg p) {
+        return s.eval_mod_new_batched(const_ptrs(a), k, hw, degree, r, P(p)); }, py::arg("encrypted"), py::arg("relin_keys"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"), POOL);
+    // additions: the real and imaginary parts of CKKS slots without a level (troy.h), BootstrapPlan (bootstrap.h) and the bootstrap as one call
+    ev.def("split_real_imag", [](const Evaluator& s, const Ciphertext& a, const GaloisKeys& k, Ciphertext& re, Ciphertext& im, PoolArg p) {
+        s.split_real_imag(a, k, re, im, P(p)); }, py::arg("encrypted"), py::arg("galois_keys"), py::arg("real2"), py::arg("imag2_alt"), POOL);
+    ev.def("split_real_imag_new", [](const Evaluator& s, const Ciphertext& a, const GaloisKeys& k, PoolArg p) {
+        return s.split_real_imag_new(a, k, P(p)); }, py::arg("encrypted"), py::arg("galois_keys"), POOL);
+    ev.def("join_real_imag", [](const Evaluator& s, const Ciphertext& re, const Ciphertext& im, Ciphertext& d, PoolArg p) {
+        s.join_real_imag(re, im, d, P(p)); }, py::arg("real"), py::arg("imag_alt"), py::arg("destination"), POOL);
+    ev.def("join_real_imag_new", [](const Evaluator& s, const Ciphertext& re, const Ciphertext& im, PoolArg p) {
+        return s.join_real_imag_new(re, im, P(p)); }, py::arg("real"), py::arg("imag_alt"), POOL);
+    py::class_<BootstrapPlan>(m, "BootstrapPlan")
+        .def(py::init([](HeContextPointer c, const CKKSEncoder& e, double scale, double hw, size_t degree, size_t r, const std::vector<size_t>& down, const std::vector<size_t>& up,
+                         double weight_scale, PoolArg p) { return std::make_unique<BootstrapPlan>(c, e, scale, hw, degree, r, down, up, weight_scale, P(p)); }),
+             py::arg("context"), py::arg("encoder"), py::arg("message_scale"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"),
+             py::arg("coeff_to_slot_layers") = std::vector<size_t>{}, py::arg("slot_to_coeff_layers") = std::vector<size_t>{}, py::arg("weight_scale") = 1099511627776.0, POOL)
+        .def("levels", &BootstrapPlan::levels).def("eval_mod_depth", &BootstrapPlan::eval_mod_depth).def("key_switches", &BootstrapPlan::key_switches)
+        .def("message_scale", &BootstrapPlan::message_scale).def("half_width", &BootstrapPlan::half_width).def("degree", &BootstrapPlan::degree)
+        .def("double_angles", &BootstrapPlan::double_angles).def("output_scale", &BootstrapPlan::output_scale).def("q0", &BootstrapPlan::q0)
+        .def("coeff_to_slot_constant", &BootstrapPlan::coeff_to_slot_constant).def("slot_to_coeff_constant", &BootstrapPlan::slot_to_coeff_constant)
+        .def("output_parms_id", [](const BootstrapPlan& s) { return s.output_parms_id(); })
+        .def("rotation_steps", [](const BootstrapPlan& s) { return s.rotation_steps(); })
+        .def("coeff_to_slot_plan", [](const BootstrapPlan& s) -> const CoeffToSlotPlan& { return s.coeff_to_slot_plan(); }, py::return_value_policy::reference_internal)
+        .def("slot_to_coeff_plan", [](const BootstrapPlan& s) -> const SlotToCoeffPlan& { return s.slot_to_coeff_plan(); }, py::return_value_policy::reference_internal);
+    m.def("chebyshev_depth", &Evaluator::chebyshev_depth, py::arg("degree"));
+    ev.def("bootstrap", [](const Evaluator& s, const Ciphertext& a, const BootstrapPlan& plan, const RelinKeys& rk, const GaloisKeys& gk, Ciphertext& d, PoolArg p) {
+        s.bootstrap(a, plan, rk, gk, d, P(p)); }, py::arg("encrypted"), py::arg("plan"), py::arg("relin_keys"), py::arg("galois_keys"), py::arg("destination"), POOL);
+    ev.def("bootstrap_new", [](const Evaluator& s, const Ciphertext& a, const BootstrapPlan& plan, const RelinKeys& rk, const GaloisKeys& gk, PoolArg p) {
+        return s.bootstrap_new(a, plan, rk, gk, P(p)); }, py::arg("encrypted"), py::arg("plan"), py::arg("relin_keys"), py::arg("galois_keys"), POOL);
     // additions: the BFV inner product, one scale-down for the sum (troy.h)
     ev.def("bfv_multiply_accumulate", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, Ciphertext& d, PoolArg p) {
         s.bfv_multiply_accumulate(const_ptrs(a), const_ptrs(b), d, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("destination"), POOL);

@@ -1,0 +1,75 @@
+// bootstrap.h -- troy::BootstrapPlan, an ADDITION to the reference's interface: the CKKS bootstrap of a fully packed ciphertext,
+//     ModRaise -> CoeffToSlot -> (real / imaginary parts) -> EvalMod on both halves at once -> (join) -> SlotToCoeff,
+// as one call, Evaluator::bootstrap.  The plan owns the two slot plans (slot_transform.h), chooses every level, scale and normalisation constant and says
+// which Galois keys are needed.  Sparse packing (fewer than N/2 slots) and sparse secrets are out of scope: the key generator makes dense ternary secrets only.
+//
+// Notation.  N the ring degree, n = N/2, q0 the first prime (the only one of the last level), D = message_scale (Delta), K = half_width, r = double_angles.
+// An exhausted ciphertext decrypts to D m modulo q0.  After mod_raise it decrypts, modulo the whole chain, to t = D m + q0 I with an integer polynomial I.
+//
+// Conditions (the caller's):
+//   K - 1 >= ||I||_inf.  For a dense ternary secret the coefficients of I behave like sums of N + 1 uniform fractions: standard deviation sqrt((N + 1) / 12).
+//     Rule of thumb K - 1 >= 6.5 sqrt((N + 1) / 12), which gives K = 64 at N = 1024 (58.7 + 1, rounded up to a power of two).
+//   |D m| / q0 <= 2^-7, eval_mod's own condition: sin(2 pi x) / (2 pi) is x up to a cubic term.  The constructor asks for q0 / D >= 2 only.
+//
+// The steps of Evaluator::bootstrap and where each factor goes -- none costs a level:
+//   1. mod_switch_to the last level if the operand is above it; its scale must be D (the evaluator's scale comparison).
+//   2. mod_raise to first_parms_id().
+//   3. 1 / q0: the scale is RELABELLED to q0, so that the coefficients read x = t / q0 = D m / q0 + I.
+//   4. coeff_to_slot with the constant c1 (below): slots c1 BR(x_k + i x_{k+n}) at the scale s1 that the evaluator tracks.
+//   5. split_real_imag: slots 2 c1 Re and (-1)^j 2 c1 Im.  1 / 2 and c1: both halves are RELABELLED to the scale 2 c1 s1, so that their slots read x.
+//   6. eval_mod_batched on the pair.  K: eval_mod relabels the working scale to 2 c1 s1 K.  Its first products are rescaled by the prime q_w under the
+//      CoeffToSlot levels, and evaluate_chebyshev asks for a working scale close to the primes, hence
+//          c1 = q_w / (2 K s1),   s1 = q0 PROD_g (weight_scale / prime of group g)   computed as the evaluator computes it,
+//      which makes the working scale q_w up to rounding.  2 pi: eval_mod's own relabel.  The slots now read D m / q0, (-1)^j on the imaginary half
+//      (sine is odd, so the sign passes; the interpolant's error is not odd but stays of its own size).
+//   7. join_real_imag: slots D / q0 (m_k + i m_{k+n}) in bit-reversed order, at the scale s_e that eval_mod leaves.
+//   8. slot_to_coeff with the constant c2 = q0 / s2, s2 = s_e PROD_g (weight_scale / prime of group g) the scale the evaluator will track: q0 / D.
+//   9. The payload is now D z for the message slots z, and the scale is SET to D, a double assignment, as eval_mod does with 2 pi.
+//
+// Levels: levels() = groups(CoeffToSlot) + depth(EvalMod) + groups(SlotToCoeff), depth(EvalMod) = Evaluator::chebyshev_depth(degree) + r, the depth that
+// evaluate_chebyshev documents plus the double angles.  The chain needs levels() + 1 data primes; every prime beyond that is a level the result can still spend.
+// Key switches: key_switches() counts the Galois key switches of one call -- the rotations and conjugations of both slot plans and the one conjugation of
+// split_real_imag; EvalMod's relinearizations (one per product step) are not Galois key switches and are not counted.  rotation_steps() is the union of
+// both slot plans' steps and step 0, which create_galois_keys_from_steps reads as the conjugation.
+#pragma once
+#include "slot_transform.h"
+
+namespace troy {
+
+class BootstrapPlan {
+public:
+    // empty layers_per_group: the slot plans' default grouping.  std::invalid_argument "[BootstrapPlan::BootstrapPlan] ..." for a non-CKKS context, a chain
+    // with fewer than levels() + 1 data levels, K, degree or double_angles outside eval_mod's ranges (K positive and finite, degree 1 .. 127, at most 16
+    // double angles), a message or weight scale that is not positive or not finite, q0 / message_scale < 2; the slot plans' own refusals pass through.
+    BootstrapPlan(HeContextPointer context, const CKKSEncoder& encoder, double message_scale, double half_width, size_t degree, size_t double_angles,
+                  std::vector<size_t> coeff_to_slot_layers = {}, std::vector<size_t> slot_to_coeff_layers = {}, double weight_scale = 1099511627776.0,
+                  MemoryPoolHandle pool = MemoryPool::GlobalPool());
+    BootstrapPlan(const BootstrapPlan&) = delete;
+    BootstrapPlan& operator=(const BootstrapPlan&) = delete;
+
+    double message_scale() const { return message_scale_; }
+    double half_width() const { return half_width_; }
+    size_t degree() const { return degree_; }
+    size_t double_angles() const { return double_angles_; }
+    size_t eval_mod_depth() const { return eval_mod_depth_; }
+    size_t levels() const { return coeff_to_slot_->levels() + eval_mod_depth_ + slot_to_coeff_->levels(); }
+    const ParmsID& output_parms_id() const { return output_parms_id_; }
+    double output_scale() const { return message_scale_; }
+    const std::vector<int>& rotation_steps() const { return rotation_steps_; }       // both plans' steps and 0, the conjugation; sorted
+    size_t key_switches() const { return coeff_to_slot_->rotations() + 1 + slot_to_coeff_->rotations(); }
+    const CoeffToSlotPlan& coeff_to_slot_plan() const { return *coeff_to_slot_; }
+    const SlotToCoeffPlan& slot_to_coeff_plan() const { return *slot_to_coeff_; }
+    double q0() const { return q0_; }
+    double coeff_to_slot_constant() const { return coeff_to_slot_->constant(); }     // c1
+    double slot_to_coeff_constant() const { return slot_to_coeff_->constant(); }     // c2
+
+private:
+    double message_scale_, half_width_, q0_ = 0.0;
+    size_t degree_, double_angles_, eval_mod_depth_ = 0;
+    ParmsID output_parms_id_;
+    std::unique_ptr<CoeffToSlotPlan> coeff_to_slot_;
+    std::unique_ptr<SlotToCoeffPlan> slot_to_coeff_;
+    std::vector<int> rotation_steps_;
+};
+
+}  // namespace troy

@@ -112,6 +112,14 @@ void add_sub_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, bool s
     env.check((subtract ? troyn_sub : troyn_add)(plan, 0, L, a, b, out, polys, env.stream));
 }
 
+void ckks_complex_split_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* a, const uint64_t* b, uint64_t* s, uint64_t* d, size_t count) {
+    env.check(troyn_ckks_complex_split(plan, L, a, b, s, d, count, env.stream));
+}
+
+void ckks_complex_join_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count) {
+    env.check(troyn_ckks_complex_join(plan, L, a, b, out, count, env.stream));
+}
+
 void ntt_step(const StepEnv& env, const troyn_plan* plan, bool inverse, const uint64_t* in, uint64_t* out, size_t count, size_t polys, uint32_t L) {
     env.check(troyn_ntt(plan, inverse ? 1 : 0, in, out, count, polys, L, 0, L, TROYN_IDX_COMPONENTWISE, 0, env.stream));
 }

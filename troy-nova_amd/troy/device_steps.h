@@ -23,6 +23,9 @@ namespace detail {
 
 // where a step runs and who hears about a failure: the pool its workspace comes from, the stream, and the caller's checker of a C-ABI
 // return code (troyn_check_public for the methods and the batched forms; the rendezvous has its own)
+// the evaluator's scale comparison (utils/basics.h:150-160, as Evaluator::add uses it), for the units that implement Evaluator methods outside troy.cpp
+bool scales_are_close(double a, double b);
+
 struct StepEnv {
     const MemoryPoolHandle& pool;   // the CALLER's handle, by reference (no reference count per call): an environment is built in the argument list of a
                                     // step or as a local next to the handle it names, and never outlives that handle
@@ -69,6 +72,10 @@ void mod_raise_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t L_in, u
 void negate_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* in, uint64_t* out, size_t polys);
 void add_sub_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, bool subtract, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t polys);
 void ntt_step(const StepEnv& env, const troyn_plan* plan, bool inverse, const uint64_t* in, uint64_t* out, size_t count, size_t polys, uint32_t L);
+// real and imaginary parts of CKKS slots (troyn_ckks_complex_split / _join, include/troyn.h): a, b, s, d, out [count][2][L][N] in NTT form; no workspace.
+//   split: s = a + b, d = mu . (b - a); join: out = a + mu . b, mu the forward transform of X^(N/2)
+void ckks_complex_split_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* a, const uint64_t* b, uint64_t* s, uint64_t* d, size_t count);
+void ckks_complex_join_step(const StepEnv& env, const troyn_plan* plan, uint32_t L, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count);
 // (c0, c1) permuted by the element, the permuted c1s switched back: c0 += ks0, c1 = ks1
 void apply_galois_step(const StepEnv& env, const troyn_plan* plan, const troyn_bgv* bgv, uint32_t L, size_t n, bool ckks, bool ntt_form, size_t galois_element,
                        const uint64_t* in, const uint64_t* const* keys, uint64_t* out, size_t count);

@@ -1089,6 +1089,7 @@ static bool are_close_double(double a, double b) {
     double s = std::max(std::max(a, b), 1.0);
     return std::fabs(a - b) < s * 2.220446049250313e-16;   // basics.h:150-160
 }
+bool detail::scales_are_close(double a, double b) { return are_close_double(a, b); }
 static void check_same_scale(const char* prompt, const Ciphertext& a, const Ciphertext& b) {
     if (!are_close_double(a.scale(), b.scale())) throw std::invalid_argument(std::string(prompt) + " Arguments have different scales.");
 }
@@ -1895,6 +1896,12 @@ size_t ps_degree(const char* P, const std::vector<double>& coefficients) {
 }
 }  // namespace
 
+size_t Evaluator::chebyshev_depth(size_t degree) {
+    size_t k, g, rec_depth;
+    ps_schedule(degree, k, g, rec_depth);
+    return rec_depth + 1;
+}
+
 void Evaluator::evaluate_polynomial(const Ciphertext& x, const std::vector<double>& coefficients, const RelinKeys& relin_keys, Ciphertext& destination,
                                     MemoryPoolHandle pool) const {
     const char* P = "[Evaluator::evaluate_polynomial]";
@@ -1922,14 +1929,23 @@ void Evaluator::evaluate_polynomial(const Ciphertext& x, const std::vector<doubl
         multiply_relinearize_rescale(*pa, *pb, relin_keys, prod, pool);
         return powers.emplace(m, std::move(prod)).first->second;
     };
-    paterson_stockmeyer(P, x, d, 0, power, [&](size_t j, size_t i) { return coef(j * k + i); }, relin_keys, destination, pool);
+    std::vector<Ciphertext> out;
+    paterson_stockmeyer(P, {&x}, d, 0, [&](size_t, size_t m) -> const Ciphertext& { return power(m); }, [&](size_t j, size_t i) { return coef(j * k + i); }, relin_keys, out, pool);
+    destination = std::move(out[0]);
 }
 
-void Evaluator::paterson_stockmeyer(const char* P, const Ciphertext& x, size_t d, size_t extra_levels, const std::function<const Ciphertext&(size_t)>& power,
-                                    const std::function<double(size_t, size_t)>& u, const RelinKeys& relin_keys, Ciphertext& destination, MemoryPoolHandle pool) const {
+// xs: C ciphertexts at one level (the callers check it), each evaluated on its own basis(c, m) with the same coefficients.  Every device call is made once
+// for all of them: in the leaf sums ciphertext c is the block c of the terms and of the result slots (slot s * C + c, zero weights outside the block: a zero
+// weight adds nothing modulo q and every input is read once per tile of 8 result rows, so the arithmetic grows as C^2: troy.h), in the recombination and the last add it is item c of the batch.  C = 1 is the
+// single-ciphertext schedule, call for call.
+void Evaluator::paterson_stockmeyer(const char* P, const std::vector<const Ciphertext*>& xs, size_t d, size_t extra_levels,
+                                    const std::function<const Ciphertext&(size_t, size_t)>& power, const std::function<double(size_t, size_t)>& u,
+                                    const RelinKeys& relin_keys, std::vector<Ciphertext>& destination, MemoryPoolHandle pool) const {
     size_t k, g, rec_depth;
     ps_schedule(d, k, g, rec_depth);
     const size_t depth = rec_depth + 1 + extra_levels;
+    const size_t C = xs.size();
+    const Ciphertext& x = *xs[0];
     auto cd0 = get_context_data(P, x.parms_id());
     const size_t L0 = x.coeff_modulus_size();
     if (L0 < depth + 1)
@@ -1937,59 +1953,87 @@ void Evaluator::paterson_stockmeyer(const char* P, const Ciphertext& x, size_t d
                                     std::to_string(L0) + ".");
     std::vector<uint64_t> moduli(L0);
     for (size_t l = 0; l < L0; l++) moduli[l] = cd0->parms().coeff_modulus()[l].value();
-    const double S = x.scale();
     const detail::StepEnv env = on_current_stream(pool, true);
     const troyn_plan* plan = context_->plan();
     const size_t n = x.poly_modulus_degree();
     auto level_down = [&](size_t steps) { auto cd = cd0; for (size_t i = 0; i < steps; i++) cd = cd->next_context_data().value(); return cd; };
 
-    // one leaf sum over `ins` at `nmod` limbs for `slots` rows of coefficients, then the batched rescale: [slots][2][nmod - 1][N]
-    auto leaves = [&](const std::vector<const Ciphertext*>& ins, size_t nmod, size_t slots, const std::vector<double>& sum_scale,
+    // one leaf sum over ins[c] at `nmod` limbs for `slots` rows of coefficients per ciphertext, then the batched rescale: [slots][C][2][nmod - 1][N].
+    // sum_scale is [slots][C]: every weight comes from the scales of its own ciphertext's operands
+    auto leaves = [&](const std::vector<std::vector<const Ciphertext*>>& ins, size_t nmod, size_t slots, const std::vector<double>& sum_scale,
                       const std::function<double(size_t, size_t)>& c, utils::DynamicArray& out) {
-        const size_t terms = ins.size();
-        std::vector<__int128> ints(slots * terms), consts(slots);
-        for (size_t s = 0; s < slots; s++) {
-            for (size_t t = 0; t < terms; t++) ints[s * terms + t] = scaled_integer(P, c(s, t + 1), sum_scale[s] / ins[t]->scale(), 62);
-            consts[s] = scaled_integer(P, c(s, 0), sum_scale[s], 126);
-        }
-        utils::DynamicArray sum(slots * 2 * nmod * n, true, pool);
-        scalar_sums_on(env, plan, moduli, static_cast<uint32_t>(nmod), ins, ints, consts, slots, 2, sum.raw_pointer());
-        out = utils::DynamicArray(slots * 2 * (nmod - 1) * n, true, pool);
-        detail::rescale_step(env, plan, static_cast<uint32_t>(nmod), sum.raw_pointer(), 2, out.raw_pointer(), slots);
+        const size_t terms = ins[0].size(), all_terms = C * terms, all_slots = slots * C;
+        std::vector<const Ciphertext*> all(all_terms);
+        std::vector<__int128> ints(all_slots * all_terms, 0), consts(all_slots);
+        for (size_t i = 0; i < C; i++) for (size_t t = 0; t < terms; t++) all[i * terms + t] = ins[i][t];
+        for (size_t s = 0; s < slots; s++)
+            for (size_t i = 0; i < C; i++) {
+                const size_t row = s * C + i;
+                for (size_t t = 0; t < terms; t++) ints[row * all_terms + i * terms + t] = scaled_integer(P, c(s, t + 1), sum_scale[row] / ins[i][t]->scale(), 62);
+                consts[row] = scaled_integer(P, c(s, 0), sum_scale[row], 126);
+            }
+        utils::DynamicArray sum(all_slots * 2 * nmod * n, true, pool);
+        scalar_sums_on(env, plan, moduli, static_cast<uint32_t>(nmod), all, ints, consts, all_slots, 2, sum.raw_pointer());
+        out = utils::DynamicArray(all_slots * 2 * (nmod - 1) * n, true, pool);
+        detail::rescale_step(env, plan, static_cast<uint32_t>(nmod), sum.raw_pointer(), 2, out.raw_pointer(), all_slots);
     };
+    // the results: item c of a block [C][2][limbs][N] becomes ciphertext c (a single result is written in place, below)
+    auto scatter = [&](const uint64_t* block, size_t limbs, const ParmsID& parms_id, std::vector<Ciphertext>& out) {
+        for (size_t i = 0; i < C; i++) {
+            out[i] = Ciphertext::like(*xs[i], 2, limbs, false, pool);
+            out[i].parms_id() = parms_id; out[i].scale() = xs[i]->scale(); out[i].is_ntt_form() = true;
+            if (block) detail::hip_check(hipMemcpyAsync(out[i].data().raw_pointer(), block + i * 2 * limbs * n, 2 * limbs * n * 8, hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
+        }
+    };
+    std::vector<Ciphertext> out(C);
 
     if (d <= 1) {
         utils::DynamicArray leaf;
-        leaves({&x}, L0, 1, {S * static_cast<double>(moduli[L0 - 1])}, [&](size_t, size_t i) { return u(0, i); }, leaf);
-        Ciphertext out = Ciphertext::like(x, 2, L0 - 1, false, pool);
-        out.parms_id() = level_down(1)->parms_id(); out.scale() = S; out.is_ntt_form() = true;
-        detail::hip_check(hipMemcpyAsync(out.data().raw_pointer(), leaf.raw_pointer(), out.data().size() * 8, hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
+        std::vector<std::vector<const Ciphertext*>> self(C);
+        std::vector<double> leaf_scale(C);
+        for (size_t i = 0; i < C; i++) { self[i] = {xs[i]}; leaf_scale[i] = xs[i]->scale() * static_cast<double>(moduli[L0 - 1]); }
+        leaves(self, L0, 1, leaf_scale, [&](size_t, size_t i) { return u(0, i); }, leaf);
+        scatter(leaf.raw_pointer(), L0 - 1, level_down(1)->parms_id(), out);
         destination = std::move(out);
         return;
     }
 
-    std::vector<const Ciphertext*> babies;
-    for (size_t i = 1; i < k; i++) babies.push_back(&power(i));
     const size_t Lrec = L0 - rec_depth;                         // limbs at the recombination level l*
     auto cd_rec = level_down(rec_depth);
-    std::vector<Ciphertext> lowered_giants(g - 1);               // only the giants above l* are copied (brought down)
-    std::vector<const Ciphertext*> giants(g - 1);
-    for (size_t j = 1; j < g; j++) {
-        const Ciphertext& G = power(j * k);
-        if (G.coeff_modulus_size() > Lrec) { mod_switch_to(G, cd_rec->parms_id(), lowered_giants[j - 1], pool); giants[j - 1] = &lowered_giants[j - 1]; }
-        else giants[j - 1] = &G;
+    std::vector<std::vector<const Ciphertext*>> babies(C);
+    std::vector<std::vector<const Ciphertext*>> giants(C, std::vector<const Ciphertext*>(g - 1));
+    std::vector<Ciphertext> lowered_giants;                      // one ciphertext: only the giants above l* are copied (brought down)
+    utils::DynamicArray giant_block;                             // several: giant j of all of them side by side, [g - 1][C][2][Lrec][N], the layout the recombination reads
+    const size_t giant_words = 2 * Lrec * n;
+    if (C == 1) lowered_giants.resize(g - 1); else giant_block = utils::DynamicArray((g - 1) * C * giant_words, true, pool);
+    for (size_t i = 0; i < C; i++) {
+        for (size_t b = 1; b < k; b++) babies[i].push_back(&power(i, b));
+        for (size_t j = 1; j < g; j++) {
+            const Ciphertext& G = power(i, j * k);
+            giants[i][j - 1] = &G;
+            if (C == 1) {
+                if (G.coeff_modulus_size() > Lrec) { mod_switch_to(G, cd_rec->parms_id(), lowered_giants[j - 1], pool); giants[i][j - 1] = &lowered_giants[j - 1]; }
+            } else {
+                detail::mod_switch_drop_step(env, plan, static_cast<uint32_t>(G.coeff_modulus_size()), static_cast<uint32_t>(Lrec), G.data().raw_pointer(), 2,
+                                             giant_block.raw_pointer() + ((j - 1) * C + i) * giant_words, 1);
+            }
+        }
     }
-    const double T = S * static_cast<double>(moduli[Lrec - 1]);
+    // every product leaf_j * x^(jk) has the scale T = S q_{l* - 1}
+    std::vector<double> T(C);
+    for (size_t i = 0; i < C; i++) T[i] = xs[i]->scale() * static_cast<double>(moduli[Lrec - 1]);
     // leaves 1..g-1 at Lrec + 1 limbs: leaf_j at T / scale(x^(jk)) after the division by q_{Lrec}
-    std::vector<double> sum_scale(g - 1);
-    for (size_t j = 1; j < g; j++) sum_scale[j - 1] = T / giants[j - 1]->scale() * static_cast<double>(moduli[Lrec]);
+    std::vector<double> sum_scale((g - 1) * C);
+    for (size_t j = 1; j < g; j++)
+        for (size_t i = 0; i < C; i++) sum_scale[(j - 1) * C + i] = T[i] / giants[i][j - 1]->scale() * static_cast<double>(moduli[Lrec]);
     utils::DynamicArray upper, leaf0;
     leaves(babies, Lrec + 1, g - 1, sum_scale, [&](size_t s, size_t i) { return u(s + 1, i); }, upper);
     // leaf_0 at Lrec limbs and scale T: its division lands on the result's level and scale
-    leaves(babies, Lrec, 1, {T}, [&](size_t, size_t i) { return u(0, i); }, leaf0);
+    leaves(babies, Lrec, 1, T, [&](size_t, size_t i) { return u(0, i); }, leaf0);
     // the recombination: SUM_j leaf_j * x^(jk), one key switch and one rescale
     // every product leaf_j * x^(jk) has the scale T: that is the scale to hold against the modulus at l*; then relinearize's key checks
-    if (!is_scale_within_bounds(T, cd_rec)) throw std::invalid_argument(std::string(P) + " Scale out of bounds");
+    for (size_t i = 0; i < C; i++)
+        if (!is_scale_within_bounds(T[i], cd_rec)) throw std::invalid_argument(std::string(P) + " Scale out of bounds");
     if (relin_keys.parms_id() != context_->key_parms_id()) throw std::invalid_argument(std::string(P) + " Relin keys has incorrect parms id.");
     const size_t key_index = RelinKeys::get_index(2);
     if (key_index >= relin_keys.data().size()) throw std::out_of_range(std::string(P) + " Key switch keys index out of range.");
@@ -2004,13 +2048,23 @@ void Evaluator::paterson_stockmeyer(const char* P, const Ciphertext& x, size_t d
     const std::vector<const uint64_t*> keys = relin_keys.get_data_ptrs(key_index);
     std::vector<const uint64_t*> a(g - 1), b(g - 1);
     const size_t leaf_words = 2 * Lrec * n;
-    for (size_t j = 0; j + 1 < g; j++) { a[j] = upper.raw_pointer() + j * leaf_words; b[j] = giants[j]->data().raw_pointer(); }
-    Ciphertext out = Ciphertext::like(*giants[0], 2, Lrec - 1, false, pool);
-    out.parms_id() = next; out.scale() = S; out.is_ntt_form() = true;
-    detail::multiply_accumulate_relinearize_rescale_step(env, plan, L, a.data(), b.data(), a.size(), keys.data(), out.data().raw_pointer(), 1);
+    for (size_t j = 0; j + 1 < g; j++) {
+        a[j] = upper.raw_pointer() + j * C * leaf_words;
+        b[j] = C == 1 ? giants[0][j]->data().raw_pointer() : giant_block.raw_pointer() + j * C * giant_words;
+    }
+    // one result is formed in its ciphertext, several in a block that is handed out afterwards
+    const size_t out_words = 2 * (Lrec - 1) * n;
+    utils::DynamicArray out_block;
+    scatter(nullptr, Lrec - 1, next, out);
+    if (C > 1) out_block = utils::DynamicArray(C * out_words, true, pool);
+    uint64_t* sum = C == 1 ? out[0].data().raw_pointer() : out_block.raw_pointer();
+    detail::multiply_accumulate_relinearize_rescale_step(env, plan, L, a.data(), b.data(), a.size(), keys.data(), sum, C);
     // leaf_0 is added outside the stream gate, which the step holds around the chain only: the gate is a throughput device for the threads that share a stream
     // (LaunchGate, above), not an ordering one -- the add follows the chain in stream order
-    detail::add_sub_step(env, plan, static_cast<uint32_t>(Lrec - 1), false, out.data().raw_pointer(), leaf0.raw_pointer(), out.data().raw_pointer(), 2);
+    detail::add_sub_step(env, plan, static_cast<uint32_t>(Lrec - 1), false, sum, leaf0.raw_pointer(), sum, 2 * C);
+    if (C > 1)
+        for (size_t i = 0; i < C; i++)
+            detail::hip_check(hipMemcpyAsync(out[i].data().raw_pointer(), sum + i * out_words, out_words * 8, hipMemcpyDeviceToDevice, env.stream), "copy_device_to_device");
     destination = std::move(out);
 }
 
@@ -2079,10 +2133,25 @@ void Evaluator::multiply_affine_relinearize_rescale_batched(const std::vector<co
 
 void Evaluator::evaluate_chebyshev(const Ciphertext& x, const std::vector<double>& coefficients, double half_width, const RelinKeys& relin_keys, Ciphertext& destination,
                                    MemoryPoolHandle pool, const char* P, size_t levels_after) const {
+    std::vector<Ciphertext> out;
+    evaluate_chebyshev_batched({&x}, coefficients, half_width, relin_keys, out, pool, P, levels_after);
+    destination = std::move(out[0]);
+}
+
+void Evaluator::evaluate_chebyshev_batched(const std::vector<const Ciphertext*>& xs, const std::vector<double>& coefficients, double half_width, const RelinKeys& relin_keys,
+                                           std::vector<Ciphertext>& destination, MemoryPoolHandle pool, const char* P, size_t levels_after) const {
     if (context_->key_context_data().value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(std::string(P) + " CKKS only.");
-    check_no_seed(P, x); check_on_device(P, context_, x);
-    if (!x.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Ciphertext must be in NTT form.");
-    if (x.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " The ciphertext must have two polynomials.");
+    const size_t C = xs.size();
+    if (C == 0) throw std::invalid_argument(std::string(P) + " Empty operand list.");
+    for (const Ciphertext* xp : xs) {
+        if (!xp) throw std::invalid_argument(std::string(P) + " Null operand.");
+        const Ciphertext& x = *xp;
+        check_no_seed(P, x); check_on_device(P, context_, x);
+        if (!x.is_ntt_form()) throw std::invalid_argument(std::string(P) + " Ciphertext must be in NTT form.");
+        if (x.polynomial_count() != 2) throw std::invalid_argument(std::string(P) + " The ciphertext must have two polynomials.");
+        if (x.parms_id() != xs[0]->parms_id()) throw std::invalid_argument(std::string(P) + " Operands have different parms_id.");
+        if (!are_close_double(x.scale(), xs[0]->scale())) throw std::invalid_argument(std::string(P) + " Operands have different scales.");
+    }
     if (!(half_width > 0.0) || !std::isfinite(half_width)) throw std::invalid_argument(std::string(P) + " The half width must be positive and finite.");
     const size_t d = ps_degree(P, coefficients);
     if (d > 127) throw std::invalid_argument(std::string(P) + " Degrees above 127 are not supported.");
@@ -2097,10 +2166,11 @@ void Evaluator::evaluate_chebyshev(const Ciphertext& x, const std::vector<double
     }
     for (size_t i = 0; i < std::max<size_t>(k, 2); i++) u[i] = r[i];
     // y = x / K: the same payload at K times the scale
-    Ciphertext y = x.clone(pool);
-    y.scale() = x.scale() * half_width;
-    // the ladder, built at the first request (after the level check): one batched step per depth
-    std::map<size_t, Ciphertext> T;
+    std::vector<Ciphertext> y(C);
+    std::vector<const Ciphertext*> ys(C);
+    for (size_t i = 0; i < C; i++) { y[i] = xs[i]->clone(pool); y[i].scale() = xs[i]->scale() * half_width; ys[i] = &y[i]; }
+    // the ladder, built at the first request (after the level check): one batched step per depth, T_m of ciphertext i at T[m][i]
+    std::map<size_t, std::vector<Ciphertext>> T;
     bool built = false;
     auto split = [](size_t m, size_t& a, size_t& b, size_t& c) { a = 1; while (a * 2 < m) a *= 2; b = m - a; c = 2 * a - m; };
     auto build = [&]() {
@@ -2115,40 +2185,49 @@ void Evaluator::evaluate_chebyshev(const Ciphertext& x, const std::vector<double
             todo.push_back(a); todo.push_back(b); todo.push_back(c);
         }
         auto clog2 = [](size_t v) { size_t q = 0; while ((size_t(1) << q) < v) q++; return q; };
-        auto at = [&](size_t m) -> const Ciphertext& { return m == 1 ? y : T.at(m); };
+        auto at = [&](size_t m, size_t i) -> const Ciphertext& { return m == 1 ? y[i] : T.at(m)[i]; };
         for (size_t dep = 1; dep <= 7; dep++) {
             std::vector<size_t> ms;
             for (size_t m : want) if (clog2(m) == dep) ms.push_back(m);
             if (ms.empty()) continue;
-            const size_t cnt = ms.size();
+            const size_t cnt = ms.size() * C;      // item t * C + i: T_(ms[t]) of ciphertext i
             std::vector<Ciphertext> lowered(cnt), out;
             std::vector<const Ciphertext*> e1(cnt), e2(cnt), ad(cnt, nullptr);
             std::vector<int64_t> alpha(cnt, 2);
             std::vector<double> gamma(cnt, -1.0), konst(cnt, 0.0);
             for (size_t t = 0; t < cnt; t++) {
-                size_t a, b, c; split(ms[t], a, b, c);
-                e1[t] = &at(a); e2[t] = &at(b);
+                size_t a, b, c; split(ms[t / C], a, b, c);
+                e1[t] = &at(a, t % C); e2[t] = &at(b, t % C);
                 if (e2[t]->coeff_modulus_size() > e1[t]->coeff_modulus_size()) { mod_switch_to(*e2[t], e1[t]->parms_id(), lowered[t], pool); e2[t] = &lowered[t]; }
-                if (c == 0) konst[t] = -1.0; else ad[t] = &at(c);
+                if (c == 0) konst[t] = -1.0; else ad[t] = &at(c, t % C);
             }
             multiply_affine_relinearize_rescale_batched(e1, e2, alpha, ad, gamma, konst, relin_keys, out, pool, P);
-            for (size_t t = 0; t < cnt; t++) T.emplace(ms[t], std::move(out[t]));
+            for (size_t t = 0; t < ms.size(); t++) {
+                std::vector<Ciphertext>& row = T[ms[t]];
+                for (size_t i = 0; i < C; i++) row.push_back(std::move(out[t * C + i]));
+            }
         }
         built = true;
     };
-    std::function<const Ciphertext&(size_t)> basis = [&](size_t m) -> const Ciphertext& {
-        if (m == 1) return y;
+    std::function<const Ciphertext&(size_t, size_t)> basis = [&](size_t i, size_t m) -> const Ciphertext& {
+        if (m == 1) return y[i];
         // deferred on purpose: paterson_stockmeyer asks for a basis element only after its level check, so a ciphertext with too few levels is
         // refused with that message before any step of the ladder runs (and fails on its own last level)
         if (!built) build();
-        return T.at(m);
+        return T.at(m)[i];
     };
-    paterson_stockmeyer(P, y, d, levels_after, basis, [&](size_t j, size_t i) { return u[j * k + i]; }, relin_keys, destination, pool);
+    paterson_stockmeyer(P, ys, d, levels_after, basis, [&](size_t j, size_t i) { return u[j * k + i]; }, relin_keys, destination, pool);
 }
 
 void Evaluator::eval_mod(const Ciphertext& encrypted, const RelinKeys& relin_keys, double half_width, size_t degree, size_t double_angles, Ciphertext& destination,
                          MemoryPoolHandle pool) const {
-    const char* P = "[Evaluator::eval_mod]";
+    std::vector<Ciphertext> out;
+    eval_mod_batched({&encrypted}, relin_keys, half_width, degree, double_angles, out, pool, "[Evaluator::eval_mod]");
+    destination = std::move(out[0]);
+}
+
+void Evaluator::eval_mod_batched(const std::vector<const Ciphertext*>& encrypted, const RelinKeys& relin_keys, double half_width, size_t degree, size_t double_angles,
+                                 std::vector<Ciphertext>& destination, MemoryPoolHandle pool, const char* P) const {
     if (degree < 1 || degree > 127) throw std::invalid_argument(std::string(P) + " The degree must be in 1 .. 127.");
     if (double_angles > 16) throw std::invalid_argument(std::string(P) + " More than 16 double-angle steps.");
     if (!(half_width > 0.0) || !std::isfinite(half_width)) throw std::invalid_argument(std::string(P) + " The half width must be positive and finite.");
@@ -2162,14 +2241,18 @@ void Evaluator::eval_mod(const Ciphertext& encrypted, const RelinKeys& relin_key
         for (size_t t = 0; t < nodes; t++) s += f[t] * std::cos(pi * j * (t + 0.5) / nodes);
         coeffs[j] = s * (j == 0 ? 1.0 : 2.0) / nodes;
     }
-    Ciphertext ct;
-    evaluate_chebyshev(encrypted, coeffs, half_width, relin_keys, ct, pool, P, double_angles);
+    std::vector<Ciphertext> ct;
+    evaluate_chebyshev_batched(encrypted, coeffs, half_width, relin_keys, ct, pool, P, double_angles);
+    const size_t C = ct.size();
     for (size_t s = 0; s < double_angles; s++) {
         std::vector<Ciphertext> next;
-        multiply_affine_relinearize_rescale_batched({&ct}, {&ct}, {2}, {nullptr}, {0.0}, {-1.0}, relin_keys, next, pool, P);
-        ct = std::move(next[0]);
+        std::vector<const Ciphertext*> e(C);
+        for (size_t i = 0; i < C; i++) e[i] = &ct[i];
+        multiply_affine_relinearize_rescale_batched(e, e, std::vector<int64_t>(C, 2), std::vector<const Ciphertext*>(C, nullptr), std::vector<double>(C, 0.0),
+                                                    std::vector<double>(C, -1.0), relin_keys, next, pool, P);
+        ct = std::move(next);
     }
-    ct.scale() *= 2.0 * pi;      // the slots read sin(2 pi x) / (2 pi)
+    for (Ciphertext& c : ct) c.scale() *= 2.0 * pi;      // the slots read sin(2 pi x) / (2 pi)
     destination = std::move(ct);
 }
 

@@ -1441,6 +1441,7 @@ class LinearTransform;     // linear_transform.h
 class SlotTransformPlan;   // slot_transform.h
 class CoeffToSlotPlan;
 class SlotToCoeffPlan;
+class BootstrapPlan;       // bootstrap.h
 
 class Evaluator {
 public:
@@ -1656,6 +1657,62 @@ public:
     // (the form that names the calling method in its refusals; `levels_after`: levels the caller still needs below the result)
     void evaluate_chebyshev(const Ciphertext& encrypted, const std::vector<double>& coefficients, double half_width, const RelinKeys& relin_keys, Ciphertext& destination,
                             MemoryPoolHandle pool, const char* method, size_t levels_after = 0) const;
+    //   chebyshev_depth: the levels evaluate_chebyshev (and evaluate_polynomial) spends on a polynomial of the given degree, by the fixed schedule above
+    static size_t chebyshev_depth(size_t degree);
+    //   evaluate_chebyshev_batched / eval_mod_batched: several ciphertexts at ONE parms_id and scale (the evaluator's scale comparison), one coefficient
+    //   vector.  Every device call that the single method makes for one ciphertext is made once for all of them -- the leaf sums, each depth of the T_m
+    //   ladder, the recombination, each double angle -- so troyn_ckks_multiply_affine_relinearize_rescale sees items x ciphertexts.  The single methods
+    //   above ARE the batch of one of this code, and the words of result i equal those of the single method on ciphertext i.  With more than one
+    //   ciphertext the giants of the recombination are gathered side by side first (one limb copy each), and the results are handed out of one block (one
+    //   copy each).  Cost: meant for a FEW ciphertexts (the pair of a bootstrap).  The leaf sums are one troyn_scalar_weighted_sums call whose weight matrix is
+    //   block-diagonal, C * slots rows by C * terms columns with explicit zeros outside the blocks, so their arithmetic and their weight table grow as C^2
+    //   (the reads per tile of 8 result rows as C * terms); for many ciphertexts call the method on small groups.  Further refusals, prefixed as above: an empty
+    //   list, a null entry, operands at different parms_id or scales.
+    void evaluate_chebyshev_batched(const std::vector<const Ciphertext*>& encrypted, const std::vector<double>& coefficients, double half_width, const RelinKeys& relin_keys,
+                                    std::vector<Ciphertext>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool(),
+                                    const char* method = "[Evaluator::evaluate_chebyshev_batched]", size_t levels_after = 0) const;
+    std::vector<Ciphertext> evaluate_chebyshev_new_batched(const std::vector<const Ciphertext*>& encrypted, const std::vector<double>& coefficients, double half_width,
+                                                           const RelinKeys& relin_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; evaluate_chebyshev_batched(encrypted, coefficients, half_width, relin_keys, d, pool); return d;
+    }
+    void eval_mod_batched(const std::vector<const Ciphertext*>& encrypted, const RelinKeys& relin_keys, double half_width, size_t degree, size_t double_angles,
+                          std::vector<Ciphertext>& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool(), const char* method = "[Evaluator::eval_mod_batched]") const;
+    std::vector<Ciphertext> eval_mod_new_batched(const std::vector<const Ciphertext*>& encrypted, const RelinKeys& relin_keys, double half_width, size_t degree,
+                                                 size_t double_angles, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::vector<Ciphertext> d; eval_mod_batched(encrypted, relin_keys, half_width, degree, double_angles, d, pool); return d;
+    }
+
+    // ADDITION to the reference's interface: the real and imaginary parts of CKKS slots without spending a level (troyn_ckks_complex_split / _join,
+    //   include/troyn.h "Real and imaginary parts of CKKS slots").  The slot order is Galois generator 3, so the monomial X^(N/2) multiplies slot j by
+    //   i (-1)^j; in NTT form that is a dyadic product with a vector of two values per limb, and it costs no key switch, no level and no scale.
+    //   split_real_imag: one complex_conjugate, then ONE kernel: real2 = w + conj(w) with slots 2 Re w, imag2_alt = (conj(w) - w) X^(N/2).  imag2_alt
+    //   holds (-1)^j 2 Im w in slot j, NOT 2 Im w: conj(w) - w = -2i Im w, and X^(N/2) contributes i (-1)^j.  The alternating sign is left in place
+    //   on purpose: an odd slot-wise function (EvalMod's sine) passes it through, and join_real_imag multiplies by i (-1)^j once more, which squares it
+    //   away.  Both results keep the operand's parms_id and scale.  Refusals as complex_conjugate's, and "[Evaluator::split_real_imag] ..." for an
+    //   operand that is not CKKS, not in NTT form, or has more than two polynomials.
+    //   join_real_imag: destination = real + imag_alt X^(N/2), slots Re + i Im for slots Re and (-1)^j Im.  The operands must have the same parms_id
+    //   and the same scale by the evaluator's scale comparison: otherwise std::invalid_argument "[Evaluator::join_real_imag] ...".
+    void split_real_imag(const Ciphertext& encrypted, const GaloisKeys& galois_keys, Ciphertext& real2, Ciphertext& imag2_alt, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    std::pair<Ciphertext, Ciphertext> split_real_imag_new(const Ciphertext& encrypted, const GaloisKeys& galois_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        std::pair<Ciphertext, Ciphertext> d; split_real_imag(encrypted, galois_keys, d.first, d.second, pool); return d;
+    }
+    void join_real_imag(const Ciphertext& real, const Ciphertext& imag_alt, Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext join_real_imag_new(const Ciphertext& real, const Ciphertext& imag_alt, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; join_real_imag(real, imag_alt, d, pool); return d;
+    }
+
+    // ADDITION to the reference's interface: the CKKS bootstrap of a fully packed ciphertext as one call (bootstrap.h states the plan, its level count and
+    //   its conditions): mod_switch_to the last level, mod_raise, a scale relabel, coeff_to_slot, split_real_imag, eval_mod_batched on the pair,
+    //   join_real_imag, slot_to_coeff.  The result is at plan.output_parms_id() with the scale plan.output_scale() = the plan's message scale, set exactly.
+    //   Keys: plan.rotation_steps() (step 0 is the conjugation key) and relinearization keys.  std::invalid_argument "[Evaluator::bootstrap] ..." for a
+    //   non-CKKS context, an operand that is not a two-polynomial ciphertext in NTT form, or whose scale differs from the plan's message scale by the
+    //   evaluator's scale comparison; the stages' own refusals pass through.
+    void bootstrap(const Ciphertext& encrypted, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys, Ciphertext& destination,
+                   MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bootstrap_new(const Ciphertext& encrypted, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys,
+                             MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bootstrap(encrypted, plan, relin_keys, galois_keys, d, pool); return d;
+    }
 
     // ADDITION to the reference's interface: the BFV inner product.  destination = the BEHZ multiply (evaluator.cu:29-116) with the tensor
     //   products of all pairs summed BEFORE its scale-down: one floor (and, in the relinearizing form, one key switch,
@@ -2226,9 +2283,11 @@ private:
     void multiply_relinearize_mod_switch_prepare(const Ciphertext& e1, const Ciphertext& e2, const RelinKeys& relin_keys, Ciphertext& out,
                                                  std::vector<const uint64_t*>& key_ptrs, MemoryPoolHandle pool) const;
     // the basis-independent part of the fixed Paterson-Stockmeyer schedule (evaluate_polynomial, evaluate_chebyshev): the level check, the leaves
-    // SUM_i u(j, i) basis(i) and the recombination SUM_j leaf_j basis(jk); basis(m) for m >= 1 is asked for only after the level check
-    void paterson_stockmeyer(const char* P, const Ciphertext& x, size_t d, size_t extra_levels, const std::function<const Ciphertext&(size_t)>& basis,
-                             const std::function<double(size_t, size_t)>& u, const RelinKeys& relin_keys, Ciphertext& destination, MemoryPoolHandle pool) const;
+    // SUM_i u(j, i) basis(i) and the recombination SUM_j leaf_j basis(jk); basis(c, m) of ciphertext c for m >= 1 is asked for only after the level check.
+    // xs are ciphertexts at one level; every device call is made once for all of them (one ciphertext: the single schedule, call for call)
+    void paterson_stockmeyer(const char* P, const std::vector<const Ciphertext*>& xs, size_t d, size_t extra_levels,
+                             const std::function<const Ciphertext&(size_t, size_t)>& basis, const std::function<double(size_t, size_t)>& u, const RelinKeys& relin_keys,
+                             std::vector<Ciphertext>& destination, MemoryPoolHandle pool) const;
     // multiply_prepare's checks for one two-polynomial CKKS / BGV pair of a sum, without the result object; the product's scale and correction factor
     void multiply_accumulate_pair_checks(const Ciphertext& e1, const Ciphertext& e2, SchemeType scheme, double& scale, uint64_t& correction_factor) const;
     void bfv_multiply_accumulate_prepare(const char* P, const std::vector<const Ciphertext*>& e1, const std::vector<const Ciphertext*>& e2,
