@@ -311,11 +311,25 @@ int troyn_mod_switch_drop(const troyn_plan* plan, uint32_t L_in, uint32_t L_out,
  *   troyn_sample_ternary            RandomGenerator::sample_poly_ternary            (:318-336)  ceil(N/16) blocks
  *   troyn_sample_centered_binomial  RandomGenerator::sample_poly_centered_binomial  (:421-440)  ceil(N/2)  blocks
  *   troyn_sample_uniform            RandomGenerator::sample_poly_uniform            (:475-481)  ceil(nmod*N/2) blocks
+ *   troyn_sample_ternary_sparse     (not in the reference)                         N/2        blocks
  *   troyn_prng_block                host_generate_uint128 (:112-117), host only: sample_uint64() = out[0]
+ *
+ * troyn_sample_ternary_sparse draws a ternary polynomial of EXACTLY `hamming_weight` nonzero coefficients (the same
+ * polynomial in every limb, -1 stored as q_i - 1), reproducible from the seed:
+ *   stream   word w_j, j = 0 .. N-1, is word j & 1 of block counter + (j >> 1) (the word order of
+ *            troyn_sample_centered_binomial); *blocks_used = N/2
+ *   key      key_j = (w_j & ~0xFFFF) | j: 48 random bits above the index, so keys are distinct (N <= 65536)
+ *   support  the `hamming_weight` coefficients with the smallest keys are nonzero
+ *   sign     bit 0 of w_j: 0 -> +1, 1 -> -1
+ * One workgroup, no workspace: row 0 of `out` (16-byte aligned) stages the keys while the call runs.
+ * TROYN_E_INVALID "[RandomGenerator::sample_poly_ternary_sparse] ..." for hamming_weight == 0 or > N, nmod out of
+ * range, a null pointer, N > 65536 or a misaligned `out`.
  * ------------------------------------------------------------------------------------- */
 int troyn_prng_block(const uint64_t seed[2], uint64_t counter, uint64_t out[2]);
 int troyn_sample_ternary(const troyn_plan* plan, uint32_t nmod, const uint64_t seed[2], uint64_t counter, uint64_t* out,
                          uint64_t* blocks_used, troyn_stream_t stream);
+int troyn_sample_ternary_sparse(const troyn_plan* plan, uint32_t nmod, const uint64_t seed[2], uint64_t counter, uint32_t hamming_weight,
+                                uint64_t* out, uint64_t* blocks_used, troyn_stream_t stream);
 int troyn_sample_centered_binomial(const troyn_plan* plan, uint32_t nmod, const uint64_t seed[2], uint64_t counter, uint64_t* out,
                                    uint64_t* blocks_used, troyn_stream_t stream);
 int troyn_sample_uniform(const troyn_plan* plan, uint32_t nmod, const uint64_t seed[2], uint64_t counter, uint64_t* out,

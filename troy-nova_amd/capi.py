@@ -91,6 +91,7 @@ SYMBOLS = {
     "troyn_bfv_decrypt_scale_and_round": (C.c_int, [vp, vp, vp, sz, vp]),
     "troyn_prng_block": (C.c_int, [p64, u64, p64]),
     "troyn_sample_ternary": (C.c_int, [vp, u32, p64, u64, vp, p64, vp]),
+    "troyn_sample_ternary_sparse": (C.c_int, [vp, u32, p64, u64, u32, vp, p64, vp]),
     "troyn_sample_centered_binomial": (C.c_int, [vp, u32, p64, u64, vp, p64, vp]),
     "troyn_sample_uniform": (C.c_int, [vp, u32, p64, u64, vp, p64, vp]),
     "troyn_sample_centered_binomial_strided": (C.c_int, [vp, u32, p64, u64, u64, vp, sz, vp]),

@@ -49,6 +49,75 @@ __global__ __launch_bounds__(256) void sample_cbd_kernel(AesRoundKeys key, u64 c
     }
 }
 
+// Fixed-Hamming-weight ternary polynomial (not in the reference, whose key generator draws dense secrets only): out [nmod][n], exactly
+// h coefficients +/-1, the same polynomial in every limb.  Contract (include/troyn.h): word w_j = word j & 1 of block counter + (j >> 1) -- the
+// word order of sample_cbd_kernel; key_j = (w_j & ~0xffff) | j (48 random bits above the index: distinct for n <= 65536); the h smallest keys are
+// the support; bit 0 of w_j is the sign (0: +1, 1: q - 1).
+// ONE workgroup of 1024 threads, no workspace and no scratch: thread t owns the word pairs (= AES blocks) t + 1024 i.
+//   phase 1  keys -> row 0 of out (the only staging the kernel needs); the sign bits of a thread's <= 64 words stay in one 64-bit register.
+//   phase 2  MSB-first radix select of the h-th smallest key: eight passes of 8 bits, each a 256-bin LDS histogram (LDS atomics) over the keys
+//            that still match the prefix, scanned by wave 0, which keeps the bucket holding the wanted rank.  ~1 KiB of LDS whatever n is.
+//   phase 3  every thread re-reads ITS OWN keys from row 0, compares with the threshold and writes 0 / +-1 to the nmod rows.
+// A thread reads back only words it wrote itself (program order), so no fence between the phases and no cross-thread hazard on out.
+constexpr unsigned SPARSE_TERNARY_THREADS = 1024;
+__global__ __launch_bounds__(SPARSE_TERNARY_THREADS) void sample_ternary_sparse_kernel(AesRoundKeys key, u64 counter, const DevModulus* mods, unsigned nmod,
+                                                                                       unsigned n, unsigned h, u64* out) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned s_bucket, s_rank;
+    const unsigned t = threadIdx.x, pairs = n >> 1;
+    u64 signs = 0;                                      // bit 2 i + k = sign of word k of this thread's i-th block (pairs / 1024 <= 32 blocks)
+    unsigned slot = 0;
+    for (unsigned p = t; p < pairs; p += SPARSE_TERNARY_THREADS, slot += 2) {
+        u64 w[2];
+        aes128_encrypt_counter(key, counter + p, (counter + p < counter) ? 1ull : 0ull, w[0], w[1]);
+        signs |= ((w[0] & 1ull) | ((w[1] & 1ull) << 1)) << slot;
+        st2(out + 2 * (size_t)p, (w[0] & ~0xffffull) | (u64)(2 * p), (w[1] & ~0xffffull) | (u64)(2 * p + 1));
+    }
+    u64 prefix = 0;                                     // the bits of the h-th smallest key found so far
+    unsigned rank = h;                                  // its 1-based rank among the keys that share them
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        if (t < 256) hist[t] = 0;
+        __syncthreads();
+        for (unsigned p = t; p < pairs; p += SPARSE_TERNARY_THREADS) {
+            const u64x2 kv = ld2(out + 2 * (size_t)p);
+            // (x >> shift) >> 8: the bits above this pass's digit (a 64-bit shift by 64 is undefined)
+            if (((kv.a >> shift) >> 8) == prefix) atomicAdd(&hist[(unsigned)(kv.a >> shift) & 255u], 1u);
+            if (((kv.b >> shift) >> 8) == prefix) atomicAdd(&hist[(unsigned)(kv.b >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (t < 64) {                                   // wave 0: lane l scans bins 4 l .. 4 l + 3
+            unsigned c[4], sum = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { c[k] = hist[4 * t + k]; sum += c[k]; }
+            unsigned incl = sum;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const unsigned v = __shfl_up(incl, d, 64); if ((int)t >= d) incl += v; }
+            unsigned before = incl - sum;               // keys in the bins below this lane's
+            if (before < rank && rank <= incl) {        // exactly one lane: the bins sum to the number of matching keys >= rank
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (rank <= before + c[k]) { s_bucket = 4 * t + k; s_rank = rank - before; break; }
+                    before += c[k];
+                }
+            }
+        }
+        __syncthreads();
+        prefix = (prefix << 8) | s_bucket;
+        rank = s_rank;
+    }
+    // prefix = the h-th smallest key (keys are distinct, so rank ended at 1): the support is key <= prefix
+    slot = 0;
+    for (unsigned p = t; p < pairs; p += SPARSE_TERNARY_THREADS, slot += 2) {
+        const u64x2 kv = ld2(out + 2 * (size_t)p);
+        const bool on0 = kv.a <= prefix, on1 = kv.b <= prefix;
+        const bool neg0 = (signs >> slot) & 1ull, neg1 = (signs >> (slot + 1)) & 1ull;
+        for (unsigned i = nmod; i-- > 0;) {             // row 0, which held the keys, last (they are in registers by now either way)
+            const u64 m1 = mods[i].q - 1;
+            st2(out + (size_t)i * n + 2 * (size_t)p, on0 ? (neg0 ? m1 : 1ull) : 0ull, on1 ? (neg1 ? m1 : 1ull) : 0ull);
+        }
+    }
+}
+
 // out [nmod][n] = the AES-CTR word stream reduced per limb (fill_uint64s + modulo_inplace_p); thread = 2 words
 __global__ __launch_bounds__(256) void sample_uniform_kernel(AesRoundKeys key, u64 counter, const DevModulus* mods, unsigned nmod, unsigned n, u64* out) {
     const size_t blk = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

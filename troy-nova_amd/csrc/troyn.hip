@@ -3701,6 +3701,23 @@ extern "C" int troyn_sample_ternary(const troyn_plan* p, uint32_t nmod, const ui
     return launch_sampler(sample_ternary_kernel, "[RandomGenerator::sample_poly_ternary]", p, nmod, seed, counter, out,
                           p ? ((size_t)p->n + 15) / 16 : 0, blocks_used, stream, p ? (size_t)p->n : 0);      // (a thread per coefficient)
 }
+// fixed Hamming weight: one workgroup selects the h smallest of N keyed words in place, row 0 of `out` staging the keys
+extern "C" int troyn_sample_ternary_sparse(const troyn_plan* p, uint32_t nmod, const uint64_t seed[2], uint64_t counter, uint32_t hamming_weight,
+                                           uint64_t* out, uint64_t* blocks_used, troyn_stream_t stream) {
+    select_device(p);
+    const char* P = "[RandomGenerator::sample_poly_ternary_sparse]";
+    if (!p || !seed || !out) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if (nmod == 0 || nmod > p->K) return fail(TROYN_E_INVALID, std::string(P) + " modulus count out of range");
+    if (hamming_weight == 0 || hamming_weight > p->n) return fail(TROYN_E_INVALID, std::string(P) + " hamming weight must be in [1, N]");
+    if (p->n < 2 || p->n > 65536) return fail(TROYN_E_INVALID, std::string(P) + " the 16-bit index of a key needs N <= 65536");
+    if ((uintptr_t)out & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned destination");
+    const AesRoundKeys k = aes128_expand(seed[0], seed[1]);
+    hipLaunchKernelGGL(sample_ternary_sparse_kernel, dim3(1), dim3(SPARSE_TERNARY_THREADS), 0, (hipStream_t)stream,
+                       k, (u64)counter, p->d_mods, (unsigned)nmod, p->n, (unsigned)hamming_weight, (u64*)out);
+    LAUNCH_CHECK();
+    if (blocks_used) *blocks_used = p->n / 2;
+    return TROYN_OK;
+}
 extern "C" int troyn_sample_centered_binomial(const troyn_plan* p, uint32_t nmod, const uint64_t seed[2], uint64_t counter, uint64_t* out,
                                               uint64_t* blocks_used, troyn_stream_t stream) {
     select_device(p);

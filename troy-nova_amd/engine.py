@@ -694,6 +694,15 @@ class Prng:
     def ternary(self, nmod):
         return self._sample("troyn_sample_ternary", nmod)
 
+    def ternary_sparse(self, nmod, h):
+        """A ternary polynomial with exactly `h` nonzero coefficients (troyn_sample_ternary_sparse: the h smallest of N keyed words)."""
+        out = torch.empty((nmod, self.plan.n), dtype=torch.int64, device=self.plan.device)
+        used = np.zeros(1, dtype=np.uint64)
+        capi.check(self.plan.lib.troyn_sample_ternary_sparse(self.plan.h, nmod, self.seed.ctypes.data_as(capi.p64), self.counter, int(h), _ptr(out),
+                                                             used.ctypes.data_as(capi.p64), _stream()))
+        self.counter += int(used[0])
+        return out
+
     def centered_binomial(self, nmod):
         return self._sample("troyn_sample_centered_binomial", nmod)
 

@@ -259,7 +259,26 @@ PYBIND11_MODULE(pytroy_raw, m) {
         .def("create_galois_keys_from_steps", [](const KeyGenerator& s, const std::vector<int>& st, bool save_seed, PoolArg p) { return s.create_galois_keys_from_steps(st, save_seed, P(p)); },
              py::arg("galois_steps"), py::arg("save_seed"), POOL)
         .def("create_galois_keys_from_elements", [](const KeyGenerator& s, const std::vector<size_t>& el, bool save_seed, PoolArg p) { return s.create_galois_keys_from_elements(el, save_seed, P(p)); },
-             py::arg("galois_elts"), py::arg("save_seed"), POOL);
+             py::arg("galois_elts"), py::arg("save_seed"), POOL)
+        // additions: a secret of a fixed Hamming weight, and the keys of the sparse-secret encapsulation (bootstrap.h)
+        .def_static("create_sparse", [](HeContextPointer c, size_t h, PoolArg p) { return new KeyGenerator(KeyGenerator::create_sparse(c, h, P(p))); },
+                    py::arg("context"), py::arg("hamming_weight"), POOL, py::return_value_policy::take_ownership)
+        .def("create_sparse_encapsulation_keys", [](const KeyGenerator& s, size_t h, bool save_seed, PoolArg p) { return s.create_sparse_encapsulation_keys(h, save_seed, P(p)); },
+             py::arg("hamming_weight"), py::arg("save_seed") = false, POOL)
+        .def("create_sparse_encapsulation_keys", [](const KeyGenerator& s, const SecretKey& sk, bool save_seed, PoolArg p) { return s.create_sparse_encapsulation_keys(sk, save_seed, P(p)); },
+             py::arg("sparse_secret_key"), py::arg("save_seed") = false, POOL);
+    // (the members are handed out as copies: a KSwitchKeys copy shares its device arrays)
+    py::class_<SparseEncapsulationKeys>(m, "SparseEncapsulationKeys").def(py::init<>())
+        .def_property_readonly("to_sparse", [](const SparseEncapsulationKeys& s) { return s.to_sparse; })
+        .def_property_readonly("to_dense", [](const SparseEncapsulationKeys& s) { return s.to_dense; })
+        .def_property_readonly("hamming_weight", [](const SparseEncapsulationKeys& s) { return s.hamming_weight; })
+        // the words of one digit of a member, [2 * K * N] as the device holds them (what is and is not zero in to_sparse can be read off)
+        .def("obtain_data", [](const SparseEncapsulationKeys& s, bool sparse, size_t digit) {
+            const KSwitchKeys& k = sparse ? s.to_sparse : s.to_dense;
+            if (k.data().size() != 1 || digit >= k.data()[0].size()) throw std::out_of_range("[SparseEncapsulationKeys::obtain_data] no such digit.");
+            const std::vector<uint64_t> v = k.data()[0][digit].as_ciphertext().data().to_vector();
+            return py::array_t<uint64_t>(v.size(), v.data()); }, py::arg("to_sparse"), py::arg("digit"))
+        .def("digit_count", [](const SparseEncapsulationKeys& s) { return s.to_sparse.data().size() == 1 ? s.to_sparse.data()[0].size() : size_t(0); });
 
     py::class_<utils::RandomGenerator>(m, "RandomGenerator")
         .def(py::init([]() { return new utils::RandomGenerator(); })).def(py::init([](uint64_t seed) { return new utils::RandomGenerator(seed); }), py::arg("seed"))
@@ -599,12 +618,19 @@ PYBIND11_MODULE(pytroy_raw, m) {
         .def("output_parms_id", [](const BootstrapPlan& s) { return s.output_parms_id(); })
         .def("rotation_steps", [](const BootstrapPlan& s) { return s.rotation_steps(); })
         .def("coeff_to_slot_plan", [](const BootstrapPlan& s) -> const CoeffToSlotPlan& { return s.coeff_to_slot_plan(); }, py::return_value_policy::reference_internal)
-        .def("slot_to_coeff_plan", [](const BootstrapPlan& s) -> const SlotToCoeffPlan& { return s.slot_to_coeff_plan(); }, py::return_value_policy::reference_internal);
+        .def("slot_to_coeff_plan", [](const BootstrapPlan& s) -> const SlotToCoeffPlan& { return s.slot_to_coeff_plan(); }, py::return_value_policy::reference_internal)
+        .def_static("half_width_for", &BootstrapPlan::half_width_for, py::arg("hamming_weight"));
     m.def("chebyshev_depth", &Evaluator::chebyshev_depth, py::arg("degree"));
     ev.def("bootstrap", [](const Evaluator& s, const Ciphertext& a, const BootstrapPlan& plan, const RelinKeys& rk, const GaloisKeys& gk, Ciphertext& d, PoolArg p) {
         s.bootstrap(a, plan, rk, gk, d, P(p)); }, py::arg("encrypted"), py::arg("plan"), py::arg("relin_keys"), py::arg("galois_keys"), py::arg("destination"), POOL);
     ev.def("bootstrap_new", [](const Evaluator& s, const Ciphertext& a, const BootstrapPlan& plan, const RelinKeys& rk, const GaloisKeys& gk, PoolArg p) {
         return s.bootstrap_new(a, plan, rk, gk, P(p)); }, py::arg("encrypted"), py::arg("plan"), py::arg("relin_keys"), py::arg("galois_keys"), POOL);
+    ev.def("bootstrap", [](const Evaluator& s, const Ciphertext& a, const BootstrapPlan& plan, const RelinKeys& rk, const GaloisKeys& gk, const SparseEncapsulationKeys& ek,
+                           Ciphertext& d, PoolArg p) { s.bootstrap(a, plan, rk, gk, ek, d, P(p)); },
+           py::arg("encrypted"), py::arg("plan"), py::arg("relin_keys"), py::arg("galois_keys"), py::arg("encapsulation_keys"), py::arg("destination"), POOL);
+    ev.def("bootstrap_new", [](const Evaluator& s, const Ciphertext& a, const BootstrapPlan& plan, const RelinKeys& rk, const GaloisKeys& gk, const SparseEncapsulationKeys& ek,
+                               PoolArg p) { return s.bootstrap_new(a, plan, rk, gk, ek, P(p)); },
+           py::arg("encrypted"), py::arg("plan"), py::arg("relin_keys"), py::arg("galois_keys"), py::arg("encapsulation_keys"), POOL);
     // additions: the BFV inner product, one scale-down for the sum (troy.h)
     ev.def("bfv_multiply_accumulate", [](const Evaluator& s, const std::vector<Ciphertext*>& a, const std::vector<Ciphertext*>& b, Ciphertext& d, PoolArg p) {
         s.bfv_multiply_accumulate(const_ptrs(a), const_ptrs(b), d, P(p)); }, py::arg("encrypted1"), py::arg("encrypted2"), py::arg("destination"), POOL);

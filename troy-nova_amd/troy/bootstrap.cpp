@@ -91,19 +91,49 @@ void Evaluator::join_real_imag(const Ciphertext& real, const Ciphertext& imag_al
     destination = std::move(out);
 }
 
-void Evaluator::bootstrap(const Ciphertext& encrypted, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys, Ciphertext& destination,
-                          MemoryPoolHandle pool) const {
+double BootstrapPlan::half_width_for(size_t hamming_weight) { return 1.0 + 6.5 * std::sqrt((static_cast<double>(hamming_weight) + 1.0) / 12.0); }
+
+void Evaluator::bootstrap_checks(const Ciphertext& encrypted, const BootstrapPlan& plan) const {
     const std::string P = "[Evaluator::bootstrap]";
     if (context_->key_context_data().value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(P + " CKKS only.");
     if (!encrypted.is_ntt_form()) throw std::invalid_argument(P + " Ciphertext must be in NTT form.");
     if (encrypted.polynomial_count() != 2) throw std::invalid_argument(P + " The ciphertext must have two polynomials.");
     if (!detail::scales_are_close(encrypted.scale(), plan.message_scale())) throw std::invalid_argument(P + " The operand's scale is not the plan's message scale.");
+}
+
+void Evaluator::bootstrap(const Ciphertext& encrypted, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys, Ciphertext& destination,
+                          MemoryPoolHandle pool) const {
+    bootstrap_checks(encrypted, plan);
     // 1. the last level: one prime, q0
     Ciphertext low;
     const Ciphertext* exhausted = &encrypted;
     if (encrypted.parms_id() != context_->last_parms_id()) { mod_switch_to(encrypted, context_->last_parms_id(), low, pool); exhausted = &low; }
-    // 2, 3. to the top; the coefficients read t / q0 = D m / q0 + I
-    Ciphertext raised = mod_raise_new(*exhausted, std::nullopt, pool);
+    // 2. to the top: t = D m + q0 I
+    bootstrap_raised(mod_raise_new(*exhausted, std::nullopt, pool), plan, relin_keys, galois_keys, destination, pool);
+}
+
+void Evaluator::bootstrap(const Ciphertext& encrypted, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys,
+                          const SparseEncapsulationKeys& encapsulation_keys, Ciphertext& destination, MemoryPoolHandle pool) const {
+    const std::string P = "[Evaluator::bootstrap]";
+    bootstrap_checks(encrypted, plan);
+    for (const KSwitchKeys* k : {&encapsulation_keys.to_sparse, &encapsulation_keys.to_dense}) {
+        if (k->data().size() != 1 || k->data()[0].empty()) throw std::invalid_argument(P + " The sparse encapsulation keys are empty.");
+        if (k->parms_id() != context_->key_parms_id()) throw std::invalid_argument(P + " The sparse encapsulation keys have another key parms_id than the context.");
+    }
+    // 1. the last level: one prime, q0;  1a. to the sparse secret there, where to_sparse has its rows
+    Ciphertext low;
+    const Ciphertext* exhausted = &encrypted;
+    if (encrypted.parms_id() != context_->last_parms_id()) { mod_switch_to(encrypted, context_->last_parms_id(), low, pool); exhausted = &low; }
+    const Ciphertext sparse = apply_keyswitching_new(*exhausted, encapsulation_keys.to_sparse, pool);
+    // 2. to the top under the sparse secret: t = D m + q0 I with I from s';  2a. back to the evaluation secret
+    const Ciphertext raised = mod_raise_new(sparse, std::nullopt, pool);
+    bootstrap_raised(apply_keyswitching_new(raised, encapsulation_keys.to_dense, pool), plan, relin_keys, galois_keys, destination, pool);
+}
+
+void Evaluator::bootstrap_raised(Ciphertext&& raised, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys, Ciphertext& destination,
+                                 MemoryPoolHandle pool) const {
+    const std::string P = "[Evaluator::bootstrap]";
+    // 3. the coefficients read t / q0 = D m / q0 + I
     raised.scale() = plan.q0();
     // 4, 5. slots c1 BR(x_k + i x_{k+n}); their parts 2 c1 Re, (-1)^j 2 c1 Im relabelled to read Re, (-1)^j Im
     const Ciphertext slots = coeff_to_slot_new(raised, plan.coeff_to_slot_plan(), galois_keys, pool);

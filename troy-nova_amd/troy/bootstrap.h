@@ -1,14 +1,17 @@
 // bootstrap.h -- troy::BootstrapPlan, an ADDITION to the reference's interface: the CKKS bootstrap of a fully packed ciphertext,
 //     ModRaise -> CoeffToSlot -> (real / imaginary parts) -> EvalMod on both halves at once -> (join) -> SlotToCoeff,
 // as one call, Evaluator::bootstrap.  The plan owns the two slot plans (slot_transform.h), chooses every level, scale and normalisation constant and says
-// which Galois keys are needed.  Sparse packing (fewer than N/2 slots) and sparse secrets are out of scope: the key generator makes dense ternary secrets only.
+// which Galois keys are needed.  Sparse packing (fewer than N/2 slots) is out of scope.  With sparse secrets K shrinks: KeyGenerator::create_sparse draws a
+// secret of a fixed Hamming weight, and the sparse-secret encapsulation below keeps a dense evaluation secret while I comes from a sparse one.
 //
 // Notation.  N the ring degree, n = N/2, q0 the first prime (the only one of the last level), D = message_scale (Delta), K = half_width, r = double_angles.
 // An exhausted ciphertext decrypts to D m modulo q0.  After mod_raise it decrypts, modulo the whole chain, to t = D m + q0 I with an integer polynomial I.
 //
 // Conditions (the caller's):
-//   K - 1 >= ||I||_inf.  For a dense ternary secret the coefficients of I behave like sums of N + 1 uniform fractions: standard deviation sqrt((N + 1) / 12).
-//     Rule of thumb K - 1 >= 6.5 sqrt((N + 1) / 12), which gives K = 64 at N = 1024 (58.7 + 1, rounded up to a power of two).
+//   K - 1 >= ||I||_inf.  For a ternary secret of Hamming weight h -- the secret under which mod_raise runs -- the coefficients of I behave like sums of
+//     h + 1 uniform fractions: standard deviation sqrt((h + 1) / 12).  Rule of thumb K - 1 >= 6.5 sqrt((h + 1) / 12) = half_width_for(h) - 1.  A dense
+//     secret of this key generator has h about 2N/3 and at most N, for which the rule reads K - 1 >= 6.5 sqrt((N + 1) / 12): half_width_for(N) is 61.1
+//     at N = 1024 (K = 64 as a power of two) and 241.2 at N = 16384 (K = 256).  h = 192 gives 27.1, and the ephemeral h = 32 of the encapsulation 11.8 (K = 12).  Which h is safe for a chain is the caller's call.
 //   |D m| / q0 <= 2^-7, eval_mod's own condition: sin(2 pi x) / (2 pi) is x up to a cubic term.  The constructor asks for q0 / D >= 2 only.
 //
 // The steps of Evaluator::bootstrap and where each factor goes -- none costs a level:
@@ -31,10 +34,27 @@
 // Key switches: key_switches() counts the Galois key switches of one call -- the rotations and conjugations of both slot plans and the one conjugation of
 // split_real_imag; EvalMod's relinearizations (one per product step) are not Galois key switches and are not counted.  rotation_steps() is the union of
 // both slot plans' steps and step 0, which create_galois_keys_from_steps reads as the conjugation.
+//
+// Sparse-secret encapsulation (Bossuat, Troncoso-Pastoriza, Hubaux 2022).  The evaluation secret s stays as it is; an ephemeral secret s' of small Hamming
+// weight is used around ModRaise only, where the modulus is q0 P (one data prime and the special prime).  Evaluator::bootstrap with SparseEncapsulationKeys:
+//   1. mod_switch_to the last level;  1a. apply_keyswitching with to_sparse (s -> s');  2. mod_raise: t = D m + q0 I with I from s';
+//   2a. apply_keyswitching with to_dense (s' -> s) at the top level;  3. onward as above.
+// The two key switches add their usual noise where the payload is D m against q0, and t against the whole chain.  K is chosen from the weight of s'.
+//   to_dense   s' -> s, KeyGenerator(s).create_keyswitching_key(s'): an ordinary key at the full key level.
+//   to_sparse  s -> s', KeyGenerator(s').create_keyswitching_key(s), in the standard KSwitchKeys layout so that apply_keyswitching reads it unchanged, but
+//              holding ONLY what a key switch at the last level reads: digit 0, limbs {0, K_key - 1} of both polynomials.  Every other word is zero on the
+//              device: an RLWE sample under a weight-32 secret at the full key modulus is not something to publish.  It never holds a seed (a seed would
+//              regenerate the dropped rows): the makers' save_seed goes to to_dense only.  Using it above the last level gives a wrong result, not an error.
+// Both members serialize as KSwitchKeys; there is no wire format of the pair.
 #pragma once
 #include "slot_transform.h"
 
 namespace troy {
+
+struct SparseEncapsulationKeys {
+    KSwitchKeys to_sparse, to_dense;
+    size_t hamming_weight = 0;        // of s', as counted when the keys were made
+};
 
 class BootstrapPlan {
 public:
@@ -46,6 +66,9 @@ public:
                   MemoryPoolHandle pool = MemoryPool::GlobalPool());
     BootstrapPlan(const BootstrapPlan&) = delete;
     BootstrapPlan& operator=(const BootstrapPlan&) = delete;
+
+    // the rule of thumb of the Conditions above for a secret of Hamming weight h: 1 + 6.5 sqrt((h + 1) / 12).  The plan takes K as given; round up as you like.
+    static double half_width_for(size_t hamming_weight);
 
     double message_scale() const { return message_scale_; }
     double half_width() const { return half_width_; }

@@ -3,6 +3,7 @@
 // function whose behaviour (checks, metadata updates, error text) is mirrored.
 #include "troy.h"
 #include "device_steps.h"
+#include "bootstrap.h"      // SparseEncapsulationKeys (KeyGenerator::create_sparse_encapsulation_keys)
 #include "../csrc/ckks_tables.hpp"
 
 #include <atomic>
@@ -3563,6 +3564,14 @@ void RandomGenerator::sample_poly_ternary(const troyn_plan* plan, size_t nmod, u
     counter_ += used;
 }
 
+void RandomGenerator::sample_poly_ternary_sparse(const troyn_plan* plan, size_t nmod, size_t hamming_weight, uint64_t* destination) {
+    std::lock_guard<std::mutex> lock(mutex_);
+    uint64_t used = 0;
+    const uint32_t h = hamming_weight > UINT32_MAX ? UINT32_MAX : static_cast<uint32_t>(hamming_weight);     // above N either way: the entry refuses it
+    troyn_check(troyn_sample_ternary_sparse(plan, static_cast<uint32_t>(nmod), seed_, counter_, h, destination, &used, current_stream()));
+    counter_ += used;
+}
+
 void RandomGenerator::sample_poly_centered_binomial(const troyn_plan* plan, size_t nmod, uint64_t* destination) {
     std::lock_guard<std::mutex> lock(mutex_);
     uint64_t used = 0;
@@ -3715,6 +3724,20 @@ KeyGenerator::KeyGenerator(HeContextPointer context, MemoryPoolHandle pool) : co
     secret_key_array_ = secret_key_.data().clone(pool);
 }
 
+KeyGenerator::KeyGenerator(HeContextPointer context, size_t hamming_weight, SparseSecret, MemoryPoolHandle pool) : context_(std::move(context)) {
+    // the constructor above with the fixed-weight sampler
+    require_device_context("[KeyGenerator::create_sparse]", context_);
+    ContextDataPointer kcd = context_->key_context_data().value();
+    if (hamming_weight == 0 || hamming_weight > kcd->parms().poly_modulus_degree())
+        throw std::invalid_argument("[KeyGenerator::create_sparse] the Hamming weight must be in 1 .. N.");
+    const uint32_t K = static_cast<uint32_t>(kcd->parms().coeff_modulus().size());
+    Plaintext sk = key_level_plaintext(context_, pool);
+    context_->random_generator().sample_poly_ternary_sparse(context_->plan(), K, hamming_weight, sk.poly());
+    troyn_check(troyn_ntt(context_->plan(), 0, sk.poly(), sk.poly(), 1, 1, K, 0, K, TROYN_IDX_COMPONENTWISE, 0, current_stream()));
+    secret_key_ = SecretKey(std::move(sk));
+    secret_key_array_ = secret_key_.data().clone(pool);
+}
+
 KeyGenerator::KeyGenerator(HeContextPointer context, const SecretKey& secret_key, MemoryPoolHandle pool) : context_(std::move(context)) {
     require_device_context("[KeyGenerator::KeyGenerator]", context_);
     secret_key_ = secret_key.clone(pool);
@@ -3778,6 +3801,45 @@ KSwitchKeys KeyGenerator::create_keyswitching_key(const SecretKey& new_key, bool
     std::vector<std::vector<PublicKey>> keys(1);
     generate_one_kswitch_key(new_key.data().raw_pointer(), keys[0], save_seed, pool);
     return KSwitchKeys(context_->key_parms_id(), std::move(keys));
+}
+
+// Sparse-secret encapsulation (bootstrap.h).  to_dense is an ordinary key at the full key level.  to_sparse is generated like any key, under s', and then
+// cut down to what a key switch at the LAST level reads: digit 0, limbs {0, K-1} of both polynomials (the C-ABI's key-switch inner product at level L walks
+// digits 0 .. L-1 and the limbs 0 .. L-1 and K-1 of each).  Every other word is set to zero on the device before the object leaves this function.
+SparseEncapsulationKeys KeyGenerator::create_sparse_encapsulation_keys(const SecretKey& sparse_secret_key, bool save_seed, MemoryPoolHandle pool) const {
+    const std::string P = "[KeyGenerator::create_sparse_encapsulation_keys]";
+    ContextDataPointer kcd = context_->key_context_data().value();
+    const size_t n = kcd->parms().poly_modulus_degree(), K = kcd->parms().coeff_modulus().size();
+    if (sparse_secret_key.data().size() != K * n || !sparse_secret_key.on_device())
+        throw std::invalid_argument(P + " the sparse secret key must be a key of this context, on the device.");
+    SparseEncapsulationKeys keys;
+    keys.to_dense = create_keyswitching_key(sparse_secret_key, save_seed, pool);
+    keys.to_sparse = KeyGenerator(context_, sparse_secret_key, pool).create_keyswitching_key(secret_key_, false, pool);     // never seeded: see troy.h
+    hipStream_t s = current_stream();
+    std::vector<PublicKey>& digits = keys.to_sparse.data()[0];
+    for (size_t i = 0; i < digits.size(); i++) {
+        Ciphertext& c = digits[i].as_ciphertext();
+        if (i > 0) { hip_check(hipMemsetAsync(c.data().raw_pointer(), 0, c.data().size() * sizeof(uint64_t), s), "memset"); continue; }
+        if (K > 2)
+            for (size_t p = 0; p < c.polynomial_count(); p++) hip_check(hipMemsetAsync(c.poly(p) + n, 0, (K - 2) * n * sizeof(uint64_t), s), "memset");
+    }
+    // the weight of s', counted on its first limb in coefficient form
+    utils::DynamicArray coefficients(n, true, pool);
+    hip_check(hipMemcpyAsync(coefficients.raw_pointer(), sparse_secret_key.data().raw_pointer(), n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s), "memcpy");
+    troyn_check(troyn_ntt(context_->plan(), 1, coefficients.raw_pointer(), coefficients.raw_pointer(), 1, 1, 1, 0, 1, TROYN_IDX_COMPONENTWISE, 0, s));
+    std::vector<uint64_t> host(n);
+    hip_check(hipMemcpyAsync(host.data(), coefficients.raw_pointer(), n * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "memcpy");
+    hip_check(hipStreamSynchronize(s), "stream_sync");
+    keys.hamming_weight = static_cast<size_t>(std::count_if(host.begin(), host.end(), [](uint64_t v) { return v != 0; }));
+    return keys;
+}
+
+SparseEncapsulationKeys KeyGenerator::create_sparse_encapsulation_keys(size_t hamming_weight, bool save_seed, MemoryPoolHandle pool) const {
+    ContextDataPointer kcd = context_->key_context_data().value();
+    if (hamming_weight == 0 || hamming_weight > kcd->parms().poly_modulus_degree())
+        throw std::invalid_argument("[KeyGenerator::create_sparse_encapsulation_keys] the Hamming weight must be in 1 .. N.");
+    const KeyGenerator ephemeral = KeyGenerator::create_sparse(context_, hamming_weight, pool);       // s': dropped when this function returns
+    return create_sparse_encapsulation_keys(ephemeral.secret_key(), save_seed, pool);
 }
 
 RelinKeys KeyGenerator::create_relin_keys(bool save_seed, size_t max_power, MemoryPoolHandle pool) const {

@@ -321,6 +321,8 @@ public:
     uint64_t sample_uint64();
     // destination: device buffer of nmod*N words (the first nmod moduli of the plan's chain)
     void sample_poly_ternary(const troyn_plan* plan, size_t nmod, uint64_t* destination);
+    // ADDITION to the reference's interface: exactly `hamming_weight` coefficients +/-1 (troyn_sample_ternary_sparse, include/troyn.h); N/2 blocks
+    void sample_poly_ternary_sparse(const troyn_plan* plan, size_t nmod, size_t hamming_weight, uint64_t* destination);
     void sample_poly_centered_binomial(const troyn_plan* plan, size_t nmod, uint64_t* destination);
     void sample_poly_uniform(const troyn_plan* plan, size_t nmod, uint64_t* destination);
     // batched encryption: take `blocks` consecutive counter values at once (returns the first); read the seed
@@ -901,10 +903,18 @@ std::vector<int> naf(int value);   // utils/number_theory.cu:6-20
 // ----------------------------------------------------------------------------------------------
 // KeyGenerator  (src/key_generator.h, key_generator.cu)
 // ----------------------------------------------------------------------------------------------
+struct SparseEncapsulationKeys;   // bootstrap.h
+
 class KeyGenerator {
 public:
     explicit KeyGenerator(HeContextPointer context, MemoryPoolHandle pool = MemoryPool::GlobalPool());                 // samples s
     KeyGenerator(HeContextPointer context, const SecretKey& secret_key, MemoryPoolHandle pool = MemoryPool::GlobalPool());
+    // ADDITION to the reference's interface: the first constructor with a secret of exactly `hamming_weight` nonzero coefficients
+    // (RandomGenerator::sample_poly_ternary_sparse, then the same NTT).  Everything the generator offers works on that secret unchanged.
+    // std::invalid_argument "[KeyGenerator::create_sparse] ..." for hamming_weight 0 or above N.  Which weight is safe for a chain is the caller's call.
+    static KeyGenerator create_sparse(HeContextPointer context, size_t hamming_weight, MemoryPoolHandle pool = MemoryPool::GlobalPool()) {
+        return KeyGenerator(std::move(context), hamming_weight, SparseSecret{}, pool);
+    }
     HeContextPointer context() const { return context_; }
     bool on_device() const { return secret_key_.on_device(); }
     // key_generator.h:35-41.  Keys of this mirror are created where the context lives (on the device), so for a device context this moves nothing
@@ -930,7 +940,15 @@ public:
         return create_galois_keys_from_elements(galois_elements, save_seed, pool);
     }
     static void compute_secret_key_powers(HeContextPointer context, size_t max_power, utils::DynamicArray& secret_key_array);
+    // ADDITION to the reference's interface: the two key-switching keys of the sparse-secret encapsulation (bootstrap.h, SparseEncapsulationKeys), between
+    // this generator's secret s and a sparse secret s'.  The first form draws s' (exactly `hamming_weight` nonzero coefficients) from the context's
+    // generator and drops it; the second takes the caller's s'.  save_seed applies to to_dense only: to_sparse never holds a seed, because a seed would
+    // regenerate the rows that are zeroed.  std::invalid_argument "[KeyGenerator::create_sparse_encapsulation_keys] ..." for a weight of 0 or above N.
+    SparseEncapsulationKeys create_sparse_encapsulation_keys(size_t hamming_weight, bool save_seed = false, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    SparseEncapsulationKeys create_sparse_encapsulation_keys(const SecretKey& sparse_secret_key, bool save_seed = false, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
 private:
+    struct SparseSecret {};
+    KeyGenerator(HeContextPointer context, size_t hamming_weight, SparseSecret, MemoryPoolHandle pool);
     void generate_one_kswitch_key(const uint64_t* new_key, std::vector<PublicKey>& destination, bool save_seed, MemoryPoolHandle pool) const;
     HeContextPointer context_;
     SecretKey secret_key_;
@@ -1713,6 +1731,16 @@ public:
                              MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
         Ciphertext d; bootstrap(encrypted, plan, relin_keys, galois_keys, d, pool); return d;
     }
+    //   The same behind a sparse-secret encapsulation (bootstrap.h, SparseEncapsulationKeys): at the last level the operand is key-switched to the sparse
+    //   secret s' (to_sparse), raised, and key-switched back to the evaluation secret at the top level (to_dense); from the 1 / q0 relabel on the call is
+    //   the one above.  I now comes from s', so the plan's K is chosen from ITS weight (BootstrapPlan::half_width_for).  Further refusals, same prefix:
+    //   encapsulation keys that are empty or carry another key parms_id than the context's.
+    void bootstrap(const Ciphertext& encrypted, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys,
+                   const SparseEncapsulationKeys& encapsulation_keys, Ciphertext& destination, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext bootstrap_new(const Ciphertext& encrypted, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys,
+                             const SparseEncapsulationKeys& encapsulation_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; bootstrap(encrypted, plan, relin_keys, galois_keys, encapsulation_keys, d, pool); return d;
+    }
 
     // ADDITION to the reference's interface: the BFV inner product.  destination = the BEHZ multiply (evaluator.cu:29-116) with the tensor
     //   products of all pairs summed BEFORE its scale-down: one floor (and, in the relinearizing form, one key switch,
@@ -2218,6 +2246,10 @@ public:
 
 private:
     ContextDataPointer get_context_data(const char* prompt, const ParmsID& id) const;
+    // both bootstrap calls: the argument checks, and everything from the 1 / q0 relabel of the raised ciphertext onward
+    void bootstrap_checks(const Ciphertext& encrypted, const BootstrapPlan& plan) const;
+    void bootstrap_raised(Ciphertext&& raised, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys, Ciphertext& destination,
+                          MemoryPoolHandle pool) const;
     void translate_inplace(Ciphertext& e1, const Ciphertext& e2, bool subtract, MemoryPoolHandle pool) const;
     void translate(const Ciphertext& e1, const Ciphertext& e2, Ciphertext& d, bool subtract, MemoryPoolHandle pool) const;
     void translate_plain_inplace(Ciphertext& encrypted, const Plaintext& plain, bool subtract, MemoryPoolHandle pool) const;
