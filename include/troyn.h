@@ -805,6 +805,31 @@ int troyn_ckks_dft_factor_diagonals(const troyn_ckks* h, uint32_t first, uint32_
                                     double constant, double* out, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Factors of the special DFT on n slots (an addition to the reference's API): the same matrices for a sparsely packed message, n a power of
+ * two with 2 <= n <= N/2.  (n = 1 has no such transform: 3 has order 2, not 1, modulo 4.)
+ *
+ * With s = N/(2n) a sparsely packed message is a polynomial p(Y), Y = X^s, of degree < 2n; t' its coefficients, w_k = t'_k + i t'_{k+n}.  Slot j
+ * evaluates p at (zeta^s)^(3^j), zeta^s a primitive 4n-th root, and 3 has order n modulo 4n: the N/2 slots are an n-vector z repeated s times.
+ * The derivation above holds verbatim for the ring of degree 2n with m' = log2 n: zh = L_{m'-1} ... L_0 BR w, BR on m' bits, and layer b's
+ * twiddle (zeta^s)^(((-3)^j mod 4 len) 4n / 4 len) = zeta^(((-3)^j mod 4 len) 2N / 4 len) is the full ring's layer b, read from the same
+ * root_powers.  The table is therefore the one of troyn_ckks_dft_factor_diagonals taken on one n x n block: n rows, diagonal indices mod n,
+ * first + count <= m', and the group with first + count == m' is the one where +k and -(2^count - k) coincide (nd = 2^count).
+ * out is double [nd][n][2], the layout troyn_ckks_encode_diagonals reads in diagonals mode with that n (which repeats a diagonal s times across
+ * the slots).  troyn_ckks_dft_factor_diagonals_sparse_count gives nd (0 for a null handle, an n that is refused, count == 0 or layers outside
+ * [0, m']).  Masks, conjugate and constant as above.
+ *
+ * CONTRACT: the words of `out` equal those of tests/sparse_bootstrap_spec.py (table), which is tests/dft_factors_spec.py's table taken on n
+ * rows of the handle's own full-ring tables: ONE product per entry, the same association, every operation rounded on its own, no FMA.  With
+ * n = N/2 the words are those of troyn_ckks_dft_factor_diagonals.
+ *
+ * No workspace; out: device memory, 16-byte aligned; caller's stream, no synchronisation.  count == 0 returns TROYN_OK and touches nothing; only
+ * the handle is looked at before.  TROYN_E_INVALID: as above, and n not a power of two, n < 2, n > N/2, layers outside [0, log2 n].
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_ckks_dft_factor_diagonals_sparse_count(const troyn_ckks* h, uint32_t n, uint32_t first, uint32_t count);
+int troyn_ckks_dft_factor_diagonals_sparse(const troyn_ckks* h, uint32_t n, uint32_t first, uint32_t count, int inverse, int col_mask, int row_mask,
+                                           int conjugate, double constant, double* out, troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Real and imaginary parts of CKKS slots (an addition to the reference's API): the two streaming steps between CoeffToSlot, EvalMod and
  * SlotToCoeff of a bootstrap, on the multiplication by i that costs no key switch, no level and no scale.
  *

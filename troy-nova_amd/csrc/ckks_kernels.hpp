@@ -379,4 +379,53 @@ static __global__ __launch_bounds__(256) void ckks_dft_factor_kernel(CkksDftFact
     a.out[(size_t)da * n + row] = make_double2(ar, ai);
 }
 
+// ---- the same factors on the sub-ring of n < N/2 slots (sparse packing; include/troyn.h, "Factors of the special DFT on n slots") ----------
+// A sparsely packed message is a polynomial in Y = X^(N/2n); its special FFT has log2 n layers, and layer b's twiddle
+// (zeta^(N/2n))^(((-3)^j mod 4 len) 4n / 4 len) is the full ring's layer b read from the same root_powers.  The table is therefore the one
+// above on n rows: diagonal indices mod n, the wrap where first + count == log2 n.  Same geometry, same association, same unit
+// (-ffp-contract=off): one thread per (diagonal, row), double2 stores coalesced along the row, no LDS.
+struct CkksDftFactorSparseArgs {
+    const double2* roots;                 // [N] root_powers
+    double2* out;                         // [nd][n]
+    double constant;
+    unsigned log_n;                       // log2 N
+    unsigned log_slots;                   // log2 n, 1 <= log_slots <= log_n - 1
+    unsigned first, count;                // layers [first, first + count), count >= 1, first + count <= log_slots
+    unsigned nd, wrap;                    // diagonals; wrap: first + count == log_slots
+    unsigned inverse, conjugate, col_mask, row_mask;     // masks: 0 none, 1 even, 2 odd
+};
+
+static __global__ __launch_bounds__(256) void ckks_dft_factor_sparse_kernel(CkksDftFactorSparseArgs a) {
+    const unsigned n = 1u << a.log_slots;
+    const unsigned row = blockIdx.x * 256u + threadIdx.x, da = blockIdx.y;
+    if (row >= n || da >= a.nd) return;
+    const unsigned reach = 1u << a.count;
+    const unsigned d = (a.wrap || da < reach) ? da << a.first : n - ((a.nd - da) << a.first);
+    const unsigned col = (row + d) & (n - 1);
+    bool present = ((row ^ col) & ~((reach - 1) << a.first)) == 0;
+    if (a.row_mask) present = present && (row & 1) == (a.row_mask == 2u);
+    if (a.col_mask) present = present && (col & 1) == (a.col_mask == 2u);
+    double ar = 0.0, ai = 0.0;
+    if (present) {
+        ar = a.constant;
+        const unsigned j = a.inverse ? col : row;
+        for (unsigned step = 0; step < a.count; step++) {
+            const unsigned b = a.inverse ? a.first + a.count - 1 - step : a.first + step;
+            const unsigned rb = (row >> b) & 1, cb = (col >> b) & 1;
+            if (a.inverse ? rb : cb) {
+                // ((-3)^j mod 4 len) (2N / 4 len) in [0, 2N): b <= log_slots - 1 <= log_n - 2
+                const unsigned k = (ckks_rotation_power(j, b) & ((8u << b) - 1)) << (a.log_n - b - 2);
+                const double2 r = a.roots[__brev(k & ((1u << a.log_n) - 1)) >> (32 - a.log_n)];
+                double tr = r.x, ti = a.inverse ? -r.y : r.y;
+                if ((k >> a.log_n) ^ (a.inverse ? cb : rb)) { tr = -tr; ti = -ti; }
+                const double nr = ar * tr - ai * ti, ni = ar * ti + ai * tr;
+                ar = nr; ai = ni;
+            }
+            if (a.inverse) { ar = ar * 0.5; ai = ai * 0.5; }
+        }
+        if (a.conjugate) ai = -ai;
+    }
+    a.out[(size_t)da * n + row] = make_double2(ar, ai);
+}
+
 }  // namespace troyn

@@ -65,4 +65,10 @@ void launch_ckks_dft_factor(const CkksDftFactorArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(ckks_dft_factor_kernel, dim3((n + 255) / 256, a.nd), dim3(256), 0, s, a);
 }
 
+// the sub-ring table: 256 rows of the n per workgroup along x, the diagonal along y
+void launch_ckks_dft_factor_sparse(const CkksDftFactorSparseArgs& a, hipStream_t s) {
+    const unsigned n = 1u << a.log_slots;
+    hipLaunchKernelGGL(ckks_dft_factor_sparse_kernel, dim3((n + 255) / 256, a.nd), dim3(256), 0, s, a);
+}
+
 }  // namespace troyn

@@ -975,6 +975,16 @@ class CkksEncoder:
                                                             float(constant), C.c_void_p(out.data_ptr()), _stream()))
         return out
 
+    def dft_factor_diagonals_sparse(self, n, first, count, inverse=False, col_mask=0, row_mask=0, conjugate=False, constant=1.0):
+        """troyn_ckks_dft_factor_diagonals_sparse: the same product on the sub-ring of n <= N/2 slots (sparse packing), log2 n layers in all
+        -> float64 [nd][n][2], the source of encode_diagonals with that n"""
+        n = int(n)
+        nd = int(self.lib.troyn_ckks_dft_factor_diagonals_sparse_count(self.h, n, first, count))
+        out = torch.empty((nd, n if nd else 0, 2), dtype=torch.float64, device=self.plan.device)
+        capi.check(self.lib.troyn_ckks_dft_factor_diagonals_sparse(self.h, n, first, count, 1 if inverse else 0, int(col_mask), int(row_mask), 1 if conjugate else 0,
+                                                                   float(constant), C.c_void_p(out.data_ptr()), _stream()))
+        return out
+
     def encode_polynomial(self, L, coeffs, scale, flags=False):
         """coeffs [batch][count] -> [batch][L][N]"""
         batch, count = coeffs.shape[0], coeffs.shape[1]

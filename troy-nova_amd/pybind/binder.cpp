@@ -608,9 +608,12 @@ PYBIND11_MODULE(pytroy_raw, m) {
         return s.join_real_imag_new(re, im, P(p)); }, py::arg("real"), py::arg("imag_alt"), POOL);
     py::class_<BootstrapPlan>(m, "BootstrapPlan")
         .def(py::init([](HeContextPointer c, const CKKSEncoder& e, double scale, double hw, size_t degree, size_t r, const std::vector<size_t>& down, const std::vector<size_t>& up,
-                         double weight_scale, PoolArg p) { return std::make_unique<BootstrapPlan>(c, e, scale, hw, degree, r, down, up, weight_scale, P(p)); }),
+                         double weight_scale, PoolArg p, size_t n, size_t radix) { return std::make_unique<BootstrapPlan>(c, e, scale, hw, degree, r, down, up, weight_scale, P(p), n, radix); }),
              py::arg("context"), py::arg("encoder"), py::arg("message_scale"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"),
-             py::arg("coeff_to_slot_layers") = std::vector<size_t>{}, py::arg("slot_to_coeff_layers") = std::vector<size_t>{}, py::arg("weight_scale") = 1099511627776.0, POOL)
+             py::arg("coeff_to_slot_layers") = std::vector<size_t>{}, py::arg("slot_to_coeff_layers") = std::vector<size_t>{}, py::arg("weight_scale") = 1099511627776.0, POOL,
+             py::arg("n") = 0, py::arg("sub_sum_radix") = 0)
+        .def("n", &BootstrapPlan::n).def("slot_count", &BootstrapPlan::slot_count).def("sub_sum_radix", &BootstrapPlan::sub_sum_radix)
+        .def("sub_sum_key_switches", &BootstrapPlan::sub_sum_key_switches).def("sub_sum_factor", &BootstrapPlan::sub_sum_factor)
         .def("levels", &BootstrapPlan::levels).def("eval_mod_depth", &BootstrapPlan::eval_mod_depth).def("key_switches", &BootstrapPlan::key_switches)
         .def("message_scale", &BootstrapPlan::message_scale).def("half_width", &BootstrapPlan::half_width).def("degree", &BootstrapPlan::degree)
         .def("double_angles", &BootstrapPlan::double_angles).def("output_scale", &BootstrapPlan::output_scale).def("q0", &BootstrapPlan::q0)
@@ -621,6 +624,13 @@ PYBIND11_MODULE(pytroy_raw, m) {
         .def("slot_to_coeff_plan", [](const BootstrapPlan& s) -> const SlotToCoeffPlan& { return s.slot_to_coeff_plan(); }, py::return_value_policy::reference_internal)
         .def_static("half_width_for", &BootstrapPlan::half_width_for, py::arg("hamming_weight"));
     m.def("chebyshev_depth", &Evaluator::chebyshev_depth, py::arg("degree"));
+    // additions: SubSum, the projection onto the sub-ring of n slots (troy.h), the step after mod_raise of a sparsely packed bootstrap
+    ev.def("sub_sum", [](const Evaluator& s, const Ciphertext& a, size_t n, const GaloisKeys& k, Ciphertext& d, size_t radix, PoolArg p) {
+        s.sub_sum(a, n, k, d, radix, P(p)); }, py::arg("encrypted"), py::arg("n"), py::arg("galois_keys"), py::arg("destination"), py::arg("radix") = 0, POOL);
+    ev.def("sub_sum_new", [](const Evaluator& s, const Ciphertext& a, size_t n, const GaloisKeys& k, size_t radix, PoolArg p) {
+        return s.sub_sum_new(a, n, k, radix, P(p)); }, py::arg("encrypted"), py::arg("n"), py::arg("galois_keys"), py::arg("radix") = 0, POOL);
+    ev.def_static("sub_sum_steps", &Evaluator::sub_sum_steps, py::arg("slot_count"), py::arg("n"), py::arg("radix") = 0);
+    ev.def_static("sub_sum_stages", &Evaluator::sub_sum_stages, py::arg("slot_count"), py::arg("n"), py::arg("radix") = 0);
     ev.def("bootstrap", [](const Evaluator& s, const Ciphertext& a, const BootstrapPlan& plan, const RelinKeys& rk, const GaloisKeys& gk, Ciphertext& d, PoolArg p) {
         s.bootstrap(a, plan, rk, gk, d, P(p)); }, py::arg("encrypted"), py::arg("plan"), py::arg("relin_keys"), py::arg("galois_keys"), py::arg("destination"), POOL);
     ev.def("bootstrap_new", [](const Evaluator& s, const Ciphertext& a, const BootstrapPlan& plan, const RelinKeys& rk, const GaloisKeys& gk, PoolArg p) {
@@ -787,7 +797,7 @@ PYBIND11_MODULE(pytroy_raw, m) {
     // addition: CoeffToSlotPlan / SlotToCoeffPlan (slot_transform.h), the factored special DFT of a bootstrap, and their evaluation
     {
         py::class_<SlotTransformPlan>(m, "SlotTransformPlan")
-            .def("n", &SlotTransformPlan::n).def("scale", &SlotTransformPlan::scale).def("constant", &SlotTransformPlan::constant)
+            .def("n", &SlotTransformPlan::n).def("slot_count", &SlotTransformPlan::slot_count).def("scale", &SlotTransformPlan::scale).def("constant", &SlotTransformPlan::constant)
             .def("groups", &SlotTransformPlan::groups).def("levels", &SlotTransformPlan::levels).def("rotations", &SlotTransformPlan::rotations)
             .def("boundary_group", &SlotTransformPlan::boundary_group).def("first_layer", &SlotTransformPlan::first_layer, py::arg("group"))
             .def("needs_conjugate", &SlotTransformPlan::needs_conjugate)
@@ -798,13 +808,15 @@ PYBIND11_MODULE(pytroy_raw, m) {
             .def("transform", [](const SlotTransformPlan& s, size_t g) -> const LinearTransform& { return s.transform(g); }, py::arg("group"), py::return_value_policy::reference_internal)
             .def("twin", [](const SlotTransformPlan& s) -> const LinearTransform& { return s.twin(); }, py::return_value_policy::reference_internal);
         py::class_<CoeffToSlotPlan, SlotTransformPlan>(m, "CoeffToSlotPlan")
-            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p) {
-                     return std::make_unique<CoeffToSlotPlan>(c, e, id, scale, layers, constant, P(p)); }),
-                 py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL);
+            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p, size_t n) {
+                     return std::make_unique<CoeffToSlotPlan>(c, e, id, scale, layers, constant, P(p), n); }),
+                 py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL,
+                 py::arg("n") = 0);
         py::class_<SlotToCoeffPlan, SlotTransformPlan>(m, "SlotToCoeffPlan")
-            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p) {
-                     return std::make_unique<SlotToCoeffPlan>(c, e, id, scale, layers, constant, P(p)); }),
-                 py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL);
+            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p, size_t n) {
+                     return std::make_unique<SlotToCoeffPlan>(c, e, id, scale, layers, constant, P(p), n); }),
+                 py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL,
+                 py::arg("n") = 0);
         m.def("default_layers_per_group", &default_layers_per_group, py::arg("layers"), py::arg("at_most") = 4);
     }
     ev.def("coeff_to_slot", [](const Evaluator& s, const Ciphertext& a, const CoeffToSlotPlan& plan, const GaloisKeys& k, Ciphertext& d, PoolArg p) {

@@ -2,6 +2,7 @@
 // (Evaluator::mod_raise, coeff_to_slot, eval_mod_batched, slot_to_coeff) and the two streaming kernels behind split_real_imag / join_real_imag.
 #include "bootstrap.h"
 
+#include <algorithm>
 #include <cmath>
 #include <set>
 
@@ -14,7 +15,8 @@ size_t log2_of(size_t n) { size_t m = 0; while ((size_t(1) << m) < n) m++; retur
 }  // namespace
 
 BootstrapPlan::BootstrapPlan(HeContextPointer context, const CKKSEncoder& encoder, double message_scale, double half_width, size_t degree, size_t double_angles,
-                             std::vector<size_t> coeff_to_slot_layers, std::vector<size_t> slot_to_coeff_layers, double weight_scale, MemoryPoolHandle pool)
+                             std::vector<size_t> coeff_to_slot_layers, std::vector<size_t> slot_to_coeff_layers, double weight_scale, MemoryPoolHandle pool, size_t n,
+                             size_t sub_sum_radix)
     : message_scale_(message_scale), half_width_(half_width), degree_(degree), double_angles_(double_angles) {
     const std::string P = "[BootstrapPlan::BootstrapPlan]";
     if (!context || !context->first_context_data().has_value()) throw std::invalid_argument(P + " the context has no parameters.");
@@ -30,7 +32,12 @@ BootstrapPlan::BootstrapPlan(HeContextPointer context, const CKKSEncoder& encode
     auto prime = [&](size_t i) { return static_cast<double>(primes[i].value()); };
     q0_ = prime(0);
     if (q0_ / message_scale < 2.0) throw std::invalid_argument(P + " q0 / message_scale must be at least 2.");
-    const size_t m = log2_of(encoder.slot_count());
+    const size_t slot_count = encoder.slot_count(), slots = n == 0 ? slot_count : n;
+    if (slots < 2 || (slots & (slots - 1)) || slots > slot_count) throw std::invalid_argument(P + " n must be a power of two in [2, slot_count] (0: the slot count).");
+    if (sub_sum_radix != 0 && (sub_sum_radix < 2 || (sub_sum_radix & (sub_sum_radix - 1)))) throw std::invalid_argument(P + " sub_sum_radix must be 0 or a power of two >= 2.");
+    sub_sum_radix_ = sub_sum_radix == 0 ? 4 : sub_sum_radix;
+    const double sub_sum_factor = static_cast<double>(slot_count / slots);      // s, a power of two: dividing by it is exact
+    const size_t m = log2_of(slots);
     const size_t gc = coeff_to_slot_layers.empty() ? default_layers_per_group(m).size() : coeff_to_slot_layers.size();
     const size_t gs = slot_to_coeff_layers.empty() ? default_layers_per_group(m).size() : slot_to_coeff_layers.size();
     eval_mod_depth_ = Evaluator::chebyshev_depth(degree) + double_angles;
@@ -41,7 +48,7 @@ BootstrapPlan::BootstrapPlan(HeContextPointer context, const CKKSEncoder& encode
     const size_t L1 = Ld - gc, L2 = L1 - eval_mod_depth_, L3 = L2 - gs;
     double s1 = q0_;
     for (size_t g = 0; g < gc; g++) s1 = s1 * weight_scale / prime(Ld - 1 - g);
-    const double c1 = prime(L1 - 1) / (2.0 * half_width * s1);
+    const double c1 = prime(L1 - 1) / (2.0 * half_width * s1);              // the slots read s x after sub_sum: the plan's constant is c1 / s
     double s = (s1 * (2.0 * c1)) * half_width;                      // EvalMod's working scale, q_w up to rounding
     const size_t cheb = eval_mod_depth_ - double_angles;
     for (size_t i = 0; i < double_angles; i++) s = s * s / prime(L1 - cheb - 1 - i);
@@ -50,14 +57,63 @@ BootstrapPlan::BootstrapPlan(HeContextPointer context, const CKKSEncoder& encode
     const double c2 = q0_ / s;
     ContextDataPointer cd = first;
     for (size_t i = 0; i < L1 - L2 + gc; i++) cd = cd->next_context_data().value();
-    coeff_to_slot_.reset(new CoeffToSlotPlan(context, encoder, first->parms_id(), weight_scale, std::move(coeff_to_slot_layers), c1, pool));
-    slot_to_coeff_.reset(new SlotToCoeffPlan(context, encoder, cd->parms_id(), weight_scale, std::move(slot_to_coeff_layers), c2, pool));
+    coeff_to_slot_.reset(new CoeffToSlotPlan(context, encoder, first->parms_id(), weight_scale, std::move(coeff_to_slot_layers), c1 / sub_sum_factor, pool, slots));
+    slot_to_coeff_.reset(new SlotToCoeffPlan(context, encoder, cd->parms_id(), weight_scale, std::move(slot_to_coeff_layers), c2, pool, slots));
     for (size_t i = 0; i < L2 - L3; i++) cd = cd->next_context_data().value();
     output_parms_id_ = cd->parms_id();
     std::set<int> steps{0};
     steps.insert(coeff_to_slot_->rotation_steps().begin(), coeff_to_slot_->rotation_steps().end());
     steps.insert(slot_to_coeff_->rotation_steps().begin(), slot_to_coeff_->rotation_steps().end());
+    for (const std::vector<int>& stage : Evaluator::sub_sum_stages(slot_count, slots, sub_sum_radix_)) {
+        steps.insert(stage.begin(), stage.end());
+        sub_sum_key_switches_ += stage.size();
+    }
     rotation_steps_.assign(steps.begin(), steps.end());
+}
+
+std::vector<std::vector<int>> Evaluator::sub_sum_stages(size_t slot_count, size_t n, size_t radix) {
+    const std::string P = "[Evaluator::sub_sum]";
+    if (slot_count < 2 || (slot_count & (slot_count - 1))) throw std::invalid_argument(P + " the slot count must be a power of two >= 2.");
+    if (n < 2 || (n & (n - 1)) || n > slot_count) throw std::invalid_argument(P + " n must be a power of two in [2, slot_count].");
+    if (radix != 0 && (radix < 2 || (radix & (radix - 1)))) throw std::invalid_argument(P + " the radix must be 0 or a power of two >= 2.");
+    if (radix == 0) radix = 4;
+    std::vector<std::vector<int>> stages;
+    // PROD_i (1 + rot_{n 2^i}): a stage of R terms from `step` is SUM_{i < R} rot_{i step}; the last one takes what remains
+    for (size_t step = n; step < slot_count;) {
+        const size_t terms = std::min(radix, slot_count / step);
+        std::vector<int> stage;
+        for (size_t i = 1; i < terms; i++) stage.push_back(static_cast<int>(i * step));
+        stages.push_back(std::move(stage));
+        step *= terms;
+    }
+    return stages;
+}
+
+std::vector<int> Evaluator::sub_sum_steps(size_t slot_count, size_t n, size_t radix) {
+    std::set<int> steps;
+    for (const std::vector<int>& stage : sub_sum_stages(slot_count, n, radix)) steps.insert(stage.begin(), stage.end());
+    return std::vector<int>(steps.begin(), steps.end());
+}
+
+void Evaluator::sub_sum(const Ciphertext& encrypted, size_t n, const GaloisKeys& galois_keys, Ciphertext& destination, size_t radix, MemoryPoolHandle pool) const {
+    const std::string P = "[Evaluator::sub_sum]";
+    auto cd = context_->get_context_data(encrypted.parms_id());
+    if (!cd.has_value()) throw std::invalid_argument(P + " parms_id not valid for context.");
+    if (cd.value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(P + " a CKKS context is needed.");
+    const std::vector<std::vector<int>> stages = sub_sum_stages(cd.value()->parms().poly_modulus_degree() / 2, n, radix);
+    if (stages.empty()) {                                             // n = slot_count: the identity, no key touched
+        if (&destination != &encrypted) destination = encrypted.clone(pool);
+        return;
+    }
+    Ciphertext current;
+    const Ciphertext* operand = &encrypted;
+    for (const std::vector<int>& stage : stages) {
+        Ciphertext next = rotate_sum_new(*operand, stage, galois_keys, pool);     // hoisted: one decomposition, one division
+        add_inplace(next, *operand, pool);
+        current = std::move(next);
+        operand = &current;
+    }
+    destination = std::move(current);
 }
 
 void Evaluator::split_real_imag(const Ciphertext& encrypted, const GaloisKeys& galois_keys, Ciphertext& real2, Ciphertext& imag2_alt, MemoryPoolHandle pool) const {
@@ -108,7 +164,7 @@ void Evaluator::bootstrap(const Ciphertext& encrypted, const BootstrapPlan& plan
     Ciphertext low;
     const Ciphertext* exhausted = &encrypted;
     if (encrypted.parms_id() != context_->last_parms_id()) { mod_switch_to(encrypted, context_->last_parms_id(), low, pool); exhausted = &low; }
-    // 2. to the top: t = D m + q0 I
+    // 2. to the top: t = D m + q0 I;  2b (in bootstrap_raised). a sparse plan keeps the Y-part of t, s times
     bootstrap_raised(mod_raise_new(*exhausted, std::nullopt, pool), plan, relin_keys, galois_keys, destination, pool);
 }
 
@@ -133,13 +189,15 @@ void Evaluator::bootstrap(const Ciphertext& encrypted, const BootstrapPlan& plan
 void Evaluator::bootstrap_raised(Ciphertext&& raised, const BootstrapPlan& plan, const RelinKeys& relin_keys, const GaloisKeys& galois_keys, Ciphertext& destination,
                                  MemoryPoolHandle pool) const {
     const std::string P = "[Evaluator::bootstrap]";
-    // 3. the coefficients read t / q0 = D m / q0 + I
+    // 2b. sparse packing: s (D p(Y) + q0 I'(Y)), a polynomial in Y = X^s whose slots repeat with period n
+    if (plan.n() != plan.slot_count()) sub_sum(raised, plan.n(), galois_keys, raised, plan.sub_sum_radix(), pool);
+    // 3. the coefficients read t / q0 = D m / q0 + I (s times that for a sparse plan)
     raised.scale() = plan.q0();
     // 4, 5. slots c1 BR(x_k + i x_{k+n}); their parts 2 c1 Re, (-1)^j 2 c1 Im relabelled to read Re, (-1)^j Im
     const Ciphertext slots = coeff_to_slot_new(raised, plan.coeff_to_slot_plan(), galois_keys, pool);
     Ciphertext re, im;
     split_real_imag(slots, galois_keys, re, im, pool);
-    const double part_scale = slots.scale() * (2.0 * plan.coeff_to_slot_constant());
+    const double part_scale = slots.scale() * (2.0 * plan.coeff_to_slot_constant() * plan.sub_sum_factor());      // s = 1 for a full plan: exact
     re.scale() = part_scale; im.scale() = part_scale;
     // 6, 7. sin(2 pi x) / (2 pi) on both halves in one schedule, then Re' + i Im'
     std::vector<Ciphertext> reduced;

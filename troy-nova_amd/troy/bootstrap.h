@@ -1,7 +1,7 @@
-// bootstrap.h -- troy::BootstrapPlan, an ADDITION to the reference's interface: the CKKS bootstrap of a fully packed ciphertext,
-//     ModRaise -> CoeffToSlot -> (real / imaginary parts) -> EvalMod on both halves at once -> (join) -> SlotToCoeff,
+// bootstrap.h -- troy::BootstrapPlan, an ADDITION to the reference's interface: the CKKS bootstrap of a fully or sparsely packed ciphertext,
+//     ModRaise -> (SubSum) -> CoeffToSlot -> (real / imaginary parts) -> EvalMod on both halves at once -> (join) -> SlotToCoeff,
 // as one call, Evaluator::bootstrap.  The plan owns the two slot plans (slot_transform.h), chooses every level, scale and normalisation constant and says
-// which Galois keys are needed.  Sparse packing (fewer than N/2 slots) is out of scope.  With sparse secrets K shrinks: KeyGenerator::create_sparse draws a
+// which Galois keys are needed.  Sparse packing (n < N/2 slots) is the section of that name below.  With sparse secrets K shrinks: KeyGenerator::create_sparse draws a
 // secret of a fixed Hamming weight, and the sparse-secret encapsulation below keeps a dense evaluation secret while I comes from a sparse one.
 //
 // Notation.  N the ring degree, n = N/2, q0 the first prime (the only one of the last level), D = message_scale (Delta), K = half_width, r = double_angles.
@@ -35,6 +35,16 @@
 // split_real_imag; EvalMod's relinearizations (one per product step) are not Galois key switches and are not counted.  rotation_steps() is the union of
 // both slot plans' steps and step 0, which create_galois_keys_from_steps reads as the conjugation.
 //
+// Sparse packing.  A trailing n (0: N/2), a power of two with 2 <= n <= N/2, is the number of message slots: the message is z tiled s = N/(2n) times, that
+// is, a polynomial p(Y) in Y = X^s.  Both slot plans are built on n slots (slot_transform.h): log2 n layers each instead of log2(N/2).
+//   2b. Evaluator::sub_sum.  After mod_raise t = D p(Y) + q0 I(X), and I is NOT a polynomial in Y.  The rotations by n i, i < s, are the automorphisms X -> X^g
+//       with g = 1 (mod 4n); they fix every X^(s k) and sum to 0 over the other monomials, so SUM_i rot_{n i} decrypts to s (D p(Y) + q0 I'(Y)), I' the
+//       Y-coefficients of I.  ||I'||_inf <= ||I||_inf: the K condition is unchanged.  The sum runs as PROD_i (1 + rot_{n 2^i}) in stages of sub_sum_radix terms.
+//   4.  1 / s goes into the CoeffToSlot constant, c1 = q_w / (2 K s1 s) (a power of two: exact), and costs no level; step 5 relabels to 2 c1 s1 s.
+//   Everything after CoeffToSlot is as above on slots of period n.  With the encapsulation sub_sum runs after the to_dense switch (2a).
+// levels() has the shorter plans' groups and nothing for SubSum; key_switches() adds SubSum's radix - 1 per stage; rotation_steps() adds its steps.
+// Not done: packing both halves into one ciphertext of period 2n (n <= N/4) would halve EvalMod; it needs a different last CoeffToSlot factor.
+//
 // Sparse-secret encapsulation (Bossuat, Troncoso-Pastoriza, Hubaux 2022).  The evaluation secret s stays as it is; an ephemeral secret s' of small Hamming
 // weight is used around ModRaise only, where the modulus is q0 P (one data prime and the special prime).  Evaluator::bootstrap with SparseEncapsulationKeys:
 //   1. mod_switch_to the last level;  1a. apply_keyswitching with to_sparse (s -> s');  2. mod_raise: t = D m + q0 I with I from s';
@@ -60,10 +70,11 @@ class BootstrapPlan {
 public:
     // empty layers_per_group: the slot plans' default grouping.  std::invalid_argument "[BootstrapPlan::BootstrapPlan] ..." for a non-CKKS context, a chain
     // with fewer than levels() + 1 data levels, K, degree or double_angles outside eval_mod's ranges (K positive and finite, degree 1 .. 127, at most 16
-    // double angles), a message or weight scale that is not positive or not finite, q0 / message_scale < 2; the slot plans' own refusals pass through.
+    // double angles), a message or weight scale that is not positive or not finite, q0 / message_scale < 2, an n that is not a power of two in [2, N/2], a sub_sum_radix that is
+    // neither 0 (the default, 4) nor a power of two >= 2; the slot plans' own refusals pass through.
     BootstrapPlan(HeContextPointer context, const CKKSEncoder& encoder, double message_scale, double half_width, size_t degree, size_t double_angles,
                   std::vector<size_t> coeff_to_slot_layers = {}, std::vector<size_t> slot_to_coeff_layers = {}, double weight_scale = 1099511627776.0,
-                  MemoryPoolHandle pool = MemoryPool::GlobalPool());
+                  MemoryPoolHandle pool = MemoryPool::GlobalPool(), size_t n = 0, size_t sub_sum_radix = 0);
     BootstrapPlan(const BootstrapPlan&) = delete;
     BootstrapPlan& operator=(const BootstrapPlan&) = delete;
 
@@ -79,16 +90,21 @@ public:
     const ParmsID& output_parms_id() const { return output_parms_id_; }
     double output_scale() const { return message_scale_; }
     const std::vector<int>& rotation_steps() const { return rotation_steps_; }       // both plans' steps and 0, the conjugation; sorted
-    size_t key_switches() const { return coeff_to_slot_->rotations() + 1 + slot_to_coeff_->rotations(); }
+    size_t key_switches() const { return sub_sum_key_switches_ + coeff_to_slot_->rotations() + 1 + slot_to_coeff_->rotations(); }
+    size_t n() const { return coeff_to_slot_->n(); }                                  // message slots; slot_count() / n() copies fill the ciphertext
+    size_t slot_count() const { return coeff_to_slot_->slot_count(); }
+    size_t sub_sum_radix() const { return sub_sum_radix_; }                           // as resolved: never 0
+    size_t sub_sum_key_switches() const { return sub_sum_key_switches_; }             // 0 when n() == slot_count()
+    double sub_sum_factor() const { return static_cast<double>(slot_count() / n()); } // s, divided out inside c1
     const CoeffToSlotPlan& coeff_to_slot_plan() const { return *coeff_to_slot_; }
     const SlotToCoeffPlan& slot_to_coeff_plan() const { return *slot_to_coeff_; }
     double q0() const { return q0_; }
-    double coeff_to_slot_constant() const { return coeff_to_slot_->constant(); }     // c1
+    double coeff_to_slot_constant() const { return coeff_to_slot_->constant(); }     // c1 (with the 1 / s of a sparse plan)
     double slot_to_coeff_constant() const { return slot_to_coeff_->constant(); }     // c2
 
 private:
     double message_scale_, half_width_, q0_ = 0.0;
-    size_t degree_, double_angles_, eval_mod_depth_ = 0;
+    size_t degree_, double_angles_, eval_mod_depth_ = 0, sub_sum_radix_ = 0, sub_sum_key_switches_ = 0;
     ParmsID output_parms_id_;
     std::unique_ptr<CoeffToSlotPlan> coeff_to_slot_;
     std::unique_ptr<SlotToCoeffPlan> slot_to_coeff_;

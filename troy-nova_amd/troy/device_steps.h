@@ -141,6 +141,9 @@ void ckks_encode_diagonals_step(const StepEnv& env, const troyn_ckks* ckks, uint
 // memory, the `src` of ckks_encode_diagonals_step in diagonals mode; masks: 0 none, 1 even, 2 odd.  No workspace.
 void ckks_dft_factor_diagonals_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t first, uint32_t count, bool inverse, int col_mask, int row_mask, bool conjugate,
                                     double constant, double* out);
+// the same on the sub-ring of n < N/2 slots (troyn_ckks_dft_factor_diagonals_sparse): out [nd][n][2], the `src` of ckks_encode_diagonals_step with that n
+void ckks_dft_factor_diagonals_sparse_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t n, uint32_t first, uint32_t count, bool inverse, int col_mask, int row_mask,
+                                           bool conjugate, double constant, double* out);
 void ckks_decode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const uint64_t* in, double scale, double* out, size_t count);
 
 // LWE (lwe.cpp): coefficient `terms[i]` of srcs[i] as an LWE ciphertext, c0 [count][L] and c1 [count][L][N]; the leaves of the packing tree

@@ -28,13 +28,14 @@ std::vector<size_t> present_diagonals(size_t m, size_t first, size_t count) {
 }  // namespace
 
 SlotTransformPlan::SlotTransformPlan(bool coeff_to_slot, HeContextPointer context, const CKKSEncoder& encoder, const ParmsID& parms_id, double scale,
-                                     std::vector<size_t> layers_per_group, double constant, MemoryPoolHandle pool)
-    : n_(encoder.slot_count()), scale_(scale), constant_(constant) {
+                                     std::vector<size_t> layers_per_group, double constant, MemoryPoolHandle pool, size_t n)
+    : n_(n == 0 ? encoder.slot_count() : n), slot_count_(encoder.slot_count()), scale_(scale), constant_(constant) {
     const std::string P = coeff_to_slot ? "[CoeffToSlotPlan::CoeffToSlotPlan]" : "[SlotToCoeffPlan::SlotToCoeffPlan]";
     if (!context || !context->get_context_data(parms_id).has_value()) throw std::invalid_argument(P + " parms_id not valid for context.");
     ContextDataPointer cd = context->get_context_data(parms_id).value();
     if (cd->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(P + " a CKKS context is needed.");
-    if (n_ < 2 || n_ * 2 != cd->parms().poly_modulus_degree()) throw std::invalid_argument(P + " the encoder does not belong to the context.");
+    if (slot_count_ < 2 || slot_count_ * 2 != cd->parms().poly_modulus_degree()) throw std::invalid_argument(P + " the encoder does not belong to the context.");
+    if (n_ < 2 || (n_ & (n_ - 1)) || n_ > slot_count_) throw std::invalid_argument(P + " n must be a power of two in [2, slot_count] (0: the slot count).");
     if (!std::isfinite(constant) || constant == 0.0) throw std::invalid_argument(P + " the constant must be finite and not zero.");
     size_t m = 0;
     while ((size_t(1) << m) < n_) m++;
@@ -44,7 +45,7 @@ SlotTransformPlan::SlotTransformPlan(bool coeff_to_slot, HeContextPointer contex
         if (c == 0) throw std::invalid_argument(P + " a group must hold at least one layer.");
         sum += c;
     }
-    if (sum != m) throw std::invalid_argument(P + " the groups must sum to log2 n layers, n the slot count (sparse packing is not supported).");
+    if (sum != m) throw std::invalid_argument(P + " the groups must sum to log2 n layers, n the plan's number of slots.");
     const size_t groups = layers_.size();
     for (size_t g = 0; g < groups; g++) {
         parms_ids_.push_back(cd->parms_id());
@@ -60,7 +61,7 @@ SlotTransformPlan::SlotTransformPlan(bool coeff_to_slot, HeContextPointer contex
         const double c = (g == 0 && constant < 0) ? -root : root;
         size_t nd = 0;
         // CoeffToSlot masks the columns of its boundary group, SlotToCoeff the rows
-        utils::DynamicArray table = encoder.dft_factor_diagonals(first, count, coeff_to_slot, coeff_to_slot ? mask : 0, coeff_to_slot ? 0 : mask, conjugate, c, nd, pool);
+        utils::DynamicArray table = encoder.dft_factor_diagonals(n_, first, count, coeff_to_slot, coeff_to_slot ? mask : 0, coeff_to_slot ? 0 : mask, conjugate, c, nd, pool);
         std::unique_ptr<LinearTransform> lt(new LinearTransform(context, encoder, n_, parms_ids_[g], scale_, present_diagonals(m, first, count),
                                                                 LinearTransform::DeviceTable{reinterpret_cast<const double*>(table.raw_pointer())}, size_t(1) << first, pool));
         steps.insert(lt->rotation_steps().begin(), lt->rotation_steps().end());
@@ -85,7 +86,8 @@ void slot_transform(const Evaluator& ev, const HeContext& context, const char* P
     auto cd = context.get_context_data(encrypted.parms_id());
     if (!cd.has_value()) throw std::invalid_argument(std::string(P) + " parms_id not valid for context.");
     if (cd.value()->parms().scheme() != SchemeType::CKKS) throw std::invalid_argument(std::string(P) + " a CKKS context is needed.");
-    if (cd.value()->parms().poly_modulus_degree() != 2 * plan.n()) throw std::invalid_argument(std::string(P) + " Sparse packing is not supported: the plan's n must be the slot count of the operand.");
+    if (cd.value()->parms().poly_modulus_degree() != 2 * plan.slot_count())
+        throw std::invalid_argument(std::string(P) + " Sparse packing is a plan's own n below its slot count: the operand belongs to a ring of another degree than the plan's.");
     if (encrypted.parms_id() != plan.parms_id()) throw std::invalid_argument(std::string(P) + " the operand is not at the level of the plan.");
     Ciphertext current;
     for (size_t g = 0; g < plan.groups(); g++) {

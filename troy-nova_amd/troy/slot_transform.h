@@ -1,6 +1,6 @@
 // slot_transform.h -- troy::CoeffToSlotPlan and troy::SlotToCoeffPlan, ADDITIONS to the reference's interface: the two linear steps of a CKKS bootstrap
 // (ModRaise -> CoeffToSlot -> EvalMod -> SlotToCoeff) on fully packed slots, as a factored special DFT whose factors are written (troyn_ckks_dft_factor_diagonals)
-// and encoded (troyn_ckks_encode_diagonals) on the device.  Sparse packing (n < slot_count) is not supported.
+// and encoded (troyn_ckks_encode_diagonals) on the device.  Sparse packing (n < slot_count slots, below) takes the same plans with log2 n layers.
 //
 // The slot order.  The library keeps the reference's slot order, Galois generator 3, and 3 = -1 (mod 4).  With N the ring degree, n = N/2, m = log2 n,
 // zeta = exp(2 pi i / 2N), t the N real coefficients and w_k = t_k + i t_{k+n}: slot j is z_j = t(zeta^(3^j)) and (zeta^(3^j))^n = i^(3^j) is +i for even j
@@ -30,6 +30,13 @@
 //
 // Slot order of the result: coeff_to_slot leaves constant * BR(w) in the slots, slot i holding w_{bitrev(i)} = t_{bitrev(i)} + i t_{bitrev(i) + n}.  EvalMod is
 // slot-wise and slot_to_coeff consumes this order, so no permutation is ever applied.
+//
+// Sparse packing.  A trailing n (0: the slot count), a power of two with 2 <= n <= slot_count, builds the transform of the sub-ring of degree 2n: with
+// s = N/(2n) the message is a polynomial p(Y), Y = X^s, its slots an n-vector repeated s times, w_k = t'_k + i t'_{k+n} on the Y-coefficients t', and
+// zh = L_{m'-1} ... L_0 BR w with m' = log2 n, layer b the full ring's layer b (troyn_ckks_dft_factor_diagonals_sparse).  layers_per_group sums to log2 n; the
+// group holding layer m' - 1 is the top one; diagonal indices are mod n; the transforms are LinearTransforms on n, whose weights repeat s times across the
+// slots.  n is even, so the even / odd masks and the conjugation carry over.  The operand must repeat with period n and be a polynomial in Y: after a
+// ModRaise that is what Evaluator::sub_sum (troy.h) restores.  Everything above reads with m' for m and t' for t; n = slot_count is the fully packed plan.
 #pragma once
 #include <memory>
 
@@ -42,7 +49,8 @@ public:
     SlotTransformPlan(const SlotTransformPlan&) = delete;
     SlotTransformPlan& operator=(const SlotTransformPlan&) = delete;
 
-    size_t n() const { return n_; }
+    size_t n() const { return n_; }                                      // the slots of the transform; slot_count() / n() copies fill the ciphertext
+    size_t slot_count() const { return slot_count_; }
     const ParmsID& parms_id() const { return parms_ids_.front(); }       // the level of the operand
     double scale() const { return scale_; }
     double constant() const { return constant_; }
@@ -60,12 +68,12 @@ public:
 
 protected:
     // throws std::invalid_argument "[CoeffToSlotPlan::CoeffToSlotPlan] ..." / "[SlotToCoeffPlan::SlotToCoeffPlan] ..." for a non-CKKS context, an unknown
-    // parms_id, groups that are empty or do not sum to log2 n, a chain with fewer levels below the operand than groups, a constant that is zero or not finite
+    // parms_id, an n that is not a power of two in [2, slot_count], groups that are empty or do not sum to log2 n, a chain with fewer levels below the operand than groups, a constant that is zero or not finite
     SlotTransformPlan(bool coeff_to_slot, HeContextPointer context, const CKKSEncoder& encoder, const ParmsID& parms_id, double scale, std::vector<size_t> layers_per_group,
-                      double constant, MemoryPoolHandle pool);
+                      double constant, MemoryPoolHandle pool, size_t n);
 
 private:
-    size_t n_, boundary_ = 0, rotations_ = 0;
+    size_t n_, slot_count_, boundary_ = 0, rotations_ = 0;
     double scale_, constant_;
     std::vector<size_t> layers_, firsts_;
     std::vector<ParmsID> parms_ids_;
@@ -80,15 +88,15 @@ std::vector<size_t> default_layers_per_group(size_t layers, size_t at_most = 4);
 class CoeffToSlotPlan : public SlotTransformPlan {
 public:
     CoeffToSlotPlan(HeContextPointer context, const CKKSEncoder& encoder, const ParmsID& parms_id, double scale, std::vector<size_t> layers_per_group = {},
-                    double constant = 1.0, MemoryPoolHandle pool = MemoryPool::GlobalPool())
-        : SlotTransformPlan(true, context, encoder, parms_id, scale, std::move(layers_per_group), constant, pool) {}
+                    double constant = 1.0, MemoryPoolHandle pool = MemoryPool::GlobalPool(), size_t n = 0)
+        : SlotTransformPlan(true, context, encoder, parms_id, scale, std::move(layers_per_group), constant, pool, n) {}
 };
 
 class SlotToCoeffPlan : public SlotTransformPlan {
 public:
     SlotToCoeffPlan(HeContextPointer context, const CKKSEncoder& encoder, const ParmsID& parms_id, double scale, std::vector<size_t> layers_per_group = {},
-                    double constant = 1.0, MemoryPoolHandle pool = MemoryPool::GlobalPool())
-        : SlotTransformPlan(false, context, encoder, parms_id, scale, std::move(layers_per_group), constant, pool) {}
+                    double constant = 1.0, MemoryPoolHandle pool = MemoryPool::GlobalPool(), size_t n = 0)
+        : SlotTransformPlan(false, context, encoder, parms_id, scale, std::move(layers_per_group), constant, pool, n) {}
 };
 
 }  // namespace troy

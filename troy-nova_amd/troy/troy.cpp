@@ -4780,6 +4780,20 @@ std::vector<Plaintext> CKKSEncoder::encode_diagonals_from(const double* source, 
     return out;
 }
 
+utils::DynamicArray CKKSEncoder::dft_factor_diagonals(size_t n, size_t first, size_t count, bool inverse, int col_mask, int row_mask, bool conjugate, double constant,
+                                                      size_t& nd, MemoryPoolHandle pool) const {
+    if (n == 0 || n == slots_) return dft_factor_diagonals(first, count, inverse, col_mask, row_mask, conjugate, constant, nd, pool);
+    const char* P = "[CKKSEncoder::dft_factor_diagonals]";
+    if (!context_->on_device()) throw std::invalid_argument(std::string(P) + " HeContext is not on device (call to_device_inplace).");
+    if (n < 2 || (n & (n - 1)) || n > slots_) throw std::invalid_argument(std::string(P) + " n must be a power of two in [2, slot_count].");
+    nd = troyn_ckks_dft_factor_diagonals_sparse_count(context_->ckks(), static_cast<uint32_t>(n), static_cast<uint32_t>(first), static_cast<uint32_t>(count));
+    if (count == 0 || nd == 0) throw std::invalid_argument(std::string(P) + " the layers must be a non-empty range inside [0, log2 n].");
+    utils::DynamicArray table(nd * n * 2, true, pool);
+    detail::ckks_dft_factor_diagonals_sparse_step(on_current_stream(pool), context_->ckks(), static_cast<uint32_t>(n), static_cast<uint32_t>(first), static_cast<uint32_t>(count), inverse,
+                                                  col_mask, row_mask, conjugate, constant, reinterpret_cast<double*>(table.raw_pointer()));
+    return table;
+}
+
 utils::DynamicArray CKKSEncoder::dft_factor_diagonals(size_t first, size_t count, bool inverse, int col_mask, int row_mask, bool conjugate, double constant, size_t& nd,
                                                       MemoryPoolHandle pool) const {
     const char* P = "[CKKSEncoder::dft_factor_diagonals]";

@@ -1315,6 +1315,10 @@ public:
     // 1 even, 2 odd columns / rows kept.  nd receives the number of diagonals.  slot_transform.h builds the plans from it.
     utils::DynamicArray dft_factor_diagonals(size_t first, size_t count, bool inverse, int col_mask, int row_mask, bool conjugate, double constant, size_t& nd,
                                              MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    // the same on the sub-ring of n slots, a power of two in [2, slot_count] (troyn_ckks_dft_factor_diagonals_sparse; sparse packing): [nd][n], log2 n layers
+    // in all.  n = 0 or n = slot_count is the call above.
+    utils::DynamicArray dft_factor_diagonals(size_t n, size_t first, size_t count, bool inverse, int col_mask, int row_mask, bool conjugate, double constant, size_t& nd,
+                                             MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     // the plaintexts of one call share their parms_id and scale: one C-ABI call, one download
     std::vector<std::vector<std::complex<double>>> decode_complex64_simd_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     std::vector<std::vector<double>> decode_float64_polynomial_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -1719,7 +1723,7 @@ public:
         Ciphertext d; join_real_imag(real, imag_alt, d, pool); return d;
     }
 
-    // ADDITION to the reference's interface: the CKKS bootstrap of a fully packed ciphertext as one call (bootstrap.h states the plan, its level count and
+    // ADDITION to the reference's interface: the CKKS bootstrap of a fully or sparsely packed ciphertext as one call (bootstrap.h states the plan, its level count and
     //   its conditions): mod_switch_to the last level, mod_raise, a scale relabel, coeff_to_slot, split_real_imag, eval_mod_batched on the pair,
     //   join_real_imag, slot_to_coeff.  The result is at plan.output_parms_id() with the scale plan.output_scale() = the plan's message scale, set exactly.
     //   Keys: plan.rotation_steps() (step 0 is the conjugation key) and relinearization keys.  std::invalid_argument "[Evaluator::bootstrap] ..." for a
@@ -1741,6 +1745,23 @@ public:
                              const SparseEncapsulationKeys& encapsulation_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
         Ciphertext d; bootstrap(encrypted, plan, relin_keys, galois_keys, encapsulation_keys, d, pool); return d;
     }
+    //   Sparse packing: a plan with n below the slot count (bootstrap.h) runs sub_sum right after mod_raise (after the to_dense switch with the encapsulation)
+    //   and uses the n-slot transforms.
+    // ADDITION to the reference's interface: SubSum, the projection of a CKKS ciphertext onto the sub-ring of n slots.  With s = slot_count / n and Y = X^s,
+    //   SUM_{i < s} rotate(encrypted, n i) decrypts to s times the part of the plaintext polynomial that is a polynomial in Y (the rotations by multiples of n
+    //   are the automorphisms that fix every X^(s k) and sum to 0 over every other monomial).  The sum is evaluated as the product PROD_i (1 + rot_{n 2^i}) in
+    //   stages of `radix` = 2^r terms (0: 4): a stage is one rotate_sum over its radix - 1 non-zero steps (one decomposition, one division) plus one add of its
+    //   operand; the last stage takes the doublings that remain.  radix >= s is a single stage.  n = slot_count is the identity and touches no key.  Level and
+    //   scale are the operand's; the factor s is the caller's (BootstrapPlan folds 1 / s into its CoeffToSlot constant).  Keys: sub_sum_steps(slot_count, n,
+    //   radix).  std::invalid_argument "[Evaluator::sub_sum] ..." for a non-CKKS context, an n that is not a power of two in [2, slot_count], a radix that is
+    //   neither 0 nor a power of two >= 2; rotate_sum's refusals pass through.
+    void sub_sum(const Ciphertext& encrypted, size_t n, const GaloisKeys& galois_keys, Ciphertext& destination, size_t radix = 0,
+                 MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    Ciphertext sub_sum_new(const Ciphertext& encrypted, size_t n, const GaloisKeys& galois_keys, size_t radix = 0, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
+        Ciphertext d; sub_sum(encrypted, n, galois_keys, d, radix, pool); return d;
+    }
+    static std::vector<int> sub_sum_steps(size_t slot_count, size_t n, size_t radix = 0);                   // sorted, without repeats
+    static std::vector<std::vector<int>> sub_sum_stages(size_t slot_count, size_t n, size_t radix = 0);    // the non-zero steps of every stage, in order
 
     // ADDITION to the reference's interface: the BFV inner product.  destination = the BEHZ multiply (evaluator.cu:29-116) with the tensor
     //   products of all pairs summed BEFORE its scale-down: one floor (and, in the relinearizing form, one key switch,
@@ -1930,14 +1951,15 @@ public:
         Ciphertext d; linear_transform_single_hoisted(encrypted, lt, galois_keys, d, pool); return d;
     }
 
-    // ADDITION to the reference's interface: CoeffToSlot / SlotToCoeff of a bootstrap on fully packed CKKS slots (slot_transform.h: the factored special DFT
+    // ADDITION to the reference's interface: CoeffToSlot / SlotToCoeff of a bootstrap on fully or sparsely packed CKKS slots (slot_transform.h: the factored special DFT
     //   for the generator-3 slot order, its factors written and encoded on the device).  Group by group in the plan's order: linear_transform
     //   (double-hoisted), then rescale_to_next; the boundary group -- the first of CoeffToSlot, the last of SlotToCoeff -- is the sum of one transform of the
     //   operand and the complex_conjugate of a second one, at the same level.  One level per group.  coeff_to_slot leaves constant * BR(t_k + i t_{k+n}) in the slots
     //   (t the coefficients of the plaintext over its scale, BR the bit reversal on log2 n bits), the order slot_to_coeff consumes; slot_to_coeff returns the
     //   ciphertext whose slots are constant * decode of those coefficients.  Keys: plan.rotation_steps() and the conjugation key (step 0 of create_galois_keys_from_steps).
     //   std::invalid_argument "[Evaluator::coeff_to_slot] ..." / "[Evaluator::slot_to_coeff] ..." for a non-CKKS context, an operand at another level than the
-    //   plan's, or a plan whose n is not the operand's slot count ("Sparse packing is not supported").
+    //   plan's, or a plan of a ring of another degree than the operand's.  A plan with n below the slot count (sparse packing) expects an operand that repeats
+    //   with period n and is a polynomial in X^(slot_count / n): Evaluator::sub_sum.
     void coeff_to_slot(const Ciphertext& encrypted, const CoeffToSlotPlan& plan, const GaloisKeys& galois_keys, Ciphertext& destination,
                        MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     Ciphertext coeff_to_slot_new(const Ciphertext& encrypted, const CoeffToSlotPlan& plan, const GaloisKeys& galois_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
