@@ -830,6 +830,34 @@ int troyn_ckks_dft_factor_diagonals_sparse(const troyn_ckks* h, uint32_t n, uint
                                            int conjugate, double constant, double* out, troyn_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Factors of the special DFT on n slots, both halves on period 2n (an addition to the reference's API): the table with which a sparsely packed
+ * bootstrap keeps the real and the imaginary parts of its slots side by side in ONE ciphertext, n a power of two with 2 <= n <= N/4.
+ *
+ * Layers [first, first + count) with first + count <= log2 n are block diagonal with blocks of at most n rows.  Taken on 2n rows they are two
+ * identical n x n blocks, no entry crosses row n, and the group is never the top one: nd = 2^(count+1) - 1 diagonals, indices mod 2n
+ * (diag_a[j] = M[j][(j + a) mod 2n]).  out is double [nd][2n][2]:
+ *   rows i <  n   the words of troyn_ckks_dft_factor_diagonals_sparse called with 2n (no masks, no conjugate);
+ *   rows i >= n   the same words turned by a quarter: by -i in the inverse direction, (re, im) -> (im, -re), and by +i in the forward one,
+ *                 (re, im) -> (-im, re).  The turn is a swap and one IEEE negation, so a present entry with a zero component yields -0.0;
+ *                 absent entries stay +0 in both words.
+ * Inverse (the last-applied group of CoeffToSlot, layers [0, c)): for u of period n, v = M u has G u in rows < n and -i G u below, and
+ * v + conj(v) holds 2 Re(G u) in slots [0, n) and 2 Im(G u) in [n, 2n).  Forward (the first-applied group of SlotToCoeff): for a real
+ * operand [a; b] of period 2n, V = M [a; b] = [F a; i F b] and V + rot_n(V) = F (a + i b), of period n.
+ * troyn_ckks_encode_diagonals reads the table unchanged with n = 2n.  troyn_ckks_dft_factor_diagonals_packed_count gives nd (0 for a null
+ * handle, an n that is refused, count == 0 or layers outside [0, log2 n]).
+ *
+ * CONTRACT: the words of `out` equal those of tests/packed_bootstrap_spec.py (table) on the handle's own full-ring tables: ONE product per
+ * entry, the association and roundings of tests/sparse_bootstrap_spec.py, no FMA; rows < n equal troyn_ckks_dft_factor_diagonals_sparse at 2n.
+ *
+ * No workspace; out: device memory, 16-byte aligned; caller's stream, no synchronisation.  count == 0 returns TROYN_OK and touches nothing; only
+ * the handle is looked at before.  TROYN_E_INVALID: null handle or pointer, misaligned pointer, n not a power of two, n < 2, n > N/4, layers
+ * outside [0, log2 n], a constant that is not finite.
+ * ------------------------------------------------------------------------------------- */
+size_t troyn_ckks_dft_factor_diagonals_packed_count(const troyn_ckks* h, uint32_t n, uint32_t first, uint32_t count);
+int troyn_ckks_dft_factor_diagonals_packed(const troyn_ckks* h, uint32_t n, uint32_t first, uint32_t count, int inverse, double constant, double* out,
+                                           troyn_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Real and imaginary parts of CKKS slots (an addition to the reference's API): the two streaming steps between CoeffToSlot, EvalMod and
  * SlotToCoeff of a bootstrap, on the multiplication by i that costs no key switch, no level and no scale.
  *

@@ -133,6 +133,8 @@ SYMBOLS = {
     "troyn_ckks_dft_factor_diagonals": (C.c_int, [vp, u32, u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]),
     "troyn_ckks_dft_factor_diagonals_sparse_count": (sz, [vp, u32, u32, u32]),
     "troyn_ckks_dft_factor_diagonals_sparse": (C.c_int, [vp, u32, u32, u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]),
+    "troyn_ckks_dft_factor_diagonals_packed_count": (sz, [vp, u32, u32, u32]),
+    "troyn_ckks_dft_factor_diagonals_packed": (C.c_int, [vp, u32, u32, u32, C.c_int, C.c_double, vp, vp]),
     "troyn_ckks_decode_polynomial": (C.c_int, [vp, u32, vp, C.c_double, vp, vp, sz, sz, vp]),
     "troyn_ckks_decode_simd": (C.c_int, [vp, u32, vp, C.c_double, vp, vp, sz, sz, vp]),
     "troyn_ckks_mod_raise_workspace_bytes": (sz, [vp, u32, u32, sz, sz, C.c_int]),

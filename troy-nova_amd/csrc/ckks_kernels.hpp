@@ -428,4 +428,55 @@ static __global__ __launch_bounds__(256) void ckks_dft_factor_sparse_kernel(Ckks
     a.out[(size_t)da * n + row] = make_double2(ar, ai);
 }
 
+// ---- real and imaginary parts side by side (include/troyn.h, "Factors of the special DFT on n slots, both halves on period 2n") ------------
+// Layers [first, first + count) with first + count <= log2 n taken on 2n rows are two identical n x n blocks and never the top group:
+// 2^(count+1) - 1 diagonals, indices mod 2n, no entry crossing row n.  Rows < n are that table; rows >= n are the same words turned by a
+// quarter, by -i in the inverse direction, (re, im) -> (im, -re), and by +i in the forward one, (re, im) -> (-im, re): a swap and one
+// negation (-x, so a zero component becomes -0.0).  Absent entries stay +0 and are not turned.  No masks, no conjugate.  Same geometry,
+// association and unit (-ffp-contract=off) as the sparse kernel: one thread per (diagonal, row), double2 stores coalesced along the row.
+struct CkksDftFactorPackedArgs {
+    const double2* roots;                 // [N] root_powers
+    double2* out;                         // [nd][2n]
+    double constant;
+    unsigned log_n;                       // log2 N
+    unsigned log_rows;                    // log2 2n, 2 <= log_rows <= log_n - 1
+    unsigned first, count;                // layers [first, first + count), count >= 1, first + count <= log_rows - 1
+    unsigned nd;                          // 2^(count+1) - 1
+    unsigned inverse;
+};
+
+static __global__ __launch_bounds__(256) void ckks_dft_factor_packed_kernel(CkksDftFactorPackedArgs a) {
+    const unsigned rows = 1u << a.log_rows;
+    const unsigned row = blockIdx.x * 256u + threadIdx.x, da = blockIdx.y;
+    if (row >= rows || da >= a.nd) return;
+    const unsigned reach = 1u << a.count;
+    const unsigned d = da < reach ? da << a.first : rows - ((a.nd - da) << a.first);
+    const unsigned col = (row + d) & (rows - 1);
+    const bool present = ((row ^ col) & ~((reach - 1) << a.first)) == 0;
+    double ar = 0.0, ai = 0.0;
+    if (present) {
+        ar = a.constant;
+        const unsigned j = a.inverse ? col : row;
+        for (unsigned step = 0; step < a.count; step++) {
+            const unsigned b = a.inverse ? a.first + a.count - 1 - step : a.first + step;
+            const unsigned rb = (row >> b) & 1, cb = (col >> b) & 1;
+            if (a.inverse ? rb : cb) {
+                // ((-3)^j mod 4 len) (2N / 4 len) in [0, 2N): b <= log_rows - 2 <= log_n - 3
+                const unsigned k = (ckks_rotation_power(j, b) & ((8u << b) - 1)) << (a.log_n - b - 2);
+                const double2 r = a.roots[__brev(k & ((1u << a.log_n) - 1)) >> (32 - a.log_n)];
+                double tr = r.x, ti = a.inverse ? -r.y : r.y;
+                if ((k >> a.log_n) ^ (a.inverse ? cb : rb)) { tr = -tr; ti = -ti; }
+                const double nr = ar * tr - ai * ti, ni = ar * ti + ai * tr;
+                ar = nr; ai = ni;
+            }
+            if (a.inverse) { ar = ar * 0.5; ai = ai * 0.5; }
+        }
+        if (row >> (a.log_rows - 1)) {                                   // the lower block: times -i (inverse) / +i (forward)
+            const double re = ar;
+            if (a.inverse) { ar = ai; ai = -re; } else { ar = -ai; ai = re; }
+        }
+    }
+    a.out[(size_t)da * rows + row] = make_double2(ar, ai);
+}
+
 }  // namespace troyn

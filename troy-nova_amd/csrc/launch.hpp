@@ -119,6 +119,7 @@ struct CkksFftArgs;
 struct CkksComposeArgs;
 struct CkksDftFactorArgs;
 struct CkksDftFactorSparseArgs;
+struct CkksDftFactorPackedArgs;
 bool ckks_fft_two_pass(unsigned log_n);
 bool launch_ckks_fft(unsigned log_n, bool decode, const CkksFftArgs& a, size_t batch, hipStream_t s);
 bool launch_ckks_fft_diagonals(unsigned log_n, bool matrix, const CkksFftArgs& a, size_t batch, hipStream_t s);
@@ -127,6 +128,7 @@ void launch_ckks_encode_polynomial(const double* coeffs, unsigned count, double 
 bool launch_ckks_compose(const CkksComposeArgs& a, size_t batch, hipStream_t s);
 void launch_ckks_dft_factor(const CkksDftFactorArgs& a, hipStream_t s);
 void launch_ckks_dft_factor_sparse(const CkksDftFactorSparseArgs& a, hipStream_t s);
+void launch_ckks_dft_factor_packed(const CkksDftFactorPackedArgs& a, hipStream_t s);
 // CKKS ModRaise (troyn_raise.hip, raise_kernels.hpp): the centred base extension of items = batch * pcount polynomials in coefficient form, `chunks`
 // workgroups per polynomial (L <= CKKS_MAX_L; false above)
 struct ModRaiseArgs;

@@ -4396,6 +4396,45 @@ extern "C" int troyn_ckks_dft_factor_diagonals_sparse(const troyn_ckks* h, uint3
     return TROYN_OK;
 }
 
+// both halves on period 2n: log2 n for a power of two 2 <= n <= N/4, 0 otherwise
+static uint32_t ckks_packed_log_slots(const troyn_ckks* h, uint32_t n) {
+    if (!h || h->plan->log_n < 3 || n < 2 || (n & (n - 1)) || n > (1u << (h->plan->log_n - 2))) return 0;
+    uint32_t m = 0;
+    while ((1u << m) < n) m++;
+    return m;
+}
+static uint32_t ckks_dft_factor_packed_count(const troyn_ckks* h, uint32_t n, uint32_t first, uint32_t count) {
+    const uint32_t m = ckks_packed_log_slots(h, n);
+    if (m == 0 || count == 0) return 0;
+    if (first > m || count > m - first) return 0;
+    return (2u << count) - 1;
+}
+
+extern "C" size_t troyn_ckks_dft_factor_diagonals_packed_count(const troyn_ckks* h, uint32_t n, uint32_t first, uint32_t count) {
+    return ckks_dft_factor_packed_count(h, n, first, count);
+}
+extern "C" int troyn_ckks_dft_factor_diagonals_packed(const troyn_ckks* h, uint32_t n, uint32_t first, uint32_t count, int inverse, double constant, double* out,
+                                                      troyn_stream_t stream) {
+    const char* P = "[troyn_ckks_dft_factor_diagonals_packed]";
+    if (!h) return fail(TROYN_E_INVALID, std::string(P) + " null handle");
+    if (count == 0) return TROYN_OK;
+    select_device(h);
+    const uint32_t m = ckks_packed_log_slots(h, n);
+    if (m == 0) return fail(TROYN_E_INVALID, std::string(P) + " n must be a power of two in [2, N/4]");
+    if (first > m || count > m - first) return fail(TROYN_E_INVALID, std::string(P) + " layers outside [0, log2 n]");
+    if (!std::isfinite(constant)) return fail(TROYN_E_INVALID, std::string(P) + " the constant is not finite");
+    if (!out) return fail(TROYN_E_INVALID, std::string(P) + " null argument");
+    if ((uintptr_t)out & 15) return fail(TROYN_E_INVALID, std::string(P) + " misaligned pointer");
+    CkksDftFactorPackedArgs a{};
+    a.roots = h->d_roots; a.out = reinterpret_cast<double2*>(out); a.constant = constant;
+    a.log_n = h->plan->log_n; a.log_rows = m + 1; a.first = first; a.count = count;
+    a.nd = ckks_dft_factor_packed_count(h, n, first, count);
+    a.inverse = inverse != 0;
+    launch_ckks_dft_factor_packed(a, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return TROYN_OK;
+}
+
 static int ckks_decode(const troyn_ckks* h, bool simd, uint32_t L, const uint64_t* plain, double scale, double* out, void* ws, size_t ws_bytes, size_t batch,
                        troyn_stream_t stream) {
     const char* P = "[CKKSEncoder::decode_internal]";

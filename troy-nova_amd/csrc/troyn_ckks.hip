@@ -71,4 +71,10 @@ void launch_ckks_dft_factor_sparse(const CkksDftFactorSparseArgs& a, hipStream_t
     hipLaunchKernelGGL(ckks_dft_factor_sparse_kernel, dim3((n + 255) / 256, a.nd), dim3(256), 0, s, a);
 }
 
+// the packed table: 256 rows of the 2n per workgroup along x, the diagonal along y
+void launch_ckks_dft_factor_packed(const CkksDftFactorPackedArgs& a, hipStream_t s) {
+    const unsigned rows = 1u << a.log_rows;
+    hipLaunchKernelGGL(ckks_dft_factor_packed_kernel, dim3((rows + 255) / 256, a.nd), dim3(256), 0, s, a);
+}
+
 }  // namespace troyn

@@ -985,6 +985,15 @@ class CkksEncoder:
                                                                    float(constant), C.c_void_p(out.data_ptr()), _stream()))
         return out
 
+    def dft_factor_diagonals_packed(self, n, first, count, inverse=False, constant=1.0):
+        """troyn_ckks_dft_factor_diagonals_packed: layers [first, first + count) of the n-slot transform on 2n rows (n <= N/4), rows >= n turned by -i
+        (inverse) / +i (forward) -> float64 [nd][2n][2], the source of encode_diagonals with n = 2n"""
+        n = int(n)
+        nd = int(self.lib.troyn_ckks_dft_factor_diagonals_packed_count(self.h, n, first, count))
+        out = torch.empty((nd, 2 * n if nd else 0, 2), dtype=torch.float64, device=self.plan.device)
+        capi.check(self.lib.troyn_ckks_dft_factor_diagonals_packed(self.h, n, first, count, 1 if inverse else 0, float(constant), C.c_void_p(out.data_ptr()), _stream()))
+        return out
+
     def encode_polynomial(self, L, coeffs, scale, flags=False):
         """coeffs [batch][count] -> [batch][L][N]"""
         batch, count = coeffs.shape[0], coeffs.shape[1]

@@ -612,7 +612,13 @@ PYBIND11_MODULE(pytroy_raw, m) {
              py::arg("context"), py::arg("encoder"), py::arg("message_scale"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"),
              py::arg("coeff_to_slot_layers") = std::vector<size_t>{}, py::arg("slot_to_coeff_layers") = std::vector<size_t>{}, py::arg("weight_scale") = 1099511627776.0, POOL,
              py::arg("n") = 0, py::arg("sub_sum_radix") = 0)
-        .def("n", &BootstrapPlan::n).def("slot_count", &BootstrapPlan::slot_count).def("sub_sum_radix", &BootstrapPlan::sub_sum_radix)
+        // the trailing `packed` (bootstrap.h "Packed") as a second overload, chosen by naming it: calls without it keep the signature above
+        .def(py::init([](HeContextPointer c, const CKKSEncoder& e, double scale, double hw, size_t degree, size_t r, const std::vector<size_t>& down, const std::vector<size_t>& up,
+                         double weight_scale, PoolArg p, size_t n, size_t radix, bool packed) { return std::make_unique<BootstrapPlan>(c, e, scale, hw, degree, r, down, up, weight_scale, P(p), n, radix, packed); }),
+             py::arg("context"), py::arg("encoder"), py::arg("message_scale"), py::arg("half_width"), py::arg("degree"), py::arg("double_angles"),
+             py::arg("coeff_to_slot_layers") = std::vector<size_t>{}, py::arg("slot_to_coeff_layers") = std::vector<size_t>{}, py::arg("weight_scale") = 1099511627776.0, POOL,
+             py::arg("n") = size_t(0), py::arg("sub_sum_radix") = size_t(0), py::kw_only(), py::arg("packed"))
+        .def("packed", &BootstrapPlan::packed).def("n", &BootstrapPlan::n).def("slot_count", &BootstrapPlan::slot_count).def("sub_sum_radix", &BootstrapPlan::sub_sum_radix)
         .def("sub_sum_key_switches", &BootstrapPlan::sub_sum_key_switches).def("sub_sum_factor", &BootstrapPlan::sub_sum_factor)
         .def("levels", &BootstrapPlan::levels).def("eval_mod_depth", &BootstrapPlan::eval_mod_depth).def("key_switches", &BootstrapPlan::key_switches)
         .def("message_scale", &BootstrapPlan::message_scale).def("half_width", &BootstrapPlan::half_width).def("degree", &BootstrapPlan::degree)
@@ -799,7 +805,7 @@ PYBIND11_MODULE(pytroy_raw, m) {
         py::class_<SlotTransformPlan>(m, "SlotTransformPlan")
             .def("n", &SlotTransformPlan::n).def("slot_count", &SlotTransformPlan::slot_count).def("scale", &SlotTransformPlan::scale).def("constant", &SlotTransformPlan::constant)
             .def("groups", &SlotTransformPlan::groups).def("levels", &SlotTransformPlan::levels).def("rotations", &SlotTransformPlan::rotations)
-            .def("boundary_group", &SlotTransformPlan::boundary_group).def("first_layer", &SlotTransformPlan::first_layer, py::arg("group"))
+            .def("boundary_group", &SlotTransformPlan::boundary_group).def("packed", &SlotTransformPlan::packed).def("packed_group", &SlotTransformPlan::packed_group).def("first_layer", &SlotTransformPlan::first_layer, py::arg("group"))
             .def("needs_conjugate", &SlotTransformPlan::needs_conjugate)
             .def("parms_id", [](const SlotTransformPlan& s) { return s.parms_id(); })
             .def("group_parms_id", [](const SlotTransformPlan& s, size_t g) { return s.group_parms_id(g); }, py::arg("group"))
@@ -811,12 +817,22 @@ PYBIND11_MODULE(pytroy_raw, m) {
             .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p, size_t n) {
                      return std::make_unique<CoeffToSlotPlan>(c, e, id, scale, layers, constant, P(p), n); }),
                  py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL,
-                 py::arg("n") = 0);
+                 py::arg("n") = 0)
+            // the trailing `packed` (slot_transform.h "Packed") as a second overload, chosen by naming it
+            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p, size_t n, bool packed) {
+                     return std::make_unique<CoeffToSlotPlan>(c, e, id, scale, layers, constant, P(p), n, packed); }),
+                 py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL,
+                 py::arg("n") = size_t(0), py::kw_only(), py::arg("packed"));
         py::class_<SlotToCoeffPlan, SlotTransformPlan>(m, "SlotToCoeffPlan")
             .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p, size_t n) {
                      return std::make_unique<SlotToCoeffPlan>(c, e, id, scale, layers, constant, P(p), n); }),
                  py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL,
-                 py::arg("n") = 0);
+                 py::arg("n") = 0)
+            // the trailing `packed` (slot_transform.h "Packed") as a second overload, chosen by naming it
+            .def(py::init([](HeContextPointer c, const CKKSEncoder& e, const ParmsID& id, double scale, const std::vector<size_t>& layers, double constant, PoolArg p, size_t n, bool packed) {
+                     return std::make_unique<SlotToCoeffPlan>(c, e, id, scale, layers, constant, P(p), n, packed); }),
+                 py::arg("context"), py::arg("encoder"), py::arg("parms_id"), py::arg("scale"), py::arg("layers_per_group") = std::vector<size_t>{}, py::arg("constant") = 1.0, POOL,
+                 py::arg("n") = size_t(0), py::kw_only(), py::arg("packed"));
         m.def("default_layers_per_group", &default_layers_per_group, py::arg("layers"), py::arg("at_most") = 4);
     }
     ev.def("coeff_to_slot", [](const Evaluator& s, const Ciphertext& a, const CoeffToSlotPlan& plan, const GaloisKeys& k, Ciphertext& d, PoolArg p) {

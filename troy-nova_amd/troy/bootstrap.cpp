@@ -16,7 +16,7 @@ size_t log2_of(size_t n) { size_t m = 0; while ((size_t(1) << m) < n) m++; retur
 
 BootstrapPlan::BootstrapPlan(HeContextPointer context, const CKKSEncoder& encoder, double message_scale, double half_width, size_t degree, size_t double_angles,
                              std::vector<size_t> coeff_to_slot_layers, std::vector<size_t> slot_to_coeff_layers, double weight_scale, MemoryPoolHandle pool, size_t n,
-                             size_t sub_sum_radix)
+                             size_t sub_sum_radix, bool packed)
     : message_scale_(message_scale), half_width_(half_width), degree_(degree), double_angles_(double_angles) {
     const std::string P = "[BootstrapPlan::BootstrapPlan]";
     if (!context || !context->first_context_data().has_value()) throw std::invalid_argument(P + " the context has no parameters.");
@@ -37,6 +37,8 @@ BootstrapPlan::BootstrapPlan(HeContextPointer context, const CKKSEncoder& encode
     if (sub_sum_radix != 0 && (sub_sum_radix < 2 || (sub_sum_radix & (sub_sum_radix - 1)))) throw std::invalid_argument(P + " sub_sum_radix must be 0 or a power of two >= 2.");
     sub_sum_radix_ = sub_sum_radix == 0 ? 4 : sub_sum_radix;
     const double sub_sum_factor = static_cast<double>(slot_count / slots);      // s, a power of two: dividing by it is exact
+    // packed: both halves in one ciphertext of period 2n; the slot plans refuse a single group
+    if (packed && (slots < 4 || slots * 2 > slot_count)) throw std::invalid_argument(P + " a packed plan needs a power of two n in [4, slot_count / 2].");
     const size_t m = log2_of(slots);
     const size_t gc = coeff_to_slot_layers.empty() ? default_layers_per_group(m).size() : coeff_to_slot_layers.size();
     const size_t gs = slot_to_coeff_layers.empty() ? default_layers_per_group(m).size() : slot_to_coeff_layers.size();
@@ -57,8 +59,8 @@ BootstrapPlan::BootstrapPlan(HeContextPointer context, const CKKSEncoder& encode
     const double c2 = q0_ / s;
     ContextDataPointer cd = first;
     for (size_t i = 0; i < L1 - L2 + gc; i++) cd = cd->next_context_data().value();
-    coeff_to_slot_.reset(new CoeffToSlotPlan(context, encoder, first->parms_id(), weight_scale, std::move(coeff_to_slot_layers), c1 / sub_sum_factor, pool, slots));
-    slot_to_coeff_.reset(new SlotToCoeffPlan(context, encoder, cd->parms_id(), weight_scale, std::move(slot_to_coeff_layers), c2, pool, slots));
+    coeff_to_slot_.reset(new CoeffToSlotPlan(context, encoder, first->parms_id(), weight_scale, std::move(coeff_to_slot_layers), c1 / sub_sum_factor, pool, slots, packed));
+    slot_to_coeff_.reset(new SlotToCoeffPlan(context, encoder, cd->parms_id(), weight_scale, std::move(slot_to_coeff_layers), c2, pool, slots, packed));
     for (size_t i = 0; i < L2 - L3; i++) cd = cd->next_context_data().value();
     output_parms_id_ = cd->parms_id();
     std::set<int> steps{0};
@@ -194,7 +196,20 @@ void Evaluator::bootstrap_raised(Ciphertext&& raised, const BootstrapPlan& plan,
     // 3. the coefficients read t / q0 = D m / q0 + I (s times that for a sparse plan)
     raised.scale() = plan.q0();
     // 4, 5. slots c1 BR(x_k + i x_{k+n}); their parts 2 c1 Re, (-1)^j 2 c1 Im relabelled to read Re, (-1)^j Im
-    const Ciphertext slots = coeff_to_slot_new(raised, plan.coeff_to_slot_plan(), galois_keys, pool);
+    Ciphertext slots = coeff_to_slot_new(raised, plan.coeff_to_slot_plan(), galois_keys, pool);
+    if (plan.packed()) {
+        // 5'. a packed plan's slots already read [2 c1 Re; 2 c1 Im] on period 2n: the same relabel, no split, no sign
+        slots.scale() = slots.scale() * (2.0 * plan.coeff_to_slot_constant() * plan.sub_sum_factor());
+        // 6'. EvalMod once, on both halves side by side;  8', 9. SlotToCoeff's packed group adds the halves as a + i b
+        std::vector<Ciphertext> reduced;
+        eval_mod_batched({&slots}, relin_keys, plan.half_width(), plan.degree(), plan.double_angles(), reduced, pool, "[Evaluator::bootstrap]");
+        Ciphertext out = slot_to_coeff_new(reduced[0], plan.slot_to_coeff_plan(), galois_keys, pool);
+        if (std::fabs(out.scale() * plan.slot_to_coeff_constant() / plan.q0() - 1.0) > 1e-9)
+            throw std::logic_error(P + " the tracked scale does not match the plan's constants.");
+        out.scale() = plan.output_scale();
+        destination = std::move(out);
+        return;
+    }
     Ciphertext re, im;
     split_real_imag(slots, galois_keys, re, im, pool);
     const double part_scale = slots.scale() * (2.0 * plan.coeff_to_slot_constant() * plan.sub_sum_factor());      // s = 1 for a full plan: exact

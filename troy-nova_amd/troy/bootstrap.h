@@ -1,5 +1,6 @@
 // bootstrap.h -- troy::BootstrapPlan, an ADDITION to the reference's interface: the CKKS bootstrap of a fully or sparsely packed ciphertext,
 //     ModRaise -> (SubSum) -> CoeffToSlot -> (real / imaginary parts) -> EvalMod on both halves at once -> (join) -> SlotToCoeff,
+// (a packed sparse plan: both halves in ONE EvalMod operand, no split and no join)
 // as one call, Evaluator::bootstrap.  The plan owns the two slot plans (slot_transform.h), chooses every level, scale and normalisation constant and says
 // which Galois keys are needed.  Sparse packing (n < N/2 slots) is the section of that name below.  With sparse secrets K shrinks: KeyGenerator::create_sparse draws a
 // secret of a fixed Hamming weight, and the sparse-secret encapsulation below keeps a dense evaluation secret while I comes from a sparse one.
@@ -43,7 +44,18 @@
 //   4.  1 / s goes into the CoeffToSlot constant, c1 = q_w / (2 K s1 s) (a power of two: exact), and costs no level; step 5 relabels to 2 c1 s1 s.
 //   Everything after CoeffToSlot is as above on slots of period n.  With the encapsulation sub_sum runs after the to_dense switch (2a).
 // levels() has the shorter plans' groups and nothing for SubSum; key_switches() adds SubSum's radix - 1 per stage; rotation_steps() adds its steps.
-// Not done: packing both halves into one ciphertext of period 2n (n <= N/4) would halve EvalMod; it needs a different last CoeffToSlot factor.
+//
+// Packed (a trailing `packed`; n a power of two with 4 <= n <= N/4, two groups or more in each slot plan).  EvalMod is slot-wise, and with n <= N/4 the
+// ciphertext has room for the real and the imaginary parts side by side on period 2n: what "would halve EvalMod" with "a different last CoeffToSlot
+// factor".  Both slot plans are built packed (slot_transform.h "Packed"):
+//   4'. coeff_to_slot's last group uses the table [G; -i G] on 2n rows and returns P = v + conj(v) = [2 c1 s1 s Re; 2 c1 s1 s Im]: the one complex_conjugate
+//       that split_real_imag spent, before the group's rescale.  5'. the same relabel, factor 2 and c1 = q_w / (2 K s1 s); the (-1)^j sign of the level-free i
+//       is not used.  6'. ONE eval_mod operand: half the products and relinearizations of steps 6, 7.  There is no join.
+//   8'. slot_to_coeff's first group uses [F; i F] on 2n rows, V = [F a; i F b], and adds rot_n(V): F (a + i b) on period n, one rotation by n before the
+//       group's rescale.  The remaining groups are the n-slot ones.
+// No mask product, no extra level: levels() is the unpacked sparse plan's, key_switches() is its count + 1 (the rotation by n), rotation_steps() has the
+// packed groups' steps mod 2n and n.  Evaluator::bootstrap runs it with and without the encapsulation: ModRaise, (to_dense), SubSum to n, 4' .. 8', scale D.
+// Refused: n outside [4, N/4], a slot plan with a single group.
 //
 // Sparse-secret encapsulation (Bossuat, Troncoso-Pastoriza, Hubaux 2022).  The evaluation secret s stays as it is; an ephemeral secret s' of small Hamming
 // weight is used around ModRaise only, where the modulus is q0 P (one data prime and the special prime).  Evaluator::bootstrap with SparseEncapsulationKeys:
@@ -71,10 +83,10 @@ public:
     // empty layers_per_group: the slot plans' default grouping.  std::invalid_argument "[BootstrapPlan::BootstrapPlan] ..." for a non-CKKS context, a chain
     // with fewer than levels() + 1 data levels, K, degree or double_angles outside eval_mod's ranges (K positive and finite, degree 1 .. 127, at most 16
     // double angles), a message or weight scale that is not positive or not finite, q0 / message_scale < 2, an n that is not a power of two in [2, N/2], a sub_sum_radix that is
-    // neither 0 (the default, 4) nor a power of two >= 2; the slot plans' own refusals pass through.
+    // neither 0 (the default, 4) nor a power of two >= 2, a packed plan with n outside [4, N/4]; the slot plans' own refusals pass through.
     BootstrapPlan(HeContextPointer context, const CKKSEncoder& encoder, double message_scale, double half_width, size_t degree, size_t double_angles,
                   std::vector<size_t> coeff_to_slot_layers = {}, std::vector<size_t> slot_to_coeff_layers = {}, double weight_scale = 1099511627776.0,
-                  MemoryPoolHandle pool = MemoryPool::GlobalPool(), size_t n = 0, size_t sub_sum_radix = 0);
+                  MemoryPoolHandle pool = MemoryPool::GlobalPool(), size_t n = 0, size_t sub_sum_radix = 0, bool packed = false);
     BootstrapPlan(const BootstrapPlan&) = delete;
     BootstrapPlan& operator=(const BootstrapPlan&) = delete;
 
@@ -90,7 +102,9 @@ public:
     const ParmsID& output_parms_id() const { return output_parms_id_; }
     double output_scale() const { return message_scale_; }
     const std::vector<int>& rotation_steps() const { return rotation_steps_; }       // both plans' steps and 0, the conjugation; sorted
-    size_t key_switches() const { return sub_sum_key_switches_ + coeff_to_slot_->rotations() + 1 + slot_to_coeff_->rotations(); }
+    // a packed plan has no split_real_imag: its conjugation and the rotation by n are counted by the slot plans
+    size_t key_switches() const { return sub_sum_key_switches_ + coeff_to_slot_->rotations() + (packed() ? 0 : 1) + slot_to_coeff_->rotations(); }
+    bool packed() const { return coeff_to_slot_->packed(); }                          // real and imaginary parts in one EvalMod operand ("Packed", above)
     size_t n() const { return coeff_to_slot_->n(); }                                  // message slots; slot_count() / n() copies fill the ciphertext
     size_t slot_count() const { return coeff_to_slot_->slot_count(); }
     size_t sub_sum_radix() const { return sub_sum_radix_; }                           // as resolved: never 0

@@ -298,6 +298,10 @@ void ckks_dft_factor_diagonals_sparse_step(const StepEnv& env, const troyn_ckks*
     env.check(troyn_ckks_dft_factor_diagonals_sparse(ckks, n, first, count, inverse ? 1 : 0, col_mask, row_mask, conjugate ? 1 : 0, constant, out, env.stream));
 }
 
+void ckks_dft_factor_diagonals_packed_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t n, uint32_t first, uint32_t count, bool inverse, double constant, double* out) {
+    env.check(troyn_ckks_dft_factor_diagonals_packed(ckks, n, first, count, inverse ? 1 : 0, constant, out, env.stream));
+}
+
 void ckks_decode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const uint64_t* in, double scale, double* out, size_t count) {
     const size_t bytes = troyn_ckks_workspace_bytes(ckks, L, count);
     utils::DynamicArray ws((bytes + 7) / 8 + 2, true, env.pool);     // (two spare words, as before the step)

@@ -144,6 +144,8 @@ void ckks_dft_factor_diagonals_step(const StepEnv& env, const troyn_ckks* ckks, 
 // the same on the sub-ring of n < N/2 slots (troyn_ckks_dft_factor_diagonals_sparse): out [nd][n][2], the `src` of ckks_encode_diagonals_step with that n
 void ckks_dft_factor_diagonals_sparse_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t n, uint32_t first, uint32_t count, bool inverse, int col_mask, int row_mask,
                                            bool conjugate, double constant, double* out);
+// both halves on period 2n (troyn_ckks_dft_factor_diagonals_packed, n <= N/4): out [nd][2n][2], the `src` of ckks_encode_diagonals_step with n = 2n
+void ckks_dft_factor_diagonals_packed_step(const StepEnv& env, const troyn_ckks* ckks, uint32_t n, uint32_t first, uint32_t count, bool inverse, double constant, double* out);
 void ckks_decode_step(const StepEnv& env, const troyn_ckks* ckks, bool simd, uint32_t L, const uint64_t* in, double scale, double* out, size_t count);
 
 // LWE (lwe.cpp): coefficient `terms[i]` of srcs[i] as an LWE ciphertext, c0 [count][L] and c1 [count][L][N]; the leaves of the packing tree

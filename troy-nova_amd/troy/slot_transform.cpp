@@ -28,8 +28,8 @@ std::vector<size_t> present_diagonals(size_t m, size_t first, size_t count) {
 }  // namespace
 
 SlotTransformPlan::SlotTransformPlan(bool coeff_to_slot, HeContextPointer context, const CKKSEncoder& encoder, const ParmsID& parms_id, double scale,
-                                     std::vector<size_t> layers_per_group, double constant, MemoryPoolHandle pool, size_t n)
-    : n_(n == 0 ? encoder.slot_count() : n), slot_count_(encoder.slot_count()), scale_(scale), constant_(constant) {
+                                     std::vector<size_t> layers_per_group, double constant, MemoryPoolHandle pool, size_t n, bool packed)
+    : n_(n == 0 ? encoder.slot_count() : n), slot_count_(encoder.slot_count()), packed_(packed), scale_(scale), constant_(constant) {
     const std::string P = coeff_to_slot ? "[CoeffToSlotPlan::CoeffToSlotPlan]" : "[SlotToCoeffPlan::SlotToCoeffPlan]";
     if (!context || !context->get_context_data(parms_id).has_value()) throw std::invalid_argument(P + " parms_id not valid for context.");
     ContextDataPointer cd = context->get_context_data(parms_id).value();
@@ -47,6 +47,10 @@ SlotTransformPlan::SlotTransformPlan(bool coeff_to_slot, HeContextPointer contex
     }
     if (sum != m) throw std::invalid_argument(P + " the groups must sum to log2 n layers, n the plan's number of slots.");
     const size_t groups = layers_.size();
+    // packed: the group of layers [0, c) -- the last of CoeffToSlot, the first of SlotToCoeff -- works on 2n rows and must not be the boundary group
+    if (packed_ && (n_ < 4 || n_ * 2 > slot_count_)) throw std::invalid_argument(P + " a packed plan needs a power of two n in [4, slot_count / 2].");
+    if (packed_ && groups < 2) throw std::invalid_argument(P + " a packed plan needs at least two groups: the packed group cannot be the boundary group.");
+    packed_group_ = coeff_to_slot ? groups - 1 : 0;
     for (size_t g = 0; g < groups; g++) {
         parms_ids_.push_back(cd->parms_id());
         if (!cd->next_context_data().has_value()) throw std::invalid_argument(P + " the chain has fewer levels below the operand than groups.");
@@ -68,12 +72,27 @@ SlotTransformPlan::SlotTransformPlan(bool coeff_to_slot, HeContextPointer contex
         rotations_ += lt->rotation_steps().size();
         return lt;
     };
+    // the packed group on 2n rows: both blocks from one table, rows >= n turned by -i (CoeffToSlot) / +i (SlotToCoeff); first is 0, never the top group
+    auto make_packed = [&](size_t g, size_t first) {
+        const size_t count = layers_[g];
+        const double c = (g == 0 && constant < 0) ? -root : root;
+        size_t nd = 0;
+        utils::DynamicArray table = encoder.dft_factor_diagonals_packed(n_, first, count, coeff_to_slot, c, nd, pool);
+        std::unique_ptr<LinearTransform> lt(new LinearTransform(context, encoder, 2 * n_, parms_ids_[g], scale_, present_diagonals(m + 1, first, count),
+                                                                LinearTransform::DeviceTable{reinterpret_cast<const double*>(table.raw_pointer())}, size_t(1) << first, pool));
+        steps.insert(lt->rotation_steps().begin(), lt->rotation_steps().end());
+        // the conjugation of P = v + conj(v) (CoeffToSlot) / the rotation by n of V + rot_n(V) (SlotToCoeff)
+        rotations_ += lt->rotation_steps().size() + 1;
+        if (!coeff_to_slot) steps.insert(static_cast<int>(n_));
+        return lt;
+    };
     size_t done = 0;
     for (size_t g = 0; g < groups; g++) {
         done += layers_[g];
         const size_t first = coeff_to_slot ? m - done : done - layers_[g];
         firsts_.push_back(first);
         const bool boundary = g == boundary_;
+        if (packed_ && g == packed_group_) { transforms_.push_back(make_packed(g, first)); continue; }
         transforms_.push_back(make(g, first, boundary ? 1 : 0, false));
         if (boundary) twin_ = make(g, first, 2, coeff_to_slot);
     }
@@ -81,7 +100,7 @@ SlotTransformPlan::SlotTransformPlan(bool coeff_to_slot, HeContextPointer contex
 }
 
 namespace {
-void slot_transform(const Evaluator& ev, const HeContext& context, const char* P, const Ciphertext& encrypted, const SlotTransformPlan& plan, const GaloisKeys& galois_keys,
+void slot_transform(const Evaluator& ev, const HeContext& context, const char* P, bool coeff_to_slot, const Ciphertext& encrypted, const SlotTransformPlan& plan, const GaloisKeys& galois_keys,
                     Ciphertext& destination, MemoryPoolHandle pool) {
     auto cd = context.get_context_data(encrypted.parms_id());
     if (!cd.has_value()) throw std::invalid_argument(std::string(P) + " parms_id not valid for context.");
@@ -98,6 +117,11 @@ void slot_transform(const Evaluator& ev, const HeContext& context, const char* P
             const Ciphertext odd = ev.linear_transform_new(operand, plan.twin(), galois_keys, pool);
             ev.add_inplace(next, ev.complex_conjugate_new(odd, galois_keys, pool), pool);
         }
+        if (plan.packed() && g == plan.packed_group()) {
+            // before the rescale, at scale * weight scale.  CoeffToSlot: v + conj(v) = [2 Re; 2 Im] on period 2n.  SlotToCoeff: V + rot_n(V) = F (a + i b) on period n
+            const Ciphertext other = coeff_to_slot ? ev.complex_conjugate_new(next, galois_keys, pool) : ev.rotate_vector_new(next, static_cast<int>(plan.n()), galois_keys, pool);
+            ev.add_inplace(next, other, pool);
+        }
         ev.rescale_to_next_inplace(next, pool);
         current = std::move(next);
     }
@@ -106,11 +130,11 @@ void slot_transform(const Evaluator& ev, const HeContext& context, const char* P
 }  // namespace
 
 void Evaluator::coeff_to_slot(const Ciphertext& encrypted, const CoeffToSlotPlan& plan, const GaloisKeys& galois_keys, Ciphertext& destination, MemoryPoolHandle pool) const {
-    slot_transform(*this, *context_, "[Evaluator::coeff_to_slot]", encrypted, plan, galois_keys, destination, pool);
+    slot_transform(*this, *context_, "[Evaluator::coeff_to_slot]", true, encrypted, plan, galois_keys, destination, pool);
 }
 
 void Evaluator::slot_to_coeff(const Ciphertext& encrypted, const SlotToCoeffPlan& plan, const GaloisKeys& galois_keys, Ciphertext& destination, MemoryPoolHandle pool) const {
-    slot_transform(*this, *context_, "[Evaluator::slot_to_coeff]", encrypted, plan, galois_keys, destination, pool);
+    slot_transform(*this, *context_, "[Evaluator::slot_to_coeff]", false, encrypted, plan, galois_keys, destination, pool);
 }
 
 }  // namespace troy

@@ -1,6 +1,7 @@
 // slot_transform.h -- troy::CoeffToSlotPlan and troy::SlotToCoeffPlan, ADDITIONS to the reference's interface: the two linear steps of a CKKS bootstrap
 // (ModRaise -> CoeffToSlot -> EvalMod -> SlotToCoeff) on fully packed slots, as a factored special DFT whose factors are written (troyn_ckks_dft_factor_diagonals)
-// and encoded (troyn_ckks_encode_diagonals) on the device.  Sparse packing (n < slot_count slots, below) takes the same plans with log2 n layers.
+// and encoded (troyn_ckks_encode_diagonals) on the device.  Sparse packing (n < slot_count slots, below) takes the same plans with log2 n layers, and with
+// n <= slot_count / 2 a packed plan keeps both halves of the slots in one ciphertext ("Packed", below).
 //
 // The slot order.  The library keeps the reference's slot order, Galois generator 3, and 3 = -1 (mod 4).  With N the ring degree, n = N/2, m = log2 n,
 // zeta = exp(2 pi i / 2N), t the N real coefficients and w_k = t_k + i t_{k+n}: slot j is z_j = t(zeta^(3^j)) and (zeta^(3^j))^n = i^(3^j) is +i for even j
@@ -37,6 +38,18 @@
 // group holding layer m' - 1 is the top one; diagonal indices are mod n; the transforms are LinearTransforms on n, whose weights repeat s times across the
 // slots.  n is even, so the even / odd masks and the conjugation carry over.  The operand must repeat with period n and be a polynomial in Y: after a
 // ModRaise that is what Evaluator::sub_sum (troy.h) restores.  Everything above reads with m' for m and t' for t; n = slot_count is the fully packed plan.
+//
+// Packed (a trailing `packed`, n a power of two with 4 <= n <= slot_count / 2, at least two groups).  The ciphertext has room for the real and the imaginary
+// parts of the n slots side by side on period 2n, so that EvalMod, which is slot-wise, runs once.  A group of layers [first, first + count) with
+// first + count <= m' is block diagonal with blocks of at most n rows: on 2n rows it is two identical n x n blocks, no entry crosses row n, and it is never
+// the top group (2^(count+1) - 1 diagonals, indices mod 2n).  The packed table (troyn_ckks_dft_factor_diagonals_packed) has that group in rows < n and the
+// same words times -i (inverse) / +i (forward) in rows >= n; it takes the place of the group of layers [0, c), which with two groups or more is never the
+// boundary group that carries the masks and the twin.
+//     CoeffToSlot, last-applied group:   u of period n, v = M1 u = [G u; -i G u], and P = v + conj(v) = [2 Re(G u); 2 Im(G u)] on period 2n: one
+//         complex_conjugate and one add before the group's rescale (where split_real_imag spent its conjugation).  coeff_to_slot returns P.
+//     SlotToCoeff, first-applied group:  P' = [a; b] real of period 2n, V = F1 P' = [F a; i F b], and V + rot_n(V) = F (a + i b) on period n: one rotation
+//         by n slots and one add before the group's rescale, the ONE key switch more than the unpacked pair of plans.  slot_to_coeff takes P'.
+// No mask product and no extra level.  rotations() counts the conjugation / the rotation by n; rotation_steps() lists the packed group's steps mod 2n and n.
 #pragma once
 #include <memory>
 
@@ -59,6 +72,8 @@ public:
     const std::vector<size_t>& layers_per_group() const { return layers_; }
     size_t first_layer(size_t group) const { return firsts_.at(group); }
     size_t boundary_group() const { return boundary_; }
+    bool packed() const { return packed_; }                              // real and imaginary parts side by side on period 2n ("Packed" above)
+    size_t packed_group() const { return packed_group_; }                // the group of layers [0, c): the last of CoeffToSlot, the first of SlotToCoeff
     const LinearTransform& transform(size_t group) const { return *transforms_.at(group); }
     const LinearTransform& twin() const { return *twin_; }               // applied to the boundary group's operand; its result is conjugated
     const ParmsID& group_parms_id(size_t group) const { return parms_ids_.at(group); }
@@ -68,12 +83,14 @@ public:
 
 protected:
     // throws std::invalid_argument "[CoeffToSlotPlan::CoeffToSlotPlan] ..." / "[SlotToCoeffPlan::SlotToCoeffPlan] ..." for a non-CKKS context, an unknown
-    // parms_id, an n that is not a power of two in [2, slot_count], groups that are empty or do not sum to log2 n, a chain with fewer levels below the operand than groups, a constant that is zero or not finite
+    // parms_id, an n that is not a power of two in [2, slot_count], groups that are empty or do not sum to log2 n, a chain with fewer levels below the operand than groups, a constant that is zero or not finite,
+    // a packed plan with n outside [4, slot_count / 2] or a single group
     SlotTransformPlan(bool coeff_to_slot, HeContextPointer context, const CKKSEncoder& encoder, const ParmsID& parms_id, double scale, std::vector<size_t> layers_per_group,
-                      double constant, MemoryPoolHandle pool, size_t n);
+                      double constant, MemoryPoolHandle pool, size_t n, bool packed);
 
 private:
-    size_t n_, slot_count_, boundary_ = 0, rotations_ = 0;
+    size_t n_, slot_count_, boundary_ = 0, packed_group_ = 0, rotations_ = 0;
+    bool packed_ = false;
     double scale_, constant_;
     std::vector<size_t> layers_, firsts_;
     std::vector<ParmsID> parms_ids_;
@@ -88,15 +105,15 @@ std::vector<size_t> default_layers_per_group(size_t layers, size_t at_most = 4);
 class CoeffToSlotPlan : public SlotTransformPlan {
 public:
     CoeffToSlotPlan(HeContextPointer context, const CKKSEncoder& encoder, const ParmsID& parms_id, double scale, std::vector<size_t> layers_per_group = {},
-                    double constant = 1.0, MemoryPoolHandle pool = MemoryPool::GlobalPool(), size_t n = 0)
-        : SlotTransformPlan(true, context, encoder, parms_id, scale, std::move(layers_per_group), constant, pool, n) {}
+                    double constant = 1.0, MemoryPoolHandle pool = MemoryPool::GlobalPool(), size_t n = 0, bool packed = false)
+        : SlotTransformPlan(true, context, encoder, parms_id, scale, std::move(layers_per_group), constant, pool, n, packed) {}
 };
 
 class SlotToCoeffPlan : public SlotTransformPlan {
 public:
     SlotToCoeffPlan(HeContextPointer context, const CKKSEncoder& encoder, const ParmsID& parms_id, double scale, std::vector<size_t> layers_per_group = {},
-                    double constant = 1.0, MemoryPoolHandle pool = MemoryPool::GlobalPool(), size_t n = 0)
-        : SlotTransformPlan(false, context, encoder, parms_id, scale, std::move(layers_per_group), constant, pool, n) {}
+                    double constant = 1.0, MemoryPoolHandle pool = MemoryPool::GlobalPool(), size_t n = 0, bool packed = false)
+        : SlotTransformPlan(false, context, encoder, parms_id, scale, std::move(layers_per_group), constant, pool, n, packed) {}
 };
 
 }  // namespace troy

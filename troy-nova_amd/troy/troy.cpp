@@ -4794,6 +4794,18 @@ utils::DynamicArray CKKSEncoder::dft_factor_diagonals(size_t n, size_t first, si
     return table;
 }
 
+utils::DynamicArray CKKSEncoder::dft_factor_diagonals_packed(size_t n, size_t first, size_t count, bool inverse, double constant, size_t& nd, MemoryPoolHandle pool) const {
+    const char* P = "[CKKSEncoder::dft_factor_diagonals_packed]";
+    if (!context_->on_device()) throw std::invalid_argument(std::string(P) + " HeContext is not on device (call to_device_inplace).");
+    if (n < 2 || (n & (n - 1)) || n > slots_ / 2) throw std::invalid_argument(std::string(P) + " n must be a power of two in [2, slot_count / 2].");
+    nd = troyn_ckks_dft_factor_diagonals_packed_count(context_->ckks(), static_cast<uint32_t>(n), static_cast<uint32_t>(first), static_cast<uint32_t>(count));
+    if (count == 0 || nd == 0) throw std::invalid_argument(std::string(P) + " the layers must be a non-empty range inside [0, log2 n].");
+    utils::DynamicArray table(nd * 2 * n * 2, true, pool);
+    detail::ckks_dft_factor_diagonals_packed_step(on_current_stream(pool), context_->ckks(), static_cast<uint32_t>(n), static_cast<uint32_t>(first), static_cast<uint32_t>(count), inverse,
+                                                  constant, reinterpret_cast<double*>(table.raw_pointer()));
+    return table;
+}
+
 utils::DynamicArray CKKSEncoder::dft_factor_diagonals(size_t first, size_t count, bool inverse, int col_mask, int row_mask, bool conjugate, double constant, size_t& nd,
                                                       MemoryPoolHandle pool) const {
     const char* P = "[CKKSEncoder::dft_factor_diagonals]";

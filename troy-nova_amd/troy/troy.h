@@ -1319,6 +1319,10 @@ public:
     // in all.  n = 0 or n = slot_count is the call above.
     utils::DynamicArray dft_factor_diagonals(size_t n, size_t first, size_t count, bool inverse, int col_mask, int row_mask, bool conjugate, double constant, size_t& nd,
                                              MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
+    // layers [first, first + count), first + count <= log2 n, of the n-slot transform on 2n rows, n a power of two in [2, slot_count / 2]: rows >= n are the
+    // block of rows < n times -i (inverse) / +i (forward) (troyn_ckks_dft_factor_diagonals_packed; slot_transform.h "Packed"): [nd][2n], nd = 2^(count+1) - 1
+    utils::DynamicArray dft_factor_diagonals_packed(size_t n, size_t first, size_t count, bool inverse, double constant, size_t& nd,
+                                                    MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     // the plaintexts of one call share their parms_id and scale: one C-ABI call, one download
     std::vector<std::vector<std::complex<double>>> decode_complex64_simd_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     std::vector<std::vector<double>> decode_float64_polynomial_batched(const std::vector<const Plaintext*>& plains, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
@@ -1746,7 +1750,8 @@ public:
         Ciphertext d; bootstrap(encrypted, plan, relin_keys, galois_keys, encapsulation_keys, d, pool); return d;
     }
     //   Sparse packing: a plan with n below the slot count (bootstrap.h) runs sub_sum right after mod_raise (after the to_dense switch with the encapsulation)
-    //   and uses the n-slot transforms.
+    //   and uses the n-slot transforms.  A packed plan (bootstrap.h "Packed", n <= N/4) keeps the real and the imaginary parts side by side on period 2n:
+    //   coeff_to_slot returns both halves, ONE eval_mod operand, slot_to_coeff adds them back; no split_real_imag, no join_real_imag, one key switch more.
     // ADDITION to the reference's interface: SubSum, the projection of a CKKS ciphertext onto the sub-ring of n slots.  With s = slot_count / n and Y = X^s,
     //   SUM_{i < s} rotate(encrypted, n i) decrypts to s times the part of the plaintext polynomial that is a polynomial in Y (the rotations by multiples of n
     //   are the automorphisms that fix every X^(s k) and sum to 0 over every other monomial).  The sum is evaluated as the product PROD_i (1 + rot_{n 2^i}) in
@@ -1959,7 +1964,9 @@ public:
     //   ciphertext whose slots are constant * decode of those coefficients.  Keys: plan.rotation_steps() and the conjugation key (step 0 of create_galois_keys_from_steps).
     //   std::invalid_argument "[Evaluator::coeff_to_slot] ..." / "[Evaluator::slot_to_coeff] ..." for a non-CKKS context, an operand at another level than the
     //   plan's, or a plan of a ring of another degree than the operand's.  A plan with n below the slot count (sparse packing) expects an operand that repeats
-    //   with period n and is a polynomial in X^(slot_count / n): Evaluator::sub_sum.
+    //   with period n and is a polynomial in X^(slot_count / n): Evaluator::sub_sum.  A packed plan (slot_transform.h "Packed"): coeff_to_slot returns
+    //   constant * [2 Re; 2 Im] of those slots on period 2n (its last group's conjugation and add included); slot_to_coeff takes such a real operand [a; b]
+    //   and treats it as a + i b (its first group's rotation by n and add included; the key of step n is in plan.rotation_steps()).
     void coeff_to_slot(const Ciphertext& encrypted, const CoeffToSlotPlan& plan, const GaloisKeys& galois_keys, Ciphertext& destination,
                        MemoryPoolHandle pool = MemoryPool::GlobalPool()) const;
     Ciphertext coeff_to_slot_new(const Ciphertext& encrypted, const CoeffToSlotPlan& plan, const GaloisKeys& galois_keys, MemoryPoolHandle pool = MemoryPool::GlobalPool()) const {
